@@ -21,11 +21,16 @@ MASTER_PORT.  Nothing here needs PyTorch by default: the RCCL id travels through
 barrier, the max-over-ranks of the timing and the record gather go through the library's own communicator
 (vo_comm_allgather_f64 / vo_pairs_gather).  --rendezvous torch keeps the torch.distributed path (gloo: ranks sharing one GPU).
 
-Prints ONE JSON line on rank 0 (see the driver contract).  `value` times HBM-resident inputs; the PCIe-inclusive rate of the
-same loop is `value_streamed_from_host`.  Also in the line: `roofline` (HIP events on the library's stream, algorithmic bytes
-from vo_stage_bytes, PMC traffic from the committed rocprofv3 pass; the bound is named per stage), `cpu_baseline` (the CPU
-oracle timed on the host cores), `config.sustained`, `config.faithful` (ORB: cv2 keypoint order + cv::solvePoly's 300 sweeps,
-the configuration whose keypoint / match indices equal cv2's) and the RANSAC iteration histogram.
+Prints ONE JSON line on rank 0 (see the driver contract).  `value` times HBM-resident inputs over exactly --steps steps after
+--warmup steps; `ms_per_step` is the time of one of them.  A plain run does only that.  --full adds every other pass, each of
+which can still be left out with its --no-* flag: `value_streamed_from_host` (the PCIe-inclusive rate of the same loop),
+`roofline` (HIP events on the library's stream, algorithmic bytes from vo_stage_bytes, PMC traffic from the committed
+rocprofv3 pass; the bound is named per stage), `cpu_baseline` (the CPU oracle timed on the host cores), `config.sustained`,
+`config.faithful` (ORB: cv2 keypoint order + cv::solvePoly's 300 sweeps, the configuration whose keypoint / match indices
+equal cv2's), the widened rows (`config.sift`, `config.jpeg_pipeline`, `config.pnp`, `config.tracks_pnp_chain`) and, for
+--workload flight, the comparison with the CPU oracle's chain.  The RANSAC iteration histogram is in every line.
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float64), see dump_outputs().
 """
 from __future__ import annotations
 
@@ -241,6 +246,40 @@ def launch_ranks(n, argv):
     return rc
 
 
+DUMP_ARRAY_BYTES = 30 << 20      # --dump-outputs: a larger array is cut to a fixed, seeded sample of its rows (64 MB in all)
+
+
+def dump_outputs(out_dir, results=None, points=None, records=None):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, one float64 .npy file each, so that two
+    builds can be compared output for output on the same seeded inputs.  results: the pair-result records (one file per
+    field; R and E as [n, 3, 3]); points: the triangulated points [n, 4, cap], of which the library fills the columns
+    [0, n_inl) of the pairs with status 0 (the rest of the reused buffer is stale: written as 0); records: the gathered
+    [rows, 16] pose records.  An array over DUMP_ARRAY_BYTES keeps a fixed, seeded sample of its rows, named in <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    if results is not None:
+        for name in results.dtype.names:
+            if name != "reserved":
+                out[name] = np.asarray(results[name], np.float64)
+        n = len(results)
+        out["R"], out["t"], out["E"] = out["R"].reshape(n, 3, 3), out["t"].reshape(n, 3), out["E"].reshape(n, 3, 3)
+    if points is not None:
+        cols = np.where(results["status"] == 0, np.minimum(results["n_inl"], points.shape[2]), 0)
+        pts = np.zeros(points.shape[:2] + (int(cols.max(initial=0)),), np.float64)
+        for p, k in enumerate(cols):
+            pts[p, :, :k] = points[p, :, :k]
+        out["points"] = pts
+    if records is not None:
+        rec = np.asarray(records, np.float64)
+        out["records"] = rec.reshape(-1, rec.shape[-1])
+    for name, a in out.items():
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), DUMP_ARRAY_BYTES // (a.nbytes // len(a)), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 class TorchCollectives:
     def __init__(self, dist, torch, on_gpu):
         self.dist, self.torch, self.on_gpu = dist, torch, on_gpu
@@ -311,7 +350,17 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="create the communicator and run the gather even with one rank")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="--rendezvous torch only; gloo: rehearse N ranks on a box with fewer GPUs (all ranks share GPU 0, records gathered by torch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beyond the headline figure (streamed-from-host rate, sustained passes, per-stage roofline, "
+                         "faithful pass, widened rows, CPU baseline, CPU oracle chain); each --no-* flag still leaves its pass out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                     # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_profile = args.no_stream_pass = args.no_sustain = True
+        args.no_faithful_pass = args.no_extras = args.no_oracle_chain = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python3 bench.py --gpus N` without a launcher: this process becomes the launcher.  It has not touched the GPU (and
@@ -467,6 +516,8 @@ def main():
         coll.barrier()
         dt = coll.allreduce_max(time.perf_counter() - t0)
         _, rounds = sharding.sharded_plan(n_items, world, C)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, records=rec)
         if rank == 0:
             ok = rec[:, 14] >= 0
             line = {"metric": f"frame-pairs/sec ({args.width}x{args.height}, " + ("SIFT feats" if sift else f"{args.nfeatures} ORB feats") + ")",
@@ -545,6 +596,8 @@ def main():
     res = last[0].results[:C].copy()
     gathered = last[0].gathered.copy() if last[0].gathered is not None else None
     iters_all = np.concatenate(iters_seen) if iters_seen else res["ransac_iters"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, last[0].points[:C] if last[0].points is not None else None, gathered)
 
     # >= sustain_seconds of back-to-back steps, `repeats` times, median; single GPU only
     sustained = None

@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -45,8 +47,12 @@ def test_product_never_imports_the_oracle():
 
 
 def test_missing_gpu_fails_loudly():
-    import torch
-    if torch.cuda.is_available():
+    # asked in a child process: torch carries its own HIP runtime, and once that has opened the GPU in this process the
+    # library's vo_create fails in every GPU test that follows in the same session
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == "True":
         pytest.skip("a GPU is present")
     from visual_odometry_amd import _lib
     with pytest.raises(_lib.VoError):

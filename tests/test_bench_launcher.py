@@ -14,12 +14,12 @@ FLAGS = ["--steps", "3", "--warmup", "1", "--width", "160", "--height", "120", "
          "--contexts", "2", "--no-cpu-baseline", "--no-profile", "--no-stream-pass", "--no-sustain", "--no-faithful-pass"]
 
 
-def _run(gpus, extra_env=None, tmp=None):
+def _run(gpus, extra_env=None, tmp=None, extra_args=()):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "VO_RENDEZVOUS_KEY")}
     env.update(VO_BENCH_STUB="tests.stub_backend", PYTHONPATH=ROOT, VO_RENDEZVOUS_DIR=str(tmp))
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + FLAGS, env=env, cwd=ROOT,
-                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + FLAGS + list(extra_args), env=env,
+                          cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
 
 
 def test_bench_starts_its_own_ranks(tmp_path):
@@ -42,6 +42,60 @@ def test_single_gpu_line_needs_no_launcher(tmp_path):
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 1 and line["config"]["n_ranks_in_communicator"] is None
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the last timed step's pair results and the gathered records as float64 .npy files."""
+    out = tmp_path / "out"
+    p = _run(2, tmp=tmp_path, extra_args=["--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    import numpy as np
+    assert sorted(os.listdir(out)) == sorted(f"{n}.npy" for n in ("n_kp1", "n_kp2", "n_match", "n_inl", "n_good", "status",
+                                                                   "ransac_iters", "R", "t", "E", "records"))
+    R, n_inl, rec = np.load(out / "R.npy"), np.load(out / "n_inl.npy"), np.load(out / "records.npy")
+    assert R.dtype == np.float64 and R.shape == (4, 3, 3) and np.array_equal(R, np.broadcast_to(np.eye(3), (4, 3, 3)))
+    assert n_inl.tolist() == [40.0] * 4                                  # rank 0's own pairs
+    assert rec.shape == (2 * 4, 16) and rec[:4, 14].tolist() == [40.0] * 4 and rec[4:, 14].tolist() == [41.0] * 4
+
+
+def test_dump_outputs_keeps_the_filled_points_and_bounds_the_size(tmp_path, monkeypatch):
+    """Triangulated points: only the columns the library fills ([0, n_inl) of pairs with status 0) are kept, the stale rest
+    of the buffer is written as 0; an array over the size bound is cut to the same seeded sample of rows every time."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    from visual_odometry_amd import _lib
+    res = np.zeros(6, _lib.PAIR_RESULT_DTYPE)
+    res["status"] = [0, 0, 1, 0, 0, 0]
+    res["n_inl"] = [3, 5, 4, 0, 2, 1]
+    pts = np.random.default_rng(1).normal(size=(6, 4, 8))
+    bench.dump_outputs(str(tmp_path / "a"), res, pts)
+    got = np.load(tmp_path / "a" / "points.npy")
+    assert got.shape == (6, 4, 5)
+    for p, k in enumerate([3, 5, 0, 0, 2, 1]):
+        assert np.array_equal(got[p, :, :k], pts[p, :, :k]) and not got[p, :, k:].any()
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 2 * 4 * 5 * 8)        # two pairs' points
+    bench.dump_outputs(str(tmp_path / "b"), res, pts)
+    bench.dump_outputs(str(tmp_path / "c"), res, pts)
+    rows = np.load(tmp_path / "b" / "points_rows.npy")
+    assert rows.shape == (2,) and np.array_equal(rows, np.load(tmp_path / "c" / "points_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "points.npy"), got[rows.astype(int)])
+    assert np.load(tmp_path / "b" / "n_inl.npy").shape == (6,)
+
+
+def test_plain_run_leaves_the_other_passes_to_full(tmp_path):
+    """Without --full the line carries the headline figure only: no streamed, sustained, faithful, roofline or CPU pass ran."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "VO_RENDEZVOUS_KEY")}
+    env.update(VO_BENCH_STUB="tests.stub_backend", PYTHONPATH=ROOT, VO_RENDEZVOUS_DIR=str(tmp_path))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--width", "160",
+                        "--height", "120", "--distinct-frames", "8", "--pairs-per-step", "4"], env=env, cwd=ROOT,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert line["value_streamed_from_host"] is None and line["config"]["sustained"] is None and line["config"]["faithful"] is None
+    assert "roofline" not in line and "stages" not in line and "cpu_baseline" not in line and "sift" not in line["config"]
 
 
 def test_failing_rank_fails_the_launch(tmp_path):

@@ -29,6 +29,6 @@ python3 tools/collect_traffic.py $O/fetch $O/write $O/${TAG}_pmc_traffic$SUF.jso
 python3 tools/pmc_summary.py $O/sq > $O/${TAG}_pmc_sq_counters$SUF.txt
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${TAG}_final_kernel_stats$SUF.csv
 cp $O/${TAG}_pmc_traffic$SUF.json profiles/${TAG}_pmc_traffic$SUF.json      # bench.py reads it for roofline.traffic
-python3 bench.py $DARGS > $O/${TAG}_final_bench$SUF.json 2> $O/bench.err
+python3 bench.py --full $DARGS > $O/${TAG}_final_bench$SUF.json 2> $O/bench.err
 rm -rf $O/stats $O/fetch $O/write $O/sq
 ls -la $O

@@ -13,7 +13,7 @@ cd $R
 for i in 1 2 3; do
   for v in $tags current; do
     if [ $v = current ]; then unset VO_HIP_LIBRARY; else export VO_HIP_LIBRARY=/tmp/libvo_$v.so; fi
-    python3 bench.py --no-cpu-baseline --no-stream-pass --no-sustain --no-profile --steps 200 | python3 -c "
+    python3 bench.py --full --no-cpu-baseline --no-stream-pass --no-sustain --no-profile --steps 200 | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$v',d['value'],d['ms_per_step'])"
   done
 done

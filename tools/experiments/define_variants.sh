@@ -21,7 +21,7 @@ for v in "$@"; do
   hipcc -shared -fPIC --offload-arch=gfx950 -o $D/libvo.so $objs jpeg_host.o -ldl || continue
   echo "== [$units] $defs"
   for rep in 1 2; do
-  ( cd $R; VO_HIP_LIBRARY=$D/libvo.so python3 bench.py --no-cpu-baseline --no-stream-pass --no-extras --no-faithful-pass --sustain-repeats 1 --sustain-seconds 4 --steps 60 --warmup 6 $BENCH_ARGS 2>/dev/null | python3 -c "
+  ( cd $R; VO_HIP_LIBRARY=$D/libvo.so python3 bench.py --full --no-cpu-baseline --no-stream-pass --no-extras --no-faithful-pass --sustain-repeats 1 --sustain-seconds 4 --steps 60 --warmup 6 $BENCH_ARGS 2>/dev/null | python3 -c "
 import json,sys,os;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);s=d['config'].get('sustained') or {}
 print('  ',d['value'],d['ms_per_step'],'sustained',s.get('pairs_per_s_median'),' '.join('%s %.4f'%(k,d['stages'][k]['ms_per_launch']) for k in os.environ['STAGES'].split() if k in d['stages']),d['config'].get('mean_inliers_last_step'))" )
   done

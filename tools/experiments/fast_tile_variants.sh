@@ -14,6 +14,6 @@ for v in "$@"; do
   [ $ok = 1 ] || continue
   hipcc -shared -fPIC --offload-arch=gfx950 -o $D/libvo.so $D/vo_api.o $D/orb_kernels.o $D/cv2order_kernels.o match_kernels.o geom_kernels.o pnp_kernels.o gather_rccl.o jpeg_kernels.o sift_batch.o jpeg_host.o -ldl || continue
   echo "== FAST_TH $th  FAST_TW $tw  FT_QCAP $qc"
-  ( cd $R; VO_HIP_LIBRARY=$D/libvo.so python3 bench.py --no-cpu-baseline --no-stream-pass --no-sustain --no-extras --no-faithful-pass $BENCH_ARGS | python3 -c "
+  ( cd $R; VO_HIP_LIBRARY=$D/libvo.so python3 bench.py --full --no-cpu-baseline --no-stream-pass --no-sustain --no-extras --no-faithful-pass $BENCH_ARGS | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('  ',d['value'],d['ms_per_step'],d['stages']['fast_score_nms']['ms_per_launch'],d['stages']['select_fast']['ms_per_launch'],d['config'].get('pairs_ok_last_step'),d['config'].get('mean_inliers_last_step'))" )
 done
