@@ -220,7 +220,8 @@ int vo_sync(vo_ctx* ctx);
 /* Orders ctx's next enqueued work after `other`'s most recent vo_frames_detect_async (same device).  Chaining the
  * detections of two contexts keeps them out of phase: one's RANSAC / pose always runs beside the other's ORB. */
 int vo_detect_after(vo_ctx* ctx, vo_ctx* other);
-/* per-pair match list of the last vo_pairs_run (capacity cap each) */
+/* per-pair match list of the last vo_pairs_run (capacity cap each).  A configure call (vo_batch_configure[_sift]) forgets
+ * that run: every pair index is then refused (VO_ERR_INVALID), as on a fresh context. */
 int vo_pair_matches(vo_ctx* ctx, int pair, int32_t* qidx, int32_t* tidx, float* dist, uint8_t* inlier_mask,
                     int cap, int32_t* n_out);
 
@@ -246,8 +247,8 @@ int vo_comm_info(vo_ctx* ctx, int32_t* n_ranks, int32_t* rank);
  * the asynchronous form, world * B * VO_RECORD_DOUBLES doubles, rank-major) is valid after the call (wait != 0) or
  * after the next vo_sync(ctx).  Without vo_comm_init (single process) it degenerates to the local records. */
 int vo_pairs_gather(vo_ctx* ctx, int B, double* gathered, int wait);
-/* Rows at and beyond the pair count of that run (a short or empty last block) arrive as zeros with VO_ERR_NOT_CONFIGURED in the
- * n_inl column.  vo_comm_allgather_f64: synchronous all-gather of n <= 4096 host doubles per rank over the same communicator
+/* Rows at and beyond the pair count of that run (a short or empty last block, or every row after a configure call, which
+ * forgets the run) arrive as zeros with VO_ERR_NOT_CONFIGURED in the n_inl column.  vo_comm_allgather_f64: synchronous all-gather of n <= 4096 host doubles per rank over the same communicator
  * (recv: world * n, rank-major) — a launcher's barrier and timing reduction without another communication library; without
  * a communicator it copies send to recv. */
 int vo_comm_allgather_f64(vo_ctx* ctx, const double* send, int n, double* recv);
@@ -358,7 +359,7 @@ int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pair_frames, c
 /* The step after the pair path ON RESIDENT DATA — VisualSlam.update_feature_mapper / estimate_current_camera_position /
  * add_information_to_map, src/visual_slam.py:183-266 and :153-180, without the bundle adjustment (src/map.py:104-186).
  * Consumes what the most recent vo_pairs_run (want_points = 1) left in HBM — the pairs' inlier lists, inlier pixel
- * coordinates and triangulated points — for ALL its B pairs, which must form a chain of distinct frames (a0, b0), (b0, b1), ...
+ * coordinates and triangulated points (a configure call in between forgets them: VO_ERR_INVALID) — for ALL its B pairs, which must form a chain of distinct frames (a0, b0), (b0, b1), ...
  * (the order the reference walks a sequence in), and runs on the context's stream without a host round trip:
  *   pair 0: initialize_map (:43-92) — the two cameras and one map point per E inlier, keyed by featureid1.  [deviation] the
  *     reference stores camera 1 = (I, 0), camera 2 = (R, t) but the points in camera-2 coordinates and leaves the

@@ -166,3 +166,32 @@ def test_sift_chain_runs_on_the_live_configuration(oracle):
     out = fe.localize_chain(n - 1, seq["K"])
     assert out["status"].tolist() == [0] * (n - 1) and out["n_inl"][1:].min() > 30
     _advances_along_a_line(out["poses"])
+
+
+def test_configure_forgets_the_last_run():
+    """A configure call may free and reallocate the pair buffers, so it forgets the most recent vo_pairs_run: after a
+    reconfigure to fewer frames / pairs (the early-return path of vo_batch_configure) and after one to SIFT, localize_chain
+    and pair_matches are refused and every gathered record carries VO_ERR_NOT_CONFIGURED, as on a fresh context."""
+    from visual_odometry_amd import _lib, synth
+    from visual_odometry_amd.frontend import FrontEnd
+    seq = synth.sequence(4, 640, 480, cache_dir="/tmp")
+    K = seq["K"]
+    c = _lib.Context(0)
+    fe = FrontEnd(480, 640, max_frames=4, max_pairs=3, nfeatures=500, ctx=c)
+    fe.upload(seq["frames"]); fe.detect(0, 4)
+    res, _ = fe.run_pairs([[0, 1], [1, 2], [2, 3]], K, want_points=True)
+    assert res["status"].tolist() == [0, 0, 0]
+    assert len(fe.pair_matches(2)[0]) > 0 and (fe.gather_records(3)[0, :, 14] > 0).all()
+    for make in (lambda: FrontEnd(480, 640, max_frames=2, max_pairs=1, nfeatures=500, ctx=c),
+                 lambda: FrontEnd(480, 640, max_frames=4, max_pairs=3, detector="sift", ctx=c)):
+        f = make()
+        with pytest.raises(_lib.VoError) as e:
+            f.localize_chain(3, K)
+        assert e.value.code == _lib.VO_ERR_INVALID
+        for pair in range(3):
+            with pytest.raises(_lib.VoError) as e:
+                f.pair_matches(pair)
+            assert e.value.code == _lib.VO_ERR_INVALID
+        rec = f.gather_records(f.max_pairs)
+        assert (rec[0, :, 14] == _lib.VO_ERR_NOT_CONFIGURED).all() and not rec[0, :, :14].any() and not rec[0, :, 15].any()
+    c.close()

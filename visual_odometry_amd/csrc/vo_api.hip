@@ -11,8 +11,43 @@
 
 #define MAX_EVENTS 160
 
+// The device (and pinned host) allocations of one lifetime: each one its own hipMalloc, all freed together by release() or
+// the destructor.  n == 0 allocates one element.
+struct DevList {
+    struct Entry { void* p; bool pinned; };
+    std::vector<Entry> ptrs;
+    DevList() = default;
+    DevList(const DevList&) = delete;
+    DevList& operator=(DevList&& o) noexcept { if (this != &o) { release(); ptrs.swap(o.ptrs); } return *this; }
+    ~DevList() { release(); }
+    template <typename T> hipError_t alloc(T** p, size_t n) { return keep(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)), (void**)p, false); }
+    template <typename T> hipError_t alloc_pinned(T** p, size_t n)
+    {
+        return keep(hipHostMalloc((void**)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault), (void**)p, true);
+    }
+    void release()
+    {
+        for (const Entry& e : ptrs) (void)(e.pinned ? hipHostFree(e.p) : hipFree(e.p));
+        ptrs.clear();
+    }
+private:
+    hipError_t keep(hipError_t e, void** p, bool pinned) { if (e == hipSuccess) ptrs.push_back({*p, pinned}); return e; }
+};
+
+// A device scratch buffer that only grows (capacity in elements): grow() is defined below vo_ctx
+template <typename T> struct Growable {
+    T* p = nullptr;
+    size_t cap = 0;
+    Growable() = default;
+    Growable(const Growable&) = delete;
+    ~Growable() { if (p) (void)hipFree(p); }
+    int grow(struct vo_ctx* ctx, size_t need, size_t n);
+    int grow(struct vo_ctx* ctx, size_t need) { return grow(ctx, need, need); }
+};
+
 // One SIFT configuration: per-slot results for max_frames slots + the scale-space scratch of one sub-batch of fb frames
 struct SiftState {
+    DevList mem;
     bool configured = false, with_operands = false;
     vo_sift_params prm{};
     int h = 0, w = 0, fstride = 0, max_frames = 0, kp_cap = 0, cap_x = 0, raw_cap = 0, cand_cap = 0, surv_cap = 0, fb = 0;
@@ -39,51 +74,53 @@ struct CommShared {
     bool last_set = false;
 };
 
+// What the most recent vo_pairs_run[_async] left in the pair buffers: cleared whenever those buffers may have changed
+struct LastRun {
+    int pairs = 0;
+    std::vector<int32_t> slots;           // its pair slots (host copy)
+    int points = 0;                       // ... and whether it triangulated (want_points)
+};
+
 struct vo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // non-blocking: no implicit ordering with the NULL stream (PyTorch / RCCL use it)
-    hipStream_t stream_hi = nullptr;      // same, highest priority: the latency-bound geometry tail (RANSAC, pose, DLT)
-    hipStream_t cur = nullptr;            // stream the StageTimer brackets are recorded on
-    hipEvent_t ev_tail[2] = {nullptr, nullptr};
-    int tail_priority = 0;
-    hipStream_t stream_side = nullptr;    // the Gaussian blur of a detection runs here, beside the keypoint-selection kernels
-    hipEvent_t ev_side[2] = {nullptr, nullptr};
     hipStream_t stream_jpg = nullptr;     // the JPEG decoder's coefficient buffer is cleared here, beside the upload of the files and k_jpeg_unstuff
     hipEvent_t ev_jpg[2] = {nullptr, nullptr};
     char err[512] = {0};
+    DevList mem;                          // context lifetime: dK, rng_tab, rng_host, raw_i
 
     bool configured = false;
+    DevList orb_mem;                      // the ORB configuration: tables, pyramid, blur, scores, ff.*, desc_x, selection state, cv2.*
     int h = 0, w = 0, max_frames = 0, max_pairs = 0;
     vo_orb_params params{};
     PyrGeom g{};
     ResizeTab tabs[VO_MAX_LEVELS]{};
-    void* tab_mem = nullptr;
-    uint8_t *pyr = nullptr, *blur = nullptr, *score = nullptr, *staging = nullptr;
+    uint8_t *pyr = nullptr, *blur = nullptr, *score = nullptr;
     uint8_t* desc_x = nullptr;            // descriptors expanded to +1 / -1 bytes for the MFMA matcher
-    uint8_t* ingest_out = nullptr; size_t ingest_out_bytes = 0;      // resized frames (frame ingest)
+    Growable<uint8_t> staging;                                       // host frames on their way into the slots
+    Growable<uint8_t> ingest_out;                                    // resized frames (frame ingest)
     SiftState sift, sift1;                                           // SIFT: the batched detector's state; the single-image call's
-    uint8_t* sift_img = nullptr; size_t sift_img_n = 0;              // the single-image call's input on the device
+    Growable<uint8_t> sift_img;                                      // the single-image call's input on the device
     int detector = 0;                                                // detector of the batched path: 0 = ORB (vo_batch_configure), 1 = SIFT (vo_batch_configure_sift)
     int sift_pairs = 0;
     // JPEG decode: the batch's files, clean streams, restart lists, coefficients, component planes, B G R output, descriptors
-    uint8_t *jpg_blob = nullptr, *jpg_clean = nullptr, *jpg_rst = nullptr, *jpg_coef = nullptr, *jpg_planes = nullptr, *jpg_out = nullptr,
-            *jpg_img = nullptr, *jpg_tab = nullptr;
-    size_t jpg_blob_n = 0, jpg_clean_n = 0, jpg_rst_n = 0, jpg_coef_n = 0, jpg_planes_n = 0, jpg_out_n = 0, jpg_img_n = 0, jpg_tab_n = 0;
-    int* ingest_tab = nullptr; size_t ingest_tab_n = 0;              // resize tables
+    Growable<uint8_t> jpg_blob, jpg_clean, jpg_rst, jpg_coef, jpg_planes, jpg_out, jpg_img, jpg_tab;
+    Growable<int> ingest_tab;                                        // resize tables
     int *sel_thr = nullptr, *sel_chunk_count = nullptr, *har_kept = nullptr;
     float* har_thr = nullptr;
-    size_t staging_bytes = 0;
     FrameFeat ff{};
+    DevList pb_mem;                       // the pair buffers, shared by ORB and SIFT
     PairBuf pb{};
     int pb_pairs = 0, pb_cap = 0;
     double* dK = nullptr;
-    int last_pairs = 0;
+    LastRun last;
 
     // scratch for the single-call operators
+    DevList raw_mem;                      // the single-call matcher: raw_desc, raw_desc_x, raw_xy, raw_count, raw_pb.*
     int raw_cap = 0;
     uint8_t* raw_desc = nullptr; float* raw_xy = nullptr; int* raw_count = nullptr; uint8_t* raw_desc_x = nullptr;
     PairBuf raw_pb{};
-    double* raw_d = nullptr; size_t raw_d_n = 0;     // generic double scratch
+    Growable<double> raw_d;                          // generic double scratch
     uint32_t* rng_tab = nullptr; uint32_t* rng_host = nullptr; uint64_t rng_seed = 0; bool rng_valid = false;   // OpenCV RNG stream for the RANSAC seed
     int* raw_i = nullptr;
 
@@ -99,15 +136,13 @@ struct vo_ctx {
     int descx_fp4 = 0;                    // operand image the resident frames' desc_x currently holds (written at detection)
     int matcher_kernel = 2;               // 2: block-scaled FP4 MFMA (default), 0: int8 MFMA on +127/-127 bytes, 1: XOR + popcount
     CommShared* cs = nullptr;             // RCCL communicator of the trajectory gather: ONE per process, shared by its contexts (vo_comm_share)
-    double *rec_send = nullptr, *rec_recv = nullptr; size_t rec_cap = 0;
+    Growable<double> rec_send, rec_recv;  // the gather's packed records: this rank's and every rank's
     int kp_order = 1;                     // 1 (default): cv2's retainBest order — keypoint / match indices as cv2 numbers them; 0: canonical (octave, y, x)
     Cv2Buf cv2{};
     bool cv2_ready = false;
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
-    std::vector<int32_t> last_slots;      // pair slots of the most recent vo_pairs_run[_async] (host copy)
-    int last_points = 0;                  // ... and whether it triangulated (want_points)
-    uint8_t* chain_mem = nullptr; size_t chain_bytes = 0;             // the localisation chain's tables (vo_tracks_pnp_batch)
+    Growable<uint8_t> chain_mem;          // the localisation chain's tables (vo_tracks_pnp_batch)
 };
 
 static const char* k_stage_names[VO_STAGE_COUNT] = {
@@ -129,11 +164,28 @@ static const char* k_stage_names[VO_STAGE_COUNT] = {
 #define FAIL(code, ...)                                                                           \
     do { snprintf(ctx->err, sizeof(ctx->err), __VA_ARGS__); return (code); } while (0)
 
-template <typename T>
-static hipError_t dmalloc(T** p, size_t n) { return hipMalloc((void**)p, (n ? n : 1) * sizeof(T)); }
+// Room for `need` elements.  Without it: wait for the context's stream (queued work may still use the buffer), free, and
+// allocate n >= need elements.
+template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
+{
+    if (need <= cap) return VO_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    HIPCHK(hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)));
+    cap = n;
+    return VO_OK;
+}
 
-static int ensure_raw_d(vo_ctx* ctx, size_t n);
-static int ensure_bytes(vo_ctx* ctx, uint8_t** p, size_t* have, size_t need);
+static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
+
+// the generic double scratch of the single-call operators, n doubles at least
+static int ensure_raw_d(vo_ctx* ctx, size_t n)
+{
+    int rc = ctx->raw_d.grow(ctx, n, n + n / 4 + 64); if (rc) return rc;
+    if (!ctx->raw_i) HIPCHK(ctx->mem.alloc(&ctx->raw_i, 16));
+    return VO_OK;
+}
 
 // ------------------------------------------------------------------ profiling brackets
 struct StageTimer {
@@ -143,10 +195,10 @@ struct StageTimer {
         if (c->prof && c->n_ev < MAX_EVENTS) {
             idx = c->n_ev++;
             c->ev_stage[idx] = stage;
-            (void)hipEventRecord(c->ev[idx][0], c->cur ? c->cur : c->stream);
+            (void)hipEventRecord(c->ev[idx][0], c->stream);
         }
     }
-    ~StageTimer() { if (idx >= 0) (void)hipEventRecord(c->ev[idx][1], c->cur ? c->cur : c->stream); }
+    ~StageTimer() { if (idx >= 0) (void)hipEventRecord(c->ev[idx][1], c->stream); }
 };
 
 static void prof_collect(vo_ctx* c)
@@ -261,20 +313,12 @@ static void build_lin_tab(int ssize, int dsize, int* ofs, uint16_t* c1, int* pmi
 }
 
 // ------------------------------------------------------------------ buffers
-static void free_pairbuf(PairBuf& pb)
-{
-    void* ptrs[] = {pb.slots, pb.nn_idx, pb.nn_dist, pb.nn_idx2, pb.nn_dist2, pb.m_q, pb.m_t, pb.m_d, pb.m_count,
-                    pb.px1, pb.px2, pb.xn1, pb.xn2, pb.mask, pb.models, pb.in1, pb.in2, pb.ipx1, pb.ipx2,
-                    pb.res, pb.X, pb.pose_mask};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    memset(&pb, 0, sizeof(pb));
-}
-
-static hipError_t alloc_pairbuf(PairBuf& pb, int P, int cap, bool with_pose_mask)
+static hipError_t alloc_pairbuf(DevList& mem, PairBuf& pb, int P, int cap, bool with_pose_mask)
 {
     hipError_t e;
     const size_t pc = (size_t)P * cap;
-#define A_(field, n) if ((e = dmalloc(&pb.field, (n))) != hipSuccess) return e
+    pb = PairBuf{};
+#define A_(field, n) if ((e = mem.alloc(&pb.field, (n))) != hipSuccess) return e
     A_(slots, (size_t)P * 2); A_(nn_idx, pc * 2); A_(nn_dist, pc * 2); A_(nn_idx2, pc); A_(nn_dist2, pc);
     A_(m_q, pc); A_(m_t, pc); A_(m_d, pc); A_(m_count, (size_t)P);
     A_(px1, pc * 2); A_(px2, pc * 2); A_(xn1, pc * 2); A_(xn2, pc * 2);
@@ -284,14 +328,6 @@ static hipError_t alloc_pairbuf(PairBuf& pb, int P, int cap, bool with_pose_mask
     if (with_pose_mask) { A_(pose_mask, pc); }
 #undef A_
     return hipSuccess;
-}
-
-static void free_cv2(vo_ctx* c)
-{
-    void* ptrs[] = {c->cv2.all_pos, c->cv2.all_resp, c->cv2.all_count, c->cv2.chunk_count, c->cv2.ones, c->cv2.work, c->cv2.lpos, c->cv2.rpos};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    memset(&c->cv2, 0, sizeof(c->cv2));
-    c->cv2_ready = false;
 }
 
 // all-winner lists + work arrays of the cv2 order mode for the current configuration.  Capacity per level: an eighth
@@ -310,10 +346,11 @@ static int alloc_cv2(vo_ctx* ctx)
     }
     cb.all_total = off;
     const size_t F = (size_t)ctx->max_frames, n = F * off;
-    HIPCHK(dmalloc(&cb.all_pos, n)); HIPCHK(dmalloc(&cb.all_resp, n)); HIPCHK(dmalloc(&cb.work, n));
-    HIPCHK(dmalloc(&cb.lpos, n)); HIPCHK(dmalloc(&cb.rpos, n));
-    HIPCHK(dmalloc(&cb.all_count, F * VO_MAX_LEVELS)); HIPCHK(dmalloc(&cb.ones, F * VO_MAX_LEVELS));
-    HIPCHK(dmalloc(&cb.chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
+    DevList& m = ctx->orb_mem;
+    HIPCHK(m.alloc(&cb.all_pos, n)); HIPCHK(m.alloc(&cb.all_resp, n)); HIPCHK(m.alloc(&cb.work, n));
+    HIPCHK(m.alloc(&cb.lpos, n)); HIPCHK(m.alloc(&cb.rpos, n));
+    HIPCHK(m.alloc(&cb.all_count, F * VO_MAX_LEVELS)); HIPCHK(m.alloc(&cb.ones, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&cb.chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
     std::vector<int> ones(F * VO_MAX_LEVELS, 1);
     HIPCHK(hipMemcpy(cb.ones, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(cb.all_count, 0, F * VO_MAX_LEVELS * sizeof(int)));
@@ -322,21 +359,16 @@ static int alloc_cv2(vo_ctx* ctx)
     return VO_OK;
 }
 
+// the ORB configuration and the pair buffers, with the last run that described them
 static void free_config(vo_ctx* c)
 {
-    free_cv2(c);
-    void* ptrs[] = {c->tab_mem, c->pyr, c->blur, c->score, c->ff.cand_pos, c->ff.cand_resp, c->ff.cand_count,
-                    c->ff.kp_pos, c->ff.kp_level, c->ff.kp_resp, c->ff.kp_angle, c->ff.kp_xy, c->ff.kp_size,
-                    c->ff.desc, c->ff.kp_count, c->ff.flags, c->ff.hist, c->ff.tile_list, c->ff.tile_count, c->sel_thr, c->sel_chunk_count, c->har_kept, c->har_thr, c->desc_x};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    c->tab_mem = nullptr; c->pyr = c->blur = c->score = nullptr; c->desc_x = nullptr; c->sel_thr = c->sel_chunk_count = c->har_kept = nullptr; c->har_thr = nullptr;
-    memset(&c->ff, 0, sizeof(c->ff));
-    free_pairbuf(c->pb);
+    c->configured = c->cv2_ready = false;
+    c->orb_mem.release();
+    c->pb_mem.release();
     c->pb_pairs = c->pb_cap = 0;
-    c->configured = false;
+    clear_last_run(c);
 }
 
-static void sift_free(SiftState& S);
 static void comm_release(vo_ctx* ctx);
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F);
@@ -352,35 +384,13 @@ extern "C" int vo_create(int device_id, vo_ctx** out)
     vo_ctx* ctx = new vo_ctx();
     ctx->device = device_id;
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        dmalloc(&ctx->dK, 16) != hipSuccess) {
+        ctx->mem.alloc(&ctx->dK, 16) != hipSuccess) {
         delete ctx;
         return VO_ERR_HIP;
     }
     for (int i = 0; i < MAX_EVENTS; i++) { (void)hipEventCreate(&ctx->ev[i][0]); (void)hipEventCreate(&ctx->ev[i][1]); }
     ctx->ev_ready = true;
     (void)hipEventCreateWithFlags(&ctx->ev_det, hipEventDisableTiming);
-    {   // experiment knob (VO_TAIL_PRIORITY=1 highest / 2 lowest): the geometry tail of a batch on a stream of its own.
-        // With the highest priority its few hundred big workgroups (k_pose: 1024 threads, k_ransac: 368 VGPRs) evict the
-        // other context's ORB kernels from whole CUs; with the lowest they wait for leftovers: both lose to one stream.
-        int lo = 0, hi = 0;
-        const char* e = getenv("VO_TAIL_PRIORITY");
-        ctx->tail_priority = e ? atoi(e) : 0;      // measured on MI355X: highest priority -17 %, lowest -6 % vs one stream: off
-        if (ctx->tail_priority && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
-            hipStreamCreateWithPriority(&ctx->stream_hi, hipStreamNonBlocking, ctx->tail_priority == 2 ? lo : hi) == hipSuccess) {
-            if (getenv("VO_DEBUG")) fprintf(stderr, "stream priority range: least %d greatest %d\n", lo, hi);
-            (void)hipEventCreateWithFlags(&ctx->ev_tail[0], hipEventDisableTiming);
-            (void)hipEventCreateWithFlags(&ctx->ev_tail[1], hipEventDisableTiming);
-        } else ctx->stream_hi = nullptr;
-    }
-    {   // experiment knob (VO_SIDE_STREAM=1): k_blur needs only the pyramid, not the keypoints, so on a stream of its own
-        // it can run beside the selection / Harris / orientation kernels of the same detection.  Measured on MI355X:
-        // 72.6 k vs 72.9 k pairs/s without (the kernels it would overlap with hold the register file, not the ALUs): off.
-        const char* e = getenv("VO_SIDE_STREAM");
-        if (e && atoi(e) == 1 && hipStreamCreateWithFlags(&ctx->stream_side, hipStreamNonBlocking) == hipSuccess) {
-            (void)hipEventCreateWithFlags(&ctx->ev_side[0], hipEventDisableTiming);
-            (void)hipEventCreateWithFlags(&ctx->ev_side[1], hipEventDisableTiming);
-        } else ctx->stream_side = nullptr;
-    }
     *out = ctx;
     return VO_OK;
 }
@@ -390,27 +400,13 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    free_config(ctx);
-    free_pairbuf(ctx->raw_pb);
-    sift_free(ctx->sift); sift_free(ctx->sift1);
-    void* ptrs[] = {ctx->staging, ctx->dK, ctx->raw_desc, ctx->raw_xy, ctx->raw_count, ctx->raw_d, ctx->raw_i, ctx->rng_tab, ctx->raw_desc_x,
-                    ctx->chain_mem, ctx->ingest_out, ctx->ingest_tab, ctx->sift_img, ctx->jpg_blob, ctx->jpg_clean, ctx->jpg_rst, ctx->jpg_coef, ctx->jpg_planes, ctx->jpg_out,
-                    ctx->jpg_img, ctx->jpg_tab};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (ctx->ev_ready) for (int i = 0; i < MAX_EVENTS; i++) { (void)hipEventDestroy(ctx->ev[i][0]); (void)hipEventDestroy(ctx->ev[i][1]); }
-    if (ctx->ev_det) (void)hipEventDestroy(ctx->ev_det);
-    if (ctx->stream_hi) { (void)hipStreamSynchronize(ctx->stream_hi); (void)hipStreamDestroy(ctx->stream_hi); }
-    if (ctx->stream_side) { (void)hipStreamSynchronize(ctx->stream_side); (void)hipStreamDestroy(ctx->stream_side); }
-    for (int i = 0; i < 2; i++) if (ctx->ev_side[i]) (void)hipEventDestroy(ctx->ev_side[i]);
     if (ctx->stream_jpg) { (void)hipStreamSynchronize(ctx->stream_jpg); (void)hipStreamDestroy(ctx->stream_jpg); }
     for (int i = 0; i < 2; i++) if (ctx->ev_jpg[i]) (void)hipEventDestroy(ctx->ev_jpg[i]);
-    for (int i = 0; i < 2; i++) if (ctx->ev_tail[i]) (void)hipEventDestroy(ctx->ev_tail[i]);
+    if (ctx->ev_ready) for (int i = 0; i < MAX_EVENTS; i++) { (void)hipEventDestroy(ctx->ev[i][0]); (void)hipEventDestroy(ctx->ev[i][1]); }
+    if (ctx->ev_det) (void)hipEventDestroy(ctx->ev_det);
     comm_release(ctx);
-    if (ctx->rec_send) (void)hipFree(ctx->rec_send);
-    if (ctx->rec_recv) (void)hipFree(ctx->rec_recv);
-    if (ctx->rng_host) (void)hipHostFree(ctx->rng_host);
     (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                           // the buffers go with their owners
 }
 
 // which image of the descriptors the matrix-core matcher reads: FP4 (block-scaled MFMA, fewer than 8192 rows per set) or int8
@@ -466,6 +462,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
     if (ctx->configured && ctx->h == h && ctx->w == w && memcmp(&ctx->params, params, sizeof(*params)) == 0 &&
         ctx->max_frames >= max_frames && ctx->max_pairs >= max_pairs && ctx->pb_cap == ctx->g.kp_cap) {
         ctx->detector = 0;
+        clear_last_run(ctx);
         return VO_OK;
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -482,9 +479,11 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
     std::vector<int> hofs(tab_ints + 1);
     std::vector<uint16_t> hc(tab_u16 + 1);
     const size_t int_bytes = (tab_ints + 1) * sizeof(int);
-    HIPCHK(hipMalloc(&ctx->tab_mem, int_bytes + (tab_u16 + 1) * sizeof(uint16_t) + 64));
-    int* d_ofs = (int*)ctx->tab_mem;
-    uint16_t* d_c = (uint16_t*)((char*)ctx->tab_mem + int_bytes);
+    DevList& m = ctx->orb_mem;
+    uint8_t* tab_mem = nullptr;
+    HIPCHK(m.alloc(&tab_mem, int_bytes + (tab_u16 + 1) * sizeof(uint16_t) + 64));
+    int* d_ofs = (int*)tab_mem;
+    uint16_t* d_c = (uint16_t*)(tab_mem + int_bytes);
     size_t oi = 0;
     for (int l = 1; l < g.nlevels; l++) {
         ResizeTab& t = ctx->tabs[l];
@@ -509,32 +508,32 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
     HIPCHK(hipMemcpy(d_c, hc.data(), (tab_u16 + 1) * sizeof(uint16_t), hipMemcpyHostToDevice));
 
     const size_t F = (size_t)max_frames, fb = (size_t)g.frame_bytes;
-    HIPCHK(hipMalloc((void**)&ctx->pyr, F * fb + 256));          // + slack: k_resize_direct reads whole dwords around its last taps
-    HIPCHK(hipMalloc((void**)&ctx->blur, F * fb));
-    HIPCHK(hipMalloc((void**)&ctx->score, F * fb));
+    HIPCHK(m.alloc(&ctx->pyr, F * fb + 256));                  // + slack: k_resize_direct reads whole dwords around its last taps
+    HIPCHK(m.alloc(&ctx->blur, F * fb));
+    HIPCHK(m.alloc(&ctx->score, F * fb));
     HIPCHK(hipMemset(ctx->pyr, 0, F * fb));
     FrameFeat& ff = ctx->ff;
-    HIPCHK(dmalloc(&ff.cand_pos, F * g.cand_total)); HIPCHK(dmalloc(&ff.cand_resp, F * g.cand_total));
-    HIPCHK(dmalloc(&ff.cand_count, F * VO_MAX_LEVELS));
-    HIPCHK(dmalloc(&ff.kp_pos, F * g.kp_cap)); HIPCHK(dmalloc(&ff.kp_level, F * g.kp_cap));
-    HIPCHK(dmalloc(&ff.kp_resp, F * g.kp_cap)); HIPCHK(dmalloc(&ff.kp_angle, F * g.kp_cap));
-    HIPCHK(dmalloc(&ff.kp_xy, F * g.kp_cap * 2)); HIPCHK(dmalloc(&ff.kp_size, F * g.kp_cap));
-    HIPCHK(dmalloc(&ff.desc, F * g.kp_cap * 32));
-    HIPCHK(dmalloc(&ctx->desc_x, F * (size_t)desc_x_rows(g.kp_cap) * 256));
+    HIPCHK(m.alloc(&ff.cand_pos, F * g.cand_total)); HIPCHK(m.alloc(&ff.cand_resp, F * g.cand_total));
+    HIPCHK(m.alloc(&ff.cand_count, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&ff.kp_pos, F * g.kp_cap)); HIPCHK(m.alloc(&ff.kp_level, F * g.kp_cap));
+    HIPCHK(m.alloc(&ff.kp_resp, F * g.kp_cap)); HIPCHK(m.alloc(&ff.kp_angle, F * g.kp_cap));
+    HIPCHK(m.alloc(&ff.kp_xy, F * g.kp_cap * 2)); HIPCHK(m.alloc(&ff.kp_size, F * g.kp_cap));
+    HIPCHK(m.alloc(&ff.desc, F * g.kp_cap * 32));
+    HIPCHK(m.alloc(&ctx->desc_x, F * (size_t)desc_x_rows(g.kp_cap) * 256));
     // k_brief writes only the rows below kp_count; k_nn_mfma still multiplies the rest of the last 16-row group and
     // relies on |dot| <= 16384, which holds for +1 / -1 bytes but not for whatever a recycled allocation held
     HIPCHK(hipMemset(ctx->desc_x, 0xFF, F * (size_t)desc_x_rows(g.kp_cap) * 256));
-    HIPCHK(dmalloc(&ff.kp_count, F)); HIPCHK(dmalloc(&ff.flags, F));
-    HIPCHK(dmalloc(&ff.hist, F * VO_MAX_LEVELS * 256));
-    HIPCHK(dmalloc(&ff.tile_list, F * (size_t)g.ftiles_total * FAST_LISTCAP));
-    HIPCHK(dmalloc(&ff.tile_count, F * (size_t)g.ftiles_total));
-    HIPCHK(dmalloc(&ctx->sel_thr, F * VO_MAX_LEVELS));
-    HIPCHK(dmalloc(&ctx->har_kept, F * VO_MAX_LEVELS));
-    HIPCHK(dmalloc(&ctx->har_thr, F * VO_MAX_LEVELS));
-    HIPCHK(dmalloc(&ctx->sel_chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
+    HIPCHK(m.alloc(&ff.kp_count, F)); HIPCHK(m.alloc(&ff.flags, F));
+    HIPCHK(m.alloc(&ff.hist, F * VO_MAX_LEVELS * 256));
+    HIPCHK(m.alloc(&ff.tile_list, F * (size_t)g.ftiles_total * FAST_LISTCAP));
+    HIPCHK(m.alloc(&ff.tile_count, F * (size_t)g.ftiles_total));
+    HIPCHK(m.alloc(&ctx->sel_thr, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&ctx->har_kept, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&ctx->har_thr, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&ctx->sel_chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
     HIPCHK(hipMemset(ff.kp_count, 0, F * sizeof(int)));
     HIPCHK(hipMemset(ff.flags, 0, F * sizeof(int)));
-    HIPCHK(alloc_pairbuf(ctx->pb, max_pairs, g.kp_cap, false));
+    HIPCHK(alloc_pairbuf(ctx->pb_mem, ctx->pb, max_pairs, g.kp_cap, false));
     ctx->pb_pairs = max_pairs; ctx->pb_cap = g.kp_cap;
     HIPCHK(hipDeviceSynchronize());                         // the initialising memsets ran on the NULL stream
     ctx->configured = true;
@@ -543,38 +542,47 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
     return VO_OK;
 }
 
-// ---- the resident gray frames of the batched path, whichever detector is configured: level 0 of the ORB pyramid slots, or the
-// SIFT slots' dense gray images
-static bool batch_ready(const vo_ctx* ctx);
-static int batch_w(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift.w : ctx->w; }
-static int batch_h(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift.h : ctx->h; }
-static int batch_max_frames(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift.max_frames : ctx->max_frames; }
-struct GraySlots { uint8_t* base; int stride; size_t frame; };          // slot k's image at base + k * frame, rows of `stride` bytes
-static GraySlots batch_gray_slots(const vo_ctx* ctx, int first_slot)
+// ---- the batched path, whichever detector is configured: ORB (vo_batch_configure) or SIFT (vo_batch_configure_sift)
+struct Batch {
+    bool sift, ready;
+    int w, h, max_frames, max_pairs, kp_cap;
+    // the slots' resident results, as the pair stage reads them
+    const uint8_t *desc, *desc_x; const float* kp_xy; const int *kp_count, *flags, *norms;
+    int fp4;                              // operand image in desc_x (ORB: the one written at detection; SIFT: int8 rows + L2 norms)
+    // slot k's gray image at gray + k * gray_frame, rows of gray_stride bytes: level 0 of the ORB pyramid, or the SIFT slots' frames
+    uint8_t* gray; int gray_stride; size_t gray_frame;
+    uint8_t* gray_slot(int k) const { return gray + (size_t)k * gray_frame; }
+};
+
+static Batch batch(const vo_ctx* ctx)
 {
     if (ctx->detector == 1) {
-        const size_t fb = (size_t)ctx->sift.fstride * ctx->sift.h;
-        return {ctx->sift.frames + (size_t)first_slot * fb, ctx->sift.fstride, fb};
+        const SiftState& S = ctx->sift;
+        return {true, S.configured, S.w, S.h, S.max_frames, ctx->sift_pairs, S.kp_cap, S.desc, S.desc_x, S.kp_xy, S.kp_count, S.flags, S.norms, 0,
+                S.frames, S.fstride, (size_t)S.fstride * S.h};
     }
-    return {ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes + ctx->g.lv[0].off, ctx->g.lv[0].stride, (size_t)ctx->g.frame_bytes};
+    const PyrGeom& g = ctx->g;
+    return {false, ctx->configured, ctx->w, ctx->h, ctx->max_frames, ctx->max_pairs, g.kp_cap, ctx->ff.desc, ctx->desc_x, ctx->ff.kp_xy,
+            ctx->ff.kp_count, ctx->ff.flags, nullptr, ctx->descx_fp4, ctx->pyr + g.lv[0].off, g.lv[0].stride, (size_t)g.frame_bytes};
 }
+
 // cvtColor(BGR2GRAY) (or a copy of gray input) of n device frames into slots first_slot..
 static void gray_into_slots(vo_ctx* ctx, hipStream_t s, const uint8_t* src, int channels, int row_stride, int64_t frame_stride, int first_slot, int n)
 {
-    if (ctx->detector == 1) {
-        const GraySlots d = batch_gray_slots(ctx, first_slot);
-        launch_gray_plain(s, src, channels, row_stride, frame_stride, d.base, ctx->sift.w, ctx->sift.h, d.stride, (int64_t)d.frame, n);
-    } else launch_gray(s, src, channels, row_stride, frame_stride, ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes, ctx->g, n);
+    const Batch b = batch(ctx);
+    if (b.sift) launch_gray_plain(s, src, channels, row_stride, frame_stride, b.gray_slot(first_slot), b.w, b.h, b.gray_stride, (int64_t)b.gray_frame, n);
+    else launch_gray(s, src, channels, row_stride, frame_stride, ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes, ctx->g, n);
 }
 
 static int frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot)
 {
-    if (ctx->detector == 1) return sift_frames_upload_enqueue(ctx, frames, F, row_stride, frame_stride, first_slot);
-    if (!ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (!frames || F < 0 || first_slot < 0 || first_slot + F > ctx->max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (row_stride < ctx->w) FAIL(VO_ERR_INVALID, "row_stride < width");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    if (row_stride < b.w) FAIL(VO_ERR_INVALID, "row_stride < width");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
+    if (b.sift) return sift_frames_upload_enqueue(ctx, frames, F, row_stride, frame_stride, first_slot);
     const LevelGeom& lv = ctx->g.lv[0];
     uint8_t* dst0 = ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes + lv.off;
     if (row_stride == ctx->w && lv.stride == ctx->w && frame_stride >= (int64_t)ctx->w * ctx->h) {
@@ -587,9 +595,9 @@ static int frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int 
         // dense frames, padded level-0 rows (width not a multiple of 64, e.g. KITTI's 1241): ONE transfer of the dense bytes into
         // a staging buffer, then a kernel lays the rows out (a 2-D copy per frame runs at a fraction of the PCIe rate)
         const size_t per = (size_t)ctx->w * ctx->h;
-        int rc = ensure_bytes(ctx, &ctx->staging, &ctx->staging_bytes, per * F); if (rc) return rc;
-        HIPCHK(hipMemcpy2DAsync(ctx->staging, per, frames, (size_t)frame_stride, per, F, hipMemcpyHostToDevice, ctx->stream));
-        launch_gray(ctx->stream, ctx->staging, 1, ctx->w, (int64_t)per, ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes, ctx->g, F);
+        int rc = ctx->staging.grow(ctx, per * F); if (rc) return rc;
+        HIPCHK(hipMemcpy2DAsync(ctx->staging.p, per, frames, (size_t)frame_stride, per, F, hipMemcpyHostToDevice, ctx->stream));
+        launch_gray(ctx->stream, ctx->staging.p, 1, ctx->w, (int64_t)per, ctx->pyr + (size_t)first_slot * ctx->g.frame_bytes, ctx->g, F);
         HIPCHK(hipGetLastError());
         return VO_OK;
     }
@@ -622,10 +630,11 @@ extern "C" int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F,
 {
     if (!ctx) return VO_ERR_INVALID;
     if (channels == 1) return vo_frames_upload(ctx, frames, F, row_stride, frame_stride, first_slot);
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (channels != 3 && channels != 4) FAIL(VO_ERR_INVALID, "channels must be 1, 3 or 4");
-    if (!frames || F < 0 || first_slot < 0 || first_slot + F > batch_max_frames(ctx)) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (row_stride < batch_w(ctx) * channels || frame_stride < (int64_t)row_stride * batch_h(ctx)) FAIL(VO_ERR_INVALID, "strides too small");
+    if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    if (row_stride < b.w * channels || frame_stride < (int64_t)row_stride * b.h) FAIL(VO_ERR_INVALID, "strides too small");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t per = (size_t)frame_stride;
@@ -633,12 +642,12 @@ extern "C" int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F,
     // the chunks follow one another in stream order — the next chunk's copy waits for the previous chunk's conversion by
     // itself — and the call returns when the last conversion has finished
     const int chunk = F < 64 ? F : 64;
-    int rc = ensure_bytes(ctx, &ctx->staging, &ctx->staging_bytes, per * chunk); if (rc) return rc;
+    int rc = ctx->staging.grow(ctx, per * chunk); if (rc) return rc;
     for (int f0 = 0; f0 < F; f0 += chunk) {
         const int n = F - f0 < chunk ? F - f0 : chunk;
-        HIPCHK(hipMemcpyAsync(ctx->staging, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, ctx->stream));
         StageTimer t(ctx, ST_GRAY);
-        gray_into_slots(ctx, ctx->stream, ctx->staging, channels, row_stride, frame_stride, first_slot + f0, n);
+        gray_into_slots(ctx, ctx->stream, ctx->staging.p, channels, row_stride, frame_stride, first_slot + f0, n);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -669,14 +678,6 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
         for (int l = 1; l < g.nlevels; l++) launch_resize(s, pyr, g, l, ctx->tabs[l], F);
     }
     if (upto < 1) return VO_OK;
-    // fork: the blur of this detection on the side stream (per-stage timing keeps everything on one stream)
-    const bool side = ctx->stream_side != nullptr && !ctx->prof && upto >= 2 && F >= 8;
-    if (side) {
-        HIPCHK(hipEventRecord(ctx->ev_side[0], s));
-        HIPCHK(hipStreamWaitEvent(ctx->stream_side, ctx->ev_side[0], 0));
-        launch_blur(ctx->stream_side, pyr, blur, g, F);
-        HIPCHK(hipEventRecord(ctx->ev_side[1], ctx->stream_side));
-    }
     {
         StageTimer t(ctx, ST_MISC);
         HIPCHK(hipMemsetAsync(ff.hist, 0, (size_t)F * VO_MAX_LEVELS * 256 * sizeof(uint32_t), s));
@@ -704,8 +705,7 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
         launch_cv2_order(s, g, ff, cb, F, ctx->har_kept + fo * VO_MAX_LEVELS);
     }
     { StageTimer t(ctx, ST_ANGLE); launch_angle(s, pyr, g, ff, F); }
-    if (side) HIPCHK(hipStreamWaitEvent(s, ctx->ev_side[1], 0));
-    else { StageTimer t(ctx, ST_BLUR); launch_blur(s, pyr, blur, g, F); }
+    { StageTimer t(ctx, ST_BLUR); launch_blur(s, pyr, blur, g, F); }
     {
         StageTimer t(ctx, ST_BRIEF);
         const int cx = desc_x_rows(g.kp_cap);
@@ -717,8 +717,9 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
 
 extern "C" int vo_batch_kp_capacity(vo_ctx* ctx)
 {
-    if (ctx && ctx->detector == 1) return ctx->sift.configured ? ctx->sift.kp_cap : 0;
-    return ctx && ctx->configured ? ctx->g.kp_cap : 0;
+    if (!ctx) return 0;
+    const Batch b = batch(ctx);
+    return b.ready ? b.kp_cap : 0;
 }
 
 extern "C" int vo_host_alloc(size_t bytes, void** out)
@@ -733,23 +734,26 @@ extern "C" void vo_host_free(void* p)
     if (p) (void)hipHostFree(p);
 }
 
-extern "C" int vo_frames_detect_async(vo_ctx* ctx, int first_slot, int F)
+// the detection of slots first_slot .. first_slot + F - 1 with the configured detector, enqueued on the context's stream
+static int detect_enqueue(vo_ctx* ctx, int first_slot, int F)
 {
-    if (!ctx) return VO_ERR_INVALID;
-    if (ctx->detector == 1) {
-        int rc = sift_frames_detect_enqueue(ctx, first_slot, F);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(ctx->ev_det, ctx->stream));
-        ctx->ev_det_set = true;
-        return VO_OK;
-    }
-    if (!ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (F < 0 || first_slot < 0 || first_slot + F > ctx->max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (F == 0) return VO_OK;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
     HIPCHK(hipSetDevice(ctx->device));
+    if (F == 0) return VO_OK;
+    if (b.sift) return sift_frames_detect_enqueue(ctx, first_slot, F);
     int rc = run_detect(ctx, first_slot, F, 2);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
+    return VO_OK;
+}
+
+extern "C" int vo_frames_detect_async(vo_ctx* ctx, int first_slot, int F)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    int rc = detect_enqueue(ctx, first_slot, F);
+    if (rc) return rc;
     HIPCHK(hipEventRecord(ctx->ev_det, ctx->stream));
     ctx->ev_det_set = true;
     return VO_OK;
@@ -774,11 +778,10 @@ extern "C" int vo_detect_after(vo_ctx* ctx, vo_ctx* other)
 // right edge of the image are the ones lost, so a caller should know before it trusts the pose of such a pair.
 static int capacity_warning(vo_ctx* ctx, const int32_t* slots, int n, int first_slot, int F)
 {
-    const int* dflags = ctx->detector == 1 ? ctx->sift.flags : ctx->ff.flags;
-    const int mf = batch_max_frames(ctx);
-    if (!dflags || mf <= 0) return VO_OK;
-    std::vector<int> fl((size_t)mf);
-    HIPCHK(hipMemcpy(fl.data(), dflags, (size_t)mf * sizeof(int), hipMemcpyDeviceToHost));
+    const Batch b = batch(ctx);
+    if (!b.ready || b.max_frames <= 0) return VO_OK;
+    std::vector<int> fl((size_t)b.max_frames);
+    HIPCHK(hipMemcpy(fl.data(), b.flags, (size_t)b.max_frames * sizeof(int), hipMemcpyDeviceToHost));
     for (int i = 0; i < F; i++) if (fl[(size_t)first_slot + i] & 1) return VO_WARN_CAPACITY;
     for (int i = 0; i < n; i++) if (fl[(size_t)slots[i]] & 1) return VO_WARN_CAPACITY;
     return VO_OK;
@@ -787,20 +790,8 @@ static int capacity_warning(vo_ctx* ctx, const int32_t* slots, int n, int first_
 extern "C" int vo_frames_detect(vo_ctx* ctx, int first_slot, int F)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (ctx->detector == 1) {
-        int rc = sift_frames_detect_enqueue(ctx, first_slot, F);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->prof) prof_collect(ctx);
-        return capacity_warning(ctx, nullptr, 0, first_slot, F);
-    }
-    if (!ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (F < 0 || first_slot < 0 || first_slot + F > ctx->max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (F == 0) return VO_OK;
-    HIPCHK(hipSetDevice(ctx->device));
-    int rc = run_detect(ctx, first_slot, F, 2);
+    int rc = detect_enqueue(ctx, first_slot, F);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->prof) prof_collect(ctx);
     return capacity_warning(ctx, nullptr, 0, first_slot, F);
@@ -844,14 +835,9 @@ static int load_single(vo_ctx* ctx, const uint8_t* img, int h, int w, int channe
     if (rc) return rc;
     if (channels == 1) return vo_frames_upload(ctx, img, 1, row_stride, 0, 0);
     const size_t bytes = (size_t)row_stride * h;
-    if (bytes > ctx->staging_bytes) {
-        if (ctx->staging) (void)hipFree(ctx->staging);
-        ctx->staging = nullptr; ctx->staging_bytes = 0;
-        HIPCHK(hipMalloc((void**)&ctx->staging, bytes));
-        ctx->staging_bytes = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(ctx->staging, img, bytes, hipMemcpyHostToDevice, ctx->stream));
-    { StageTimer t(ctx, ST_GRAY); launch_gray(ctx->stream, ctx->staging, channels, row_stride, 0, ctx->pyr, ctx->g, 1); }
+    rc = ctx->staging.grow(ctx, bytes); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->staging.p, img, bytes, hipMemcpyHostToDevice, ctx->stream));
+    { StageTimer t(ctx, ST_GRAY); launch_gray(ctx->stream, ctx->staging.p, channels, row_stride, 0, ctx->pyr, ctx->g, 1); }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return VO_OK;
 }
@@ -944,8 +930,8 @@ extern "C" int vo_stage_blur(vo_ctx* ctx, const uint8_t* img, int h, int w, int 
 static int ensure_rng(vo_ctx* ctx, uint64_t seed)
 {
     if (ctx->rng_valid && ctx->rng_seed == seed) return VO_OK;
-    if (!ctx->rng_tab) HIPCHK(dmalloc(&ctx->rng_tab, RNG_TAB_N));
-    if (!ctx->rng_host) HIPCHK(hipHostMalloc((void**)&ctx->rng_host, RNG_TAB_N * sizeof(uint32_t), hipHostMallocDefault));
+    if (!ctx->rng_tab) HIPCHK(ctx->mem.alloc(&ctx->rng_tab, RNG_TAB_N));
+    if (!ctx->rng_host) HIPCHK(ctx->mem.alloc_pinned(&ctx->rng_host, RNG_TAB_N));
     // an earlier asynchronous batch may still be reading the table (and the host buffer may still be feeding the
     // previous copy): the rewrite is ordered on the ctx stream, behind both
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -959,10 +945,6 @@ static int ensure_rng(vo_ctx* ctx, uint64_t seed)
     ctx->rng_seed = seed; ctx->rng_valid = true;
     return VO_OK;
 }
-
-static int batch_cap(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift.kp_cap : ctx->g.kp_cap; }
-static bool batch_ready(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift.configured : ctx->configured; }
-static int batch_max_pairs(const vo_ctx* ctx) { return ctx->detector == 1 ? ctx->sift_pairs : ctx->max_pairs; }
 
 // vo_pair_opts.match_mode -> k_match_select mode.  BFMatcher(crossCheck=True) of OpenCV 4.x is the strict mutual
 // nearest neighbour (batchDistance compares the forward result too: `d < d0 && sidx[idx] == i`); the older
@@ -995,53 +977,43 @@ static int run_pairs(vo_ctx* ctx, PairBuf pb, const uint8_t* desc, const uint8_t
     { StageTimer t(ctx, ST_MATCH_SELECT); launch_match_select(s, kp_xy, kp_count, cap, pb, P, select_mode, ratio, ctx->dK, l2_norms ? 1 : 0); }
     if (!do_geometry) return VO_OK;
     { int rc = ensure_rng(ctx, rp.seed); if (rc) return rc; }
-    const bool hi = ctx->stream_hi != nullptr && P >= 16;     // the tail on the high-priority stream, fenced by two events
-    if (hi) {
-        HIPCHK(hipEventRecord(ctx->ev_tail[0], s));
-        HIPCHK(hipStreamWaitEvent(ctx->stream_hi, ctx->ev_tail[0], 0));
-        s = ctx->stream_hi; ctx->cur = s;
-    }
     { StageTimer t(ctx, ST_RANSAC); launch_ransac(s, pb, cap, P, rp, ctx->rng_tab, RNG_TAB_N); }
     { StageTimer t(ctx, ST_POSE); launch_pose(s, pb, cap, P, rp); }
     if (want_points) { StageTimer t(ctx, ST_TRIANGULATE); launch_triangulate_pairs(s, pb, cap, P, rp); }
-    if (hi) {
-        ctx->cur = nullptr;
-        HIPCHK(hipEventRecord(ctx->ev_tail[1], s));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_tail[1], 0));
-    }
     return VO_OK;
 }
 
 static int pairs_enqueue(vo_ctx* ctx, const int32_t* pair_slots, int B, const double* K, const vo_pair_opts* opts,
                          vo_pair_result* results, double* X, int32_t x_cap, bool* whole_x_out)
 {
-    const bool sift = ctx->detector == 1;
-    if (sift ? !ctx->sift.configured : !ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    const int max_pairs = sift ? ctx->sift_pairs : ctx->max_pairs, max_frames = sift ? ctx->sift.max_frames : ctx->max_frames;
-    if (!pair_slots || !K || !opts || !results || B < 0 || B > max_pairs) FAIL(VO_ERR_INVALID, "bad pair batch arguments");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (!pair_slots || !K || !opts || !results || B < 0 || B > b.max_pairs) FAIL(VO_ERR_INVALID, "bad pair batch arguments");
     if (opts->match_mode < 0 || opts->match_mode > 2) FAIL(VO_ERR_INVALID, "match_mode must be 0, 1 or 2");
     if (!(opts->ransac_prob > 0 && opts->ransac_prob < 1)) FAIL(VO_ERR_INVALID, "ransac_prob must be in (0, 1)");
     for (int i = 0; i < 2 * B; i++)
-        if (pair_slots[i] < 0 || pair_slots[i] >= max_frames) FAIL(VO_ERR_INVALID, "pair slot %d out of range", pair_slots[i]);
+        if (pair_slots[i] < 0 || pair_slots[i] >= b.max_frames) FAIL(VO_ERR_INVALID, "pair slot %d out of range", pair_slots[i]);
     *whole_x_out = false;
-    ctx->last_pairs = B;
-    ctx->last_slots.assign(pair_slots, pair_slots + 2 * (size_t)B);
-    ctx->last_points = opts->want_points != 0;
-    if (B == 0) return VO_OK;
+    clear_last_run(ctx);                                    // the pair buffers are about to be overwritten
+    const bool wp = opts->want_points != 0;
+    auto done = [&]() {
+        ctx->last.pairs = B;
+        ctx->last.slots.assign(pair_slots, pair_slots + 2 * (size_t)B);
+        ctx->last.points = wp;
+        return VO_OK;
+    };
+    if (B == 0) return done();
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const int cap = batch_cap(ctx);
+    const int cap = b.kp_cap;
     HIPCHK(hipMemcpyAsync(ctx->pb.slots, pair_slots, (size_t)B * 2 * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->dK, K, 9 * sizeof(double), hipMemcpyHostToDevice, s));
     RansacParams rp{};
     rp.prob = opts->ransac_prob; rp.thresh_px = opts->ransac_thresh; rp.max_iters = opts->ransac_max_iters;
     rp.seed = opts->ransac_seed; rp.dist_thresh = opts->pose_dist_thresh; rp.dk_early = ctx->dk_early;
     memcpy(rp.K, K, sizeof(rp.K));
-    const bool wp = opts->want_points != 0;
-    int rc = sift ? run_pairs(ctx, ctx->pb, ctx->sift.desc, ctx->sift.desc_x, ctx->sift.kp_xy, ctx->sift.kp_count, cap, B,
-                              map_select_mode(opts->match_mode), opts->ratio, rp, true, wp, 0, ctx->sift.norms)
-                  : run_pairs(ctx, ctx->pb, ctx->ff.desc, ctx->desc_x, ctx->ff.kp_xy, ctx->ff.kp_count, cap, B,
-                              map_select_mode(opts->match_mode), opts->ratio, rp, true, wp, ctx->descx_fp4);
+    int rc = run_pairs(ctx, ctx->pb, b.desc, b.desc_x, b.kp_xy, b.kp_count, cap, B, map_select_mode(opts->match_mode), opts->ratio, rp, true, wp,
+                       b.fp4, b.norms);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(results, ctx->pb.res, (size_t)B * sizeof(vo_pair_result), hipMemcpyDeviceToHost, s));
@@ -1049,8 +1021,7 @@ static int pairs_enqueue(vo_ctx* ctx, const int32_t* pair_slots, int B, const do
     if (X && wp && x_cap < 1) FAIL(VO_ERR_INVALID, "x_cap must be positive");
     if (whole_x) HIPCHK(hipMemcpyAsync(X, ctx->pb.X, (size_t)B * 4 * cap * sizeof(double), hipMemcpyDeviceToHost, s));
     *whole_x_out = whole_x;
-    ctx->last_pairs = B;
-    return VO_OK;
+    return done();
 }
 
 extern "C" int vo_pairs_run(vo_ctx* ctx, const int32_t* pair_slots, int B, const double* K, const vo_pair_opts* opts,
@@ -1062,7 +1033,7 @@ extern "C" int vo_pairs_run(vo_ctx* ctx, const int32_t* pair_slots, int B, const
     if (rc || B == 0) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->prof) prof_collect(ctx);
-    const int cap = batch_cap(ctx);
+    const int cap = batch(ctx).kp_cap;
     if (X && opts->want_points && !whole_x) {
         for (int p = 0; p < B; p++) {
             const int n = results[p].status == VO_OK ? (results[p].n_inl < x_cap ? results[p].n_inl : x_cap) : 0;
@@ -1082,7 +1053,8 @@ extern "C" int vo_pairs_run_async(vo_ctx* ctx, const int32_t* pair_slots, int B,
                                   vo_pair_result* results, double* X, int32_t x_cap)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (X && opts && opts->want_points && batch_ready(ctx) && x_cap != batch_cap(ctx))
+    const Batch b = batch(ctx);
+    if (X && opts && opts->want_points && b.ready && x_cap != b.kp_cap)
         FAIL(VO_ERR_INVALID, "vo_pairs_run_async needs x_cap == vo_batch_kp_capacity()");
     bool whole_x = false;
     return pairs_enqueue(ctx, pair_slots, B, K, opts, results, X, x_cap, &whole_x);
@@ -1101,15 +1073,16 @@ extern "C" int vo_pair_matches(vo_ctx* ctx, int pair, int32_t* qidx, int32_t* ti
                                int cap, int32_t* n_out)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (pair < 0 || pair >= ctx->last_pairs || !n_out) FAIL(VO_ERR_INVALID, "bad pair index");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (pair < 0 || pair >= ctx->last.pairs || !n_out) FAIL(VO_ERR_INVALID, "bad pair index");
     HIPCHK(hipSetDevice(ctx->device));
     int n = 0;
     HIPCHK(hipStreamSynchronize(ctx->stream));              // an asynchronous batch may still be running
     HIPCHK(hipMemcpy(&n, ctx->pb.m_count + pair, sizeof(int), hipMemcpyDeviceToHost));
     if (n > cap) n = cap;
     *n_out = n;
-    const size_t o = (size_t)pair * batch_cap(ctx);
+    const size_t o = (size_t)pair * b.kp_cap;
     if (n > 0) {
         if (qidx) HIPCHK(hipMemcpy(qidx, ctx->pb.m_q + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
         if (tidx) HIPCHK(hipMemcpy(tidx, ctx->pb.m_t + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
@@ -1210,32 +1183,26 @@ static int comm_bracket_end(vo_ctx* ctx)
 extern "C" int vo_pairs_gather(vo_ctx* ctx, int B, double* gathered, int wait)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (B < 0 || B > batch_max_pairs(ctx) || !gathered) FAIL(VO_ERR_INVALID, "bad gather arguments");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (B < 0 || B > b.max_pairs || !gathered) FAIL(VO_ERR_INVALID, "bad gather arguments");
     if (B == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const int world = ctx->cs ? ctx->cs->world : 1;
-    const size_t n = (size_t)B * VO_RECORD_DOUBLES;
-    if (n * world > ctx->rec_cap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->rec_send) (void)hipFree(ctx->rec_send);
-        if (ctx->rec_recv) (void)hipFree(ctx->rec_recv);
-        ctx->rec_send = ctx->rec_recv = nullptr; ctx->rec_cap = 0;
-        HIPCHK(dmalloc(&ctx->rec_send, (size_t)batch_max_pairs(ctx) * VO_RECORD_DOUBLES));
-        HIPCHK(dmalloc(&ctx->rec_recv, (size_t)batch_max_pairs(ctx) * VO_RECORD_DOUBLES * world));
-        ctx->rec_cap = (size_t)batch_max_pairs(ctx) * VO_RECORD_DOUBLES * world;
-    }
+    const size_t n = (size_t)B * VO_RECORD_DOUBLES, mp = (size_t)b.max_pairs * VO_RECORD_DOUBLES;
+    int rc = ctx->rec_send.grow(ctx, n, mp); if (rc) return rc;
+    rc = ctx->rec_recv.grow(ctx, n * world, mp * world); if (rc) return rc;
     hipStream_t s = ctx->stream;
     StageTimer t(ctx, ST_GATHER);
-    launch_pack_records(s, ctx->pb.res, B, ctx->last_pairs, ctx->rec_send);
+    launch_pack_records(s, ctx->pb.res, B, ctx->last.pairs, ctx->rec_send.p);      // pairs past the last run: VO_ERR_NOT_CONFIGURED
     HIPCHK(hipGetLastError());
-    const double* src = ctx->rec_send;
+    const double* src = ctx->rec_send.p;
     if (ctx->cs) {
-        int rc = comm_bracket_begin(ctx); if (rc) return rc;
-        const char* e = rccl_all_gather_f64(ctx->cs->comm, ctx->rec_send, ctx->rec_recv, n, s);
+        rc = comm_bracket_begin(ctx); if (rc) return rc;
+        const char* e = rccl_all_gather_f64(ctx->cs->comm, ctx->rec_send.p, ctx->rec_recv.p, n, s);
         if (e) FAIL(VO_ERR_HIP, "ncclAllGather failed: %s", e);
         rc = comm_bracket_end(ctx); if (rc) return rc;
-        src = ctx->rec_recv;
+        src = ctx->rec_recv.p;
     }
     HIPCHK(hipMemcpyAsync(gathered, src, n * world * sizeof(double), hipMemcpyDeviceToHost, s));
     if (wait) HIPCHK(hipStreamSynchronize(s));
@@ -1253,12 +1220,12 @@ extern "C" int vo_comm_allgather_f64(vo_ctx* ctx, const double* send, int n, dou
     if (!ctx->cs) { memcpy(recv, send, (size_t)n * sizeof(double)); return VO_OK; }
     int rc = ensure_raw_d(ctx, (size_t)n * (world + 1)); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(ctx->raw_d, send, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->raw_d.p, send, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
     rc = comm_bracket_begin(ctx); if (rc) return rc;
-    const char* e = rccl_all_gather_f64(ctx->cs->comm, ctx->raw_d, ctx->raw_d + n, (size_t)n, s);
+    const char* e = rccl_all_gather_f64(ctx->cs->comm, ctx->raw_d.p, ctx->raw_d.p + n, (size_t)n, s);
     if (e) FAIL(VO_ERR_HIP, "ncclAllGather failed: %s", e);
     rc = comm_bracket_end(ctx); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(recv, ctx->raw_d + n, (size_t)n * world * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(recv, ctx->raw_d.p + n, (size_t)n * world * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VO_OK;
 }
@@ -1269,16 +1236,15 @@ static int ensure_raw(vo_ctx* ctx, int cap)
     if (cap <= ctx->raw_cap) return VO_OK;
     cap = align_up(cap + cap / 4 + 64, 64);
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    free_pairbuf(ctx->raw_pb);
-    void* ptrs[] = {ctx->raw_desc, ctx->raw_xy, ctx->raw_count, ctx->raw_desc_x};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    ctx->raw_desc = nullptr; ctx->raw_xy = nullptr; ctx->raw_count = nullptr; ctx->raw_desc_x = nullptr; ctx->raw_cap = 0;
-    HIPCHK(dmalloc(&ctx->raw_desc, (size_t)2 * cap * 32));
-    HIPCHK(dmalloc(&ctx->raw_desc_x, (size_t)2 * desc_x_rows(cap) * 256));
-    HIPCHK(dmalloc(&ctx->raw_xy, (size_t)2 * cap * 2));
-    HIPCHK(dmalloc(&ctx->raw_count, 2));
+    DevList& m = ctx->raw_mem;
+    m.release();
+    ctx->raw_cap = 0;
+    HIPCHK(m.alloc(&ctx->raw_desc, (size_t)2 * cap * 32));
+    HIPCHK(m.alloc(&ctx->raw_desc_x, (size_t)2 * desc_x_rows(cap) * 256));
+    HIPCHK(m.alloc(&ctx->raw_xy, (size_t)2 * cap * 2));
+    HIPCHK(m.alloc(&ctx->raw_count, 2));
     HIPCHK(hipMemsetAsync(ctx->raw_xy, 0, (size_t)2 * cap * 2 * sizeof(float), ctx->stream));
-    HIPCHK(alloc_pairbuf(ctx->raw_pb, 1, cap, true));
+    HIPCHK(alloc_pairbuf(m, ctx->raw_pb, 1, cap, true));
     ctx->raw_cap = cap;
     return VO_OK;
 }
@@ -1347,10 +1313,10 @@ extern "C" int vo_match_l2(vo_ctx* ctx, const float* q, int nq, const float* t, 
     int rc = ensure_raw_d(ctx, (nf + ni) / 2 + 64 + (size_t)(nq + nt));
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    float* dq = (float*)ctx->raw_d; float* dt = dq + (size_t)nq * dim;
+    float* dq = (float*)ctx->raw_d.p; float* dt = dq + (size_t)nq * dim;
     int* fi = (int*)(dt + (size_t)nt * dim); int* ri = fi + nq;
     float* fd = (float*)(ri + nt); float* rd = fd + nq;
-    unsigned long long* fkey = (unsigned long long*)((double*)ctx->raw_d + (nf + ni) / 2 + 32); unsigned long long* rkey = fkey + nq;
+    unsigned long long* fkey = (unsigned long long*)((double*)ctx->raw_d.p + (nf + ni) / 2 + 32); unsigned long long* rkey = fkey + nq;
     HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dt, t, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice, s));
     {
@@ -1442,9 +1408,9 @@ extern "C" int vo_knn2_l2(vo_ctx* ctx, const float* q, int nq, const float* t, i
     int rc = ensure_raw_d(ctx, (nf + no) / 2 + 64 + nk);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    float* dq = (float*)ctx->raw_d; float* dt = dq + (size_t)nq * dim;
+    float* dq = (float*)ctx->raw_d.p; float* dt = dq + (size_t)nq * dim;
     int* di = (int*)(dt + (size_t)nt * dim); float* dd = (float*)(di + 2 * nq);
-    unsigned long long* part = (unsigned long long*)((double*)ctx->raw_d + (nf + no) / 2 + 32);
+    unsigned long long* part = (unsigned long long*)((double*)ctx->raw_d.p + (nf + no) / 2 + 32);
     HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dt, t, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice, s));
     { StageTimer tm(ctx, ST_MATCH_NN); launch_nn_l2_knn2(s, dq, nq, dt, nt, dim, di, dd, part); }
@@ -1564,18 +1530,6 @@ extern "C" int vo_recover_pose(vo_ctx* ctx, const double* E, const double* p1, c
     return VO_OK;
 }
 
-static int ensure_raw_d(vo_ctx* ctx, size_t n)
-{
-    if (n <= ctx->raw_d_n) return VO_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (ctx->raw_d) (void)hipFree(ctx->raw_d);
-    ctx->raw_d = nullptr; ctx->raw_d_n = 0;
-    HIPCHK(dmalloc(&ctx->raw_d, n + n / 4 + 64));
-    ctx->raw_d_n = n + n / 4 + 64;
-    if (!ctx->raw_i) HIPCHK(dmalloc(&ctx->raw_i, 16));
-    return VO_OK;
-}
-
 extern "C" int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, const double* x1, const double* x2,
                               int M, double* X)
 {
@@ -1586,7 +1540,7 @@ extern "C" int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, c
     int rc = ensure_raw_d(ctx, 24 + (size_t)8 * M);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d;
+    double* d = ctx->raw_d.p;
     double *dP1 = d, *dP2 = d + 12, *dx1 = d + 24, *dx2 = dx1 + 2 * (size_t)M, *dX = dx2 + 2 * (size_t)M;
     HIPCHK(hipMemcpyAsync(dP1, P1, 12 * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dP2, P2, 12 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1608,7 +1562,7 @@ extern "C" int vo_stage_five_point(vo_ctx* ctx, const double* x1, const double* 
     int rc = ensure_raw_d(ctx, 128);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d;
+    double* d = ctx->raw_d.p;
     HIPCHK(hipMemcpyAsync(d, x1, 10 * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d + 10, x2, 10 * sizeof(double), hipMemcpyHostToDevice, s));
     launch_five_point_raw(s, d, d + 10, d + 20, ctx->raw_i, ctx->dk_early);
@@ -1633,7 +1587,7 @@ extern "C" int vo_stage_retain_best(vo_ctx* ctx, const float* response, int n, i
     int rc = ensure_raw_d(ctx, (size_t)3 * n + 64);                 // floats + uint2 work + lpos + rpos + order, in doubles
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    uint2* work = (uint2*)ctx->raw_d;
+    uint2* work = (uint2*)ctx->raw_d.p;
     float* dresp = (float*)(work + n);
     uint32_t* lpos = (uint32_t*)(dresp + n); uint32_t* rpos = lpos + n;
     int* dorder = (int*)(rpos + n); int* dn = dorder + n;
@@ -1663,7 +1617,7 @@ extern "C" int vo_reprojection_filter(vo_ctx* ctx, const double* poses, int ncam
     int rc = ensure_raw_d(ctx, nd + ni / 2 + nobs / 8 + 64);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d;
+    double* d = ctx->raw_d.p;
     double *dposes = d, *dpoints = dposes + (size_t)16 * ncam, *dxy = dpoints + (size_t)3 * npt, *dK = dxy + (size_t)2 * nobs;
     double* derr = dK + 16;
     int* dcam = (int*)(derr + nobs + 8); int* dpt = dcam + nobs; int* dbad = dpt + nobs;
@@ -1704,7 +1658,7 @@ extern "C" int vo_solve_pnp_ransac_batch(vo_ctx* ctx, const double* obj, const d
     const size_t nd = (size_t)5 * total + 9 + (size_t)6 * B, ni = (size_t)3 * B + 1;
     rc = ensure_raw_d(ctx, nd + (ni + 1) / 2 + (size_t)(total + 7) / 8 + 8); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* dobj = ctx->raw_d; double* dimg = dobj + (size_t)3 * total; double* dK = dimg + (size_t)2 * total;
+    double* dobj = ctx->raw_d.p; double* dimg = dobj + (size_t)3 * total; double* dK = dimg + (size_t)2 * total;
     double* drv = dK + 9; double* dtv = drv + (size_t)3 * B;
     int* doff = (int*)(dtv + (size_t)3 * B); int* dninl = doff + B + 1; int* dst = dninl + B;
     uint8_t* dmask = (uint8_t*)(dst + B + ((3 * B + 1) & 1));
@@ -1756,10 +1710,10 @@ extern "C" int vo_rodrigues(vo_ctx* ctx, const double* in, int in_is_matrix, dou
     HIPCHK(hipSetDevice(ctx->device));
     int rc = ensure_raw_d(ctx, 32); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(ctx->raw_d, in, (in_is_matrix ? 9 : 3) * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_rodrigues(s, ctx->raw_d, in_is_matrix, ctx->raw_d + 16);
+    HIPCHK(hipMemcpyAsync(ctx->raw_d.p, in, (in_is_matrix ? 9 : 3) * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_rodrigues(s, ctx->raw_d.p, in_is_matrix, ctx->raw_d.p + 16);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, ctx->raw_d + 16, (in_is_matrix ? 3 : 9) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, ctx->raw_d.p + 16, (in_is_matrix ? 3 : 9) * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VO_OK;
 }
@@ -1785,34 +1739,18 @@ static void linear_tab(int ssize, int dsize, bool clamp_weight, int* ofs, short*
     }
 }
 
-static int ensure_bytes(vo_ctx* ctx, uint8_t** p, size_t* have, size_t need)
-{
-    if (need <= *have) return VO_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIPCHK(hipMalloc((void**)p, need));
-    *have = need;
-    return VO_OK;
-}
-
 // device tables for (sw, sh) -> (dw, dh): [xofs dw][xa dw pairs][yofs dh][yb dh pairs] as ints
 static int ingest_tables(vo_ctx* ctx, int sw, int sh, int dw, int dh, const int** xofs, const void** xa, const int** yofs, const void** yb)
 {
     const size_t n = (size_t)2 * (dw + dh);
-    if (n > ctx->ingest_tab_n) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->ingest_tab) (void)hipFree(ctx->ingest_tab);
-        ctx->ingest_tab = nullptr; ctx->ingest_tab_n = 0;
-        HIPCHK(dmalloc(&ctx->ingest_tab, n));
-        ctx->ingest_tab_n = n;
-    }
+    int rc = ctx->ingest_tab.grow(ctx, n); if (rc) return rc;
+    int* d = ctx->ingest_tab.p;
     std::vector<int> host(n);
     linear_tab(sw, dw, true, host.data(), (short*)(host.data() + dw));
     linear_tab(sh, dh, false, host.data() + 2 * dw, (short*)(host.data() + 2 * dw + dh));
-    HIPCHK(hipMemcpyAsync(ctx->ingest_tab, host.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d, host.data(), n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));                       // `host` is a stack vector
-    *xofs = ctx->ingest_tab; *xa = ctx->ingest_tab + dw; *yofs = ctx->ingest_tab + 2 * dw; *yb = ctx->ingest_tab + 2 * dw + dh;
+    *xofs = d; *xa = d + dw; *yofs = d + 2 * dw; *yb = d + 2 * dw + dh;
     return VO_OK;
 }
 
@@ -1824,16 +1762,16 @@ extern "C" int vo_resize_linear(vo_ctx* ctx, const uint8_t* src, int sh, int sw,
         row_stride < sw * channels || dst_stride < dw * channels) FAIL(VO_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t sbytes = (size_t)row_stride * sh, dbytes = (size_t)dst_stride * dh;
-    int rc = ensure_bytes(ctx, &ctx->staging, &ctx->staging_bytes, sbytes); if (rc) return rc;
-    rc = ensure_bytes(ctx, &ctx->ingest_out, &ctx->ingest_out_bytes, dbytes); if (rc) return rc;
+    int rc = ctx->staging.grow(ctx, sbytes); if (rc) return rc;
+    rc = ctx->ingest_out.grow(ctx, dbytes); if (rc) return rc;
     const int* xofs; const void* xa; const int* yofs; const void* yb;
     rc = ingest_tables(ctx, sw, sh, dw, dh, &xofs, &xa, &yofs, &yb); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(ctx->staging, src, sbytes, hipMemcpyHostToDevice, s));
-    { StageTimer t(ctx, ST_MISC); launch_resize_linear(s, ctx->staging, sw, sh, channels, row_stride, 0, ctx->ingest_out, dw, dh, dst_stride, 0,
+    HIPCHK(hipMemcpyAsync(ctx->staging.p, src, sbytes, hipMemcpyHostToDevice, s));
+    { StageTimer t(ctx, ST_MISC); launch_resize_linear(s, ctx->staging.p, sw, sh, channels, row_stride, 0, ctx->ingest_out.p, dw, dh, dst_stride, 0,
                                                        xofs, xa, yofs, yb, sw == 2 * dw && sh == 2 * dh, 1); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out, dbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out.p, dbytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
     return VO_OK;
@@ -1870,8 +1808,8 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
     if (dw > sw || dh > sh) FAIL(VO_ERR_UNSUPPORTED, "INTER_AREA enlargement (a bilinear variant in OpenCV) is not built");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t sbytes = (size_t)row_stride * sh, dbytes = (size_t)dst_stride * dh;
-    int rc = ensure_bytes(ctx, &ctx->staging, &ctx->staging_bytes, sbytes); if (rc) return rc;
-    rc = ensure_bytes(ctx, &ctx->ingest_out, &ctx->ingest_out_bytes, dbytes); if (rc) return rc;
+    int rc = ctx->staging.grow(ctx, sbytes); if (rc) return rc;
+    rc = ctx->ingest_out.grow(ctx, dbytes); if (rc) return rc;
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);     // as resize() forms them
     const int isx = (int)lrint(scale_x), isy = (int)lrint(scale_y);
     const bool fast = fabs(scale_x - isx) < DBL_EPSILON && fabs(scale_y - isy) < DBL_EPSILON;
@@ -1881,14 +1819,8 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
     if (!fast) {
         const int nx = area_tab(sw, dw, scale_x, hxs, hxa, hxst), ny = area_tab(sh, dh, scale_y, hys, hya, hyst);
         const size_t n = (size_t)2 * nx + 2 * ny + dw + dh + 2;
-        if (n > ctx->ingest_tab_n) {
-            HIPCHK(hipStreamSynchronize(s));
-            if (ctx->ingest_tab) (void)hipFree(ctx->ingest_tab);
-            ctx->ingest_tab = nullptr; ctx->ingest_tab_n = 0;
-            HIPCHK(dmalloc(&ctx->ingest_tab, n));
-            ctx->ingest_tab_n = n;
-        }
-        int* d = ctx->ingest_tab;
+        rc = ctx->ingest_tab.grow(ctx, n); if (rc) return rc;
+        int* d = ctx->ingest_tab.p;
         int* dxs = d; float* dxa = (float*)(d + nx); int* dxst = d + 2 * nx;
         int* dys = dxst + dw + 1; float* dya = (float*)(dys + ny); int* dyst = dys + 2 * ny;
         HIPCHK(hipMemcpyAsync(dxs, hxs.data(), (size_t)nx * 4, hipMemcpyHostToDevice, s));
@@ -1899,11 +1831,11 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
         HIPCHK(hipMemcpyAsync(dyst, hyst.data(), (size_t)(dh + 1) * 4, hipMemcpyHostToDevice, s));
         xsi = dxs; xal = dxa; xst = dxst; ysi = dys; yal = dya; yst = dyst;
     }
-    HIPCHK(hipMemcpyAsync(ctx->staging, src, sbytes, hipMemcpyHostToDevice, s));
-    { StageTimer t(ctx, ST_MISC); launch_resize_area(s, ctx->staging, channels, row_stride, ctx->ingest_out, dw, dh, dst_stride,
+    HIPCHK(hipMemcpyAsync(ctx->staging.p, src, sbytes, hipMemcpyHostToDevice, s));
+    { StageTimer t(ctx, ST_MISC); launch_resize_area(s, ctx->staging.p, channels, row_stride, ctx->ingest_out.p, dw, dh, dst_stride,
                                                      fast ? isx : 0, fast ? isy : 0, xsi, xal, xst, ysi, yal, yst); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out, dbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out.p, dbytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));                                 // also keeps the host tables alive until copied
     if (ctx->prof) prof_collect(ctx);
     return VO_OK;
@@ -1913,7 +1845,8 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
 static int ingest_from_device(vo_ctx* ctx, const uint8_t* src, int n, int sh, int sw, int channels, int row_stride, int64_t frame_stride,
                               int first_slot, uint8_t* resized_out)
 {
-    const int dw = batch_w(ctx), dh = batch_h(ctx);
+    const Batch b = batch(ctx);
+    const int dw = b.w, dh = b.h;
     const size_t dper = (size_t)dw * dh * channels;
     hipStream_t s = ctx->stream;
     if (sw == dw && sh == dh && (!resized_out || (row_stride == dw * channels && frame_stride == (int64_t)dper))) {
@@ -1924,23 +1857,22 @@ static int ingest_from_device(vo_ctx* ctx, const uint8_t* src, int n, int sh, in
         HIPCHK(hipStreamSynchronize(s));
         return VO_OK;
     }
-    int rc = ensure_bytes(ctx, &ctx->ingest_out, &ctx->ingest_out_bytes, dper * n); if (rc) return rc;
+    int rc = ctx->ingest_out.grow(ctx, dper * n); if (rc) return rc;
     const int* xofs; const void* xa; const int* yofs; const void* yb;
     rc = ingest_tables(ctx, sw, sh, dw, dh, &xofs, &xa, &yofs, &yb); if (rc) return rc;
-    const GraySlots g0 = batch_gray_slots(ctx, first_slot);
     {
         StageTimer t(ctx, ST_MISC);
         if (channels == 1 && !resized_out)                   // gray input: straight into the slots' gray frames
-            launch_resize_linear(s, src, sw, sh, 1, row_stride, frame_stride, g0.base, dw, dh, g0.stride, (int64_t)g0.frame,
+            launch_resize_linear(s, src, sw, sh, 1, row_stride, frame_stride, b.gray_slot(first_slot), dw, dh, b.gray_stride, (int64_t)b.gray_frame,
                                  xofs, xa, yofs, yb, sw == 2 * dw && sh == 2 * dh, n);
         else
-            launch_resize_linear(s, src, sw, sh, channels, row_stride, frame_stride, ctx->ingest_out, dw, dh, dw * channels,
+            launch_resize_linear(s, src, sw, sh, channels, row_stride, frame_stride, ctx->ingest_out.p, dw, dh, dw * channels,
                                  (int64_t)dper, xofs, xa, yofs, yb, sw == 2 * dw && sh == 2 * dh, n);
     }
     if (!(channels == 1 && !resized_out)) {
         StageTimer t(ctx, ST_GRAY);
-        gray_into_slots(ctx, s, ctx->ingest_out, channels, dw * channels, (int64_t)dper, first_slot, n);
-        if (resized_out) HIPCHK(hipMemcpyAsync(resized_out, ctx->ingest_out, dper * n, hipMemcpyDeviceToHost, s));
+        gray_into_slots(ctx, s, ctx->ingest_out.p, channels, dw * channels, (int64_t)dper, first_slot, n);
+        if (resized_out) HIPCHK(hipMemcpyAsync(resized_out, ctx->ingest_out.p, dper * n, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
@@ -1954,21 +1886,21 @@ extern "C" int vo_frames_ingest(vo_ctx* ctx, const uint8_t* frames, int F, int s
                                 int64_t frame_stride, int first_slot, uint8_t* resized_out)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (!frames || F < 0 || first_slot < 0 || first_slot + F > batch_max_frames(ctx)) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
     if (sh < 1 || sw < 1 || (channels != 1 && channels != 3 && channels != 4) || row_stride < sw * channels ||
         frame_stride < (int64_t)row_stride * sh) FAIL(VO_ERR_INVALID, "bad source geometry");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    const int dw = batch_w(ctx), dh = batch_h(ctx);
-    const size_t per = (size_t)frame_stride, dper = (size_t)dw * dh * channels;
+    const size_t per = (size_t)frame_stride, dper = (size_t)b.w * b.h * channels;
     size_t chunk = (size_t)512 * 1024 * 1024 / per; if (chunk < 1) chunk = 1; if (chunk > (size_t)F) chunk = F;
-    int rc = ensure_bytes(ctx, &ctx->staging, &ctx->staging_bytes, per * chunk); if (rc) return rc;
+    int rc = ctx->staging.grow(ctx, per * chunk); if (rc) return rc;
     hipStream_t s = ctx->stream;
     for (int f0 = 0; f0 < F; f0 += (int)chunk) {
         const int n = F - f0 < (int)chunk ? F - f0 : (int)chunk;
-        HIPCHK(hipMemcpyAsync(ctx->staging, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, s));
-        rc = ingest_from_device(ctx, ctx->staging, n, sh, sw, channels, row_stride, (int64_t)per, first_slot + f0,
+        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, s));
+        rc = ingest_from_device(ctx, ctx->staging.p, n, sh, sw, channels, row_stride, (int64_t)per, first_slot + f0,
                                 resized_out ? resized_out + (size_t)f0 * dper : nullptr);
         if (rc) return rc;
     }
@@ -1991,14 +1923,6 @@ static int sift_gauss_taps(double sigma, float* k)
     return n;
 }
 
-static void sift_free(SiftState& S)
-{
-    void* ptrs[] = {S.frames, S.kp_xy, S.kp_size, S.kp_angle, S.kp_resp, S.kp_oct, S.kp_count, S.flags, S.desc, S.desc_x, S.norms,
-                    S.G, S.up, S.cand, S.surv, S.kraw, S.ksorted, S.kfin, S.rank, S.counts, S.fin_count, S.fin_flags};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    S = SiftState();
-}
-
 // Buffers of one SIFT configuration: the per-slot results (keypoints, descriptors, matcher operands) for max_frames slots and
 // the scale-space scratch of one sub-batch of `fb` frames.
 static int sift_setup(vo_ctx* ctx, SiftState& S, int h, int w, const vo_sift_params* p, int max_frames, int kp_cap, int raw_cap, int cand_cap,
@@ -2010,7 +1934,7 @@ static int sift_setup(vo_ctx* ctx, SiftState& S, int h, int w, const vo_sift_par
         S.raw_cap == raw_cap && S.cand_cap == cand_cap && S.surv_cap == surv_cap && S.fb >= fb && S.with_operands == with_operands)
         return VO_OK;
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    sift_free(S);
+    S = SiftState();                                           // frees the previous configuration's buffers
     S.h = h; S.w = w; S.prm = *p; S.max_frames = max_frames; S.kp_cap = kp_cap; S.raw_cap = raw_cap; S.cand_cap = cand_cap; S.surv_cap = surv_cap;
     S.fb = fb; S.with_operands = with_operands; S.cap_x = desc_x_rows(kp_cap);
     S.fstride = w;                                             // dense rows: a batch of frames is one transfer (the first sweep's loader reads bytes)
@@ -2043,20 +1967,21 @@ static int sift_setup(vo_ctx* ctx, SiftState& S, int h, int w, const vo_sift_par
     }
     for (int i = 0; i < 64; i++) S.E.tab[i] = (float)pow(2.0, i / 64.0);
     const size_t F = (size_t)max_frames, B = (size_t)fb;
-    HIPCHK(dmalloc(&S.frames, F * S.fstride * h + 64));
-    HIPCHK(dmalloc(&S.kp_xy, F * kp_cap * 2)); HIPCHK(dmalloc(&S.kp_size, F * kp_cap)); HIPCHK(dmalloc(&S.kp_angle, F * kp_cap));
-    HIPCHK(dmalloc(&S.kp_resp, F * kp_cap)); HIPCHK(dmalloc(&S.kp_oct, F * kp_cap));
-    HIPCHK(dmalloc(&S.kp_count, F)); HIPCHK(dmalloc(&S.flags, F));
+    DevList& m = S.mem;
+    HIPCHK(m.alloc(&S.frames, F * S.fstride * h + 64));
+    HIPCHK(m.alloc(&S.kp_xy, F * kp_cap * 2)); HIPCHK(m.alloc(&S.kp_size, F * kp_cap)); HIPCHK(m.alloc(&S.kp_angle, F * kp_cap));
+    HIPCHK(m.alloc(&S.kp_resp, F * kp_cap)); HIPCHK(m.alloc(&S.kp_oct, F * kp_cap));
+    HIPCHK(m.alloc(&S.kp_count, F)); HIPCHK(m.alloc(&S.flags, F));
     HIPCHK(hipMemset(S.kp_count, 0, F * sizeof(int))); HIPCHK(hipMemset(S.flags, 0, F * sizeof(int)));
-    HIPCHK(dmalloc(&S.desc, F * kp_cap * 128));
+    HIPCHK(m.alloc(&S.desc, F * kp_cap * 128));
     if (with_operands) {
-        HIPCHK(dmalloc(&S.desc_x, F * (size_t)S.cap_x * 128)); HIPCHK(dmalloc(&S.norms, F * (size_t)S.cap_x));
+        HIPCHK(m.alloc(&S.desc_x, F * (size_t)S.cap_x * 128)); HIPCHK(m.alloc(&S.norms, F * (size_t)S.cap_x));
         HIPCHK(hipMemset(S.desc_x, 0, F * (size_t)S.cap_x * 128)); HIPCHK(hipMemset(S.norms, 0, F * (size_t)S.cap_x * sizeof(int)));
     }
-    HIPCHK(dmalloc(&S.G, B * gtot));                                       // (the up-sampled base image is never stored: S.up stays null)
-    HIPCHK(dmalloc(&S.cand, B * cand_cap)); HIPCHK(dmalloc(&S.surv, B * surv_cap));
-    HIPCHK(dmalloc(&S.kraw, B * raw_cap)); HIPCHK(dmalloc(&S.ksorted, B * raw_cap)); HIPCHK(dmalloc(&S.kfin, B * kp_cap));
-    HIPCHK(dmalloc(&S.rank, B * 4097)); HIPCHK(dmalloc(&S.counts, B * 4)); HIPCHK(dmalloc(&S.fin_count, B)); HIPCHK(dmalloc(&S.fin_flags, B));
+    HIPCHK(m.alloc(&S.G, B * gtot));                                       // (the up-sampled base image is never stored: S.up stays null)
+    HIPCHK(m.alloc(&S.cand, B * cand_cap)); HIPCHK(m.alloc(&S.surv, B * surv_cap));
+    HIPCHK(m.alloc(&S.kraw, B * raw_cap)); HIPCHK(m.alloc(&S.ksorted, B * raw_cap)); HIPCHK(m.alloc(&S.kfin, B * kp_cap));
+    HIPCHK(m.alloc(&S.rank, B * 4097)); HIPCHK(m.alloc(&S.counts, B * 4)); HIPCHK(m.alloc(&S.fin_count, B)); HIPCHK(m.alloc(&S.fin_flags, B));
     HIPCHK(hipDeviceSynchronize());
     S.configured = true;
     return VO_OK;
@@ -2143,9 +2068,9 @@ extern "C" int vo_sift_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     const size_t img_bytes = (size_t)row_stride * h;
-    rc = ensure_bytes(ctx, &ctx->sift_img, &ctx->sift_img_n, img_bytes); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->sift_img, img, img_bytes, hipMemcpyHostToDevice, s));
-    rc = sift_detect_enqueue(ctx, S, ctx->sift_img, channels, row_stride, 0, 1); if (rc) return rc;
+    rc = ctx->sift_img.grow(ctx, img_bytes); if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->sift_img.p, img, img_bytes, hipMemcpyHostToDevice, s));
+    rc = sift_detect_enqueue(ctx, S, ctx->sift_img.p, channels, row_stride, 0, 1); if (rc) return rc;
     int counts[4] = {0, 0, 0, 0}, fin = 0, fl = 0;
     HIPCHK(hipMemcpyAsync(counts, S.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&fin, S.fin_count, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2206,6 +2131,7 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     if (kp_cap > 65536) FAIL(VO_ERR_INVALID, "kp_cap > 65536");
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    clear_last_run(ctx);                                        // the pair buffers may be replaced below
     // frames per launch chain: the small octaves' launches are latency-bound (a dependent chain of ~50 launches per sub-batch)
     // and the wave-per-keypoint kernels like long grids, so the more frames share a chain the better (1280 x 720, pairs/s with
     // 64 / 96 / 128 / 192 / 256 frames: 4.59 / 4.68 / 4.79 / 4.94 / 4.94 k): up to 192 frames, within 48 GB of scale-space scratch
@@ -2227,8 +2153,9 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     int rc = sift_setup(ctx, ctx->sift, h, w, params, max_frames, kp_cap, raw_cap, cand_cap, raw_cap, fb, true);
     if (rc) return rc;
     if (ctx->pb_pairs < max_pairs || ctx->pb_cap != kp_cap) {
-        free_pairbuf(ctx->pb);
-        HIPCHK(alloc_pairbuf(ctx->pb, max_pairs, kp_cap, false));
+        ctx->pb_mem.release();
+        ctx->pb_pairs = ctx->pb_cap = 0;
+        HIPCHK(alloc_pairbuf(ctx->pb_mem, ctx->pb, max_pairs, kp_cap, false));
         ctx->pb_pairs = max_pairs; ctx->pb_cap = kp_cap;
     }
     ctx->sift_pairs = max_pairs;
@@ -2265,13 +2192,10 @@ extern "C" int vo_frame_features_sift(vo_ctx* ctx, int slot, float* kp_xy, float
     return warn;
 }
 
+// (frames_upload_enqueue has checked the arguments)
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot)
 {
     SiftState& S = ctx->sift;
-    if (!frames || F < 0 || first_slot < 0 || first_slot + F > S.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (row_stride < S.w) FAIL(VO_ERR_INVALID, "row_stride < width");
-    if (F == 0) return VO_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t fbytes = (size_t)S.fstride * S.h;
     uint8_t* dst0 = S.frames + (size_t)first_slot * fbytes;
     if (row_stride == S.w && S.fstride == S.w && frame_stride >= (int64_t)S.w * S.h) {
@@ -2283,11 +2207,10 @@ static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F,
     return VO_OK;
 }
 
+// (detect_enqueue has checked the arguments)
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F)
 {
     SiftState& S = ctx->sift;
-    if (F < 0 || first_slot < 0 || first_slot + F > S.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t fbytes = (size_t)S.fstride * S.h;
     for (int f0 = 0; f0 < F; f0 += S.fb) {
         const int n = F - f0 < S.fb ? F - f0 : S.fb;
@@ -2309,10 +2232,10 @@ extern "C" int vo_jpeg_info(const uint8_t* data, size_t nbytes, int32_t* h, int3
     return rc;
 }
 
-// Decodes files [f0, f0 + n) of the blob into ctx->jpg_out (device, B G R, image k at k * out_frame bytes, rows of
+// Decodes files [f0, f0 + n) of the blob into ctx->jpg_out.p (device, B G R, image k at k * out_frame bytes, rows of
 // out_w * 3 bytes).  Every file must be exactly out_h x out_w.  Leaves the work queued on the context's stream.
 // With `gray` (device; image k's plane at gray + k * gray_frame, rows of gray_stride >= align_up(out_w, 4) bytes) the colour
-// conversion writes cvtColor(BGR2GRAY) of the decoded pixels there instead and ctx->jpg_out is not touched.
+// conversion writes cvtColor(BGR2GRAY) of the decoded pixels there instead and ctx->jpg_out.p is not touched.
 static int jpeg_decode_device(vo_ctx* ctx, const uint8_t* blob, const int64_t* offsets, int f0, int n, int out_h, int out_w,
                               uint8_t* gray = nullptr, size_t gray_frame = 0, int gray_stride = 0)
 {
@@ -2354,14 +2277,14 @@ static int jpeg_decode_device(vo_ctx* ctx, const uint8_t* blob, const int64_t* o
     }
     if (bytes > 0xf0000000ull) FAIL(VO_ERR_UNSUPPORTED, "JPEG batch too large for one launch");
     int rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_blob, &ctx->jpg_blob_n, bytes + 16))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_clean, &ctx->jpg_clean_n, clean + 16))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_rst, &ctx->jpg_rst_n, (rst + 4) * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_coef, &ctx->jpg_coef_n, blocks * 128 + 16))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_planes, &ctx->jpg_planes_n, planes + 256))) return rc;
-    if (!gray && (rc = ensure_bytes(ctx, &ctx->jpg_out, &ctx->jpg_out_n, (size_t)n * out_h * out_w * 3 + 16))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_img, &ctx->jpg_img_n, (size_t)n * sizeof(JpegImage)))) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->jpg_tab, &ctx->jpg_tab_n, tabs.size() * sizeof(JpegTables)))) return rc;
+    if ((rc = ctx->jpg_blob.grow(ctx, bytes + 16))) return rc;
+    if ((rc = ctx->jpg_clean.grow(ctx, clean + 16))) return rc;
+    if ((rc = ctx->jpg_rst.grow(ctx, (rst + 4) * sizeof(uint32_t)))) return rc;
+    if ((rc = ctx->jpg_coef.grow(ctx, blocks * 128 + 16))) return rc;
+    if ((rc = ctx->jpg_planes.grow(ctx, planes + 256))) return rc;
+    if (!gray && (rc = ctx->jpg_out.grow(ctx, (size_t)n * out_h * out_w * 3 + 16))) return rc;
+    if ((rc = ctx->jpg_img.grow(ctx, (size_t)n * sizeof(JpegImage)))) return rc;
+    if ((rc = ctx->jpg_tab.grow(ctx, tabs.size() * sizeof(JpegTables)))) return rc;
     hipStream_t s = ctx->stream;
     // The coefficient blocks start out cleared (the entropy decoder stores only the coefficients the stream names): 2.8 MB per
     // 1280 x 720 file.  The fill runs on a stream of its own — ordered behind everything queued so far (the previous batch's
@@ -2377,22 +2300,22 @@ static int jpeg_decode_device(vo_ctx* ctx, const uint8_t* blob, const int64_t* o
     if (ctx->stream_jpg) {
         HIPCHK(hipEventRecord(ctx->ev_jpg[0], s));
         HIPCHK(hipStreamWaitEvent(ctx->stream_jpg, ctx->ev_jpg[0], 0));
-        HIPCHK(hipMemsetAsync(ctx->jpg_coef, 0, blocks * 128, ctx->stream_jpg));
+        HIPCHK(hipMemsetAsync(ctx->jpg_coef.p, 0, blocks * 128, ctx->stream_jpg));
         HIPCHK(hipEventRecord(ctx->ev_jpg[1], ctx->stream_jpg));
         cleared = ctx->ev_jpg[1];
-    } else HIPCHK(hipMemsetAsync(ctx->jpg_coef, 0, blocks * 128, s));
-    HIPCHK(hipMemcpyAsync(ctx->jpg_blob, blob + base, bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->jpg_img, imgs.data(), (size_t)n * sizeof(JpegImage), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->jpg_tab, tabs.data(), tabs.size() * sizeof(JpegTables), hipMemcpyHostToDevice, s));
+    } else HIPCHK(hipMemsetAsync(ctx->jpg_coef.p, 0, blocks * 128, s));
+    HIPCHK(hipMemcpyAsync(ctx->jpg_blob.p, blob + base, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->jpg_img.p, imgs.data(), (size_t)n * sizeof(JpegImage), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->jpg_tab.p, tabs.data(), tabs.size() * sizeof(JpegTables), hipMemcpyHostToDevice, s));
     {
         StageTimer t(ctx, ST_MISC);
-        launch_jpeg_decode(s, ctx->jpg_blob, (JpegImage*)ctx->jpg_img, (const JpegTables*)ctx->jpg_tab, n, ctx->jpg_clean, (uint32_t*)ctx->jpg_rst,
-                           (int16_t*)ctx->jpg_coef, ctx->jpg_planes, gray ? gray : ctx->jpg_out, max_blocks, out_w, out_h, gray != nullptr, packed_tables, cleared);
+        launch_jpeg_decode(s, ctx->jpg_blob.p, (JpegImage*)ctx->jpg_img.p, (const JpegTables*)ctx->jpg_tab.p, n, ctx->jpg_clean.p, (uint32_t*)ctx->jpg_rst.p,
+                           (int16_t*)ctx->jpg_coef.p, ctx->jpg_planes.p, gray ? gray : ctx->jpg_out.p, max_blocks, out_w, out_h, gray != nullptr, packed_tables, cleared);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));                  // the host vectors must outlive their copies
     if (getenv("VO_DEBUG")) {
-        HIPCHK(hipMemcpy(imgs.data(), ctx->jpg_img, (size_t)n * sizeof(JpegImage), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(imgs.data(), ctx->jpg_img.p, (size_t)n * sizeof(JpegImage), hipMemcpyDeviceToHost));
         uint32_t mx = 0; double sum = 0;
         for (int k = 0; k < n; k++) { mx = imgs[k].sync_rounds > mx ? imgs[k].sync_rounds : mx; sum += imgs[k].sync_rounds; }
         fprintf(stderr, "jpeg: %d files, synchronisation rounds mean %.2f max %u (clean bytes of file 0: %u)\n", n, sum / n, mx, imgs[0].clean_len);
@@ -2424,7 +2347,7 @@ extern "C" int vo_jpeg_decode_batch(vo_ctx* ctx, const uint8_t* blob, const int6
         const int n = F - f0 < chunk ? F - f0 : chunk;
         const int rc = jpeg_decode_device(ctx, blob, offsets, f0, n, h, w);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(bgr_out + (size_t)f0 * per, ctx->jpg_out, per * n, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(bgr_out + (size_t)f0 * per, ctx->jpg_out.p, per * n, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if (ctx->prof) prof_collect(ctx);
@@ -2448,8 +2371,9 @@ extern "C" int vo_jpeg_decode(vo_ctx* ctx, const uint8_t* data, size_t nbytes, u
 extern "C" int vo_frames_ingest_jpeg(vo_ctx* ctx, const uint8_t* blob, const int64_t* offsets, int F, int first_slot, uint8_t* resized_out)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (!blob || !offsets || F < 0 || first_slot < 0 || first_slot + F > batch_max_frames(ctx)) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (!blob || !offsets || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
     for (int f = 0; f < F; f++) if (offsets[f + 1] < offsets[f] + 4) FAIL(VO_ERR_INVALID, "file %d is empty", f);
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2457,21 +2381,20 @@ extern "C" int vo_frames_ingest_jpeg(vo_ctx* ctx, const uint8_t* blob, const int
     const int irc = jpeg_info(blob + offsets[0], (size_t)(offsets[1] - offsets[0]), &sh, &sw, &nc, &sa, &orr);
     if (irc) FAIL(irc, "file 0 is not a baseline JPEG");
     const int chunk = jpeg_chunk(sh, sw, F);
-    const int dw = batch_w(ctx), dh = batch_h(ctx);
+    const int dw = b.w, dh = b.h;
     const size_t dper = (size_t)dw * dh * 3;
     for (int f0 = 0; f0 < F; f0 += chunk) {
         const int n = F - f0 < chunk ? F - f0 : chunk;
-        const GraySlots g0 = batch_gray_slots(ctx, first_slot + f0);
-        if (sw == dw && sh == dh && !resized_out && g0.stride >= align_up(dw, 4)) {
+        if (sw == dw && sh == dh && !resized_out && b.gray_stride >= align_up(dw, 4)) {
             // files of the configured size and nobody wants the colour frames: cv::resize is a copy, so the decoder's colour
             // conversion writes the gray frames of the slots itself (no B G R frames in memory, no k_gray pass)
-            const int rc = jpeg_decode_device(ctx, blob, offsets, f0, n, sh, sw, g0.base, g0.frame, g0.stride);
+            const int rc = jpeg_decode_device(ctx, blob, offsets, f0, n, sh, sw, b.gray_slot(first_slot + f0), b.gray_frame, b.gray_stride);
             if (rc) return rc;
             continue;
         }
         int rc = jpeg_decode_device(ctx, blob, offsets, f0, n, sh, sw);
         if (rc) return rc;
-        rc = ingest_from_device(ctx, ctx->jpg_out, n, sh, sw, 3, sw * 3, (int64_t)sh * sw * 3, first_slot + f0,
+        rc = ingest_from_device(ctx, ctx->jpg_out.p, n, sh, sw, 3, sw * 3, (int64_t)sh * sw * 3, first_slot + f0,
                                 resized_out ? resized_out + (size_t)f0 * dper : nullptr);
         if (rc) return rc;
     }
@@ -2503,7 +2426,7 @@ extern "C" int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pai
     int rc = ensure_raw_d(ctx, fc + n_int / 2 + 64);                 // parents (u64) + the int arrays
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    unsigned long long* dparent = (unsigned long long*)ctx->raw_d;
+    unsigned long long* dparent = (unsigned long long*)ctx->raw_d.p;
     int* di = (int*)(dparent + fc);
     int *dpf = di, *doff = dpf + 2 * P, *dq = doff + P + 1, *dt = dq + total, *drf = dt + total, *dri = drf + fc, *dh = dri + fc, *dbad = dh + fc;
     HIPCHK(hipMemsetAsync(dparent, 0, fc * sizeof(unsigned long long), s));
@@ -2542,14 +2465,17 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
                                    double max_point_norm, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_map)
 {
     if (!ctx) return VO_ERR_INVALID;
-    if (!batch_ready(ctx)) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (B < 1 || B != ctx->last_pairs || !K || !poses || !n_corr || !n_inl || !status || !n_map)
-        FAIL(VO_ERR_INVALID, "vo_tracks_pnp_batch takes all %d pairs of the most recent vo_pairs_run", ctx->last_pairs);
-    if (!ctx->last_points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
-    const int F = batch_max_frames(ctx), cap = batch_cap(ctx);
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (B < 1 || B != ctx->last.pairs || !K || !poses || !n_corr || !n_inl || !status || !n_map)
+        FAIL(VO_ERR_INVALID, "vo_tracks_pnp_batch takes all %d pairs of the most recent vo_pairs_run", ctx->last.pairs);
+    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
+    const int F = b.max_frames, cap = b.kp_cap;
+    const int32_t* sl = ctx->last.slots.data();
+    for (int i = 0; i < 2 * B; i++)
+        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
     {   // the pairs must be a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference processes a sequence in
         std::vector<char> seen((size_t)F, 0);
-        const int32_t* sl = ctx->last_slots.data();
         seen[(size_t)sl[0]] = 1;
         for (int p = 0; p < B; p++) {
             if ((p > 0 && sl[2 * p] != sl[2 * p - 1]) || seen[(size_t)sl[2 * p + 1]])
@@ -2569,8 +2495,8 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
                  o_rv = take(24), o_tv = take(24), o_P1 = take(96), o_P2 = take(96), o_Xw = take((size_t)cap * 32), o_poses = take((size_t)(B + 1) * 96), o_K = take(72),
                  o_inmap = take(fc), o_camok = take((size_t)F * 4), o_off = take(8), o_pmask = take((size_t)cap), o_pninl = take(4), o_pst = take(4),
                  o_alive = take(4), o_ncorr = take((size_t)B * 4), o_ninl = take((size_t)B * 4), o_st = take((size_t)B * 4), o_nmap = take((size_t)B * 4), o_mc = take(4);
-    rc = ensure_bytes(ctx, &ctx->chain_mem, &ctx->chain_bytes, need); if (rc) return rc;
-    uint8_t* m = ctx->chain_mem;
+    rc = ctx->chain_mem.grow(ctx, need); if (rc) return rc;
+    uint8_t* m = ctx->chain_mem.p;
     ChainBuf cb;
     cb.parent = (unsigned long long*)(m + o_parent); cb.map_pt = (double*)(m + o_pt); cb.cam = (double*)(m + o_cam); cb.obj = (double*)(m + o_obj);
     cb.img = (double*)(m + o_img); cb.rvec = (double*)(m + o_rv); cb.tvec = (double*)(m + o_tv); cb.P1 = (double*)(m + o_P1); cb.P2 = (double*)(m + o_P2);
@@ -2638,7 +2564,8 @@ extern "C" const char* vo_stage_name(int stage)
 // input once and writes its output once; padding columns are not counted).
 extern "C" double vo_stage_bytes(vo_ctx* ctx, int stage, int F)
 {
-    if (ctx && ctx->detector == 1 && ctx->sift.configured) {
+    const Batch bt = ctx ? batch(ctx) : Batch{};
+    if (bt.sift && bt.ready) {
         // SIFT: float planes.  One layer sweep reads its source plane and writes a Gaussian plane; per octave nLayers + 2
         // sweeps; the base image: u8 in, float out, one blur; next-octave seeds.  The extrema search reads the octave's nLayers + 3
         // Gaussian planes (the DoG planes are differences made in registers, never stored).
