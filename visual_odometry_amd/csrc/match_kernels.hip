@@ -288,17 +288,19 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 #define MF_STAGE_ROWS 128                 // rows of B per LDS stage (8 groups of 16, 16 KB), double buffered
 #endif                                    // (64 / 128 / 256 rows: 0.220 / 0.214 / 0.215 ms per 256 pairs)
 #define MF_LD (MF_STAGE_ROWS * 128 / 16 / MM_THREADS)   // 16-byte staging loads per thread and stage
-template <bool KNN2>
-__global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x,
-                                                PairBuf pb, int dir_first, int row_blocks)
+typedef float v2f __attribute__((ext_vector_type(2)));
+// Single pass for the cross-check (COLS): the accumulators of one (row block of A) x (all of B) sweep also give the
+// reverse direction.  acc + (S - 1 - i) = S (dot + 256) + (S - 1 - j) + (S - 1 - i): the low part stays below 2 S, the spacing
+// of dot + 256 (always even), so within column j it is the key S (dot + 256) + (S - 1 - i) plus a constant — nearer first,
+// then the lower row (< 2^23: exact).  Rows at or past na (an active wave's partial block reads padding descriptors and
+// has finite dot products) get -2^24 instead and never win.  Each lane folds its 16 rows with v_max3_i32, the four 16-lane
+// groups meet by v_permlane32_swap / v_permlane16_swap, and ds_max_i32 keeps the workgroup's column maxima in LDS
+// (round16(kp_cap) ints, dynamic); they go to pb.nn_colkey[p][row block][j] as S (dot + 256) + (S - 1 - i), and k_match_select takes the
+// maximum over the row blocks.
+template <bool KNN2, bool COLS>
+__device__ __forceinline__ void nn_fp4_body(uint8_t (*s_b)[MF_STAGE_ROWS * 128], int* s_col, const uint8_t* desc_x, int kp_cap, int cap_x,
+                                            const PairBuf& pb, int p, int dir, int fa, int fb, int na, int nb, int rbk, int row0)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t s_b[2][MF_STAGE_ROWS * 128];
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int p = bid / row_blocks, dir = dir_first + blockIdx.z;
-    const int fa = pb.slots[2 * p + dir], fb = pb.slots[2 * p + (dir ^ 1)];
-    const int na = min(kp_count[fa], kp_cap), nb = min(kp_count[fb], kp_cap);
-    const int row0 = (bid % row_blocks) * MM_BLOCK_ROWS;
-    if (row0 >= na) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
     const uint8_t* A = desc_x + (size_t)fa * cap_x * 256;
@@ -320,6 +322,46 @@ __global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, co
     v4i best[MM_RB], best2[MM_RB];
 #pragma unroll
     for (int rb = 0; rb < MM_RB; rb++) { best[rb] = (v4i){INT_MIN, INT_MIN, INT_MIN, INT_MIN}; best2[rb] = best[rb]; }
+
+    v2f coff[MM_RB][2];                                         // COLS: S - 1 - i of the lane's 16 rows, -2^24 past na
+    if (COLS) {
+#pragma unroll
+        for (int rb = 0; rb < MM_RB; rb++)
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    const int i = wrow0 + rb * 16 + lg * 4 + 2 * h + e;
+                    coff[rb][h][e] = i < na ? (float)(MF_S - 1 - i) : -16777216.f;
+                }
+        for (int c = tid; c < ((nb + 15) & ~15); c += MM_THREADS) s_col[c] = INT_MIN;   // ordered before the ds_max by the first barrier
+    }
+    // the column maximum of one group's 16 x 64 accumulators, per lane (column li, the lane's 16 rows)
+    auto colmax = [&](const v4f (&acc)[MM_RB]) -> int {
+        int x[16];
+#pragma unroll
+        for (int rb = 0; rb < MM_RB; rb++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const v2f t = (v2f){acc[rb][2 * h], acc[rb][2 * h + 1]} + coff[rb][h];
+                x[rb * 4 + 2 * h] = __float_as_int(t.x); x[rb * 4 + 2 * h + 1] = __float_as_int(t.y);
+            }
+        const int m0 = max(max(x[0], x[1]), x[2]), m1 = max(max(x[3], x[4]), x[5]), m2 = max(max(x[6], x[7]), x[8]);
+        const int m3 = max(max(x[9], x[10]), x[11]), m4 = max(max(x[12], x[13]), x[14]);
+        return max(max(max(m0, m1), m2), max(max(m3, m4), x[15]));
+    };
+    // columns j0 + li (c0, lanes 0-15 write) and j0 + 16 + li (c1, lanes 32-47 write, if two): the four row quads of a column
+    // meet across the 16-lane groups
+    auto colflush = [&](int c0, int c1, int j0, bool two) {
+        const auto h = __builtin_amdgcn_permlane32_swap(c0, c1, false, false);      // lanes 0-31: c0, lanes 32-63: c1
+        const int m = max((int)h[0], (int)h[1]);
+        const auto q = __builtin_amdgcn_permlane16_swap(m, m, false, false);
+        const int v = max((int)q[0], (int)q[1]);
+        // ds_max_i32 in asm: the compiler takes an LDS atomic to alias the next stage's LDS-DMA and would drain it first
+        // (s_waitcnt vmcnt(0) per step); s_col is only read after the lgkmcnt(0) and barrier that end the sweep
+        if (!(lane & 16) && (two || lane < 32))
+            asm volatile("ds_max_i32 %0, %1" :: "v"((unsigned)(uintptr_t)(__attribute__((address_space(3))) int*)(s_col + j0 + (lane >> 5) * 16 + li)), "v"(v) : "memory");
+    };
 
     const int nstages = (nb + MF_STAGE_ROWS - 1) / MF_STAGE_ROWS;
     const bool active = wrow0 < na;
@@ -374,6 +416,7 @@ __global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, co
                         best[rb][r] = max(best[rb][r], k1);
                     } else best[rb][r] = max(max(best[rb][r], k0), k1);
                 }
+            if (COLS) colflush(colmax(acc0), colmax(acc1), (first + g) * 16, true);
         }
         for (; g < ngf + (tail ? 1 : 0); g++) {                 // an odd full group and / or the partial one
             v4f acc[MM_RB];
@@ -389,6 +432,7 @@ __global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, co
                     if (KNN2) best2[rb][r] = max(best2[rb][r], min(best[rb][r], key));
                     best[rb][r] = max(best[rb][r], key);
                 }
+            if (COLS) colflush(colmax(acc), INT_MIN, (first + g) * 16, false);
         }
     }
 #undef MF_GLDS
@@ -416,28 +460,70 @@ __global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, co
                 }
             }
         }
+    if (COLS) {                                                  // this row block's reverse-direction keys, column j -> S (dot + 256) + (S - 1 - i)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        int* part = pb.nn_colkey + ((size_t)p * rbk + row0 / MM_BLOCK_ROWS) * kp_cap;
+        for (int c = tid; c < nb; c += MM_THREADS) {
+            const int k = s_col[c];
+            part[c] = k >= 0 ? (int)__int_as_float(k) - (MF_S - 1 - c) : -1;
+        }
+    }
+}
+
+// cols: 1 = the single pass for the cross-check (dir_first 0, gridDim.z 1, nb ints of dynamic LDS); a runtime flag, so that
+// the kernel keeps its name for the profilers
+template <bool KNN2>
+__global__ __launch_bounds__(MM_THREADS) void k_nn_fp4(const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x,
+                                                PairBuf pb, int dir_first, int row_blocks, int cols)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_b[2][MF_STAGE_ROWS * 128];
+    extern __shared__ int s_col[];
+    const int bid = xcd_tile(blockIdx.x, gridDim.x);
+    const int p = bid / row_blocks, dir = dir_first + blockIdx.z;
+    const int fa = pb.slots[2 * p + dir], fb = pb.slots[2 * p + (dir ^ 1)];
+    const int na = min(kp_count[fa], kp_cap), nb = min(kp_count[fb], kp_cap);
+    const int row0 = (bid % row_blocks) * MM_BLOCK_ROWS;
+    if (row0 >= na) return;
+    if (!KNN2 && cols) nn_fp4_body<false, true>(s_b, s_col, desc_x, kp_cap, cap_x, pb, p, dir, fa, fb, na, nb, row_blocks, row0);
+    else nn_fp4_body<KNN2, false>(s_b, s_col, desc_x, kp_cap, cap_x, pb, p, dir, fa, fb, na, nb, row_blocks, row0);
+}
+
+// the single pass's column keys: one LDS int per column of B (on top of the 32 KB B stages) and one partial row per row block
+#define NN_COLS_MAX 4096
+size_t nn_colkey_ints(int P, int kp_cap)
+{
+    return kp_cap <= NN_COLS_MAX ? (size_t)P * ((kp_cap + MM_BLOCK_ROWS - 1) / MM_BLOCK_ROWS) * kp_cap : 0;
 }
 
 // dirs_mask: bit 0 = forward (frame1 -> frame2), bit 1 = reverse. knn2 applies to the forward direction.
-void launch_match_nn(hipStream_t s, const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x, PairBuf pb, int P,
-                     int dirs_mask, int knn2, int fp4)
+// Returns 1 when the FP4 single pass ran for dirs_mask 3: the reverse direction is then in pb.nn_colkey, for
+// launch_match_select.  Above NN_COLS_MAX columns (or without the partial buffer) both directions run as two sweeps.
+int launch_match_nn(hipStream_t s, const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x, PairBuf pb, int P,
+                    int dirs_mask, int knn2, int fp4)
 {
-    if (P <= 0) return;
+    if (P <= 0) return 0;
     dim3 block(MM_THREADS);
     const int gx = (kp_cap + MM_BLOCK_ROWS - 1) / MM_BLOCK_ROWS;
     if (fp4) {
-        if (knn2) hipLaunchKernelGGL(k_nn_fp4<true>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx);
-        else if (dirs_mask == 3) hipLaunchKernelGGL(k_nn_fp4<false>, dim3(gx * P, 1, 2), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx);
-        else hipLaunchKernelGGL(k_nn_fp4<false>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, dirs_mask == 2 ? 1 : 0, gx);
-        return;
+        if (knn2) hipLaunchKernelGGL(k_nn_fp4<true>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx, 0);
+        else if (dirs_mask == 3 && pb.nn_colkey && kp_cap <= NN_COLS_MAX) {
+            const size_t shmem = (size_t)((kp_cap + 15) & ~15) * sizeof(int);
+            hipLaunchKernelGGL(k_nn_fp4<false>, dim3(gx * P, 1, 1), block, shmem, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx, 1);
+            return 1;
+        }
+        else if (dirs_mask == 3) hipLaunchKernelGGL(k_nn_fp4<false>, dim3(gx * P, 1, 2), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx, 0);
+        else hipLaunchKernelGGL(k_nn_fp4<false>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, dirs_mask == 2 ? 1 : 0, gx, 0);
+        return 0;
     }
     if (knn2) {
         hipLaunchKernelGGL(k_nn_mfma<true>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx);
-        return;
+        return 0;
     }
     if (dirs_mask == 3) hipLaunchKernelGGL(k_nn_mfma<false>, dim3(gx * P, 1, 2), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx);
     else if (dirs_mask == 1) hipLaunchKernelGGL(k_nn_mfma<false>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 0, gx);
     else if (dirs_mask == 2) hipLaunchKernelGGL(k_nn_mfma<false>, dim3(gx * P, 1, 1), block, 0, s, desc_x, kp_count, kp_cap, cap_x, pb, 1, gx);
+    return 0;
 }
 
 // ------------------------------------------------------------------ L2 nearest neighbours of SIFT rows on the matrix cores
@@ -644,7 +730,7 @@ __device__ __forceinline__ int excl_scan_256(int v, int* s_w, int* total)
 }
 
 __global__ __launch_bounds__(256) void k_match_select(const float* kp_xy, const int* kp_count, int kp_cap, PairBuf pb,
-                                                      int mode, double ratio, const double* Kd, int l2)
+                                                      int mode, double ratio, const double* Kd, int l2, int col_parts)
 {
     extern __shared__ unsigned long long s_best[];      // [kp_cap] for mode 1
     __shared__ int s_w[4];
@@ -654,6 +740,29 @@ __global__ __launch_bounds__(256) void k_match_select(const float* kp_xy, const 
     const size_t o0 = ((size_t)p * 2) * kp_cap, o1 = o0 + kp_cap, op = (size_t)p * kp_cap;
     const int* fidx = pb.nn_idx + o0; const int* fdist = pb.nn_dist + o0;
     const int* ridx = pb.nn_idx + o1; const int* rdist = pb.nn_dist + o1;
+    if (col_parts) {
+        // the FP4 single pass: the reverse nearest neighbour of train row t is the largest key of its column over the row
+        // blocks of frame 1 that ran (S (dot + 256) + (S - 1 - i): the lowest row wins ties), decoded like the row direction
+        const int* part = pb.nn_colkey + (size_t)p * ((kp_cap + MM_BLOCK_ROWS - 1) / MM_BLOCK_ROWS) * kp_cap;
+        const int rbk = (nq + MM_BLOCK_ROWS - 1) / MM_BLOCK_ROWS;
+        // four columns per thread and round: every load of a round is issued before its stores (latency bound otherwise)
+        for (int t0 = tid; t0 < nt; t0 += 4 * 256) {
+            int k[4] = {-1, -1, -1, -1};
+#pragma unroll 4
+            for (int g = 0; g < rbk; g++)
+#pragma unroll
+                for (int u = 0; u < 4; u++) k[u] = max(k[u], part[(size_t)g * kp_cap + min(t0 + u * 256, nt - 1)]);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int t = t0 + u * 256;
+                if (t < nt) {
+                    pb.nn_idx[o1 + t] = k[u] >= 0 ? MF_S - 1 - (k[u] & (MF_S - 1)) : -1;
+                    pb.nn_dist[o1 + t] = k[u] >= 0 ? (512 - (k[u] >> 13)) >> 1 : INT_MAX;
+                }
+            }
+        }
+        __syncthreads();                                  // (a workgroup-scope fence: the writes are visible to ridx / rdist below)
+    }
     if (mode == 1) {
         for (int q = tid; q < nq; q += 256) s_best[q] = ~0ULL;
         __syncthreads();
@@ -703,13 +812,13 @@ __global__ __launch_bounds__(256) void k_match_select(const float* kp_xy, const 
 }
 
 void launch_match_select(hipStream_t s, const float* kp_xy, const int* kp_count, int kp_cap, PairBuf pb, int P,
-                         int mode, double ratio, const double* K, int l2)
+                         int mode, double ratio, const double* K, int l2, int col_parts)
 {
     if (P <= 0) return;
     size_t shmem = mode == 1 ? (size_t)kp_cap * 8 : 8;
     // above the 64 KB default a workgroup must opt in to its dynamic LDS (the API layer bounds kp_cap * 8 by 160 KB)
     if (shmem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_match_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    hipLaunchKernelGGL(k_match_select, dim3(P), dim3(256), shmem, s, kp_xy, kp_count, kp_cap, pb, mode, ratio, K, l2);
+    hipLaunchKernelGGL(k_match_select, dim3(P), dim3(256), shmem, s, kp_xy, kp_count, kp_cap, pb, mode, ratio, K, l2, col_parts);
 }
 
 // ------------------------------------------------------------------ BFMatcher(NORM_L2) on float descriptors

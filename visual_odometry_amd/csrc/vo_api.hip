@@ -326,6 +326,7 @@ static hipError_t alloc_pairbuf(DevList& mem, PairBuf& pb, int P, int cap, bool 
     A_(in1, pc * 2); A_(in2, pc * 2); A_(ipx1, pc * 2); A_(ipx2, pc * 2);
     A_(res, (size_t)P); A_(X, pc * 4);
     if (with_pose_mask) { A_(pose_mask, pc); }
+    if (const size_t n = nn_colkey_ints(P, cap)) { A_(nn_colkey, n); }
 #undef A_
     return hipSuccess;
 }
@@ -957,6 +958,7 @@ static int run_pairs(vo_ctx* ctx, PairBuf pb, const uint8_t* desc, const uint8_t
 {
     hipStream_t s = ctx->stream;
     HIPCHK(hipMemsetAsync(pb.res, 0, (size_t)P * sizeof(vo_pair_result), s));
+    int col_parts = 0;                                           // the FP4 single pass left the reverse direction as column keys
     if (l2_norms) {                                              // SIFT rows: squared L2 distances on the int8 matrix cores
         StageTimer t(ctx, ST_MATCH_NN);
         const int cx = desc_x_rows(cap);
@@ -972,9 +974,9 @@ static int run_pairs(vo_ctx* ctx, PairBuf pb, const uint8_t* desc, const uint8_t
             if (select_mode == 3) launch_match_nn_popcount(s, desc, kp_count, cap, pb, P, 1, 1);
             else launch_match_nn_popcount(s, desc, kp_count, cap, pb, P, dirs, 0);
         } else if (select_mode == 3) launch_match_nn(s, desc_x, kp_count, cap, cx, pb, P, 1, 1, descx_fp4);   // the image that was written,
-        else launch_match_nn(s, desc_x, kp_count, cap, cx, pb, P, dirs, 0, descx_fp4);                        // whatever the setter says now
+        else col_parts = launch_match_nn(s, desc_x, kp_count, cap, cx, pb, P, dirs, 0, descx_fp4);            // whatever the setter says now
     }
-    { StageTimer t(ctx, ST_MATCH_SELECT); launch_match_select(s, kp_xy, kp_count, cap, pb, P, select_mode, ratio, ctx->dK, l2_norms ? 1 : 0); }
+    { StageTimer t(ctx, ST_MATCH_SELECT); launch_match_select(s, kp_xy, kp_count, cap, pb, P, select_mode, ratio, ctx->dK, l2_norms ? 1 : 0, col_parts); }
     if (!do_geometry) return VO_OK;
     { int rc = ensure_rng(ctx, rp.seed); if (rc) return rc; }
     { StageTimer t(ctx, ST_RANSAC); launch_ransac(s, pb, cap, P, rp, ctx->rng_tab, RNG_TAB_N); }

@@ -103,6 +103,7 @@ struct PairBuf {
     int*      nn_dist;    // [P][2][kp_cap]
     int*      nn_idx2;    // [P][kp_cap] second neighbour (knn2)
     int*      nn_dist2;   // [P][kp_cap]
+    int*      nn_colkey;  // [P][row blocks][kp_cap] reverse-direction keys of the single-pass FP4 matcher (nullptr: kp_cap too large)
     int*      m_q;        // [P][kp_cap]
     int*      m_t;        // [P][kp_cap]
     float*    m_d;        // [P][kp_cap]
@@ -227,12 +228,15 @@ __device__ __forceinline__ int xcd_tile(int b, int n)
 // expanded descriptors: [frame][cap_x / 16][16 chunks][16 rows][16 B] of +1 / -1 bytes, cap_x = desc_x_rows(kp_cap)
 static inline int desc_x_rows(int kp_cap) { return (kp_cap + 255) & ~255; }
 void launch_desc_expand(hipStream_t s, const uint8_t* desc, const int* kp_count, int kp_cap, int cap_x, uint8_t* desc_x, int F, int fp4);
-void launch_match_nn(hipStream_t s, const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x, PairBuf pb, int P,
-                     int dirs_mask, int knn2, int fp4);
+// returns 1 when the reverse direction was left as per-row-block column keys in pb.nn_colkey (launch_match_select's col_parts)
+int launch_match_nn(hipStream_t s, const uint8_t* desc_x, const int* kp_count, int kp_cap, int cap_x, PairBuf pb, int P,
+                    int dirs_mask, int knn2, int fp4);
+size_t nn_colkey_ints(int P, int kp_cap);   // size of PairBuf::nn_colkey; 0 above the single pass's LDS capacity
 void launch_match_nn_popcount(hipStream_t s, const uint8_t* desc, const int* kp_count, int kp_cap, PairBuf pb, int P,
                               int dirs_mask, int knn2);
 void launch_match_select(hipStream_t s, const float* kp_xy, const int* kp_count, int kp_cap, PairBuf pb, int P,
-                         int mode, double ratio, const double* K, int l2 = 0);   // l2: nn_dist holds squared L2 distances, reported as sqrtf
+                         int mode, double ratio, const double* K, int l2 = 0,   // l2: nn_dist holds squared L2 distances, reported as sqrtf
+                         int col_parts = 0);                                     // col_parts: reverse direction from pb.nn_colkey
 
 size_t nn_l2_knn2_keys(int na, int nb);
 void launch_nn_l2_knn2(hipStream_t s, const float* A, int na, const float* B, int nb, int dim, int* idx, float* dist, unsigned long long* part);
