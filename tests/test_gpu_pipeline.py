@@ -259,7 +259,8 @@ def test_library_gather_equals_local_records(seq_small):
     """vo_pairs_gather: the [R|t] + counts records packed on the device (k_pack_records) and all-gathered by the
     library itself (ncclAllGather from librccl.so on the context's stream).  Without a communicator it returns the
     local records; with a world-size-1 RCCL communicator the same bytes must come back through the collective.  Both
-    equal sharding.pack_records of the structured results (the host-side statement of the record layout)."""
+    equal sharding.pack_records of the structured results (the host-side statement of the record layout).  The launchers'
+    small all-gather of host doubles (vo_comm_allgather_f64) returns its input through the same communicator."""
     from visual_odometry_amd import _lib
     from visual_odometry_amd.frontend import FrontEnd
     from visual_odometry_amd.sharding import pack_records
@@ -277,6 +278,12 @@ def test_library_gather_equals_local_records(seq_small):
         assert np.array_equal(got[0], want)
         part = fe.gather_records(2, world=1).copy()                    # a shorter prefix of the same run
         assert np.array_equal(part[0], want[:2])
+        for n in (1, 4096):                                            # one value (the barrier) up to the largest n
+            v = np.random.default_rng(n).standard_normal(n)
+            got = c.allgather(v, 1)
+            assert got.shape == (1, n) and np.array_equal(got[0], v)
+        with pytest.raises(_lib.VoError):
+            c.allgather(np.zeros(4097), 1)
     finally:
         c.comm_destroy()
     c.close()

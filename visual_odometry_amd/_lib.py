@@ -260,6 +260,32 @@ def ptr(a):
     return None if a is None else a.ctypes.data
 
 
+class KeypointBuffers:
+    """Host arrays for up to `cap` keypoints, filled by the keypoint downloads (vo_*detect_and_compute, vo_frame_features*)."""
+
+    def __init__(self, cap, desc_width, desc_dtype=np.uint8):
+        self.cap = int(cap)
+        self.xy = np.empty((self.cap, 2), np.float32)
+        self.size, self.angle, self.response = (np.empty(self.cap, np.float32) for _ in range(3))
+        self.octave = np.empty(self.cap, np.int32)
+        self.desc = np.empty((self.cap, desc_width), desc_dtype)
+        self.n = C.c_int32(0)
+
+    def args(self):
+        """The call's trailing arguments: the six arrays, their capacity and the count's address."""
+        return (self.xy.ctypes.data, self.size.ctypes.data, self.angle.ctypes.data, self.response.ctypes.data,
+                self.octave.ctypes.data, self.desc.ctypes.data, self.cap, C.addressof(self.n))
+
+    def result(self, rc, desc_dtype=None):
+        """dict(xy [N,2] f32, size, angle, response [N] f32, octave [N] i32, desc [N, width], truncated) of the call that
+        returned rc; desc_dtype converts the descriptors."""
+        k = min(self.n.value, self.cap)
+        out = {name: getattr(self, name)[:k].copy() for name in ("xy", "size", "angle", "response", "octave")}
+        out["desc"] = self.desc[:k].astype(desc_dtype) if desc_dtype else self.desc[:k].copy()
+        out["truncated"] = rc == VO_WARN_CAPACITY
+        return out
+
+
 class PinnedArray:
     """numpy view over page-locked host memory from vo_host_alloc (freed with the object)."""
 

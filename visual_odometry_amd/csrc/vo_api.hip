@@ -87,7 +87,7 @@ struct vo_ctx {
     hipStream_t stream_jpg = nullptr;     // the JPEG decoder's coefficient buffer is cleared here, beside the upload of the files and k_jpeg_unstuff
     hipEvent_t ev_jpg[2] = {nullptr, nullptr};
     char err[512] = {0};
-    DevList mem;                          // context lifetime: dK, rng_tab, rng_host, raw_i
+    DevList mem;                          // context lifetime: dK, rng_tab, rng_host
 
     bool configured = false;
     DevList orb_mem;                      // the ORB configuration: tables, pyramid, blur, scores, ff.*, desc_x, selection state, cv2.*
@@ -120,9 +120,8 @@ struct vo_ctx {
     int raw_cap = 0;
     uint8_t* raw_desc = nullptr; float* raw_xy = nullptr; int* raw_count = nullptr; uint8_t* raw_desc_x = nullptr;
     PairBuf raw_pb{};
-    Growable<double> raw_d;                          // generic double scratch
+    Growable<uint8_t> scratch;                       // one call's device memory, laid out by ScratchLayout
     uint32_t* rng_tab = nullptr; uint32_t* rng_host = nullptr; uint64_t rng_seed = 0; bool rng_valid = false;   // OpenCV RNG stream for the RANSAC seed
-    int* raw_i = nullptr;
 
     bool prof = false;
     float prof_ms[VO_STAGE_COUNT] = {0};
@@ -142,7 +141,6 @@ struct vo_ctx {
     bool cv2_ready = false;
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
-    Growable<uint8_t> chain_mem;          // the localisation chain's tables (vo_tracks_pnp_batch)
 };
 
 static const char* k_stage_names[VO_STAGE_COUNT] = {
@@ -179,13 +177,24 @@ template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
 
 static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
 
-// the generic double scratch of the single-call operators, n doubles at least
-static int ensure_raw_d(vo_ctx* ctx, size_t n)
-{
-    int rc = ctx->raw_d.grow(ctx, n, n + n / 4 + 64); if (rc) return rc;
-    if (!ctx->raw_i) HIPCHK(ctx->mem.alloc(&ctx->raw_i, 16));
-    return VO_OK;
-}
+// The device memory of one call: typed sub-buffers of ctx->scratch, each on a 256-byte boundary.  take() names a pointer
+// and its element count; place() grows the buffer to what was taken and sets the pointers, so size and offsets agree.
+struct ScratchLayout {
+    size_t bytes = 0;                     // all sub-buffers: they start at ctx->scratch.p
+    template <typename T> void take(T** p, size_t n)
+    {
+        slots.push_back({p, bytes, [](void* dst, uint8_t* at) { *static_cast<T**>(dst) = reinterpret_cast<T*>(at); }});
+        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
+    }
+    int place(vo_ctx* ctx)
+    {
+        int rc = ctx->scratch.grow(ctx, bytes, bytes + bytes / 4 + 64); if (rc) return rc;
+        for (const Slot& s : slots) s.set(s.dst, ctx->scratch.p + s.off);
+        return VO_OK;
+    }
+    struct Slot { void* dst; size_t off; void (*set)(void*, uint8_t*); };
+    std::vector<Slot> slots;
+};
 
 // ------------------------------------------------------------------ profiling brackets
 struct StageTimer {
@@ -410,8 +419,24 @@ extern "C" void vo_destroy(vo_ctx* ctx)
     delete ctx;                           // the buffers go with their owners
 }
 
-// which image of the descriptors the matrix-core matcher reads: FP4 (block-scaled MFMA, fewer than 8192 rows per set) or int8
-static int matcher_fp4(const vo_ctx* ctx, int cap) { return ctx->matcher_kernel == 2 && cap < 8192; }   // else the int8 image
+// The Hamming nearest-neighbour kernel for sets of `cap` rows and, on the matrix cores, the image of the descriptors (desc_x)
+// it reads: detection writes that image, the single-call matcher expands it.  The matrix-core kernels carry the column index
+// inside their accumulator: fewer than 127^2 = 16129 rows per set.
+enum { NN_POPCOUNT, NN_INT8, NN_FP4 };
+static int nn_kernel(const vo_ctx* ctx, int cap)
+{
+    if (ctx->matcher_kernel == 1 || cap >= 16129) return NN_POPCOUNT;          // XOR + popcount on the packed descriptors
+    return ctx->matcher_kernel == 2 && cap < 8192 ? NN_FP4 : NN_INT8;          // block-scaled FP4 MFMA: fewer than 8192 rows
+}
+
+// The Hamming nearest neighbours of P pairs into pb (dirs_mask, knn2 as launch_match_nn takes them) on nn_kernel's kernel.  The
+// matrix cores read desc_x as image `fp4`: the one that was written, whatever the setter says now.  Returns col_parts.
+static int launch_hamming_nn(const vo_ctx* ctx, const PairBuf& pb, const uint8_t* desc, const uint8_t* desc_x, int fp4,
+                             const int* kp_count, int cap, int P, int dirs, int knn2)
+{
+    if (nn_kernel(ctx, cap) == NN_POPCOUNT) { launch_match_nn_popcount(ctx->stream, desc, kp_count, cap, pb, P, dirs, knn2); return 0; }
+    return launch_match_nn(ctx->stream, desc_x, kp_count, cap, desc_x_rows(cap), pb, P, dirs, knn2, fp4);
+}
 
 extern "C" int vo_set_matcher_kernel(vo_ctx* ctx, int kind)
 {
@@ -710,7 +735,7 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
     {
         StageTimer t(ctx, ST_BRIEF);
         const int cx = desc_x_rows(g.kp_cap);
-        ctx->descx_fp4 = matcher_fp4(ctx, g.kp_cap);
+        ctx->descx_fp4 = nn_kernel(ctx, g.kp_cap) == NN_FP4;
         launch_brief(s, blur, g, ff, F, ctx->desc_x + (size_t)first_slot * cx * 256, cx, ctx->descx_fp4);
     }
     return VO_OK;
@@ -798,6 +823,23 @@ extern "C" int vo_frames_detect(vo_ctx* ctx, int first_slot, int F)
     return capacity_warning(ctx, nullptr, 0, first_slot, F);
 }
 
+// The device arrays of a detector's keypoints: [slot][kp_cap] each, xy two floats and desc desc_bytes per keypoint
+struct KpArrays { const float *xy, *size, *angle, *resp; const int* octave; const uint8_t* desc; int desc_bytes; };
+
+// n keypoints from row `first` of the arrays into the caller's (a NULL output is skipped)
+static int download_keypoints(vo_ctx* ctx, const KpArrays& d, size_t first, int n, float* kp_xy, float* kp_size, float* kp_angle,
+                              float* kp_response, int32_t* kp_octave, uint8_t* desc)
+{
+    if (n <= 0) return VO_OK;
+    if (kp_xy) HIPCHK(hipMemcpy(kp_xy, d.xy + first * 2, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (kp_size) HIPCHK(hipMemcpy(kp_size, d.size + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (kp_angle) HIPCHK(hipMemcpy(kp_angle, d.angle + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (kp_response) HIPCHK(hipMemcpy(kp_response, d.resp + first, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (kp_octave) HIPCHK(hipMemcpy(kp_octave, d.octave + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    if (desc) HIPCHK(hipMemcpy(desc, d.desc + first * d.desc_bytes, (size_t)n * d.desc_bytes, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
 extern "C" int vo_frame_features(vo_ctx* ctx, int slot, float* kp_xy, float* kp_size, float* kp_angle, float* kp_response,
                                  int32_t* kp_octave, uint8_t* desc, int cap, int32_t* n_out)
 {
@@ -805,24 +847,17 @@ extern "C" int vo_frame_features(vo_ctx* ctx, int slot, float* kp_xy, float* kp_
     if (!ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (slot < 0 || slot >= ctx->max_frames || !n_out) FAIL(VO_ERR_INVALID, "bad slot");
     HIPCHK(hipSetDevice(ctx->device));
-    const PyrGeom& g = ctx->g;
+    const FrameFeat& ff = ctx->ff;
     int n = 0, flags = 0;
     HIPCHK(hipStreamSynchronize(ctx->stream));              // an asynchronous detection may still be running
-    HIPCHK(hipMemcpy(&n, ctx->ff.kp_count + slot, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&flags, ctx->ff.flags + slot, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n, ff.kp_count + slot, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&flags, ff.flags + slot, sizeof(int), hipMemcpyDeviceToHost));
     int warn = (flags & 1) ? VO_WARN_CAPACITY : VO_OK;
     if (n > cap) { n = cap; warn = VO_WARN_CAPACITY; }
     *n_out = n;
-    const size_t o = (size_t)slot * g.kp_cap;
-    if (n > 0) {
-        if (kp_xy) HIPCHK(hipMemcpy(kp_xy, ctx->ff.kp_xy + o * 2, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_size) HIPCHK(hipMemcpy(kp_size, ctx->ff.kp_size + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_angle) HIPCHK(hipMemcpy(kp_angle, ctx->ff.kp_angle + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_response) HIPCHK(hipMemcpy(kp_response, ctx->ff.kp_resp + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_octave) HIPCHK(hipMemcpy(kp_octave, ctx->ff.kp_level + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        if (desc) HIPCHK(hipMemcpy(desc, ctx->ff.desc + o * 32, (size_t)n * 32, hipMemcpyDeviceToHost));
-    }
-    return warn;
+    const int rc = download_keypoints(ctx, {ff.kp_xy, ff.kp_size, ff.kp_angle, ff.kp_resp, ff.kp_level, ff.desc, 32}, (size_t)slot * ctx->g.kp_cap, n,
+                                      kp_xy, kp_size, kp_angle, kp_response, kp_octave, desc);
+    return rc ? rc : warn;
 }
 
 // upload one host image (any channel count) into slot 0 and build its gray level 0
@@ -958,23 +993,12 @@ static int run_pairs(vo_ctx* ctx, PairBuf pb, const uint8_t* desc, const uint8_t
 {
     hipStream_t s = ctx->stream;
     HIPCHK(hipMemsetAsync(pb.res, 0, (size_t)P * sizeof(vo_pair_result), s));
+    const int knn2 = select_mode == 3, dirs = select_mode == 1 ? 2 : select_mode == 2 ? 3 : 1;
     int col_parts = 0;                                           // the FP4 single pass left the reverse direction as column keys
-    if (l2_norms) {                                              // SIFT rows: squared L2 distances on the int8 matrix cores
+    {
         StageTimer t(ctx, ST_MATCH_NN);
-        const int cx = desc_x_rows(cap);
-        const int dirs = select_mode == 0 ? 1 : select_mode == 1 ? 2 : 3;
-        if (select_mode == 3) launch_match_nn_l2i8(s, desc_x, l2_norms, kp_count, cap, cx, pb, P, 1, 1);
-        else launch_match_nn_l2i8(s, desc_x, l2_norms, kp_count, cap, cx, pb, P, dirs, 0);
-    } else {
-        StageTimer t(ctx, ST_MATCH_NN);
-        const int cx = desc_x_rows(cap);
-        const int dirs = select_mode == 0 ? 1 : select_mode == 1 ? 2 : 3;
-        // (the matrix-core kernel carries the column index inside its accumulator: fewer than 127^2 = 16129 rows per set)
-        if (ctx->matcher_kernel == 1 || cap >= 16129) {          // XOR + popcount on the packed descriptors
-            if (select_mode == 3) launch_match_nn_popcount(s, desc, kp_count, cap, pb, P, 1, 1);
-            else launch_match_nn_popcount(s, desc, kp_count, cap, pb, P, dirs, 0);
-        } else if (select_mode == 3) launch_match_nn(s, desc_x, kp_count, cap, cx, pb, P, 1, 1, descx_fp4);   // the image that was written,
-        else col_parts = launch_match_nn(s, desc_x, kp_count, cap, cx, pb, P, dirs, 0, descx_fp4);            // whatever the setter says now
+        if (l2_norms) launch_match_nn_l2i8(s, desc_x, l2_norms, kp_count, cap, desc_x_rows(cap), pb, P, dirs, knn2);   // SIFT rows: squared L2 distances
+        else col_parts = launch_hamming_nn(ctx, pb, desc, desc_x, descx_fp4, kp_count, cap, P, dirs, knn2);
     }
     { StageTimer t(ctx, ST_MATCH_SELECT); launch_match_select(s, kp_xy, kp_count, cap, pb, P, select_mode, ratio, ctx->dK, l2_norms ? 1 : 0, col_parts); }
     if (!do_geometry) return VO_OK;
@@ -1220,14 +1244,17 @@ extern "C" int vo_comm_allgather_f64(vo_ctx* ctx, const double* send, int n, dou
     HIPCHK(hipSetDevice(ctx->device));
     const int world = ctx->cs ? ctx->cs->world : 1;
     if (!ctx->cs) { memcpy(recv, send, (size_t)n * sizeof(double)); return VO_OK; }
-    int rc = ensure_raw_d(ctx, (size_t)n * (world + 1)); if (rc) return rc;
+    double *dsend, *drecv;
+    ScratchLayout sc;
+    sc.take(&dsend, n); sc.take(&drecv, (size_t)n * world);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(ctx->raw_d.p, send, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dsend, send, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
     rc = comm_bracket_begin(ctx); if (rc) return rc;
-    const char* e = rccl_all_gather_f64(ctx->cs->comm, ctx->raw_d.p, ctx->raw_d.p + n, (size_t)n, s);
+    const char* e = rccl_all_gather_f64(ctx->cs->comm, dsend, drecv, (size_t)n, s);
     if (e) FAIL(VO_ERR_HIP, "ncclAllGather failed: %s", e);
     rc = comm_bracket_end(ctx); if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(recv, ctx->raw_d.p + n, (size_t)n * world * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(recv, drecv, (size_t)n * world * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VO_OK;
 }
@@ -1251,6 +1278,23 @@ static int ensure_raw(vo_ctx* ctx, int cap)
     return VO_OK;
 }
 
+// Query and train descriptors into sets 0 and 1 of the single-call matcher, with their counts {nq, nt} (host memory that
+// outlives the upload) and the pair's slots.  Only the matrix cores get the operand image; *fp4 names it.
+static int upload_raw_pair(vo_ctx* ctx, const uint8_t* q, const uint8_t* t, const int* counts, int* fp4)
+{
+    static const int slots[2] = {0, 1};
+    int rc = ensure_raw(ctx, counts[0] > counts[1] ? counts[0] : counts[1]); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const int cap = ctx->raw_cap, kernel = nn_kernel(ctx, cap);
+    HIPCHK(hipMemcpyAsync(ctx->raw_desc, q, (size_t)counts[0] * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->raw_desc + (size_t)cap * 32, t, (size_t)counts[1] * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->raw_count, counts, 2 * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ctx->raw_pb.slots, slots, sizeof(slots), hipMemcpyHostToDevice, s));
+    *fp4 = kernel == NN_FP4;
+    if (kernel != NN_POPCOUNT) { StageTimer tm(ctx, ST_BRIEF); launch_desc_expand(s, ctx->raw_desc, ctx->raw_count, cap, desc_x_rows(cap), ctx->raw_desc_x, 2, *fp4); }
+    return VO_OK;
+}
+
 static int match_raw(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int select_mode, double ratio,
                      int32_t* qidx, int32_t* tidx, float* dist, int32_t* n_out)
 {
@@ -1263,20 +1307,14 @@ static int match_raw(vo_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, in
     if (select_mode == 1 && (size_t)align_up((nq > nt ? nq : nt) + (nq > nt ? nq : nt) / 4 + 64, 64) * 8 > 160 * 1024)
         FAIL(VO_ERR_INVALID, "cross_check = 1 (legacy rule) supports at most 16000 descriptors per set (LDS), got %d / %d", nq, nt);
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw(ctx, nq > nt ? nq : nt);
-    if (rc) return rc;
+    const int counts[2] = {nq, nt};
+    int fp4 = 0;
+    int rc = upload_raw_pair(ctx, q, t, counts, &fp4); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    const int cap = ctx->raw_cap;
-    const int counts[2] = {nq, nt}, slots[2] = {0, 1};
     const double Kid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    HIPCHK(hipMemcpyAsync(ctx->raw_desc, q, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_desc + (size_t)cap * 32, t, (size_t)nt * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_count, counts, sizeof(counts), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_pb.slots, slots, sizeof(slots), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ctx->dK, Kid, sizeof(Kid), hipMemcpyHostToDevice, s));
     RansacParams rp{};
-    { StageTimer tm(ctx, ST_BRIEF); launch_desc_expand(s, ctx->raw_desc, ctx->raw_count, cap, desc_x_rows(cap), ctx->raw_desc_x, 2, matcher_fp4(ctx, cap)); }
-    rc = run_pairs(ctx, ctx->raw_pb, ctx->raw_desc, ctx->raw_desc_x, ctx->raw_xy, ctx->raw_count, cap, 1, select_mode, ratio, rp, false, false, matcher_fp4(ctx, cap));
+    rc = run_pairs(ctx, ctx->raw_pb, ctx->raw_desc, ctx->raw_desc_x, ctx->raw_xy, ctx->raw_count, ctx->raw_cap, 1, select_mode, ratio, rp, false, false, fp4);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     int n = 0;
@@ -1311,14 +1349,12 @@ extern "C" int vo_match_l2(vo_ctx* ctx, const float* q, int nq, const float* t, 
     *n_out = 0;
     if (nq == 0 || nt == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t nf = (size_t)(nq + nt) * dim, ni = (size_t)2 * (nq + nt);
-    int rc = ensure_raw_d(ctx, (nf + ni) / 2 + 64 + (size_t)(nq + nt));
-    if (rc) return rc;
+    float *dq, *dt, *fd, *rd; int *fi, *ri; unsigned long long *fkey, *rkey;
+    ScratchLayout sc;
+    sc.take(&dq, (size_t)nq * dim); sc.take(&dt, (size_t)nt * dim);
+    sc.take(&fi, nq); sc.take(&ri, nt); sc.take(&fd, nq); sc.take(&rd, nt); sc.take(&fkey, nq); sc.take(&rkey, nt);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    float* dq = (float*)ctx->raw_d.p; float* dt = dq + (size_t)nq * dim;
-    int* fi = (int*)(dt + (size_t)nt * dim); int* ri = fi + nq;
-    float* fd = (float*)(ri + nt); float* rd = fd + nq;
-    unsigned long long* fkey = (unsigned long long*)((double*)ctx->raw_d.p + (nf + ni) / 2 + 32); unsigned long long* rkey = fkey + nq;
     HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dt, t, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice, s));
     {
@@ -1365,23 +1401,11 @@ extern "C" int vo_knn2_hamming(vo_ctx* ctx, const uint8_t* q, int nq, const uint
     if (nt == 0) { for (int i = 0; i < 2 * nq; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return VO_OK; }
     if (nq > 65535 || nt > 65535) FAIL(VO_ERR_INVALID, "at most 65535 descriptors per set");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw(ctx, nq > nt ? nq : nt);
-    if (rc) return rc;
+    const int counts[2] = {nq, nt};
+    int fp4 = 0;
+    int rc = upload_raw_pair(ctx, q, t, counts, &fp4); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    const int cap = ctx->raw_cap, cx = desc_x_rows(cap), fp4 = matcher_fp4(ctx, cap);
-    const int counts[2] = {nq, nt}, slots[2] = {0, 1};
-    HIPCHK(hipMemcpyAsync(ctx->raw_desc, q, (size_t)nq * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_desc + (size_t)cap * 32, t, (size_t)nt * 32, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_count, counts, sizeof(counts), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ctx->raw_pb.slots, slots, sizeof(slots), hipMemcpyHostToDevice, s));
-    {
-        StageTimer tm(ctx, ST_MATCH_NN);
-        if (ctx->matcher_kernel == 1 || cap >= 16129) launch_match_nn_popcount(s, ctx->raw_desc, ctx->raw_count, cap, ctx->raw_pb, 1, 1, 1);
-        else {
-            launch_desc_expand(s, ctx->raw_desc, ctx->raw_count, cap, cx, ctx->raw_desc_x, 2, fp4);
-            launch_match_nn(s, ctx->raw_desc_x, ctx->raw_count, cap, cx, ctx->raw_pb, 1, 1, 1, fp4);
-        }
-    }
+    { StageTimer tm(ctx, ST_MATCH_NN); launch_hamming_nn(ctx, ctx->raw_pb, ctx->raw_desc, ctx->raw_desc_x, fp4, ctx->raw_count, ctx->raw_cap, 1, 1, 1); }
     HIPCHK(hipGetLastError());
     std::vector<int> i0(nq), d0(nq), i1(nq), d1(nq);
     HIPCHK(hipMemcpyAsync(i0.data(), ctx->raw_pb.nn_idx, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1406,13 +1430,12 @@ extern "C" int vo_knn2_l2(vo_ctx* ctx, const float* q, int nq, const float* t, i
     if (nq == 0) return VO_OK;
     if (nt == 0) { for (int i = 0; i < 2 * nq; i++) { idx[i] = -1; dist[i] = FLT_MAX; } return VO_OK; }
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t nf = (size_t)(nq + nt) * dim, no = (size_t)4 * nq, nk = nn_l2_knn2_keys(nq, nt);
-    int rc = ensure_raw_d(ctx, (nf + no) / 2 + 64 + nk);
-    if (rc) return rc;
+    float *dq, *dt, *dd; int* di; unsigned long long* part;
+    ScratchLayout sc;
+    sc.take(&dq, (size_t)nq * dim); sc.take(&dt, (size_t)nt * dim); sc.take(&di, (size_t)2 * nq); sc.take(&dd, (size_t)2 * nq);
+    sc.take(&part, nn_l2_knn2_keys(nq, nt));
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    float* dq = (float*)ctx->raw_d.p; float* dt = dq + (size_t)nq * dim;
-    int* di = (int*)(dt + (size_t)nt * dim); float* dd = (float*)(di + 2 * nq);
-    unsigned long long* part = (unsigned long long*)((double*)ctx->raw_d.p + (nf + no) / 2 + 32);
     HIPCHK(hipMemcpyAsync(dq, q, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dt, t, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice, s));
     { StageTimer tm(ctx, ST_MATCH_NN); launch_nn_l2_knn2(s, dq, nq, dt, nt, dim, di, dd, part); }
@@ -1539,11 +1562,11 @@ extern "C" int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, c
     if (!P1 || !P2 || M < 0 || (M > 0 && (!x1 || !x2 || !X))) FAIL(VO_ERR_INVALID, "bad arguments");
     if (M == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw_d(ctx, 24 + (size_t)8 * M);
-    if (rc) return rc;
+    double *dP1, *dP2, *dx1, *dx2, *dX;
+    ScratchLayout sc;
+    sc.take(&dP1, 12); sc.take(&dP2, 12); sc.take(&dx1, (size_t)2 * M); sc.take(&dx2, (size_t)2 * M); sc.take(&dX, (size_t)4 * M);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d.p;
-    double *dP1 = d, *dP2 = d + 12, *dx1 = d + 24, *dx2 = dx1 + 2 * (size_t)M, *dX = dx2 + 2 * (size_t)M;
     HIPCHK(hipMemcpyAsync(dP1, P1, 12 * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dP2, P2, 12 * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dx1, x1, (size_t)2 * M * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1561,19 +1584,20 @@ extern "C" int vo_stage_five_point(vo_ctx* ctx, const double* x1, const double* 
     if (!ctx) return VO_ERR_INVALID;
     if (!x1 || !x2 || !E || !n_models) FAIL(VO_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw_d(ctx, 128);
-    if (rc) return rc;
+    double *dx1, *dx2, *dE; int* dnm;
+    ScratchLayout sc;
+    sc.take(&dx1, 10); sc.take(&dx2, 10); sc.take(&dE, 10 * 9); sc.take(&dnm, 1);   // at most 10 models
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d.p;
-    HIPCHK(hipMemcpyAsync(d, x1, 10 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d + 10, x2, 10 * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_five_point_raw(s, d, d + 10, d + 20, ctx->raw_i, ctx->dk_early);
+    HIPCHK(hipMemcpyAsync(dx1, x1, 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dx2, x2, 10 * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_five_point_raw(s, dx1, dx2, dE, dnm, ctx->dk_early);
     HIPCHK(hipGetLastError());
     int nm = 0;
-    HIPCHK(hipMemcpyAsync(&nm, ctx->raw_i, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nm, dnm, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     *n_models = nm;
-    if (nm > 0) HIPCHK(hipMemcpy(E, d + 20, (size_t)nm * 9 * sizeof(double), hipMemcpyDeviceToHost));
+    if (nm > 0) HIPCHK(hipMemcpy(E, dE, (size_t)nm * 9 * sizeof(double), hipMemcpyDeviceToHost));
     return VO_OK;
 }
 
@@ -1586,13 +1610,11 @@ extern "C" int vo_stage_retain_best(vo_ctx* ctx, const float* response, int n, i
     *n_out = 0;
     if (n == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw_d(ctx, (size_t)3 * n + 64);                 // floats + uint2 work + lpos + rpos + order, in doubles
-    if (rc) return rc;
+    uint2* work; float* dresp; uint32_t *lpos, *rpos; int *dorder, *dn;
+    ScratchLayout sc;
+    sc.take(&work, n); sc.take(&dresp, n); sc.take(&lpos, n); sc.take(&rpos, n); sc.take(&dorder, n); sc.take(&dn, 1);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    uint2* work = (uint2*)ctx->raw_d.p;
-    float* dresp = (float*)(work + n);
-    uint32_t* lpos = (uint32_t*)(dresp + n); uint32_t* rpos = lpos + n;
-    int* dorder = (int*)(rpos + n); int* dn = dorder + n;
     HIPCHK(hipMemcpyAsync(dresp, response, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
     launch_retain_raw(s, dresp, n, n_points, work, lpos, rpos, dorder, dn);
     HIPCHK(hipGetLastError());
@@ -1614,16 +1636,12 @@ extern "C" int vo_reprojection_filter(vo_ctx* ctx, const double* poses, int ncam
         FAIL(VO_ERR_INVALID, "bad arguments");
     if (nobs == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t nd = (size_t)16 * ncam + (size_t)3 * npt + (size_t)2 * nobs + 9 + (size_t)nobs + 64;
-    const size_t ni = (size_t)2 * nobs + 16;                       // ints, stored in the double scratch as well
-    int rc = ensure_raw_d(ctx, nd + ni / 2 + nobs / 8 + 64);
-    if (rc) return rc;
+    double *dposes, *dpoints, *dxy, *dK, *derr; int *dcam, *dpt, *dbad; uint8_t* dkeep;
+    ScratchLayout sc;
+    sc.take(&dposes, (size_t)16 * ncam); sc.take(&dpoints, (size_t)3 * npt); sc.take(&dxy, (size_t)2 * nobs); sc.take(&dK, 9);
+    sc.take(&derr, nobs); sc.take(&dcam, nobs); sc.take(&dpt, nobs); sc.take(&dbad, 1); sc.take(&dkeep, nobs);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* d = ctx->raw_d.p;
-    double *dposes = d, *dpoints = dposes + (size_t)16 * ncam, *dxy = dpoints + (size_t)3 * npt, *dK = dxy + (size_t)2 * nobs;
-    double* derr = dK + 16;
-    int* dcam = (int*)(derr + nobs + 8); int* dpt = dcam + nobs; int* dbad = dpt + nobs;
-    uint8_t* dkeep = (uint8_t*)(dbad + 8);
     HIPCHK(hipMemcpyAsync(dposes, poses, (size_t)16 * ncam * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dpoints, points, (size_t)3 * npt * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dxy, obs_xy, (size_t)2 * nobs * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1656,14 +1674,12 @@ extern "C" int vo_solve_pnp_ransac_batch(vo_ctx* ctx, const double* obj, const d
     if (total > 0 && (!obj || !img || !mask)) FAIL(VO_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(ctx->device));
     int rc = ensure_rng(ctx, seed); if (rc) return rc;
-    // doubles: obj 3T, img 2T, K 9, rvec 3B, tvec 3B; then ints: offsets B+1, ninl B, status B; then mask T bytes
-    const size_t nd = (size_t)5 * total + 9 + (size_t)6 * B, ni = (size_t)3 * B + 1;
-    rc = ensure_raw_d(ctx, nd + (ni + 1) / 2 + (size_t)(total + 7) / 8 + 8); if (rc) return rc;
+    double *dobj, *dimg, *dK, *drv, *dtv; int *doff, *dninl, *dst; uint8_t* dmask;
+    ScratchLayout sc;
+    sc.take(&dobj, (size_t)3 * total); sc.take(&dimg, (size_t)2 * total); sc.take(&dK, 9); sc.take(&drv, (size_t)3 * B); sc.take(&dtv, (size_t)3 * B);
+    sc.take(&doff, (size_t)B + 1); sc.take(&dninl, B); sc.take(&dst, B); sc.take(&dmask, total);
+    rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    double* dobj = ctx->raw_d.p; double* dimg = dobj + (size_t)3 * total; double* dK = dimg + (size_t)2 * total;
-    double* drv = dK + 9; double* dtv = drv + (size_t)3 * B;
-    int* doff = (int*)(dtv + (size_t)3 * B); int* dninl = doff + B + 1; int* dst = dninl + B;
-    uint8_t* dmask = (uint8_t*)(dst + B + ((3 * B + 1) & 1));
     std::vector<int> off(B + 1);
     for (int b = 0; b <= B; b++) off[b] = offsets[b] - offsets[0];
     if (total > 0) {
@@ -1710,12 +1726,15 @@ extern "C" int vo_rodrigues(vo_ctx* ctx, const double* in, int in_is_matrix, dou
     if (!ctx) return VO_ERR_INVALID;
     if (!in || !out) FAIL(VO_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_raw_d(ctx, 32); if (rc) return rc;
+    double *din, *dout;
+    ScratchLayout sc;
+    sc.take(&din, 9); sc.take(&dout, 9);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(ctx->raw_d.p, in, (in_is_matrix ? 9 : 3) * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_rodrigues(s, ctx->raw_d.p, in_is_matrix, ctx->raw_d.p + 16);
+    HIPCHK(hipMemcpyAsync(din, in, (in_is_matrix ? 9 : 3) * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_rodrigues(s, din, in_is_matrix, dout);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, ctx->raw_d.p + 16, (in_is_matrix ? 3 : 9) * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, dout, (in_is_matrix ? 3 : 9) * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VO_OK;
 }
@@ -1820,11 +1839,10 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
     std::vector<int> hxs, hys, hxst, hyst; std::vector<float> hxa, hya;
     if (!fast) {
         const int nx = area_tab(sw, dw, scale_x, hxs, hxa, hxst), ny = area_tab(sh, dh, scale_y, hys, hya, hyst);
-        const size_t n = (size_t)2 * nx + 2 * ny + dw + dh + 2;
-        rc = ctx->ingest_tab.grow(ctx, n); if (rc) return rc;
-        int* d = ctx->ingest_tab.p;
-        int* dxs = d; float* dxa = (float*)(d + nx); int* dxst = d + 2 * nx;
-        int* dys = dxst + dw + 1; float* dya = (float*)(dys + ny); int* dyst = dys + 2 * ny;
+        int *dxs, *dxst, *dys, *dyst; float *dxa, *dya;
+        ScratchLayout sc;
+        sc.take(&dxs, nx); sc.take(&dxa, nx); sc.take(&dxst, (size_t)dw + 1); sc.take(&dys, ny); sc.take(&dya, ny); sc.take(&dyst, (size_t)dh + 1);
+        rc = sc.place(ctx); if (rc) return rc;
         HIPCHK(hipMemcpyAsync(dxs, hxs.data(), (size_t)nx * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(dxa, hxa.data(), (size_t)nx * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(dxst, hxst.data(), (size_t)(dw + 1) * 4, hipMemcpyHostToDevice, s));
@@ -2101,16 +2119,11 @@ extern "C" int vo_sift_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h
     if (nw > 0) {
         rc = sift_describe_enqueue(ctx, S, 0, 1); if (rc) return rc;
         HIPCHK(hipStreamSynchronize(s));
-        if (kp_xy) HIPCHK(hipMemcpy(kp_xy, S.kp_xy, (size_t)nw * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_size) HIPCHK(hipMemcpy(kp_size, S.kp_size, (size_t)nw * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_angle) HIPCHK(hipMemcpy(kp_angle, S.kp_angle, (size_t)nw * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_response) HIPCHK(hipMemcpy(kp_response, S.kp_resp, (size_t)nw * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_octave) HIPCHK(hipMemcpy(kp_octave, S.kp_oct, (size_t)nw * sizeof(int), hipMemcpyDeviceToHost));
-        if (desc) {
-            std::vector<uint8_t> d8((size_t)nw * 128);
-            HIPCHK(hipMemcpy(d8.data(), S.desc, d8.size(), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < d8.size(); i++) desc[i] = (float)d8[i];     // cv2 hands the integer bin values out as float32
-        }
+        std::vector<uint8_t> d8(desc ? (size_t)nw * 128 : 0);
+        rc = download_keypoints(ctx, {S.kp_xy, S.kp_size, S.kp_angle, S.kp_resp, S.kp_oct, S.desc, 128}, 0, nw,
+                                kp_xy, kp_size, kp_angle, kp_response, kp_octave, desc ? d8.data() : nullptr);
+        if (rc) return rc;
+        for (size_t i = 0; i < d8.size(); i++) desc[i] = (float)d8[i];         // cv2 hands the integer bin values out as float32
     }
     if (ctx->prof) prof_collect(ctx);
     if (m > cap) warn = VO_WARN_CAPACITY;
@@ -2181,15 +2194,9 @@ extern "C" int vo_frame_features_sift(vo_ctx* ctx, int slot, float* kp_xy, float
     if (n > S.kp_cap) n = S.kp_cap;
     if (n > cap) { n = cap; warn = VO_WARN_CAPACITY; }
     *n_out = n;
-    const size_t o = (size_t)slot * S.kp_cap;
-    if (n > 0) {
-        if (kp_xy) HIPCHK(hipMemcpy(kp_xy, S.kp_xy + o * 2, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_size) HIPCHK(hipMemcpy(kp_size, S.kp_size + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_angle) HIPCHK(hipMemcpy(kp_angle, S.kp_angle + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_response) HIPCHK(hipMemcpy(kp_response, S.kp_resp + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-        if (kp_octave) HIPCHK(hipMemcpy(kp_octave, S.kp_oct + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-        if (desc) HIPCHK(hipMemcpy(desc, S.desc + o * 128, (size_t)n * 128, hipMemcpyDeviceToHost));
-    }
+    const int rc = download_keypoints(ctx, {S.kp_xy, S.kp_size, S.kp_angle, S.kp_resp, S.kp_oct, S.desc, 128}, (size_t)slot * S.kp_cap, n,
+                                      kp_xy, kp_size, kp_angle, kp_response, kp_octave, desc);
+    if (rc) return rc;
     if (flags & 2) FAIL(VO_ERR_INVALID, "a SIFT descriptor row broke the norm bound of the integer matcher (slot %d)", slot);
     return warn;
 }
@@ -2424,13 +2431,12 @@ extern "C" int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pai
             FAIL(VO_ERR_INVALID, "match %d refers to a missing feature", i);
     HIPCHK(hipSetDevice(ctx->device));
     const size_t fc = (size_t)F * cap;
-    const size_t n_int = (size_t)2 * P + (P + 1) + (size_t)2 * total + 3 * fc + 16;
-    int rc = ensure_raw_d(ctx, fc + n_int / 2 + 64);                 // parents (u64) + the int arrays
-    if (rc) return rc;
+    unsigned long long* dparent; int *dpf, *doff, *dq, *dt, *drf, *dri, *dh, *dbad;
+    ScratchLayout sc;
+    sc.take(&dparent, fc); sc.take(&dpf, (size_t)2 * P); sc.take(&doff, (size_t)P + 1); sc.take(&dq, total); sc.take(&dt, total);
+    sc.take(&drf, fc); sc.take(&dri, fc); sc.take(&dh, fc); sc.take(&dbad, 1);
+    int rc = sc.place(ctx); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    unsigned long long* dparent = (unsigned long long*)ctx->raw_d.p;
-    int* di = (int*)(dparent + fc);
-    int *dpf = di, *doff = dpf + 2 * P, *dq = doff + P + 1, *dt = dq + total, *drf = dt + total, *dri = drf + fc, *dh = dri + fc, *dbad = dh + fc;
     HIPCHK(hipMemsetAsync(dparent, 0, fc * sizeof(unsigned long long), s));
     HIPCHK(hipMemsetAsync(dbad, 0, sizeof(int), s));
     if (P > 0) {
@@ -2489,24 +2495,15 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
     HIPCHK(hipSetDevice(ctx->device));
     int rc = ensure_rng(ctx, seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
-    // one allocation, carved up (8-byte quantities first)
     const size_t fc = (size_t)F * cap;
-    size_t need = 0;
-    auto take = [&](size_t bytes) { const size_t o = need; need += (bytes + 15) & ~(size_t)15; return o; };
-    const size_t o_parent = take(fc * 8), o_pt = take(fc * 24), o_cam = take((size_t)F * 96), o_obj = take((size_t)cap * 24), o_img = take((size_t)cap * 16),
-                 o_rv = take(24), o_tv = take(24), o_P1 = take(96), o_P2 = take(96), o_Xw = take((size_t)cap * 32), o_poses = take((size_t)(B + 1) * 96), o_K = take(72),
-                 o_inmap = take(fc), o_camok = take((size_t)F * 4), o_off = take(8), o_pmask = take((size_t)cap), o_pninl = take(4), o_pst = take(4),
-                 o_alive = take(4), o_ncorr = take((size_t)B * 4), o_ninl = take((size_t)B * 4), o_st = take((size_t)B * 4), o_nmap = take((size_t)B * 4), o_mc = take(4);
-    rc = ctx->chain_mem.grow(ctx, need); if (rc) return rc;
-    uint8_t* m = ctx->chain_mem.p;
-    ChainBuf cb;
-    cb.parent = (unsigned long long*)(m + o_parent); cb.map_pt = (double*)(m + o_pt); cb.cam = (double*)(m + o_cam); cb.obj = (double*)(m + o_obj);
-    cb.img = (double*)(m + o_img); cb.rvec = (double*)(m + o_rv); cb.tvec = (double*)(m + o_tv); cb.P1 = (double*)(m + o_P1); cb.P2 = (double*)(m + o_P2);
-    cb.Xw = (double*)(m + o_Xw); cb.poses = (double*)(m + o_poses); double* dK = (double*)(m + o_K);
-    cb.in_map = m + o_inmap; cb.cam_ok = (int*)(m + o_camok); cb.off = (int*)(m + o_off); cb.pmask = m + o_pmask; cb.pninl = (int*)(m + o_pninl);
-    cb.pstatus = (int*)(m + o_pst); cb.alive = (int*)(m + o_alive); cb.n_corr = (int*)(m + o_ncorr); cb.n_inl = (int*)(m + o_ninl);
-    cb.status = (int*)(m + o_st); cb.n_map = (int*)(m + o_nmap); cb.map_count = (int*)(m + o_mc);
-    HIPCHK(hipMemsetAsync(m, 0, need, s));                           // empty feature_mapper, empty map, no cameras
+    ChainBuf cb; double* dK;
+    ScratchLayout sc;
+    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
+    sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4); sc.take(&cb.poses, (size_t)(B + 1) * 12);
+    sc.take(&dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
+    sc.take(&cb.alive, 1); sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&cb.map_count, 1);
+    rc = sc.place(ctx); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty map, no cameras
     HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
     {
         StageTimer t(ctx, ST_MISC);

@@ -51,19 +51,12 @@ class OrbDetector:
             raise TypeError("image must be a uint8 array of shape HxW, HxWx3 (BGR) or HxWx4 (BGRA)")
         h, w = img.shape[:2]
         ch = 1 if img.ndim == 2 else img.shape[2]
-        cap = self.capacity()
-        xy = np.empty((cap, 2), np.float32); size = np.empty(cap, np.float32); ang = np.empty(cap, np.float32)
-        resp = np.empty(cap, np.float32); octv = np.empty(cap, np.int32); desc = np.empty((cap, 32), np.uint8)
-        n = C.c_int32(0)
+        kp = _lib.KeypointBuffers(self.capacity(), 32)
         ctx = self.ctx
         ctx.set_keypoint_order(self.keypoint_order)
         rc = ctx.check(ctx.lib.vo_orb_detect_and_compute(
-            ctx.handle, img.ctypes.data, h, w, ch, img.strides[0], C.addressof(self.params),
-            xy.ctypes.data, size.ctypes.data, ang.ctypes.data, resp.ctypes.data, octv.ctypes.data,
-            desc.ctypes.data, cap, C.addressof(n)))
-        k = n.value
-        return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
-                    octave=octv[:k].copy(), desc=desc[:k].copy(), truncated=(rc == _lib.VO_WARN_CAPACITY))
+            ctx.handle, img.ctypes.data, h, w, ch, img.strides[0], C.addressof(self.params), *kp.args()))
+        return kp.result(rc)
 
     def detectAndCompute(self, image, mask=None):
         if mask is not None:
@@ -135,21 +128,16 @@ class SiftDetector:
         ch = 1 if img.ndim == 2 else img.shape[2]
         ctx = self.ctx
         while True:
-            xy = np.empty((cap, 2), np.float32); size = np.empty(cap, np.float32); ang = np.empty(cap, np.float32)
-            resp = np.empty(cap, np.float32); octv = np.empty(cap, np.int32); desc = np.empty((cap, 128), np.float32)
-            n = C.c_int32(0)
+            kp = _lib.KeypointBuffers(cap, 128, np.float32)
             rc = ctx.lib.vo_sift_detect_and_compute(ctx.handle, img.ctypes.data, h, w, ch, img.strides[0], C.addressof(self.params),
-                                                    xy.ctypes.data, size.ctypes.data, ang.ctypes.data, resp.ctypes.data, octv.ctypes.data,
-                                                    desc.ctypes.data, cap, C.addressof(n))
+                                                    *kp.args())
             if rc == _lib.VO_ERR_UNSUPPORTED:
                 raise NotImplementedError(ctx.last_error())
             ctx.check(rc)
-            if n.value <= cap or cap >= (1 << 18):
+            if kp.n.value <= cap or cap >= (1 << 18):
                 break
             cap = 1 << 18                                      # the device lists' own capacity
-        k = min(n.value, cap)
-        return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(), octave=octv[:k].copy(),
-                    desc=desc[:k].copy(), truncated=(rc == _lib.VO_WARN_CAPACITY))
+        return kp.result(rc)
 
     def detectAndCompute(self, image, mask=None):
         if mask is not None:

@@ -116,19 +116,12 @@ class FrontEnd:
     def features(self, slot):
         """Keypoints and descriptors of a detected slot.  ORB: desc [n, 32] uint8; SIFT: desc [n, 128] float32 (the integer bin
         values 0..255 cv2 returns as floats)."""
-        cap = self.kp_cap
         sift = self.detector == "sift"
-        xy = np.empty((cap, 2), np.float32); size = np.empty(cap, np.float32); ang = np.empty(cap, np.float32)
-        resp = np.empty(cap, np.float32); octv = np.empty(cap, np.int32); desc = np.empty((cap, 128 if sift else 32), np.uint8)
-        n = C.c_int32(0)
+        kp = _lib.KeypointBuffers(self.kp_cap, 128 if sift else 32)
         c = self.ctx
         fn = c.lib.vo_frame_features_sift if sift else c.lib.vo_frame_features
-        rc = c.check(fn(c.handle, int(slot), xy.ctypes.data, size.ctypes.data, ang.ctypes.data,
-                        resp.ctypes.data, octv.ctypes.data, desc.ctypes.data, cap, C.addressof(n)))
-        k = n.value
-        d = desc[:k].astype(np.float32) if sift else desc[:k].copy()
-        return dict(xy=xy[:k].copy(), size=size[:k].copy(), angle=ang[:k].copy(), response=resp[:k].copy(),
-                    octave=octv[:k].copy(), desc=d, truncated=(rc == _lib.VO_WARN_CAPACITY))
+        rc = c.check(fn(c.handle, int(slot), *kp.args()))
+        return kp.result(rc, np.float32 if sift else None)
 
     def make_opts(self, match_mode=MATCH_CROSSCHECK, ratio=0.75, prob=0.99, thresh=1.0, max_iters=1000,
                   seed=OPENCV_RNG_SEED, dist_thresh=50.0, want_points=False):

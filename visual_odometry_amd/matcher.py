@@ -39,15 +39,8 @@ class HammingMatcher:
 
     def match_arrays(self, query, train):
         q, t = _desc(query), _desc(train)
-        nq = len(q)
-        qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
-        n = C.c_int32(0)
         mode = 0 if not self.crossCheck else (1 if self.legacy_crosscheck else 2)
-        ctx = self.ctx
-        ctx.check(ctx.lib.vo_match_hamming(ctx.handle, q.ctypes.data, nq, t.ctypes.data, len(t), mode,
-                                           qi.ctypes.data, ti.ctypes.data, d.ctypes.data, C.addressof(n)))
-        k = n.value
-        return qi[:k].copy(), ti[:k].copy(), d[:k].copy()
+        return _matches(self.ctx, "vo_match_hamming", q, t, mode)
 
     def match(self, queryDescriptors, trainDescriptors):
         qi, ti, d = self.match_arrays(queryDescriptors, trainDescriptors)
@@ -55,14 +48,7 @@ class HammingMatcher:
 
     def ratio_match_arrays(self, query, train, ratio):
         q, t = _desc(query), _desc(train)
-        nq = len(q)
-        qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
-        n = C.c_int32(0)
-        ctx = self.ctx
-        ctx.check(ctx.lib.vo_knn2_ratio_hamming(ctx.handle, q.ctypes.data, nq, t.ctypes.data, len(t), float(ratio),
-                                                qi.ctypes.data, ti.ctypes.data, d.ctypes.data, C.addressof(n)))
-        k = n.value
-        return qi[:k].copy(), ti[:k].copy(), d[:k].copy()
+        return _matches(self.ctx, "vo_knn2_ratio_hamming", q, t, float(ratio))
 
     def ratio_match(self, queryDescriptors, trainDescriptors, ratio=0.75):
         """knnMatch(k=2) followed by `m.distance < ratio * n.distance` (feature_detection.py:24-26)."""
@@ -99,19 +85,9 @@ class L2Matcher:
         return self._ctx
 
     def match_arrays(self, query, train):
-        q = np.ascontiguousarray(query, dtype=np.float32); t = np.ascontiguousarray(train, dtype=np.float32)
-        if q.ndim != 2 or t.ndim != 2 or (len(q) and len(t) and q.shape[1] != t.shape[1]):
-            raise ValueError("descriptors must be N x dim float32 arrays of equal dim")
-        nq = len(q)
-        dim = q.shape[1] if nq else (t.shape[1] if len(t) else 1)
-        qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
-        n = C.c_int32(0)
+        q, t, dim = self._rows(query, train)
         mode = 0 if not self.crossCheck else (1 if self.legacy_crosscheck else 2)
-        ctx = self.ctx
-        ctx.check(ctx.lib.vo_match_l2(ctx.handle, q.ctypes.data, nq, t.ctypes.data, len(t), int(dim), mode,
-                                      qi.ctypes.data, ti.ctypes.data, d.ctypes.data, C.addressof(n)))
-        k = n.value
-        return qi[:k].copy(), ti[:k].copy(), d[:k].copy()
+        return _matches(self.ctx, "vo_match_l2", q, t, dim, mode)
 
     def match(self, queryDescriptors, trainDescriptors):
         qi, ti, d = self.match_arrays(queryDescriptors, trainDescriptors)
@@ -131,14 +107,7 @@ class L2Matcher:
 
     def ratio_match_arrays(self, query, train, ratio):
         q, t, dim = self._rows(query, train)
-        nq = len(q)
-        qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
-        n = C.c_int32(0)
-        ctx = self.ctx
-        ctx.check(ctx.lib.vo_knn2_ratio_l2(ctx.handle, q.ctypes.data, nq, t.ctypes.data, len(t), dim, float(ratio),
-                                           qi.ctypes.data, ti.ctypes.data, d.ctypes.data, C.addressof(n)))
-        k = n.value
-        return qi[:k].copy(), ti[:k].copy(), d[:k].copy()
+        return _matches(self.ctx, "vo_knn2_ratio_l2", q, t, dim, float(ratio))
 
     def ratio_match(self, queryDescriptors, trainDescriptors, ratio=0.75):
         """knnMatch(k=2) followed by `m.distance < ratio * n.distance` (feature_detection.py:24-26) in one call."""
@@ -151,6 +120,18 @@ class L2Matcher:
         if q.ndim != 2 or t.ndim != 2 or (len(q) and len(t) and q.shape[1] != t.shape[1]):
             raise ValueError("descriptors must be N x dim float32 arrays of equal dim")
         return q, t, int(q.shape[1] if len(q) else (t.shape[1] if len(t) else 1))
+
+
+def _matches(ctx, fn, q, t, *args):
+    """The matcher entry point `fn` on query rows q and train rows t (then its own args): (query idx, train idx, distance) of
+    its matches, at most one per query row."""
+    nq = len(q)
+    qi = np.empty(max(nq, 1), np.int32); ti = np.empty(max(nq, 1), np.int32); d = np.empty(max(nq, 1), np.float32)
+    n = C.c_int32(0)
+    ctx.check(getattr(ctx.lib, fn)(ctx.handle, q.ctypes.data, nq, t.ctypes.data, len(t), *args,
+                                   qi.ctypes.data, ti.ctypes.data, d.ctypes.data, C.addressof(n)))
+    k = n.value
+    return qi[:k].copy(), ti[:k].copy(), d[:k].copy()
 
 
 def _knn_rows(arrays, k, cross_check):
