@@ -377,6 +377,42 @@ int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pair_frames, c
 int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iterations, double reproj_err, double confidence, uint64_t seed,
                         double max_point_norm, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_map);
 
+/* ------------------------------------------------------------------ bundle adjustment
+ * Map.optimize_map — src/map.py:104-186, called at the end of every frame (src/visual_slam.py:90, :265, :367): g2o's
+ * Levenberg-Marquardt over VertexSE3Expmap cameras (fixed where cam_fixed is set), marginalised VertexPointXYZ points and
+ * one EdgeProjectXYZ2UV per observation with information I, RobustKernelHuber(huber_delta) and
+ * CameraParameters(focal, (cx, cy), 0) — ONE focal length, as the reference passes camera_matrix[0, 0] only (map.py:113).
+ * OptimizationAlgorithmLevenberg over BlockSolverSE3: tau 1e-5, lambda from the first linearisation, at most 10 trials per
+ * iteration, Schur complement on the points, exactly `iterations` iterations unless 10 trials fail, rho == 0 or lambda
+ * overflows (there is no convergence test).  g2o is not vendored: this restates its 2020 sources (g2o-python 0.0.11) from
+ * memory; parity with a g2o build is unpinned, the checker is the numpy restatement tests/ba_reference.py.
+ * B independent problems, one workgroup each: problem b owns cameras cam_off[b] .. cam_off[b+1], points pt_off[b] ..,
+ * observations obs_off[b] ..; obs_cam / obs_pt are indices LOCAL to the problem.  poses: [camera][12] world -> camera
+ * [R | t] (3 x 4 row-major), in / out; points: [point][3], in / out (map.py:175-186 writes both back).  A fixed camera
+ * and a point without observations keep their input bytes; a free camera's R comes back from the unit quaternion g2o
+ * keeps.  chi2: [B][2] = activeRobustChi2 before and after; iterations_run / trials_run: LM iterations started and linear
+ * solves attempted.  Two calls on the same input return the same bytes (every sum has a fixed order).
+ * status[b]: VO_OK; VO_ERR_UNSUPPORTED for a problem with more than VO_BA_MAX_CAMERAS cameras or VO_BA_MAX_FREE free ones
+ * (a map that large needs a multi-workgroup solver); VO_ERR_INVALID for an observation that names a missing camera or
+ * point.  Such a problem's data come back unchanged and the rest of the batch is solved.
+ * vo_bundle_adjust: one problem; a negative status is the return value. */
+#define VO_BA_MAX_CAMERAS 64
+#define VO_BA_MAX_FREE    16
+typedef struct {
+    int32_t iterations;     /* 40 (map.py:171), at most 1000 */
+    int32_t reserved;
+    double  huber_delta;    /* 1.0 (g2o's RobustKernelHuber default); <= 0: no robust kernel */
+} vo_ba_opts;
+int vo_bundle_adjust_batch(vo_ctx* ctx, int B, const int32_t* cam_off, const int32_t* pt_off, const int32_t* obs_off,
+                           double* poses, const uint8_t* cam_fixed, double* points, const int32_t* obs_cam,
+                           const int32_t* obs_pt, const double* obs_xy, double focal, double cx, double cy,
+                           const vo_ba_opts* opts, double* chi2, int32_t* iterations_run, int32_t* trials_run,
+                           int32_t* status);
+int vo_bundle_adjust(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int ncam, double* points, int npt,
+                     const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs,
+                     double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2 /* [2] */,
+                     int32_t* iterations_run, int32_t* trials_run);
+
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since

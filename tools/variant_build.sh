@@ -11,7 +11,7 @@ i=0
 for fl in "$@"; do
   i=$((i+1))
   hipcc -O3 -fPIC -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Wno-unused-function $fl -c $src.hip -o /tmp/var_$src.o || exit 1
-  objs=""; for f in vo_api orb_kernels match_kernels geom_kernels pnp_kernels cv2order_kernels gather_rccl jpeg_kernels sift_batch jpeg_host; do
+  objs=""; for f in vo_api orb_kernels match_kernels geom_kernels pnp_kernels ba_kernels cv2order_kernels gather_rccl jpeg_kernels sift_batch jpeg_host; do
     if [ $f = $src ]; then objs="$objs /tmp/var_$src.o"; else objs="$objs $f.o"; fi; done
   hipcc -shared -fPIC --offload-arch=gfx950 -o /tmp/libvo_var$i.so $objs -ldl || exit 1
   echo "== $src $fl"

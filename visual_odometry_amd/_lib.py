@@ -18,6 +18,7 @@ VO_ERR_INVALID, VO_ERR_HIP, VO_ERR_TOO_FEW, VO_ERR_NO_MODEL, VO_ERR_NOT_CONFIGUR
 VO_ERR_UNSUPPORTED = -7
 VO_STAGE_COUNT = 24
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
+VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
 
 
 class OrbParams(C.Structure):
@@ -35,6 +36,10 @@ class PairOpts(C.Structure):
     _fields_ = [("match_mode", C.c_int32), ("ratio", C.c_double), ("ransac_prob", C.c_double),
                 ("ransac_thresh", C.c_double), ("ransac_max_iters", C.c_int32), ("ransac_seed", C.c_uint64),
                 ("pose_dist_thresh", C.c_double), ("want_points", C.c_int32)]
+
+
+class BaOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("huber_delta", C.c_double)]
 
 
 PAIR_RESULT_DTYPE = np.dtype([("n_kp1", "<i4"), ("n_kp2", "<i4"), ("n_match", "<i4"), ("n_inl", "<i4"),
@@ -91,6 +96,8 @@ _SIGS = {
     "vo_comm_allgather_f64": (C.c_int, [_P, _P, C.c_int, _P]),
     "vo_pair_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "vo_reprojection_filter": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_double, _P, _P]),
+    "vo_bundle_adjust_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    "vo_bundle_adjust": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P, _P]),
     "vo_rodrigues": (C.c_int, [_P, _P, C.c_int, _P]),

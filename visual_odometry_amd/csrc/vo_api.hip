@@ -1661,6 +1661,143 @@ extern "C" int vo_reprojection_filter(vo_ctx* ctx, const double* poses, int ncam
     return VO_OK;
 }
 
+// ------------------------------------------------------------------ bundle adjustment: Map.optimize_map, src/map.py:104-186
+// The host's part is the bookkeeping g2o's graph does: reject what the kernel cannot hold, sort each problem's observations
+// by point (counting sort, stable in input order: a lane owns a point) and list, per block (c1 <= c2) of free cameras, the
+// observation pairs that share a point (a wave owns a block of the Schur complement).
+extern "C" int vo_bundle_adjust_batch(vo_ctx* ctx, int B, const int32_t* cam_off, const int32_t* pt_off, const int32_t* obs_off,
+                                      double* poses, const uint8_t* cam_fixed, double* points, const int32_t* obs_cam,
+                                      const int32_t* obs_pt, const double* obs_xy, double focal, double cx, double cy,
+                                      const vo_ba_opts* opts, double* chi2, int32_t* iterations_run, int32_t* trials_run,
+                                      int32_t* status)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (B < 0 || !opts || (B > 0 && (!cam_off || !pt_off || !obs_off || !chi2 || !iterations_run || !trials_run || !status)))
+        FAIL(VO_ERR_INVALID, "bad arguments");
+    if (opts->iterations < 0 || opts->iterations > 1000) FAIL(VO_ERR_INVALID, "iterations must be 0 .. 1000, got %d", opts->iterations);
+    if (!(focal == focal) || !(cx == cx) || !(cy == cy) || !(opts->huber_delta == opts->huber_delta)) FAIL(VO_ERR_INVALID, "camera parameters must be numbers");
+    if (B == 0) return VO_OK;
+    if (cam_off[0] < 0 || pt_off[0] < 0 || obs_off[0] < 0) FAIL(VO_ERR_INVALID, "offsets must not be negative");
+    for (int b = 0; b < B; b++)
+        if (cam_off[b + 1] < cam_off[b] || pt_off[b + 1] < pt_off[b] || obs_off[b + 1] < obs_off[b]) FAIL(VO_ERR_INVALID, "offsets must not decrease");
+    const int c0 = cam_off[0], p0 = pt_off[0], o0 = obs_off[0];
+    const int ncam = cam_off[B] - c0, npt = pt_off[B] - p0, nobs = obs_off[B] - o0;
+    if ((ncam > 0 && (!poses || !cam_fixed)) || (npt > 0 && !points) || (nobs > 0 && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
+
+    std::vector<BaProblem> prob(B);
+    std::vector<int> col(ncam, -1), pt_first((size_t)npt + B, 0), s_cam(nobs), s_pt(nobs), blk_first, fill;
+    std::vector<double> s_xy((size_t)2 * nobs);
+    std::vector<int2> pairs;
+    int max_free = 0;
+    for (int b = 0; b < B; b++) {
+        BaProblem& q = prob[b];
+        q.cam0 = cam_off[b] - c0; q.pt0 = pt_off[b] - p0; q.obs0 = obs_off[b] - o0;
+        q.ncam = cam_off[b + 1] - cam_off[b]; q.npt = pt_off[b + 1] - pt_off[b]; q.nobs = obs_off[b + 1] - obs_off[b];
+        q.pair0 = (int)pairs.size(); q.blk0 = (int)blk_first.size(); q.nfree = 0; q.skip = 0;
+        status[b] = VO_OK; chi2[2 * b] = chi2[2 * b + 1] = 0; iterations_run[b] = trials_run[b] = 0;
+        const uint8_t* fx = cam_fixed + cam_off[b];
+        for (int i = 0; i < q.ncam; i++) if (!fx[i]) q.nfree++;
+        const int32_t* oc = obs_cam + obs_off[b]; const int32_t* op = obs_pt + obs_off[b];
+        if (q.ncam > VO_BA_MAX_CAMERAS || q.nfree > VO_BA_MAX_FREE) status[b] = VO_ERR_UNSUPPORTED;
+        else for (int i = 0; i < q.nobs; i++) if (oc[i] < 0 || oc[i] >= q.ncam || op[i] < 0 || op[i] >= q.npt) { status[b] = VO_ERR_INVALID; break; }
+        if (status[b] != VO_OK) { q.skip = 1; q.nfree = 0; continue; }
+        int* cl = col.data() + q.cam0;
+        for (int i = 0, f = 0; i < q.ncam; i++) if (!fx[i]) cl[i] = f++;
+        max_free = std::max(max_free, q.nfree);
+        // counting sort by point
+        int* first = pt_first.data() + q.pt0 + b;
+        for (int i = 0; i < q.nobs; i++) first[op[i] + 1]++;
+        for (int p = 0; p < q.npt; p++) first[p + 1] += first[p];
+        fill.assign(first, first + q.npt);
+        for (int i = 0; i < q.nobs; i++) {
+            const int j = q.obs0 + fill[op[i]]++;
+            s_cam[j] = oc[i]; s_pt[j] = op[i];
+            s_xy[2 * (size_t)j] = obs_xy[2 * ((size_t)obs_off[b] + i)]; s_xy[2 * (size_t)j + 1] = obs_xy[2 * ((size_t)obs_off[b] + i) + 1];
+        }
+        // pair lists per block, blocks in the order (0,0) (0,1) .. (0,F-1) (1,1) ..; within a block by point, then input order
+        const int F = q.nfree, nblk = F * (F + 1) / 2;
+        auto blk = [F](int a, int c) { return a * F - a * (a - 1) / 2 + (c - a); };
+        std::vector<size_t> cnt((size_t)nblk + 1, 0);
+        const int* sc = s_cam.data() + q.obs0;
+        for (int pass = 0; pass < 2; pass++) {
+            for (int p = 0; p < q.npt; p++)
+                for (int j1 = first[p]; j1 < first[p + 1]; j1++) {
+                    const int a = cl[sc[j1]]; if (a < 0) continue;
+                    for (int j2 = first[p]; j2 < first[p + 1]; j2++) {
+                        const int c = cl[sc[j2]]; if (c < a) continue;
+                        if (pass == 0) cnt[blk(a, c) + 1]++;
+                        else pairs[(size_t)q.pair0 + cnt[blk(a, c)]++] = make_int2(j1, j2);
+                    }
+                }
+            if (pass == 0) {
+                for (int k = 0; k < nblk; k++) cnt[k + 1] += cnt[k];
+                if ((size_t)q.pair0 + cnt[nblk] > (size_t)INT32_MAX) FAIL(VO_ERR_INVALID, "problem %d: too many observation pairs", b);
+                for (int k = 0; k <= nblk; k++) blk_first.push_back((int)cnt[k]);
+                pairs.resize((size_t)q.pair0 + cnt[nblk]);
+            }
+        }
+    }
+
+    HIPCHK(hipSetDevice(ctx->device));
+    BaBuf D{};
+    BaProblem* dprob; int *dcol, *dptf, *dcam, *dpt, *dblk; double* dxy; int2* dpairs;
+    ScratchLayout sc;
+    sc.take(&dprob, B); sc.take(&D.poses, (size_t)12 * ncam); sc.take(&dcol, ncam); sc.take(&D.X, (size_t)3 * npt); sc.take(&D.X2, (size_t)3 * npt);
+    sc.take(&dptf, pt_first.size()); sc.take(&dcam, nobs); sc.take(&dpt, nobs); sc.take(&dxy, (size_t)2 * nobs); sc.take(&D.W, (size_t)18 * nobs);
+    sc.take(&D.Hpp, (size_t)6 * npt); sc.take(&D.bp, (size_t)3 * npt); sc.take(&D.Hpi, (size_t)6 * npt); sc.take(&dpairs, pairs.size());
+    sc.take(&dblk, blk_first.size()); sc.take(&D.chi2, (size_t)2 * B); sc.take(&D.iterations_run, B); sc.take(&D.trials_run, B);
+    int rc = sc.place(ctx); if (rc) return rc;
+    D.prob = dprob; D.cam_col = dcol; D.pt_first = dptf; D.obs_cam = dcam; D.obs_pt = dpt; D.obs_xy = dxy; D.pairs = dpairs; D.blk_first = dblk;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(dprob, prob.data(), (size_t)B * sizeof(BaProblem), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dptf, pt_first.data(), pt_first.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    if (ncam > 0) {
+        HIPCHK(hipMemcpyAsync(D.poses, poses + (size_t)12 * c0, (size_t)12 * ncam * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dcol, col.data(), (size_t)ncam * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    if (npt > 0) HIPCHK(hipMemcpyAsync(D.X, points + (size_t)3 * p0, (size_t)3 * npt * sizeof(double), hipMemcpyHostToDevice, s));
+    if (nobs > 0) {
+        HIPCHK(hipMemcpyAsync(dcam, s_cam.data(), (size_t)nobs * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dpt, s_pt.data(), (size_t)nobs * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dxy, s_xy.data(), (size_t)2 * nobs * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    if (!pairs.empty()) HIPCHK(hipMemcpyAsync(dpairs, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    if (!blk_first.empty()) HIPCHK(hipMemcpyAsync(dblk, blk_first.data(), blk_first.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(D.chi2, 0, (size_t)2 * B * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(D.iterations_run, 0, (size_t)B * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(D.trials_run, 0, (size_t)B * sizeof(int), s));
+    HIPCHK(hipStreamSynchronize(s));                                 // the staging vectors live on this stack
+    const BaParams prm{focal, cx, cy, opts->huber_delta, opts->iterations};
+    { StageTimer t(ctx, ST_MISC); launch_bundle_adjust(s, D, prm, B, max_free); }
+    HIPCHK(hipGetLastError());
+    if (ncam > 0) HIPCHK(hipMemcpyAsync(poses + (size_t)12 * c0, D.poses, (size_t)12 * ncam * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (npt > 0) HIPCHK(hipMemcpyAsync(points + (size_t)3 * p0, D.X, (size_t)3 * npt * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(chi2, D.chi2, (size_t)2 * B * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(iterations_run, D.iterations_run, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(trials_run, D.trials_run, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
+extern "C" int vo_bundle_adjust(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int ncam, double* points, int npt,
+                                const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs,
+                                double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2,
+                                int32_t* iterations_run, int32_t* trials_run)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (ncam < 0 || npt < 0 || nobs < 0 || !chi2 || !iterations_run || !trials_run) FAIL(VO_ERR_INVALID, "bad arguments");
+    const int32_t co[2] = {0, ncam}, po[2] = {0, npt}, oo[2] = {0, nobs};
+    int32_t status = 0;
+    int rc = vo_bundle_adjust_batch(ctx, 1, co, po, oo, poses, cam_fixed, points, obs_cam, obs_pt, obs_xy, focal, cx, cy, opts,
+                                    chi2, iterations_run, trials_run, &status);
+    if (rc) return rc;
+    if (status == VO_ERR_UNSUPPORTED)
+        FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment holds at most %d cameras, %d of them free, per problem", VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE);
+    if (status == VO_ERR_INVALID) FAIL(VO_ERR_INVALID, "an observation refers to a missing camera or point");
+    return VO_OK;
+}
+
 // ------------------------------------------------------------------ "next" row: PnP-RANSAC localisation
 extern "C" int vo_solve_pnp_ransac_batch(vo_ctx* ctx, const double* obj, const double* img, const int32_t* offsets, int B,
                                          const double* K, int iterations, double reproj_err, double confidence, uint64_t seed,

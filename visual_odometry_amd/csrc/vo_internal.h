@@ -277,5 +277,27 @@ void launch_chain_gather(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, Ch
 void launch_chain_pose(hipStream_t s, PairBuf pb, int p, const double* Kd, ChainBuf cb);
 void launch_chain_triangulate(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb);
 void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb);
+// ---- bundle adjustment (ba_kernels.hip): Map.optimize_map, src/map.py:104-186.  One workgroup per problem.
+struct BaProblem {
+    int cam0, pt0, obs0, pair0, blk0;   // where the problem's cameras / points / observations / pair list / block offsets start
+    int ncam, npt, nobs, nfree;
+    int skip;                           // 1: rejected on the host (status says why), its data stay as they are
+};
+struct BaBuf {
+    const BaProblem* prob;              // [B]
+    double*       poses;                // [cameras][12] world -> camera [R | t], in / out
+    const int*    cam_col;              // [cameras] column block of a free camera in S, -1 for a fixed one
+    double*       X; double* X2;        // [points][3]: in / out, and the trial estimate
+    const int*    pt_first;             // per problem npt + 1: first observation of a point (observations sorted by point)
+    const int*    obs_cam; const int* obs_pt; const double* obs_xy;   // sorted observations, indices local to the problem
+    double*       W;                    // [observations][18]: w Jp^T Jx of a free camera's observation
+    double*       Hpp; double* bp; double* Hpi;   // [points][6], [3], [6]: H_pp, b_p, (H_pp + lambda I)^-1 (symmetric: 00 01 02 11 12 22)
+    const int2*   pairs;                // per block (c1 <= c2) of free cameras: the (observation of c1, observation of c2) that share a point
+    const int*    blk_first;            // per problem nfree (nfree + 1) / 2 + 1 offsets into its pairs
+    double*       chi2;                 // [B][2] robust chi2 before, after
+    int*          iterations_run; int* trials_run;   // [B]
+};
+struct BaParams { double focal, cx, cy, delta; int iterations; };
+void launch_bundle_adjust(hipStream_t s, const BaBuf& D, const BaParams& P, int B, int max_free);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

@@ -1,10 +1,14 @@
-"""Reprojection-error filter over all map observations (reference: src/map.py:46-94).
+"""Map methods on the GPU.  Reprojection-error filter over all map observations (reference: src/map.py:46-94).
+
+Also the map's bundle adjustment (reference: src/map.py:104-186, g2o) as one device call: bundle_adjust / optimize_map.
 
 The reference walks Python lists of Observation / TrackedCamera / TrackedPoint objects and multiplies 4x4
 matrices per observation; here the same quantities go to the GPU as arrays (one lane per observation).  The
 object-level helpers accept the reference's record types unchanged (duck typed: .camera_id/.pose(),
 .point_id/.point, .camera_id/.point_id/.image_coordinates)."""
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 
@@ -29,15 +33,19 @@ def reprojection_sqerr(poses, points, obs_cam, obs_pt, obs_xy, camera_matrix, th
     return err, keep.astype(bool)
 
 
-def _arrays(cameras, points, observations):
+def _index_arrays(cameras, points, observations):
     cam_row = {c.camera_id: i for i, c in enumerate(cameras)}
     pt_row = {p.point_id: i for i, p in enumerate(points)}
-    poses = np.stack([c.pose() for c in cameras]) if cameras else np.zeros((0, 4, 4))
     pts = np.array([p.point for p in points], dtype=np.float64).reshape(-1, 3)
     oc = np.array([cam_row[o.camera_id] for o in observations], np.int32)
     op = np.array([pt_row[o.point_id] for o in observations], np.int32)
     xy = np.array([o.image_coordinates for o in observations], dtype=np.float64).reshape(-1, 2)
-    return poses, pts, oc, op, xy
+    return pts, oc, op, xy
+
+
+def _arrays(cameras, points, observations):
+    poses = np.stack([c.pose() for c in cameras]) if cameras else np.zeros((0, 4, 4))
+    return (poses,) + _index_arrays(cameras, points, observations)
 
 
 def remove_observations_with_reprojection_errors_above_threshold(cameras, points, observations, camera_matrix,
@@ -80,3 +88,74 @@ def feature_tracks(n_frames, cap, pair_frames, matches, ctx=None):
     ctx.check(ctx.lib.vo_feature_tracks(ctx.handle, int(n_frames), int(cap), pf.ctypes.data, off.ctypes.data, mq.ctypes.data,
                                         mt.ctypes.data, P, rf.ctypes.data, ri.ctypes.data, hops.ctypes.data))
     return rf, ri, hops
+
+
+def _ba_problem(poses, fixed, points, obs_cam, obs_pt, obs_xy):
+    poses = np.array(poses, np.float64).reshape(-1, 12)
+    fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8)).ravel()
+    points = np.array(points, np.float64).reshape(-1, 3)
+    oc = np.ascontiguousarray(obs_cam, np.int32).ravel(); op = np.ascontiguousarray(obs_pt, np.int32).ravel()
+    xy = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+    if len(fixed) != len(poses):
+        raise ValueError("one fixed flag per camera")
+    if not (len(op) == len(oc) == len(xy)):
+        raise ValueError("observation arrays differ in length")
+    return poses, fixed, points, oc, op, xy
+
+
+def bundle_adjust_batch(problems, focal, cx, cy, iterations=40, huber_delta=1.0, ctx=None):
+    """Map.optimize_map (map.py:104-186) for B independent maps in one launch, one workgroup each.  problems: a list of
+    (poses [ncam, 3, 4] world -> camera [R | t], fixed [ncam], points [npt, 3], obs_cam, obs_pt, obs_xy [nobs, 2]) with
+    obs_cam / obs_pt indexing that problem's rows.  Returns one dict per problem: poses, points (new arrays), chi2_before,
+    chi2_after (g2o's activeRobustChi2), iterations, trials, status (VO_OK; VO_ERR_UNSUPPORTED beyond 64 cameras / 16 free
+    cameras, VO_ERR_INVALID for an observation of a missing camera or point: such a problem comes back unchanged)."""
+    probs = [_ba_problem(*p) for p in problems]
+    B = len(probs)
+    off = np.zeros((3, B + 1), np.int32)
+    for b, p in enumerate(probs):
+        off[:, b + 1] = off[:, b] + (len(p[0]), len(p[2]), len(p[3]))
+    cat = lambda k, shape, dt: np.ascontiguousarray(np.concatenate([p[k] for p in probs]) if B else np.zeros(shape, dt))  # noqa: E731
+    poses, fixed, points = cat(0, (0, 12), np.float64), cat(1, 0, np.uint8), cat(2, (0, 3), np.float64)
+    oc, op, xy = cat(3, 0, np.int32), cat(4, 0, np.int32), cat(5, (0, 2), np.float64)
+    chi2 = np.zeros((B, 2)); it = np.zeros(B, np.int32); tr = np.zeros(B, np.int32); st = np.zeros(B, np.int32)
+    opts = _lib.BaOpts(int(iterations), 0, float(huber_delta))
+    ctx = ctx or _lib.default_context()
+    ctx.check(ctx.lib.vo_bundle_adjust_batch(ctx.handle, B, off[0].ctypes.data, off[1].ctypes.data, off[2].ctypes.data, poses.ctypes.data,
+                                             fixed.ctypes.data, points.ctypes.data, oc.ctypes.data, op.ctypes.data, xy.ctypes.data,
+                                             float(focal), float(cx), float(cy), ctypes.addressof(opts), chi2.ctypes.data,
+                                             it.ctypes.data, tr.ctypes.data, st.ctypes.data))
+    return [dict(poses=poses[off[0, b]:off[0, b + 1]].reshape(-1, 3, 4).copy(), points=points[off[1, b]:off[1, b + 1]].copy(),
+                 chi2_before=float(chi2[b, 0]), chi2_after=float(chi2[b, 1]), iterations=int(it[b]), trials=int(tr[b]),
+                 status=int(st[b])) for b in range(B)]
+
+
+def bundle_adjust(poses, fixed, points, obs_cam, obs_pt, obs_xy, focal, cx, cy, iterations=40, huber_delta=1.0, ctx=None):
+    """One map (vo_bundle_adjust): dict(poses, points, chi2_before, chi2_after, iterations, trials, status).  A map the
+    kernel cannot hold or an observation of a missing camera / point raises VoError; the inputs are not modified."""
+    poses, fixed, points, oc, op, xy = _ba_problem(poses, fixed, points, obs_cam, obs_pt, obs_xy)
+    chi2 = np.zeros(2); it = np.zeros(1, np.int32); tr = np.zeros(1, np.int32)
+    opts = _lib.BaOpts(int(iterations), 0, float(huber_delta))
+    ctx = ctx or _lib.default_context()
+    rc = ctx.check(ctx.lib.vo_bundle_adjust(ctx.handle, poses.ctypes.data, fixed.ctypes.data, len(poses), points.ctypes.data, len(points),
+                                            oc.ctypes.data, op.ctypes.data, xy.ctypes.data, len(oc), float(focal), float(cx), float(cy),
+                                            ctypes.addressof(opts), chi2.ctypes.data, it.ctypes.data, tr.ctypes.data))
+    return dict(poses=poses.reshape(-1, 3, 4), points=points, chi2_before=float(chi2[0]), chi2_after=float(chi2[1]),
+                iterations=int(it[0]), trials=int(tr[0]), status=int(rc))
+
+
+def optimize_map(cameras, points, observations, camera_matrix, iterations=40, ctx=None):
+    """map.py:104-186 — Map.optimize_map: cameras need .camera_id, .R, .t, .fixed; points .point_id, .point; observations
+    .camera_id, .point_id, .image_coordinates.  One focal length, camera_matrix[0, 0], as the reference passes it (:113).
+    Writes camera.t (a 3-vector), camera.R and point.point (a fresh array) back as :175-186 do; returns (chi2 before, after)."""
+    K = np.asarray(camera_matrix, np.float64).reshape(3, 3)
+    pts, oc, op, xy = _index_arrays(cameras, points, observations)
+    poses = np.zeros((len(cameras), 3, 4))
+    for i, c in enumerate(cameras):
+        poses[i, :, :3] = np.asarray(c.R, np.float64).reshape(3, 3); poses[i, :, 3] = np.asarray(c.t, np.float64).ravel()
+    r = bundle_adjust(poses, [bool(c.fixed) for c in cameras], pts, oc, op, xy, K[0, 0], K[0, 2], K[1, 2], iterations, 1.0, ctx)
+    for i, c in enumerate(cameras):
+        c.t = r["poses"][i, :, 3].copy()
+        c.R = r["poses"][i, :, :3].copy()
+    for i, p in enumerate(points):
+        p.point = np.copy(r["points"][i])
+    return r["chi2_before"], r["chi2_after"]
