@@ -851,18 +851,20 @@ void launch_fast(hipStream_t s, const uint8_t* pyr, uint8_t* score, uint32_t* hi
 
 // ------------------------------------------------------------------ retainBest by FAST score
 // KeyPointsFilter::runByImageBorder + retainBest(2*quota): the kept SET is {score >= n-th largest score}.
-// (1) k_sel_threshold: the n-th largest score per (frame, level) from the 256-bin histogram;
-// (2) k_sel_rows<count>: one wavefront per row of FAST tiles counts the listed winners that reach the threshold;
-// (3) k_sel_rows<emit>: each wavefront sums the counts of the tile rows above it (its output offset), gathers its
-//     kept winners into LDS, ranks them in (y, x) order and writes (x, y, score) at offset + rank — canonical
+// (1) k_sel_rows<count>: one wavefront per row of FAST tiles takes the n-th largest score of its (frame, level) from the
+//     256-bin histogram (sel_threshold) and counts the listed winners that reach it;
+// (2) k_sel_rows<emit>: each wavefront sums the counts of the tile rows above it (its output offset), marks its kept
+//     winners in a bitmap of the tile row, ranks them in (y, x) order and writes (x, y, score) at offset + rank — canonical
 //     raster order with no sort, no workgroup barrier and no pass over a score map.
+// In cv2 keypoint order the same two launches also produce the raster-ordered list of ALL listed winners (the list cv2's
+// first retainBest permutes, cv2order_kernels.hip): its tile-row counts are sums of tile_count, its ranks come from a second
+// bitmap filled in the same pass over the tile lists, and the one write loop stores into both lists.
 
-__global__ __launch_bounds__(64) void k_sel_threshold(PyrGeom g, FrameFeat ff, int* thr)
+// The n-th largest score of a (frame, level) from its histogram `h`, by one wavefront; every lane returns it.  1: fewer than
+// n winners, keep them all; 256: keep nothing.
+__device__ __forceinline__ int sel_threshold(const PyrGeom& g, const LevelGeom& lv, const uint32_t* h, int lane)
 {
-    const int l = blockIdx.x, f = blockIdx.y, lane = threadIdx.x;
-    const LevelGeom lv = g.lv[l];
     const int want = g.score_type == 0 ? 2 * lv.quota : lv.quota;
-    const uint32_t* h = ff.hist + ((size_t)f * VO_MAX_LEVELS + l) * 256;
     // lane j owns scores 255-4j .. 252-4j (descending), so an inclusive scan over lanes is a suffix sum
     uint32_t c[4];
     int own = 0;
@@ -883,137 +885,195 @@ __global__ __launch_bounds__(64) void k_sel_threshold(PyrGeom g, FrameFeat ff, i
     int result = 1;                                   // fewer than `want` candidates: keep them all
     if (found) result = __shfl(T, __ffsll((long long)found) - 1, 64);
     if (want <= 0 || lv.w <= 2 * g.edge || lv.h <= 2 * g.edge) result = 256;      // keep nothing
-    if (lane == 0) {
-        thr[f * VO_MAX_LEVELS + l] = result;
-        if (result > 255) ff.cand_count[f * VO_MAX_LEVELS + l] = 0;     // such a level may own no scan chunk at all
-    }
+    return __builtin_amdgcn_readfirstlane(result);    // the same in every lane: hand it out as a scalar
 }
 
-// One wavefront per (frame, level, row of FAST tiles).  COUNT: how many listed winners reach the threshold.
-// EMIT: the kept winners of the tile row are gathered into LDS (ballot + prefix), each one's rank among them in
-// (y, x) order comes from a bitmap of the tile row's pixels (set bits in front of its own: keys are unique), and it is
-// written at base + rank, base = the kept counts of the tile rows above: canonical raster order without sorting, without
-// comparing winners with one another and without touching a score map.
-template <bool EMIT>
-__global__ __launch_bounds__(64) void k_sel_rows(const uint32_t* tile_list, const int* tile_count, PyrGeom g, FrameFeat ff,
-                                                 const int* thr, int* chunk_count)
+// One wavefront per (frame, level, row of FAST tiles).  COUNT: how many listed winners reach the threshold (ALL: and how many
+// are listed at all).  EMIT: every kept winner of the tile row sets the bit of its pixel in a bitmap of the tile row
+// (FAST_TH rows x level width), the words' population counts are scanned, a winner's rank in (y, x) order is the number of
+// set bits in front of its own (keys are unique), and it is written at base + rank, base = the kept counts of the tile rows
+// above: canonical raster order without sorting, without comparing winners with one another and without touching a score
+// map.  ALL keeps a second bitmap with every listed winner and writes each one into the all-winner list as well.
+template <bool EMIT, bool ALL>
+__device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* tile_count, const PyrGeom& g, const FrameFeat& ff,
+                                         int* thr, int* chunk_count, const Cv2Buf& cb, uint32_t* s_sel)
 {
-    extern __shared__ uint32_t s_sel[];               // EMIT: [NW] bitmap of the tile row's pixels, then [NW] set bits in front of each word
     const int f = blockIdx.y, lane = threadIdx.x;
     int l = 0;
     while (l + 1 < g.nlevels && (int)blockIdx.x >= g.lv[l + 1].sel_chunk_base) l++;
     const LevelGeom lv = g.lv[l];
     const int chunk = blockIdx.x - lv.sel_chunk_base;                 // tile row
-    const int T = thr[f * VO_MAX_LEVELS + l];
-    int* my_count = chunk_count + (size_t)f * g.sel_chunks_total + blockIdx.x;
     const int nchunks = (l + 1 < g.nlevels ? g.lv[l + 1].sel_chunk_base : g.sel_chunks_total) - lv.sel_chunk_base;
-    if (T > 255) {
-        if (!EMIT && lane == 0) *my_count = 0;
-        if (EMIT && chunk == 0 && lane == 0) ff.cand_count[f * VO_MAX_LEVELS + l] = 0;
-        return;
-    }
+    const size_t cslot = (size_t)f * g.sel_chunks_total + blockIdx.x;
     const size_t tile0 = (size_t)f * g.ftiles_total + lv.ftile_base + (size_t)chunk * lv.ftiles_x;
     if (!EMIT) {
-        int n = 0;                                    // wave-uniform: kept winners of this tile row
-        for (int t = 0; t < lv.ftiles_x; t++) {
-            const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
-            const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
-            for (int j0 = 0; j0 < cnt; j0 += 64) {
-                const int j = j0 + lane;
-                const uint32_t e = j < cnt ? lst[j] : 0u;
-                n += (int)__popcll(__ballot(j < cnt && (int)(e >> 16) >= T));
+        const int T = sel_threshold(g, lv, ff.hist + ((size_t)f * VO_MAX_LEVELS + l) * 256, lane);
+        int n = 0, na = 0;                            // wave-uniform: kept / listed winners of this tile row
+        if (ALL || T <= 255)
+            for (int t = 0; t < lv.ftiles_x; t++) {
+                const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
+                const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
+                na += cnt;
+                for (int j0 = 0; j0 < cnt; j0 += 64) {
+                    const int j = j0 + lane;
+                    const uint32_t e = j < cnt ? lst[j] : 0u;
+                    n += (int)__popcll(__ballot(j < cnt && (int)(e >> 16) >= T));
+                }
             }
+        // every store of the wave comes after its last load: a store in front of them would turn the wave-uniform loads above
+        // (tile counts, list bases) from scalar into vector loads
+        if (lane != 0) return;
+        chunk_count[cslot] = n;
+        if (ALL) cb.chunk_count[cslot] = na;
+        if (chunk == 0) thr[f * VO_MAX_LEVELS + l] = T;
+        if (blockIdx.x == 0) {
+            // the detection's first selection wave of this frame: nothing has set a flag yet, and a level too small to hold a
+            // keypoint (narrower than two border widths) has no tile row, so nobody else would write its counts
+            ff.flags[f] = 0;
+            for (int k = 0; k < g.nlevels; k++)
+                if ((k + 1 < g.nlevels ? g.lv[k + 1].sel_chunk_base : g.sel_chunks_total) == g.lv[k].sel_chunk_base) {
+                    ff.cand_count[f * VO_MAX_LEVELS + k] = 0;
+                    if (ALL) cb.all_count[f * VO_MAX_LEVELS + k] = 0;
+                }
         }
-        if (lane == 0) *my_count = n;
         return;
     }
-    int base = 0;
-    {
-        const int* cc = chunk_count + (size_t)f * g.sel_chunks_total + lv.sel_chunk_base;
-        for (int c = lane; c < chunk; c += 64) base += cc[c];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) base += __shfl_xor(base, d, 64);
+    const int T = thr[f * VO_MAX_LEVELS + l];
+    if (!ALL && T > 255) {
+        if (chunk == 0 && lane == 0) ff.cand_count[f * VO_MAX_LEVELS + l] = 0;
+        return;
     }
-    // Rank of every kept winner in (y, x) order without comparing winners with one another and without a copy of them: a bit
-    // per pixel of the tile row (FAST_TH rows x level width) is set for every kept winner, the words' population counts are
-    // scanned, and a winner's rank is the number of set bits in front of its own.  The tile lists are read twice (L2).
+    int base = 0, abase = 0;
+    {
+        const size_t c0 = (size_t)f * g.sel_chunks_total + lv.sel_chunk_base;
+        for (int c = lane; c < chunk; c += 64) { base += chunk_count[c0 + c]; if (ALL) abase += cb.chunk_count[c0 + c]; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { base += __shfl_xor(base, d, 64); if (ALL) abase += __shfl_xor(abase, d, 64); }
+    }
+    // Rank of every winner in (y, x) order without comparing winners with one another and without a copy of them: a bit per
+    // pixel of the tile row is set for every kept winner (ALL: in a second bitmap for every listed winner), the words'
+    // population counts are scanned, and a winner's rank is the number of set bits in front of its own.  The tile lists are
+    // read twice (L2).
     const int W32 = (lv.w + 31) >> 5, NW = FAST_TH * W32;
-    uint32_t* s_bm = s_sel;
+    uint32_t* s_bm = s_sel;                           // [NW] kept bitmap, [NW] set bits in front of each word;
     uint32_t* s_pf = s_sel + NW;
-    for (int i = lane; i < NW; i += 64) s_bm[i] = 0u;
+    uint32_t* s_abm = s_sel + 2 * NW;                 // ALL: the same pair for every listed winner
+    uint32_t* s_apf = s_sel + 3 * NW;
+    for (int i = lane; i < NW; i += 64) { s_bm[i] = 0u; if (ALL) s_abm[i] = 0u; }
     __syncthreads();
     for (int t = 0; t < lv.ftiles_x; t++) {
         const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
         const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
         for (int j = lane; j < cnt; j += 64) {
             const uint32_t e = lst[j];
-            if ((int)(e >> 16) >= T) { const uint32_t gx = (uint32_t)(lv.fox + t * FAST_TW) + (e & 255u); atomicOr(&s_bm[((e >> 8) & 255u) * W32 + (gx >> 5)], 1u << (gx & 31u)); }
+            const bool kept = (int)(e >> 16) >= T;
+            if (ALL || kept) {
+                const uint32_t gx = (uint32_t)(lv.fox + t * FAST_TW) + (e & 255u), wd = ((e >> 8) & 255u) * W32 + (gx >> 5), bit = 1u << (gx & 31u);
+                if (ALL) atomicOr(&s_abm[wd], bit);
+                if (kept) atomicOr(&s_bm[wd], bit);
+            }
         }
     }
     __syncthreads();
-    int n;
+    int n, na = 0;
     {
         const int per = (NW + 63) / 64, w0 = lane * per, w1 = min(NW, w0 + per);
-        int own = 0;
-        for (int wd = w0; wd < w1; wd++) own += __popc(s_bm[wd]);
-        int inc = own;
+        int own = 0, aown = 0;
+        for (int wd = w0; wd < w1; wd++) { own += __popc(s_bm[wd]); if (ALL) aown += __popc(s_abm[wd]); }
+        int inc = own, ainc = aown;
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v;
+            if (ALL) { const int av = __shfl_up(ainc, d, 64); if (lane >= d) ainc += av; }
+        }
         n = __shfl(inc, 63, 64);
-        int acc = inc - own;
-        for (int wd = w0; wd < w1; wd++) { s_pf[wd] = (uint32_t)acc; acc += __popc(s_bm[wd]); }
+        if (ALL) na = __shfl(ainc, 63, 64);
+        int acc = inc - own, aacc = ainc - aown;
+        for (int wd = w0; wd < w1; wd++) {
+            s_pf[wd] = (uint32_t)acc; acc += __popc(s_bm[wd]);
+            if (ALL) { s_apf[wd] = (uint32_t)aacc; aacc += __popc(s_abm[wd]); }
+        }
     }
     __syncthreads();
     bool overflow = false;
     uint32_t* out_pos = ff.cand_pos + (size_t)f * g.cand_total + lv.cand_off;
     float* out_resp = ff.cand_resp + (size_t)f * g.cand_total + lv.cand_off;
+    uint32_t* all_pos = ALL ? cb.all_pos + (size_t)f * cb.all_total + cb.all_off[l] : nullptr;
+    float* all_resp = ALL ? cb.all_resp + (size_t)f * cb.all_total + cb.all_off[l] : nullptr;
+    const int all_cap = ALL ? cb.all_cap[l] : 0;
     for (int t = 0; t < lv.ftiles_x; t++) {
         const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
         const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
         for (int j = lane; j < cnt; j += 64) {
             const uint32_t e = lst[j];
-            if ((int)(e >> 16) >= T) {
+            const bool kept = (int)(e >> 16) >= T;
+            if (ALL || kept) {
                 const uint32_t ly = (e >> 8) & 255u, gx = (uint32_t)(lv.fox + t * FAST_TW) + (e & 255u);
                 const int wd = (int)(ly * W32 + (gx >> 5));
-                const int pos = base + (int)s_pf[wd] + __popc(s_bm[wd] & ((1u << (gx & 31u)) - 1u));
-                if (pos < lv.cand_cap) { out_pos[pos] = (((uint32_t)(lv.foy + chunk * FAST_TH) + ly) << 16) | gx; out_resp[pos] = (float)(e >> 16); }
-                else overflow = true;
+                const uint32_t below = (1u << (gx & 31u)) - 1u, key = (((uint32_t)(lv.foy + chunk * FAST_TH) + ly) << 16) | gx;
+                const float score = (float)(e >> 16);
+                if (ALL) {
+                    const int apos = abase + (int)s_apf[wd] + __popc(s_abm[wd] & below);
+                    if (apos < all_cap) { all_pos[apos] = key; all_resp[apos] = score; }
+                    else overflow = true;
+                }
+                if (kept) {
+                    const int pos = base + (int)s_pf[wd] + __popc(s_bm[wd] & below);
+                    if (pos < lv.cand_cap) { out_pos[pos] = key; out_resp[pos] = score; }
+                    else overflow = true;
+                }
             }
         }
     }
     if (overflow) atomicOr(&ff.flags[f], 1);
-    if (chunk == nchunks - 1 && lane == 0) ff.cand_count[f * VO_MAX_LEVELS + l] = min(base + n, lv.cand_cap);
+    if (chunk == nchunks - 1 && lane == 0) {
+        ff.cand_count[f * VO_MAX_LEVELS + l] = min(base + n, lv.cand_cap);
+        if (ALL) cb.all_count[f * VO_MAX_LEVELS + l] = min(abase + na, all_cap);
+    }
 }
 
-// LDS of k_sel_rows<emit>: one bit per pixel of a row of FAST tiles + the scanned word counts
-static size_t sel_bitmap_bytes(const PyrGeom& g)
+// Two kernels of one name: canonical keypoint order (no Cv2Buf: none of the all-winner code is in it) and cv2 order
+template <bool EMIT>
+__global__ __launch_bounds__(64) void k_sel_rows(const uint32_t* tile_list, const int* tile_count, PyrGeom g, FrameFeat ff,
+                                                 int* thr, int* chunk_count)
+{
+    extern __shared__ uint32_t s_sel[];               // EMIT: the bitmap and its scanned word counts
+    sel_rows<EMIT, false>(tile_list, tile_count, g, ff, thr, chunk_count, Cv2Buf(), s_sel);
+}
+template <bool EMIT>
+__global__ __launch_bounds__(64) void k_sel_rows(const uint32_t* tile_list, const int* tile_count, PyrGeom g, FrameFeat ff,
+                                                 int* thr, int* chunk_count, Cv2Buf cb)
+{
+    extern __shared__ uint32_t s_sel[];               // EMIT: the two bitmaps and their scanned word counts
+    sel_rows<EMIT, true>(tile_list, tile_count, g, ff, thr, chunk_count, cb, s_sel);
+}
+
+// LDS of k_sel_rows<emit>: per list one bit per pixel of a row of FAST tiles + the scanned word counts
+static size_t sel_bitmap_bytes(const PyrGeom& g, bool all)
 {
     int w = 0;
     for (int l = 0; l < g.nlevels; l++) w = g.lv[l].w > w ? g.lv[l].w : w;
-    return (size_t)2 * FAST_TH * ((w + 31) / 32) * 4;
+    return (size_t)(all ? 4 : 2) * FAST_TH * ((w + 31) / 32) * 4;
 }
 
+// cb: the all-winner arrays of the cv2 keypoint order, offset to the first frame like ff; nullptr = canonical order
 void launch_select_fast(hipStream_t s, const PyrGeom& g, FrameFeat ff, int F, int* thr, int* chunk_count,
-                        const uint32_t* tile_list, const int* tile_count)
+                        const uint32_t* tile_list, const int* tile_count, const Cv2Buf* cb)
 {
-    hipLaunchKernelGGL(k_sel_threshold, dim3(g.nlevels, F), dim3(64), 0, s, g, ff, thr);
-    if (g.sel_chunks_total <= 0) return;
-    hipLaunchKernelGGL(k_sel_rows<false>, dim3(g.sel_chunks_total, F), dim3(64), 0, s, tile_list, tile_count, g, ff, thr, chunk_count);
-    hipLaunchKernelGGL(k_sel_rows<true>, dim3(g.sel_chunks_total, F), dim3(64), sel_bitmap_bytes(g), s, tile_list, tile_count, g, ff, thr, chunk_count);
-}
-
-// cv2-order mode: the same two kernels with threshold 1 and the all-winner list geometry give the raster-ordered list
-// of every NMS winner inside the border, which is what cv2's first retainBest permutes (cv2order_kernels.hip)
-void launch_all_winners(hipStream_t s, const PyrGeom& g, FrameFeat ff, const Cv2Buf& cb, int F, const uint32_t* tile_list, const int* tile_count)
-{
-    if (g.sel_chunks_total <= 0) return;
-    PyrGeom ga = g;
-    for (int l = 0; l < g.nlevels; l++) { ga.lv[l].cand_off = cb.all_off[l]; ga.lv[l].cand_cap = cb.all_cap[l]; }
-    ga.cand_total = cb.all_total;
-    FrameFeat fa = ff;
-    fa.cand_pos = cb.all_pos; fa.cand_resp = cb.all_resp; fa.cand_count = cb.all_count;
-    hipLaunchKernelGGL(k_sel_rows<false>, dim3(g.sel_chunks_total, F), dim3(64), 0, s, tile_list, tile_count, ga, fa, cb.ones, cb.chunk_count);
-    hipLaunchKernelGGL(k_sel_rows<true>, dim3(g.sel_chunks_total, F), dim3(64), sel_bitmap_bytes(g), s, tile_list, tile_count, ga, fa, cb.ones, cb.chunk_count);
+    if (g.sel_chunks_total <= 0) {                    // no level can hold a keypoint: no selection wave would clear these
+        (void)hipMemsetAsync(ff.flags, 0, (size_t)F * sizeof(int), s);
+        (void)hipMemsetAsync(ff.cand_count, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s);
+        if (cb) (void)hipMemsetAsync(cb->all_count, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s);
+        return;
+    }
+    const dim3 grid(g.sel_chunks_total, F);
+    if (cb) {
+        hipLaunchKernelGGL(k_sel_rows<false>, grid, dim3(64), 0, s, tile_list, tile_count, g, ff, thr, chunk_count, *cb);
+        hipLaunchKernelGGL(k_sel_rows<true>, grid, dim3(64), sel_bitmap_bytes(g, true), s, tile_list, tile_count, g, ff, thr, chunk_count, *cb);
+    } else {
+        hipLaunchKernelGGL(k_sel_rows<false>, grid, dim3(64), 0, s, tile_list, tile_count, g, ff, thr, chunk_count);
+        hipLaunchKernelGGL(k_sel_rows<true>, grid, dim3(64), sel_bitmap_bytes(g, false), s, tile_list, tile_count, g, ff, thr, chunk_count);
+    }
 }
 
 // ------------------------------------------------------------------ Harris response (orb.cpp HarrisResponses)

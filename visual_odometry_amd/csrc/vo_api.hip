@@ -359,10 +359,8 @@ static int alloc_cv2(vo_ctx* ctx)
     DevList& m = ctx->orb_mem;
     HIPCHK(m.alloc(&cb.all_pos, n)); HIPCHK(m.alloc(&cb.all_resp, n)); HIPCHK(m.alloc(&cb.work, n));
     HIPCHK(m.alloc(&cb.lpos, n)); HIPCHK(m.alloc(&cb.rpos, n));
-    HIPCHK(m.alloc(&cb.all_count, F * VO_MAX_LEVELS)); HIPCHK(m.alloc(&cb.ones, F * VO_MAX_LEVELS));
+    HIPCHK(m.alloc(&cb.all_count, F * VO_MAX_LEVELS));
     HIPCHK(m.alloc(&cb.chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
-    std::vector<int> ones(F * VO_MAX_LEVELS, 1);
-    HIPCHK(hipMemcpy(cb.ones, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(cb.all_count, 0, F * VO_MAX_LEVELS * sizeof(int)));
     HIPCHK(hipDeviceSynchronize());
     ctx->cv2_ready = true;
@@ -704,31 +702,34 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
         for (int l = 1; l < g.nlevels; l++) launch_resize(s, pyr, g, l, ctx->tabs[l], F);
     }
     if (upto < 1) return VO_OK;
-    {
-        StageTimer t(ctx, ST_MISC);
-        HIPCHK(hipMemsetAsync(ff.hist, 0, (size_t)F * VO_MAX_LEVELS * 256 * sizeof(uint32_t), s));
-        HIPCHK(hipMemsetAsync(ff.flags, 0, (size_t)F * sizeof(int), s));
-        // a level too small to hold a keypoint (narrower than two border widths) has no FAST tiles and no selection chunk: nobody
-        // would write its candidate count
-        HIPCHK(hipMemsetAsync(ff.cand_count, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s));
-        if (ctx->kp_order == 1 && ctx->cv2_ready)
-            HIPCHK(hipMemsetAsync(ctx->cv2.all_count + (size_t)first_slot * VO_MAX_LEVELS, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s));
-    }
-    { StageTimer t(ctx, ST_FAST); launch_fast(s, pyr, score, ff.hist, g, F, upto < 2 ? nullptr : ff.tile_list, ff.tile_count); }
-    if (upto < 2) return VO_OK;
-    { StageTimer t(ctx, ST_SELECT_FAST); launch_select_fast(s, g, ff, F, ctx->sel_thr + (size_t)first_slot * VO_MAX_LEVELS, ctx->sel_chunk_count + (size_t)first_slot * g.sel_chunks_total, ff.tile_list, ff.tile_count); }
-    if (g.score_type == 0) { StageTimer t(ctx, ST_HARRIS); launch_harris(s, pyr, g, ff, F); }
-    { StageTimer t(ctx, ST_SELECT_HARRIS); launch_select_harris(s, g, ff, F, ctx->har_thr + (size_t)first_slot * VO_MAX_LEVELS, ctx->har_kept + (size_t)first_slot * VO_MAX_LEVELS); }
-    if (ctx->kp_order == 1 && ctx->cv2_ready) {
-        // cv2's list order: permute every level's keypoints the way retainBest's nth_element / partition leave them
-        StageTimer t(ctx, ST_CV2_ORDER);
-        Cv2Buf cb = ctx->cv2;
+    const bool cv2 = ctx->kp_order == 1 && ctx->cv2_ready;
+    Cv2Buf cb = ctx->cv2;
+    if (cv2) {
         const size_t fo = (size_t)first_slot;
         cb.all_pos += fo * cb.all_total; cb.all_resp += fo * cb.all_total; cb.work += fo * cb.all_total;
         cb.lpos += fo * cb.all_total; cb.rpos += fo * cb.all_total;
-        cb.all_count += fo * VO_MAX_LEVELS; cb.ones += fo * VO_MAX_LEVELS; cb.chunk_count += fo * g.sel_chunks_total;
-        launch_all_winners(s, g, ff, cb, F, ff.tile_list, ff.tile_count);
-        launch_cv2_order(s, g, ff, cb, F, ctx->har_kept + fo * VO_MAX_LEVELS);
+        cb.all_count += fo * VO_MAX_LEVELS; cb.chunk_count += fo * g.sel_chunks_total;
+    }
+    {
+        StageTimer t(ctx, ST_MISC);
+        HIPCHK(hipMemsetAsync(ff.hist, 0, (size_t)F * VO_MAX_LEVELS * 256 * sizeof(uint32_t), s));
+        // the selection clears the flags and writes every level's counts itself (launch_select_fast); a run that stops at the
+        // score map leaves them cleared as before
+        if (upto < 2) {
+            HIPCHK(hipMemsetAsync(ff.flags, 0, (size_t)F * sizeof(int), s));
+            HIPCHK(hipMemsetAsync(ff.cand_count, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s));
+            if (cv2) HIPCHK(hipMemsetAsync(cb.all_count, 0, (size_t)F * VO_MAX_LEVELS * sizeof(int), s));
+        }
+    }
+    { StageTimer t(ctx, ST_FAST); launch_fast(s, pyr, score, ff.hist, g, F, upto < 2 ? nullptr : ff.tile_list, ff.tile_count); }
+    if (upto < 2) return VO_OK;
+    { StageTimer t(ctx, ST_SELECT_FAST); launch_select_fast(s, g, ff, F, ctx->sel_thr + (size_t)first_slot * VO_MAX_LEVELS, ctx->sel_chunk_count + (size_t)first_slot * g.sel_chunks_total, ff.tile_list, ff.tile_count, cv2 ? &cb : nullptr); }
+    if (g.score_type == 0) { StageTimer t(ctx, ST_HARRIS); launch_harris(s, pyr, g, ff, F); }
+    { StageTimer t(ctx, ST_SELECT_HARRIS); launch_select_harris(s, g, ff, F, ctx->har_thr + (size_t)first_slot * VO_MAX_LEVELS, ctx->har_kept + (size_t)first_slot * VO_MAX_LEVELS); }
+    if (cv2) {
+        // cv2's list order: permute every level's keypoints the way retainBest's nth_element / partition leave them
+        StageTimer t(ctx, ST_CV2_ORDER);
+        launch_cv2_order(s, g, ff, cb, F, ctx->har_kept + (size_t)first_slot * VO_MAX_LEVELS);
     }
     { StageTimer t(ctx, ST_ANGLE); launch_angle(s, pyr, g, ff, F); }
     { StageTimer t(ctx, ST_BLUR); launch_blur(s, pyr, blur, g, F); }

@@ -88,8 +88,7 @@ struct Cv2Buf {
     uint32_t* all_pos;    // [F][all_total]  (y << 16 | x)
     float*    all_resp;   // [F][all_total]  FAST score
     int*      all_count;  // [F][VO_MAX_LEVELS]
-    int*      chunk_count;// [F][sel_chunks_total + 1]
-    int*      ones;       // [F][VO_MAX_LEVELS] selection threshold 1 = keep every listed winner
+    int*      chunk_count;// [F][sel_chunks_total + 1] listed winners per row of FAST tiles
     uint2*    work;       // [F][all_total]  (response bits, index into the all-list)
     uint32_t* lpos;       // [F][all_total]  positions where the left / right cursor of a partition pass stops
     uint32_t* rpos;
@@ -149,11 +148,11 @@ void launch_gray_plain(hipStream_t s, const uint8_t* src, int channels, int row_
 void launch_resize(hipStream_t s, uint8_t* pyr, const PyrGeom& g, int level, const ResizeTab& tab, int F);
 void launch_fast(hipStream_t s, const uint8_t* pyr, uint8_t* score, uint32_t* hist, const PyrGeom& g, int F,
                  uint32_t* tile_list, int* tile_count);      // tile_list == nullptr: dense score map instead of winner lists
+// cb != nullptr (cv2 keypoint order): the same two launches also write the raster-ordered list of every NMS winner inside the
+// border (the list cv2's first retainBest sees) into cb->all_*
 void launch_select_fast(hipStream_t s, const PyrGeom& g, FrameFeat ff, int F, int* thr, int* chunk_count,
-                        const uint32_t* tile_list, const int* tile_count);
+                        const uint32_t* tile_list, const int* tile_count, const Cv2Buf* cb);
 void launch_harris(hipStream_t s, const uint8_t* pyr, const PyrGeom& g, FrameFeat ff, int F);
-// raster-ordered list of every NMS winner inside the border (the list cv2's first retainBest sees), per level
-void launch_all_winners(hipStream_t s, const PyrGeom& g, FrameFeat ff, const Cv2Buf& cb, int F, const uint32_t* tile_list, const int* tile_count);
 void launch_cv2_order(hipStream_t s, const PyrGeom& g, FrameFeat ff, Cv2Buf cb, int F, const int* kept);
 void launch_retain_raw(hipStream_t s, const float* resp, int n, int n_points, uint2* a, uint32_t* lpos, uint32_t* rpos,
                        int* order, int* n_out);
