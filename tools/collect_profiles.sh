@@ -5,7 +5,10 @@
 #   rocprofv3 --kernel-trace --stats          -> per-kernel average durations (single context: no co-running stream)
 #   rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE   -> HBM traffic per launch and per step (separate passes, MI355X_MICROARCH.md)
 #   rocprofv3 --pmc SQ_*                      -> VALU / SALU / LDS instruction counts, wave cycles, issue stalls
+# Counters are collected in runs of their own, apart from any tracing; every GPU step runs under a time limit and the
+# script stops at the first one that fails.
 set -e
+T="timeout -k 10 300"
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r04}
 DET=${2:-orb}
@@ -14,10 +17,10 @@ O=$R/gpurun_out/prof_$TAG$SUF
 rm -rf $O; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 B="python3 $R/bench.py --contexts 1 --no-cpu-baseline --no-stream-pass --no-sustain --no-faithful-pass --no-extras $DARGS"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 8 --warmup 2 --no-profile > $O/stats.log 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B --steps 3 --warmup 1 --no-profile > $O/fetch.log 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- $B --steps 3 --warmup 1 --no-profile > $O/write.log 2>&1
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT --output-format csv -d $O/sq -- $B --steps 3 --warmup 1 --no-profile > $O/sq.log 2>&1
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 8 --warmup 2 --no-profile > $O/stats.log 2>&1
+$T rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B --steps 3 --warmup 1 --no-profile > $O/fetch.log 2>&1
+$T rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $B --steps 3 --warmup 1 --no-profile > $O/write.log 2>&1
+$T rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT --output-format csv -d $O/sq -- $B --steps 3 --warmup 1 --no-profile > $O/sq.log 2>&1
 cd $R
 # static opcode classes of the dominant kernel, from this build's own ISA (bench.py prices the issue bound with them)
 if [ $DET = sift ]; then echo "{}" > $O/isa_mix.json; else
@@ -29,6 +32,6 @@ python3 tools/collect_traffic.py $O/fetch $O/write $O/${TAG}_pmc_traffic$SUF.jso
 python3 tools/pmc_summary.py $O/sq > $O/${TAG}_pmc_sq_counters$SUF.txt
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${TAG}_final_kernel_stats$SUF.csv
 cp $O/${TAG}_pmc_traffic$SUF.json profiles/${TAG}_pmc_traffic$SUF.json      # bench.py reads it for roofline.traffic
-python3 bench.py --full $DARGS > $O/${TAG}_final_bench$SUF.json 2> $O/bench.err
+timeout -k 10 900 python3 bench.py --full $DARGS > $O/${TAG}_final_bench$SUF.json 2> $O/bench.err
 rm -rf $O/stats $O/fetch $O/write $O/sq
 ls -la $O

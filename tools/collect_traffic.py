@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn two rocprofv3 --pmc runs of bench.py (one with FETCH_SIZE, one with WRITE_SIZE, as
-MI355X_MICROARCH.md prescribes: separate passes, --kernel-trace only) into profiles/<tag>_pmc_traffic.json.
+MI355X_MICROARCH.md prescribes: separate passes, no tracing beside the counters) into profiles/<tag>_pmc_traffic.json.
 
 Units and gfx950 corrections (MI355X_MICROARCH.md, HBM section): both counters are in KiB; WRITE_SIZE reads
 16-byte-per-lane streaming stores exactly; FETCH_SIZE reports half of the bytes of a WIDE COALESCED STREAMING read
@@ -75,7 +75,7 @@ def main():
     out["_meta"] = {"frames_per_launch": int(sys.argv[4]) if len(sys.argv) > 4 else 257,
                     "bench_steps_incl_warmup": steps, "source_hash": source_hash(), "library_version": version,
                     "isa_mix": json.load(open(sys.argv[7])) if len(sys.argv) > 7 else {},
-                    "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --contexts 1 --steps 3 --warmup 1 --no-cpu-baseline --no-profile ... (tools/collect_profiles.sh)"}
+                    "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --contexts 1 --steps 3 --warmup 1 --no-cpu-baseline --no-profile ... (tools/collect_profiles.sh)"}
     json.dump(out, open(sys.argv[3], "w"), indent=1)
     print(json.dumps(out, indent=1))
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic (GPU box): A/B of compile-time knobs under the three-context bench loop.  Each argument is "units:defines", e.g.
-#   tools/experiments/define_variants.sh ":" "cv2order_kernels:-DCV_LDS_CAP=2048" "geom_kernels,vo_api:-DFP_LANES=32"
+#   tools/experiments/define_variants.sh ":" "cv2order_kernels:-DCV_LDS_CAP=2048" "geom_kernels:-DRS_SOLVERS=4"
 # The named units are rebuilt with the defines into a private library (/tmp), the others come from the tree's objects; the product
 # library is never touched.  Two bench runs per variant (value, ms per step, sustained median, the stage times named in $STAGES).
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}

@@ -1,7 +1,7 @@
 """Diagnostic: cycles k_ransac spends per phase (needs a library whose geom_kernels.hip was built with -DVO_EXP_TIMING, which
 repurposes the count fields of vo_pair_result as clock64() deltas; never use such a build for anything else)."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from visual_odometry_amd import synth
 from visual_odometry_amd.frontend import FrontEnd
 C = 64

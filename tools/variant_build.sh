@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostic (GPU box): rebuild ONE source with extra macros into a PRIVATE library copy (the product library is never touched;
 # the copy is selected with VO_HIP_LIBRARY) and run a command with it — by default the bench, printing one stage.
-#   tools/variant_build.sh geom_kernels "-DRS_WAVES=8" ["-DRS_WAVES=6" ...]
+#   tools/variant_build.sh geom_kernels "-DRS_WAVES=8" ["-DRS_SOLVERS=1" "-DRS_SOLVERS=4" "-DVO_EXP_TIMING" ...]
 #   env: BENCH_ARGS (extra bench.py flags), STAGE (stage to print, default essential_ransac), RUN (a command to run instead of the bench)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R/visual_odometry_amd/csrc

@@ -5,10 +5,10 @@
 //   cv2.recoverPose(E, p1, p2, K)                              src/image_pair.py:304-308
 //   cv2.triangulatePoints(P, P0, p1.T, p2.T) and `/= w`        src/image_pair.py:332-339
 //
-// Mapping: one wavefront (64 lanes) per frame pair.  A RANSAC round solves 64 five-point samples,
-// one per lane (Nister's solver: Householder null space, 10x20 elimination, degree-10 root finding
-// by Durand-Kerner); the models are then scored strictly in OpenCV's sequential order, each model
-// by all 64 lanes over the correspondences with a wavefront ballot + popcount, so the adaptive
+// Mapping: one workgroup (4 wavefronts) per frame pair.  A RANSAC round solves 16 five-point samples per
+// solver wave, one per quad of lanes (Nister's solver: Householder null space, 10x20 elimination, degree-10
+// root finding by Durand-Kerner); the models are then scored strictly in OpenCV's sequential order, each model
+// by the 64 lanes of a wave over the correspondences with a wavefront ballot + popcount, so the adaptive
 // iteration count (RANSACUpdateNumIters) and the strict `>` best-model rule are emulated exactly.
 // Compiled with -ffp-contract=off: every operation rounds on its own.
 #include "vo_internal.h"
@@ -199,14 +199,59 @@ __device__ __forceinline__ void conv(const double* a, const double* b, double* r
         for (int j = 0; j <= NB; j++) r[i + j] += a[i] * b[j];
 }
 
-// cv::solvePoly's Durand-Kerner sweeps (Gauss-Seidel updates from the starting points (1+i)^k).
-// FULL: degree 10 (the normal case, static indices).  OpenCV always runs its 300 sweeps (its exit test is
-// maxDiff <= 0); early == false does the same (vo_set_poly_solver(ctx, 1)).  With early == true a lane stops as soon as further sweeps can only move rounding noise: every correction
-// below 4 ulp of its root, or the largest correction has been small and has stopped shrinking for two sweeps
-// (the noise floor of an ill-conditioned / multiple root).  The roots agree with the full iteration to
-// that noise floor; the exit is per lane, so a sample's result does not depend on its wave mates.
-template <bool FULL>
-__device__ __forceinline__ void dk_iterate(const double* c, int n, double* rr, double* ri, bool early)
+// ------------------------------------------------------------------ quad exchange
+// A five-point sample is solved by four adjacent lanes (a quad).  Values travel inside the quad with DPP quad_perm
+// moves, a double as its two 32-bit halves; every lane of the quad must be active at such a move.
+template <int O>
+__device__ __forceinline__ int quad_bcast(int v) { return __builtin_amdgcn_mov_dpp(v, O * 0x55, 0xf, 0xf, true); }
+template <int O>
+__device__ __forceinline__ double quad_bcast(double v)
+{
+    const int lo = quad_bcast<O>(__double2loint(v)), hi = quad_bcast<O>(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double quad_bcast_from(int o, double v)      // o: a constant once the caller's loop is unrolled
+{
+    switch (o) {
+    case 0: return quad_bcast<0>(v);
+    case 1: return quad_bcast<1>(v);
+    case 2: return quad_bcast<2>(v);
+    default: return quad_bcast<3>(v);
+    }
+}
+__device__ __forceinline__ double sel4(int q, double a, double b, double c, double d) { return q == 0 ? a : q == 1 ? b : q == 2 ? c : d; }
+
+// cv::solvePoly's Durand-Kerner sweeps (Gauss-Seidel updates from the starting points (1+i)^k).  OpenCV always runs its
+// 300 sweeps (its exit test is maxDiff <= 0); early == false does the same (vo_set_poly_solver(ctx, 1)).  With early ==
+// true a sample stops as soon as further sweeps can only move rounding noise: every correction below 4 ulp of its root,
+// or the largest correction has been small and has stopped shrinking for two sweeps (the noise floor of an
+// ill-conditioned / multiple root).  The roots agree with the full iteration to that noise floor; the exit is per
+// sample, so a sample's result does not depend on its wave mates.
+//
+// dk_exit: the exit rule after a sweep, shared by the two forms below.  max_diff is the largest SQUARED correction.
+__device__ __forceinline__ bool dk_exit(double max_diff, double max_mag, bool conv_all, bool early, double& prev, int& stall)
+{
+    if (max_diff <= 0 || (early && conv_all)) return true;
+    const double small = 1e-7 * (1.0 + max_mag);
+    if (early && max_diff < small * small) {
+        if (max_diff > 0.25 * prev) { if (++stall >= 2) return true; }
+        else stall = 0;
+    }
+    prev = max_diff;
+    return false;
+}
+
+// Degree 10, the normal case: the work of a sweep is dealt over the quad, the root state (rr, ri) is replicated in its
+// four lanes.  Lane q owns the roots q, q + 4, q + 8 (slots 0..2; slot 2 is idle in lanes 2 and 3).
+//  - The polynomial value at root i depends only on last sweep's root i: each lane runs the Horner recurrences of its
+//    three roots, interleaved, each in the operation order of the sequential form.
+//  - The denominator of root k is c10 * prod_{j != k} (p_k - r_j) taken in ascending j, with this sweep's new r_j for
+//    j < k.  Each lane keeps the running products of its roots; as soon as root i is new, every lane multiplies the factor
+//    j = i into the products of the roots k > i it owns, so a product receives its factors in ascending j.  At step i the
+//    owner of root i appends the old-root factors j > i, divides, and hands the correction to the quad.
+//  - Every lane applies the correction to its copy of root i and runs the exit tests itself: all four lanes hold the same
+//    values, so the exit is uniform over the quad.
+__device__ __forceinline__ void dk_iterate_quad(const double* c, double* rr, double* ri, bool early, int q)
 {
     double prev = 1e300;
     int stall = 0;
@@ -215,56 +260,77 @@ __device__ __forceinline__ void dk_iterate(const double* c, int n, double* rr, d
     for (int iter = 0; iter < sweeps; iter++) {
         bool conv_all = true;
         double max_diff = 0, max_mag = 0;
-        if (FULL) {
-            // The polynomial value at root i depends only on that root's value from the previous sweep, not on this
-            // sweep's updates of the roots before it: the ten Horner recurrences are evaluated first, interleaved
-            // (ten independent dependency chains instead of one), each in exactly the operation order of the
-            // sequential form.  Only the denominators, which do use the updated roots, stay in Gauss-Seidel order;
-            // the scheduler overlaps root i + 1's leading factors with the tail of root i.
-            double nr[10], ni[10];
+        double pr[3], pi[3], nr[3], ni[3], dr[3], di[3];
 #pragma unroll
-            for (int i = 0; i < 10; i++) { nr[i] = c[10]; ni[i] = 0; }
+        for (int t = 0; t < 2; t++) {
+            pr[t] = sel4(q, rr[4 * t], rr[4 * t + 1], rr[4 * t + 2], rr[4 * t + 3]);
+            pi[t] = sel4(q, ri[4 * t], ri[4 * t + 1], ri[4 * t + 2], ri[4 * t + 3]);
+        }
+        pr[2] = (q & 1) ? rr[9] : rr[8]; pi[2] = (q & 1) ? ri[9] : ri[8];
 #pragma unroll
-            for (int j = 0; j < 10; j++)
+        for (int t = 0; t < 3; t++) { nr[t] = c[10]; ni[t] = 0; dr[t] = c[10]; di[t] = 0; }
 #pragma unroll
-                for (int i = 0; i < 10; i++) {
-                    const cplx np = cmul({nr[i], ni[i]}, {rr[i], ri[i]});
-                    nr[i] = np.re + c[9 - j]; ni[i] = np.im;
-                }
+        for (int j = 0; j < 10; j++)
 #pragma unroll
-            for (int i = 0; i < 10; i++) {
-                const cplx p = {rr[i], ri[i]};
-                cplx denom = {c[10], 0};
-                bool coincident = false;                 // two estimates exactly equal: OpenCV skips that factor
+            for (int t = 0; t < 3; t++) {
+                const cplx np = cmul({nr[t], ni[t]}, {pr[t], pi[t]});
+                nr[t] = np.re + c[9 - j]; ni[t] = np.im;
+            }
 #pragma unroll
-                for (int j = 0; j < 10; j++)
-                    if (j != i) {
-                        const cplx d = {p.re - rr[j], p.im - ri[j]};
-                        coincident |= d.re == 0 && d.im == 0;
-                        denom = cmul(denom, d);
-                    }
-                if (__ballot(coincident)) {              // wave-uniform branch; never taken from the distinct starting points (1+i)^k in practice
-                  if (coincident) {
+        for (int i = 0; i < 10; i++) {
+            const int t = i >> 2, o = i & 3;
+            // owner: the old-root factors j > i (lanes that do not own root i compute on, their result is not used)
+            cplx denom = {dr[t], di[t]};
+#pragma unroll
+            for (int j = i + 1; j < 10; j++) denom = cmul(denom, {pr[t] - rr[j], pi[t] - ri[j]});
+            // Two estimates exactly equal: OpenCV skips that factor.  A factor (0, 0) leaves both parts of every later
+            // product at zero or NaN, so only such a product is formed again with the exact test; one that merely
+            // underflowed has no factor to skip and comes out the same.
+            const bool coincident = q == o && !(fabs(denom.re) > 0) && !(fabs(denom.im) > 0);
+            if (__any(coincident)) {                     // wave-uniform branch; never taken from the distinct starting points (1+i)^k in practice
+                if (coincident) {
                     denom = {c[10], 0};
 #pragma unroll
                     for (int j = 0; j < 10; j++)
                         if (j != i) {
-                            const cplx d = {p.re - rr[j], p.im - ri[j]};
+                            const cplx d = {rr[i] - rr[j], ri[i] - ri[j]};
                             if (d.re != 0 || d.im != 0) denom = cmul(denom, d);
                         }
-                  }
                 }
-                const cplx num = cdiv({nr[i], ni[i]}, denom);
-                rr[i] = p.re - num.re; ri[i] = p.im - num.im;
-                // squared magnitudes: the exit tests compare squares (no square root per root)
-                const double ab2 = num.re * num.re + num.im * num.im;
-                max_diff = fmax(max_diff, ab2);
-                const double mag = fabs(rr[i]) + fabs(ri[i]);
-                max_mag = fmax(max_mag, mag);
-                const double lim = 4 * DBL_EPSILON * mag;
-                conv_all &= ab2 <= lim * lim;
             }
-        } else {
+            cplx num = cdiv({nr[t], ni[t]}, denom);
+            num.re = quad_bcast_from(o, num.re); num.im = quad_bcast_from(o, num.im);
+            rr[i] = rr[i] - num.re; ri[i] = ri[i] - num.im;
+            // squared magnitudes: the exit tests compare squares (no square root per root)
+            const double ab2 = num.re * num.re + num.im * num.im;
+            max_diff = fmax(max_diff, ab2);
+            const double mag = fabs(rr[i]) + fabs(ri[i]);
+            max_mag = fmax(max_mag, mag);
+            const double lim = 4 * DBL_EPSILON * mag;
+            conv_all &= ab2 <= lim * lim;
+            // the new root i is the factor j = i of every root k > i
+#pragma unroll
+            for (int t2 = t; t2 < 3; t2++) {
+                if (t2 == t && o == 3) continue;
+                const cplx m = cmul({dr[t2], di[t2]}, {pr[t2] - rr[i], pi[t2] - ri[i]});
+                const bool mine = t2 > t || q > o;
+                dr[t2] = mine ? m.re : dr[t2]; di[t2] = mine ? m.im : di[t2];
+            }
+        }
+        if (dk_exit(max_diff, max_mag, conv_all, early, prev, stall)) break;
+    }
+}
+
+// Degree below 10 (a vanishing leading coefficient, rare): the sequential form, run by every lane of the quad on its copy.
+__device__ __forceinline__ void dk_iterate_low(const double* c, int n, double* rr, double* ri, bool early)
+{
+    double prev = 1e300;
+    int stall = 0;
+    const int sweeps = early ? VO_DK_FAST_CAP : VO_DK_ITERS;
+#pragma unroll 1
+    for (int iter = 0; iter < sweeps; iter++) {
+        bool conv_all = true;
+        double max_diff = 0, max_mag = 0;
 #pragma unroll
         for (int i = 0; i < 10; i++) {
             if (i < n) {
@@ -297,30 +363,35 @@ __device__ __forceinline__ void dk_iterate(const double* c, int n, double* rr, d
                 conv_all &= ab2 <= lim * lim;
             }
         }
-        }
-        // max_diff holds the largest SQUARED correction of the sweep
-        if (max_diff <= 0 || (early && conv_all)) break;
-        const double small = 1e-7 * (1.0 + max_mag);
-        if (early && max_diff < small * small) {
-            if (max_diff > 0.25 * prev) { if (++stall >= 2) break; }
-            else stall = 0;
-        }
-        prev = max_diff;
+        if (dk_exit(max_diff, max_mag, conv_all, early, prev, stall)) break;
     }
 }
 
-// ------------------------------------------------------------------ five-point solver, one sample per lane
+// ------------------------------------------------------------------ five-point solver, one sample per quad
 // x1, x2: 5 normalised correspondences (interleaved x,y). Writes up to 10 row-major 3x3 models
-// (x2^T E x1 = 0, unit Frobenius norm) to Eout and returns their number.
-// cm: this lane's slice of the 10x20 elimination matrix in LDS, element (r, k) at cm[(r*20 + k) * FP_LANES]
-// (consecutive lanes hold consecutive doubles: conflict-free ds_read/write_b64).
-#ifndef FP_LANES
-#define FP_LANES 64          // samples solved per round = lanes of the solver wave; 32 -> 51 KB of LDS, 64 -> 102 KB (measured: -1 % on
-#endif                     // the easy bench sequence, ransac -27 % / +5.7 % pairs/s once pairs need 80 iterations)
-#define CM(r, k) cm[((r) * 20 + (k)) * FP_LANES]
+// (x2^T E x1 = 0, unit Frobenius norm) to Eout and returns their number.  Called by the four lanes of a quad with the
+// same arguments (q = lane & 3); the return value and every early return are uniform over the quad.
+//   null space, constraints, polynomial: every lane computes them (5 % of a solve; the same values in the four lanes)
+//   10x20 elimination: lane q owns the columns 5q .. 5q+4
+//   Durand-Kerner: see dk_iterate_quad
+//   models: the real roots are dealt over the lanes in ascending index, four per pass
+// cm: the wave's block of elimination matrices in LDS, 200 doubles per sample: element (r, 5 * qo + j) of the quad's
+// sample is held by lane qo of the quad at cm[(r * 5 + j) * 64 + lane] (consecutive lanes hold consecutive doubles:
+// conflict-free ds_read/write_b64; a pivot-column read is one address per quad).
+#define FP_QUADS 16          // samples a wave solves at once
 typedef __attribute__((address_space(3))) double lds_double;
-__device__ __noinline__ int five_point_solve(const double* x1, const double* x2, double* Eout, lds_double* cm, bool dk_early)
+#define CMQ(r, j) cm[((r) * 5 + (j)) * 64 + lane]                                   // own column j
+#define CMK(r, k) cm[((r) * 5 + (k) % 5) * 64 + (lane & ~3) + (k) / 5]              // column k of the quad's sample
+__device__ __forceinline__ void quad_lds_sync()
 {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __noinline__ int five_point_solve_quad(const double* x1, const double* x2, double* Eout, lds_double* cm, bool dk_early)
+{
+    const int lane = threadIdx.x & 63, q = lane & 3;
     double basis[36];
     {
         // Householder QR of Q^T (9 x 5); null space = last 4 columns of the orthogonal factor
@@ -379,7 +450,7 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
         }
     }
 
-    // 10 cubic constraints in (x, y, z): det(E) = 0 and (E E^T - 0.5 tr(E E^T) I) E = 0
+    // 10 cubic constraints in (x, y, z): det(E) = 0 and (E E^T - 0.5 tr(E E^T) I) E = 0; each lane stores its columns
     {
         double E[3][3][4];
 #pragma unroll
@@ -403,7 +474,7 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
                 mul21_acc(m, E[0][c], 1.0, row);
             }
 #pragma unroll
-            for (int i = 0; i < 20; i++) CM(0, i) = row[i];
+            for (int j = 0; j < 5; j++) CMQ(0, j) = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
         }
         double L[3][3][10];
 #pragma unroll
@@ -432,35 +503,41 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
 #pragma unroll
                 for (int k = 0; k < 3; k++) mul21_acc(L[r][k], E[k][c], 1.0, row);
 #pragma unroll
-                for (int i = 0; i < 20; i++) CM(1 + r * 3 + c, i) = row[i];
+                for (int j = 0; j < 5; j++) CMQ(1 + r * 3 + c, j) = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
             }
     }
+    quad_lds_sync();
 
-    // Gauss-Jordan with partial pivoting on the left 10 columns
+    // Gauss-Jordan with partial pivoting on the left 10 columns.  Pivot search and the multipliers read column `col`,
+    // which every lane of the quad loads before its owner overwrites it; the row updates are element-wise.
 #pragma unroll 1
     for (int col = 0; col < 10; col++) {
         int piv = col;
-        double best = fabs(CM(col, col));
+        double best = fabs(CMK(col, col));
 #pragma unroll 1
-        for (int r = col + 1; r < 10; r++) { double v = fabs(CM(r, col)); if (v > best) { best = v; piv = r; } }
+        for (int r = col + 1; r < 10; r++) { double v = fabs(CMK(r, col)); if (v > best) { best = v; piv = r; } }
         if (best < 1e-300) return 0;
-        double prow[20];
-        const double inv = 1.0 / CM(piv, col);
+        double prow[5], f[10];
+        const double inv = 1.0 / CMK(piv, col);
+        quad_lds_sync();
 #pragma unroll
-        for (int k = 0; k < 20; k++) {
-            const double a = CM(piv, k), b = CM(col, k);
-            prow[k] = a * inv;
-            CM(piv, k) = b;                      // row swap (no-op when piv == col)
-            CM(col, k) = prow[k];
+        for (int j = 0; j < 5; j++) {
+            const double a = CMQ(piv, j), b = CMQ(col, j);
+            prow[j] = a * inv;
+            CMQ(piv, j) = b;                      // row swap (no-op when piv == col)
+            CMQ(col, j) = prow[j];
         }
-#pragma unroll 1
+        quad_lds_sync();
+#pragma unroll
+        for (int r = 0; r < 10; r++) f[r] = CMK(r, col);
+        quad_lds_sync();
+#pragma unroll
         for (int r = 0; r < 10; r++) {
-            if (r == col) continue;
-            const double f = CM(r, col);
-            if (f == 0) continue;
+            if (r == col || f[r] == 0) continue;
 #pragma unroll
-            for (int k = 0; k < 20; k++) CM(r, k) -= f * prow[k];
+            for (int j = 0; j < 5; j++) CMQ(r, j) -= f[r] * prow[j];
         }
+        quad_lds_sync();
     }
 
     // B(z) [x y 1]^T = 0
@@ -469,7 +546,7 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
     for (int i = 0; i < 3; i++) {
         double r1[10], r2[10];
 #pragma unroll
-        for (int k = 0; k < 10; k++) { r1[k] = CM(2 * i + 4, 10 + k); r2[k] = CM(2 * i + 5, 10 + k); }
+        for (int k = 0; k < 10; k++) { r1[k] = CMK(2 * i + 4, 10 + k); r2[k] = CMK(2 * i + 5, 10 + k); }
         Bx[i][3] = -r2[0]; Bx[i][2] = r1[0] - r2[1]; Bx[i][1] = r1[1] - r2[2]; Bx[i][0] = r1[2];
         By[i][3] = -r2[3]; By[i][2] = r1[3] - r2[4]; By[i][1] = r1[4] - r2[5]; By[i][0] = r1[5];
         Bc[i][4] = -r2[6]; Bc[i][3] = r1[6] - r2[7]; Bc[i][2] = r1[7] - r2[8]; Bc[i][1] = r1[8] - r2[9]; Bc[i][0] = r1[9];
@@ -499,9 +576,7 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
         for (int i = 0; i < 11; i++) c[i] += t3[i];
     }
 
-    // cv::solvePoly: Durand-Kerner from the starting points (1+i)^k, Gauss-Seidel updates.  OpenCV
-    // iterates a fixed 300 times (its exit test is maxDiff <= 0); here the loop also stops once every
-    // correction is below 4 ulp of its root, after which further sweeps only move rounding noise.
+    // cv::solvePoly: Durand-Kerner from the starting points (1+i)^k, Gauss-Seidel updates
     int n = 10;
     while (n > 1 && !(fabs(c[n]) > DBL_EPSILON)) n--;
     double rr[10], ri[10];
@@ -510,46 +585,73 @@ __device__ __noinline__ int five_point_solve(const double* x1, const double* x2,
 #pragma unroll
         for (int i = 0; i < 10; i++) { rr[i] = p.re; ri[i] = p.im; p = cmul(p, r); }
     }
-    if (n == 10) dk_iterate<true>(c, 10, rr, ri, dk_early);
-    else dk_iterate<false>(c, n, rr, ri, dk_early);
+    if (n == 10) dk_iterate_quad(c, rr, ri, dk_early, q);
+    else dk_iterate_low(c, n, rr, ri, dk_early);
 
-    // real roots, in ascending index (OpenCV's order).  Lanes hold their real roots at different indices, so instead
-    // of ten wave-wide passes each lane walks the set bits of its own mask: the wave makes max-popcount passes.
+    // real roots, in ascending index (OpenCV's order): root number 4 * pass + q of the sample goes to lane q, so a
+    // sample needs at most three passes.  The models a pass keeps are stored in root order by the whole quad.
     uint32_t real_mask = 0;
 #pragma unroll
-    for (int q = 0; q < 10; q++) {
-        double zi = ri[q];
+    for (int k = 0; k < 10; k++) {
+        double zi = ri[k];
         if (fabs(zi) < 1e-100) zi = 0;
-        if (q < n && !(fabs(zi) > 1e-10)) real_mask |= 1u << q;
+        if (k < n && !(fabs(zi) > 1e-10)) real_mask |= 1u << k;
     }
+    const int nreal = __popc(real_mask);
     int count = 0;
 #pragma unroll 1
-    while (real_mask) {
-        const int i = __ffs((int)real_mask) - 1;
-        real_mask &= real_mask - 1;
+    for (int m0 = 0; m0 < nreal; m0 += 4) {
+        const int m = m0 + q;
         double zr = 0;
+        {
+            int ord = 0;
 #pragma unroll
-        for (int q = 0; q < 10; q++) if (q == i) zr = rr[q];
-        double z1 = zr, z2 = z1 * z1, z3 = z2 * z1, z4 = z3 * z1;
-        double bz[9], xy1[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            bz[j * 3 + 0] = Bx[j][3] * z3 + Bx[j][2] * z2 + Bx[j][1] * z1 + Bx[j][0];
-            bz[j * 3 + 1] = By[j][3] * z3 + By[j][2] * z2 + By[j][1] * z1 + By[j][0];
-            bz[j * 3 + 2] = Bc[j][4] * z4 + Bc[j][3] * z3 + Bc[j][2] * z2 + Bc[j][1] * z1 + Bc[j][0];
+            for (int k = 0; k < 10; k++) {
+                const bool set = (real_mask >> k) & 1;
+                if (set && ord == m) zr = rr[k];
+                ord += set;
+            }
         }
-        solve_z<3>(bz, xy1);
-        if (fabs(xy1[2]) < 1e-10) continue;
-        double x = xy1[0] / xy1[2], y = xy1[1] / xy1[2], nrm = 0, e[9];
+        double en[9];
 #pragma unroll
-        for (int k = 0; k < 9; k++) {
-            e[k] = basis[k] * x + basis[9 + k] * y + basis[18 + k] * z1 + basis[27 + k];
-            nrm += e[k] * e[k];
+        for (int k = 0; k < 9; k++) en[k] = 0;
+        int keep = 0;
+        if (m < nreal) {
+            double z1 = zr, z2 = z1 * z1, z3 = z2 * z1, z4 = z3 * z1;
+            double bz[9], xy1[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                bz[j * 3 + 0] = Bx[j][3] * z3 + Bx[j][2] * z2 + Bx[j][1] * z1 + Bx[j][0];
+                bz[j * 3 + 1] = By[j][3] * z3 + By[j][2] * z2 + By[j][1] * z1 + By[j][0];
+                bz[j * 3 + 2] = Bc[j][4] * z4 + Bc[j][3] * z3 + Bc[j][2] * z2 + Bc[j][1] * z1 + Bc[j][0];
+            }
+            solve_z<3>(bz, xy1);
+            if (!(fabs(xy1[2]) < 1e-10)) {
+                double x = xy1[0] / xy1[2], y = xy1[1] / xy1[2], nrm = 0, e[9];
+#pragma unroll
+                for (int k = 0; k < 9; k++) {
+                    e[k] = basis[k] * x + basis[9 + k] * y + basis[18 + k] * z1 + basis[27 + k];
+                    nrm += e[k] * e[k];
+                }
+                nrm = sqrt(nrm);
+#pragma unroll
+                for (int k = 0; k < 9; k++) en[k] = e[k] / nrm;
+                keep = 1;
+            }
         }
-        nrm = sqrt(nrm);
-#pragma unroll
-        for (int k = 0; k < 9; k++) Eout[count * 9 + k] = e[k] / nrm;
-        count++;
+        // the quad stores lane o's model: every branch below is uniform over the quad
+#define FP_STORE_MODEL(o)                                                                             \
+        if (quad_bcast<o>(keep)) {                                                                    \
+            double w[9];                                                                              \
+            _Pragma("unroll") for (int k = 0; k < 9; k++) w[k] = quad_bcast<o>(en[k]);                \
+            double* dst = Eout + count * 9;                                                           \
+            dst[q] = sel4(q, w[0], w[1], w[2], w[3]);                                                 \
+            dst[4 + q] = sel4(q, w[4], w[5], w[6], w[7]);                                             \
+            dst[8] = w[8];                                                                            \
+            count++;                                                                                  \
+        }
+        FP_STORE_MODEL(0) FP_STORE_MODEL(1) FP_STORE_MODEL(2) FP_STORE_MODEL(3)
+#undef FP_STORE_MODEL
     }
     return count;
 }
@@ -600,23 +702,29 @@ __device__ __forceinline__ int count_inliers(const double* E, const double* x1, 
 }
 
 // ------------------------------------------------------------------ RANSACPointSetRegistrator::run, one workgroup (4 waves) per pair
-// Round = RS_ROUND (64) minimal samples, one per lane of the solver wave — the adaptive count ends at 9..30 on textured
-// pairs (one round), 50..1000 on wide-baseline or low-inlier pairs, where a 64-sample round halves the number of
-// rounds; the elimination matrices (102 KB) are the only large LDS user and the models live in global memory (L2).  (1) sample indices: the RNG stream (OpenCV's MWC, data independent) is read
+// Round = RS_ROUND minimal samples, 16 per solver wave (one per quad) — the adaptive count ends at 9..30 on textured
+// pairs (one round), 50..1000 on wide-baseline or low-inlier pairs; the elimination matrices (25.6 KB per solver wave)
+// are the only large LDS user and the models live in global memory (L2).  E, mask and inlier count do not depend on the
+// round size; the reported iteration count can, where a sample without models sits at the end of a round.
+// (1) sample indices: the RNG stream (OpenCV's MWC, data independent) is read
 // from a table, `% M` is taken by all threads in parallel, thread 0 only applies the repeat rejection;
-// (2) wave 0 solves the samples, one per lane, elimination matrices in LDS; (3) the models
+// (2) the first RS_SOLVERS waves solve the samples, one per quad, elimination matrices in LDS; (3) the models
 // are scored four at a time (one per wave, ballot + popcount over the correspondences) and consumed strictly
 // in OpenCV's order, so the adaptive iteration count and the strict `>` rule behave as in the serial loop.
-#define RS_STREAM 512                     // RNG numbers staged per round (64 subsets x 5 + rejections)
-#define RS_ROUND FP_LANES
+#define RS_STREAM 512                     // RNG numbers staged per round (up to 64 subsets x 5 + rejections)
 #define RS_SCORE_G 4                       // models a wave scores at once
 #ifndef RS_WAVES
-#define RS_WAVES 4                         // wavefronts of the workgroup: wave 0 solves, all of them score
+#define RS_WAVES 4                         // wavefronts of the workgroup: the first RS_SOLVERS solve, all of them score
 #endif
+#ifndef RS_SOLVERS
+#define RS_SOLVERS 4                       // solver waves: 1, 2 or 4 -> 16, 32 or 64 samples and 26, 51 or 102 KB of LDS per round
+#endif                                     // (measured: 2 and 4 tie while one round serves every pair, 4 wins beyond; docs/experiments.md)
+#define RS_ROUND (FP_QUADS * RS_SOLVERS)
 #define RS_THREADS (64 * RS_WAVES)
+static_assert(RS_SOLVERS >= 1 && RS_SOLVERS <= RS_WAVES && RS_ROUND <= 64, "the sampler and the model list hold at most 64 samples per round");
 
 struct RansacShared {
-    double cm[200 * FP_LANES];          // 102400 B
+    double cm[200 * RS_ROUND];
     uint32_t stream[RS_STREAM];
     int sub[64][5];
     int nm[64];
@@ -628,7 +736,7 @@ struct RansacShared {
 
 __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap, RansacParams rp, const uint32_t* rng_tab, int rng_n)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // dynamic: FP_LANES = 64 needs more than the static 64 KB
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // dynamic: RS_SOLVERS = 4 needs more than the static 64 KB
     RansacShared& sh = *(RansacShared*)s_dyn;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int M = pb.m_count[p];
@@ -646,14 +754,17 @@ __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap
     const float t = (float)(threshold * threshold);
 
     if (M == 5) {       // ptsetreg.cpp: count == modelPoints -> all solutions, every point an inlier
-        if (tid == 0) {
+        if (tid < 4) {                   // one quad
             double* models = pb.models + (size_t)p * 64 * 90;
-            int nm = five_point_solve(x1, x2, models, (lds_double*)sh.cm, rp.dk_early != 0);
-            for (int k = 0; k < 9; k++) res->E[k] = nm > 0 ? models[k] : 0.0;
-            res->status = nm > 0 ? VO_OK : VO_ERR_NO_MODEL;
-            res->n_inl = nm > 0 ? 5 : 0;
-            res->reserved = nm;          // number of stacked models left in pb.models
-            res->ransac_iters = 0;
+            const int nm = five_point_solve_quad(x1, x2, models, (lds_double*)sh.cm, rp.dk_early != 0);
+            __threadfence_block();       // lane 0 reads what the quad stored
+            if (tid == 0) {
+                for (int k = 0; k < 9; k++) res->E[k] = nm > 0 ? models[k] : 0.0;
+                res->status = nm > 0 ? VO_OK : VO_ERR_NO_MODEL;
+                res->n_inl = nm > 0 ? 5 : 0;
+                res->reserved = nm;      // number of stacked models left in pb.models
+                res->ransac_iters = 0;
+            }
         }
         if (tid < 5) mask[tid] = 1;
         return;
@@ -673,7 +784,7 @@ __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap
     for (int r0 = 0; r0 < niters; r0 += RS_ROUND) {
         const int nh = min(RS_ROUND, niters - r0);
         // (1) sample indices.  Subset h starts where subset h - 1 stopped in the RNG stream, and a subset that draws an
-        //     index twice uses extra numbers; that happens in well under 1 % of the subsets, so the 64 lanes of wave 0 draw
+        //     index twice uses extra numbers; that happens in well under 1 % of the subsets, so the lanes of wave 0 draw
         //     their subsets in parallel from assumed start positions (5 numbers per earlier subset), a prefix sum of the
         //     numbers actually used gives the true starts, and the lanes repeat until the starts stop moving (one or two
         //     passes; each pass fixes at least the first lane that was wrong, so it ends).
@@ -723,20 +834,24 @@ __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap
 #ifdef VO_EXP_TIMING
         if (r0 == 0) tB = clock64();
 #endif
-        // (2) solve
-        if (wave == 0) {
-            int nm = 0;
-            if (lane < nh) {
+        // (2) solve: sample h = 16 * wave + lane / 4, by the four lanes of its quad
+        if (wave < RS_SOLVERS) {
+            const int h = wave * FP_QUADS + (lane >> 2);
+            if (h < nh) {
                 double s1[10], s2[10];
 #pragma unroll
                 for (int i = 0; i < 5; i++) {
-                    const int v = sh.sub[lane][i];
+                    const int v = sh.sub[h][i];
                     s1[2 * i] = x1[2 * v]; s1[2 * i + 1] = x1[2 * v + 1];
                     s2[2 * i] = x2[2 * v]; s2[2 * i + 1] = x2[2 * v + 1];
                 }
-                nm = five_point_solve(s1, s2, gmodels + lane * 90, (lds_double*)sh.cm + lane, rp.dk_early != 0);
+                const int nm = five_point_solve_quad(s1, s2, gmodels + h * 90, (lds_double*)sh.cm + wave * (200 * FP_QUADS), rp.dk_early != 0);
+                if ((lane & 3) == 0) sh.nm[h] = nm;
             }
-            sh.nm[lane] = nm;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int nm = lane < nh ? sh.nm[lane] : 0;
             // exclusive prefix of the model counts + flattened (sample, model) list
             int inc = nm;
 #pragma unroll
@@ -1116,14 +1231,17 @@ void launch_pose(hipStream_t s, PairBuf pb, int kp_cap, int P, RansacParams rp)
 __global__ __launch_bounds__(64) void k_five_point_raw(const double* x1, const double* x2, double* E, int* nm, int dk_early)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    if (threadIdx.x == 0 && blockIdx.x == 0) *nm = five_point_solve(x1, x2, E, (lds_double*)s_dyn, dk_early != 0);
+    if (threadIdx.x < 4 && blockIdx.x == 0) {       // one quad
+        const int n = five_point_solve_quad(x1, x2, E, (lds_double*)s_dyn, dk_early != 0);
+        if (threadIdx.x == 0) *nm = n;
+    }
 }
 
 void launch_five_point_raw(hipStream_t s, const double* x1, const double* x2, double* E, int* nm, int dk_early)
 {
     static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_five_point_raw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(200 * FP_LANES * sizeof(double))); attr = true; }
-    hipLaunchKernelGGL(k_five_point_raw, dim3(1), dim3(64), 200 * FP_LANES * sizeof(double), s, x1, x2, E, nm, dk_early);
+    if (!attr) { (void)hipFuncSetAttribute((const void*)k_five_point_raw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(200 * FP_QUADS * sizeof(double))); attr = true; }
+    hipLaunchKernelGGL(k_five_point_raw, dim3(1), dim3(64), 200 * FP_QUADS * sizeof(double), s, x1, x2, E, nm, dk_early);
 }
 
 // ------------------------------------------------------------------ reprojection-error filter
