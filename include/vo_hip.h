@@ -413,11 +413,62 @@ int vo_bundle_adjust(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int n
                      double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2 /* [2] */,
                      int32_t* iterations_run, int32_t* trials_run);
 
+/* ------------------------------------------------------------------ the complete per-frame map step on resident data
+ * vo_tracks_pnp_batch's walk joined to what ends every frame of VisualSlam.estimate_current_camera_position
+ * (src/visual_slam.py:190-266) and of its caller (:306-311), on a map that stays on the device: points, cameras and the
+ * Observation list (src/map.py).  Same input as vo_tracks_pnp_batch (all B pairs of the most recent vo_pairs_run with
+ * want_points, a chain of distinct frames), same stop rule and statuses; additionally the run's match_mode must be
+ * one-to-one (0 or 2): with ratio matches two inliers can share a track root and the reference's insert order is not
+ * defined by the data (VO_ERR_UNSUPPORTED).
+ *   pair 0: initialize_map (:43-92) — cameras as vo_tracks_pnp_batch stores them (first fixed, second free), one point
+ *     per E inlier under featureid1, per inlier in match order the observations (point, camera 1, keypoint1), (point,
+ *     camera 2, keypoint2) (:79-87); optimize_map (:90).  No filter, no PnP (len(list_of_frames) < 3, :198).
+ *   pair p >= 1: correspondences -> solvePnPRansac -> camera -> triangulation as vo_tracks_pnp_batch, reading the map
+ *     points and the camera of frame 1 as bundle adjustment and filter left them; add_information_to_map (:152-179):
+ *     every inlier within max_point_norm, in match order, decided against the map as it was before the loop (:154-156) —
+ *     root in the map: one observation (that point, camera 2, keypoint2) (:121-129); otherwise a new point under featureid1
+ *     with observations on camera 1, then camera 2 (:101-119); freeze_nonlast_cameras (:270-275): all cameras fixed but
+ *     the last free_cameras (1 .. VO_BA_MAX_FREE covers unfreeze_cameras, :281-286); optimize_map (:265, src/map.py:104-186:
+ *     vo_bundle_adjust's kernel on the resident lists, poses and points written back); the filter (:266, map.py:46-70):
+ *     an observation stays when its squared reprojection error < filter_threshold, points are not removed;
+ *     limit_number_of_camera_in_map(max_cameras) (:311, map.py:299-318): beyond that, remove_camera_from_map(cameras[0])
+ *     (map.py:188-232) — its observations go, then every point that is left with exactly ONE observation and that
+ *     observation (a point with none is not counted by the defaultdict and stays); a removed point's feature id can
+ *     receive a new point later.
+ * A pair whose localisation fails does none of this and ends the chain [deviation, as vo_tracks_pnp_batch].
+ * ba_iterations = 0, filter_threshold <= 0 and max_cameras >= B + 1 give vo_tracks_pnp_batch's poses and counts, byte for
+ * byte.  max_cameras + 1 must not exceed VO_BA_MAX_CAMERAS (VO_ERR_UNSUPPORTED); max_cameras >= 2.
+ * poses_pnp: every camera as it entered the map (rows 0, 1: the initial pair; then solvePnPRansac's result); poses: every
+ * camera as the map last held it (at the end of the chain, or when it was evicted); zeros for a pair not localised.
+ * n_pts / n_obs / n_cam: the map's sizes after every pair; chi2 [B][2], ba_iterations_run, ba_trials_run: as
+ * vo_bundle_adjust reports them, per pair.
+ * vo_slam_map_size / vo_slam_map: which = 0 the map at the end of the chain, 1 the snapshot — a device-to-device copy
+ * taken during the run at pair snapshot_pair after stage 1 add_information_to_map (before bundle adjustment), 2 bundle
+ * adjustment, 3 the filter, 4 the camera limit (the seam the tests use, as vo_stage_* is for the detector).  cam_frame:
+ * index of the camera's frame in the chain; pt_feature: [npt][2] = (index of the frame in the chain, keypoint) of the
+ * owning feature id.  A configure call or a vo_pairs_run forgets both maps (VO_ERR_INVALID). */
+typedef struct {
+    int32_t pnp_iterations; double reproj_err, confidence; uint64_t seed;   /* cv2's 100, 8.0, 0.99 (:231-235) */
+    double  max_point_norm;          /* 50 (:177) */
+    int32_t ba_iterations;           /* 40 (map.py:172); 0: no bundle adjustment */
+    double  huber_delta;             /* 1.0 (map.py:161) */
+    int32_t free_cameras;            /* 2 (:270-275) */
+    double  filter_threshold;        /* 1.0 (:266); <= 0: no filter */
+    int32_t max_cameras;             /* 18 (:311) */
+    int32_t snapshot_pair, snapshot_stage;   /* -1, 0: none */
+} vo_slam_opts;
+int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_opts* opts, double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
+                  int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                  double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run);
+int vo_slam_map_size(vo_ctx* ctx, int which, int32_t* ncam, int32_t* npt, int32_t* nobs);
+int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[ncam][12]*/, uint8_t* cam_fixed, int32_t* pt_feature /*[npt][2]*/,
+                double* points /*[npt][3]*/, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy /*[nobs][2]*/);
+
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since
  * the last vo_profile_reset. */
-#define VO_STAGE_COUNT 24
+#define VO_STAGE_COUNT 28
 int vo_profile_enable(vo_ctx* ctx, int on);
 int vo_profile_reset(vo_ctx* ctx);
 int vo_profile_read(vo_ctx* ctx, float* ms /*VO_STAGE_COUNT*/, int32_t* launches /*VO_STAGE_COUNT*/);

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("VO_HIP_LIBRARY") or os.path.join(_HERE, "libvo_hip.so
 VO_OK, VO_WARN_CAPACITY = 0, 1
 VO_ERR_INVALID, VO_ERR_HIP, VO_ERR_TOO_FEW, VO_ERR_NO_MODEL, VO_ERR_NOT_CONFIGURED, VO_ERR_AMBIGUOUS = -1, -2, -3, -4, -5, -6
 VO_ERR_UNSUPPORTED = -7
-VO_STAGE_COUNT = 24
+VO_STAGE_COUNT = 28
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
 VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
 
@@ -40,6 +40,13 @@ class PairOpts(C.Structure):
 
 class BaOpts(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("huber_delta", C.c_double)]
+
+
+class SlamOpts(C.Structure):
+    _fields_ = [("pnp_iterations", C.c_int32), ("reproj_err", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64),
+                ("max_point_norm", C.c_double), ("ba_iterations", C.c_int32), ("huber_delta", C.c_double),
+                ("free_cameras", C.c_int32), ("filter_threshold", C.c_double), ("max_cameras", C.c_int32),
+                ("snapshot_pair", C.c_int32), ("snapshot_stage", C.c_int32)]
 
 
 PAIR_RESULT_DTYPE = np.dtype([("n_kp1", "<i4"), ("n_kp2", "<i4"), ("n_match", "<i4"), ("n_inl", "<i4"),
@@ -87,6 +94,9 @@ _SIGS = {
     "vo_knn2_l2": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "vo_knn2_ratio_l2": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
     "vo_tracks_pnp_batch": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, C.c_double, _P, _P, _P, _P, _P]),
+    "vo_slam_chain": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vo_slam_map_size": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "vo_slam_map": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_comm_unique_id": (C.c_int, [_P]),
     "vo_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "vo_comm_destroy": (C.c_int, [_P]),

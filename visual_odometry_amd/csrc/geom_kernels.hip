@@ -12,6 +12,7 @@
 // iteration count (RANSACUpdateNumIters) and the strict `>` best-model rule are emulated exactly.
 // Compiled with -ffp-contract=off: every operation rounds on its own.
 #include "vo_internal.h"
+#include "chain_common.h"
 #include <float.h>
 
 #define WAVE 64
@@ -1255,15 +1256,7 @@ __global__ void k_reprojection(const double* poses, int ncam, const double* poin
     if (i >= nobs) return;
     const int ci = obs_cam[i], pi = obs_pt[i];
     if (ci < 0 || ci >= ncam || pi < 0 || pi >= npt) { atomicOr(bad, 1); sqerr[i] = 0; keep[i] = 0; return; }
-    const double* T = poses + 16 * (size_t)ci;
-    const double* X = points + 3 * (size_t)pi;
-    double c[3], t[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) c[r] = T[4 * r] * X[0] + T[4 * r + 1] * X[1] + T[4 * r + 2] * X[2] + T[4 * r + 3] * 1.0;
-#pragma unroll
-    for (int r = 0; r < 3; r++) t[r] = Kd[3 * r] * c[0] + Kd[3 * r + 1] * c[1] + Kd[3 * r + 2] * c[2];
-    const double dx = t[0] / t[2] - obs_xy[2 * i], dy = t[1] / t[2] - obs_xy[2 * i + 1];
-    const double e = dx * dx + dy * dy;
+    const double e = reprojection_sqerr_one(poses + 16 * (size_t)ci, points + 3 * (size_t)pi, Kd, obs_xy[2 * i], obs_xy[2 * i + 1]);
     sqerr[i] = e;
     keep[i] = e < threshold ? 1 : 0;
 }
@@ -1320,7 +1313,7 @@ void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, 
 
 // ------------------------------------------------------------------ the localisation chain on resident pair results
 // VisualSlam's steady state (src/visual_slam.py:183-266, 153-180) for the pairs vo_pairs_run left in HBM, in their order,
-// without a host round trip and without the bundle adjustment (src/map.py:104-186, out of scope):
+// without a host round trip and without the bundle adjustment (src/map.py:104-186; vo_slam_chain runs it after every pair, slam_kernels.hip):
 //   update_feature_mapper (:183-188)            -> k_chain_link, all pairs at once (a feature id is a key of one pair only)
 //   initialize_map (:43-92)                     -> k_chain_init: cameras of pair 0, one map point per inlier keyed by featureid1
 //   estimate_current_camera_position (:190-235) -> k_chain_gather: matches whose track root is in the map -> (map, image) coordinates
@@ -1328,17 +1321,6 @@ void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, 
 //   add_information_to_map (:153-180)           -> k_chain_triangulate with K pose(frame2), K pose(frame1); k_chain_insert:
 //                                                  points beyond 50 units dropped, a point whose root is unmapped is added under
 //                                                  featureid1 (as add_new_match_to_map does)
-__device__ __forceinline__ size_t chain_key(int f, int i, int cap) { return (size_t)f * cap + i; }
-
-__device__ __forceinline__ void chain_root(const unsigned long long* parent, int cap, int F, int& f, int& i)
-{
-    for (int n = 0; n <= F; n++) {                      // track_feature_back_in_time (:94-99)
-        const unsigned long long v = parent[chain_key(f, i, cap)];
-        if (v == 0) return;
-        f = (int)((v >> 20) & 0xfffffu); i = (int)(v & 0xfffffu);
-    }
-}
-
 __global__ void k_chain_link(PairBuf pb, int kp_cap, ChainBuf cb)
 {
     const int p = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1352,28 +1334,6 @@ __global__ void k_chain_link(PairBuf pb, int kp_cap, ChainBuf cb)
 void launch_chain_link(hipStream_t s, PairBuf pb, int kp_cap, int P, ChainBuf cb)
 {
     hipLaunchKernelGGL(k_chain_link, dim3((kp_cap + 255) / 256, P), dim3(256), 0, s, pb, kp_cap, cb);
-}
-
-// the j-th inlier's match index: inliers are numbered in match order, as k_pose compacts them (and as X's columns run)
-template <typename F>
-__device__ __forceinline__ void chain_for_each_inlier(const PairBuf& pb, int kp_cap, int p, int* s_w, F&& body)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int M = pb.m_count[p];
-    const uint8_t* mask = pb.mask + (size_t)p * kp_cap;
-    int base = 0;
-    for (int b = 0; b < M; b += 256) {
-        const int i = b + tid;
-        const bool f = i < M && mask[i] != 0;
-        const unsigned long long bal = __ballot(f);
-        __syncthreads();
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int off = 0, tot = 0;
-        for (int w = 0; w < 4; w++) { const int c = s_w[w]; if (w < wave) off += c; tot += c; }
-        body(f, i, base + off + (int)__popcll(bal & ((1ULL << lane) - 1)));
-        base += tot;
-    }
 }
 
 // [deviation, documented in DESIGN.md] the reference stores camera 1 = (I, 0) and camera 2 = (R, t) but its first points in

@@ -1,0 +1,305 @@
+// slam_kernels.hip — the map step that ends every frame of the reference's loop, on a map that stays in HBM (vo_slam_chain):
+//   add_information_to_map with its Observations (src/visual_slam.py:101-180) -> k_slam_add
+//   freeze_nonlast_cameras (:270-275)                                         -> k_slam_add (the flags are part of the camera list)
+//   Map.optimize_map's graph bookkeeping (src/map.py:121-164)                 -> k_slam_ba_prepare, then k_bundle_adjust (ba_kernels.hip)
+//   remove_observations_with_reprojection_errors_above_threshold (:46-70)     -> k_slam_filter
+//   limit_number_of_camera_in_map / remove_camera_from_map (:188-232, 299-318)-> k_slam_limit
+// One workgroup of 256 lanes per map and kernel: the walk is sequential by nature and the maps are the reference's size.
+// Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
+// order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
+#include "chain_common.h"
+
+#define SLAM_THREADS 256
+#define SLAM_WAVES (SLAM_THREADS / 64)
+
+// Ordered exclusive prefix sum over get(0) .. get(n - 1), 256 items per round: put(i, sum of the items before i, get(i)).
+// n is uniform.  Within a round every get() runs before every put() (barriers), and a round's put() never writes where a
+// later round's get() reads as long as put(i, pos, ..) writes at or below position i: a list can be compacted in place.
+template <typename G, typename W>
+__device__ __forceinline__ int slam_scan(int n, int* s_w, G&& get, W&& put)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int b = 0; b < n; b += SLAM_THREADS) {
+        const int i = b + tid;
+        const int v = i < n ? get(i) : 0;
+        int x = v;
+        for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
+        __syncthreads();
+        if (lane == 63) s_w[wave] = x;
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < SLAM_WAVES; w++) { const int c = s_w[w]; if (w < wave) off += c; tot += c; }
+        if (i < n) put(i, base + off + x - v, v);
+        base += tot;
+    }
+    return base;
+}
+
+// initialize_map (:56-87) for pair 0, add_information_to_map's loop (:152-179) for pair p >= 1: the camera of frame 2 joins the
+// camera list, and every E inlier in match order appends what the reference appends — a new point under featureid1 with its
+// observations on camera 1 and camera 2, or one observation of the point its track root owns.  Pass 1 takes every decision
+// against the map as it was before the loop (the snapshot of :154-156) and stores it; pass 2 writes, after a barrier.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
+                                                           ChainBuf cb, SlamBuf sb)
+{
+    __shared__ int s_w[SLAM_WAVES], s_cnt[3][SLAM_WAVES];
+    if (!cb.alive[0]) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
+    const int ncam0 = sb.m.cnt[0], npt0 = sb.m.cnt[1], nobs0 = sb.m.cnt[2];
+    const int newn = ncam0 + (p == 0 ? 2 : 1);
+    if (newn > sb.cam_cap || (p > 0 && ncam0 < 1)) return;   // cannot happen: the host sizes the list from max_cameras
+    const int c1 = newn - 2, c2 = newn - 1;
+    if (p == 0) {
+        if (tid < 24) sb.m.cam_pose[tid] = cb.poses[tid];
+        if (tid < 2) sb.m.cam_frame[tid] = tid;
+    } else {
+        if (tid < 12) sb.m.cam_pose[(size_t)c2 * 12 + tid] = cb.cam[(size_t)f2 * 12 + tid];
+        if (tid == 0) sb.m.cam_frame[c2] = p + 1;
+    }
+    // initialize_map: first camera fixed, second free; afterwards freeze_nonlast_cameras: all fixed but the last free_cameras
+    for (int c = tid; c < newn; c += SLAM_THREADS) sb.m.cam_fixed[c] = p == 0 ? (c == 0) : (c < newn - free_cameras);
+
+    chain_for_each_inlier(pb, kp_cap, p, s_w, [&](bool f, int i, int pos) {
+        if (!f) return;
+        int d = -1;                                            // -1: new point, -2: skipped, >= 0: observation of that point
+        if (p > 0) {
+            const double x = cb.Xw[4 * (size_t)pos], y = cb.Xw[4 * (size_t)pos + 1], z = cb.Xw[4 * (size_t)pos + 2];
+            if (!(sqrt(x * x + y * y + z * z) <= max_norm)) d = -2;   // np.linalg.norm(match.point) > 50: continue (NaN: kept out)
+            else {
+                int rf = f2, ri = pb.m_t[(size_t)p * kp_cap + i];
+                chain_root(cb.parent, kp_cap, F, rf, ri);
+                d = sb.pt_of[chain_key(rf, ri, kp_cap)] - 1;
+            }
+        }
+        sb.dec[i] = d;
+    });
+    __syncthreads();
+
+    const int M = pb.m_count[p];
+    const uint8_t* mask = pb.mask + (size_t)p * kp_cap;
+    const double* px1 = pb.px1 + (size_t)p * kp_cap * 2;
+    const double* px2 = pb.px2 + (size_t)p * kp_cap * 2;
+    int ibase = 0, pbase = 0, obase = 0;
+    for (int b = 0; b < M; b += SLAM_THREADS) {
+        const int i = b + tid;
+        const bool inl = i < M && mask[i] != 0;
+        const int d = inl ? sb.dec[i] : -2;
+        const bool is_new = d == -1, is_old = d >= 0;
+        const unsigned long long bal_i = __ballot(inl), bal_n = __ballot(is_new), bal_o = __ballot(is_old);
+        __syncthreads();
+        if (lane == 0) { s_cnt[0][wave] = __popcll(bal_i); s_cnt[1][wave] = __popcll(bal_n); s_cnt[2][wave] = __popcll(bal_o); }
+        __syncthreads();
+        int off[3] = {0, 0, 0}, tot[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++)
+            for (int w = 0; w < SLAM_WAVES; w++) { const int c = s_cnt[k][w]; if (w < wave) off[k] += c; tot[k] += c; }
+        const unsigned long long lower = (1ULL << lane) - 1;
+        const int ipos = ibase + off[0] + (int)__popcll(bal_i & lower);
+        const int nb = off[1] + (int)__popcll(bal_n & lower), ob = off[2] + (int)__popcll(bal_o & lower);
+        const int pi = npt0 + pbase + nb, oi = nobs0 + obase + 2 * nb + ob;
+        if (is_new && pi < sb.pt_cap && oi + 2 <= sb.obs_cap) {     // add_new_match_to_map / initialize_map's loop
+            const size_t k = chain_key(f1, pb.m_q[(size_t)p * kp_cap + i], kp_cap);
+            double X[3];
+            for (int a = 0; a < 3; a++) X[a] = p == 0 ? cb.map_pt[3 * k + a] : cb.Xw[4 * (size_t)ipos + a];
+            if (p > 0) { cb.in_map[k] = 1; for (int a = 0; a < 3; a++) cb.map_pt[3 * k + a] = X[a]; }
+            sb.pt_of[k] = pi + 1;
+            sb.m.pt_key[pi] = (int)k;
+            for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)pi + a] = X[a];
+            sb.m.obs_cam[oi] = c1; sb.m.obs_pt[oi] = pi;
+            sb.m.obs_xy[2 * (size_t)oi] = px1[2 * i]; sb.m.obs_xy[2 * (size_t)oi + 1] = px1[2 * i + 1];
+            sb.m.obs_cam[oi + 1] = c2; sb.m.obs_pt[oi + 1] = pi;
+            sb.m.obs_xy[2 * (size_t)oi + 2] = px2[2 * i]; sb.m.obs_xy[2 * (size_t)oi + 3] = px2[2 * i + 1];
+        }
+        if (is_old && oi < sb.obs_cap) {                            // add_new_observation_of_existing_point
+            sb.m.obs_cam[oi] = c2; sb.m.obs_pt[oi] = d;
+            sb.m.obs_xy[2 * (size_t)oi] = px2[2 * i]; sb.m.obs_xy[2 * (size_t)oi + 1] = px2[2 * i + 1];
+        }
+        ibase += tot[0]; pbase += tot[1]; obase += 2 * tot[1] + tot[2];
+    }
+    __syncthreads();
+    if (tid == 0) { sb.m.cnt[0] = newn; sb.m.cnt[1] = min(npt0 + pbase, sb.pt_cap); sb.m.cnt[2] = min(nobs0 + obase, sb.obs_cap); }
+}
+
+void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_add, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+// g2o's graph bookkeeping for the resident map — the lists the host loop of vo_bundle_adjust_batch builds, entry for entry:
+// camera -> column of S, the observations sorted by point (stable in input order) with pt_first, and per block (c1 <= c2) of
+// free cameras the (observation of c1, observation of c2) that share a point: blocks (0,0) (0,1) .. (F-1,F-1), within a block
+// by point, then input order.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_ba_prepare(ChainBuf cb, SlamBuf sb)
+{
+    __shared__ int s_w[SLAM_WAVES], s_col[VO_BA_MAX_CAMERAS], s_nfree, s_over;
+    const int tid = threadIdx.x;
+    const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
+    if (!cb.alive[0] || ncam > VO_BA_MAX_CAMERAS) {
+        if (tid == 0) { BaProblem q{}; q.skip = 1; sb.prob[0] = q; }
+        return;
+    }
+    if (tid == 0) {
+        int f = 0;
+        for (int i = 0; i < ncam; i++) { const int c = sb.m.cam_fixed[i] ? -1 : f++; s_col[i] = c; sb.cam_col[i] = c; }
+        s_nfree = f; s_over = 0;
+    }
+    for (int q = tid; q < npt; q += SLAM_THREADS) sb.tmp[q] = 0;
+    __syncthreads();
+    const int nfree = s_nfree;
+    for (int i = tid; i < nobs; i += SLAM_THREADS) atomicAdd(&sb.tmp[sb.m.obs_pt[i]], 1);
+    __syncthreads();
+    // pt_first; tmp becomes the points' fill cursors
+    slam_scan(npt, s_w, [&](int q) { return sb.tmp[q]; }, [&](int q, int at, int) { sb.pt_first[q] = at; sb.tmp[q] = at; });
+    if (tid == 0) sb.pt_first[npt] = nobs;
+    __syncthreads();
+    // every observation takes a slot of its point; the lane that owns the point then puts its slots in input order
+    for (int i = tid; i < nobs; i += SLAM_THREADS) sb.idx[atomicAdd(&sb.tmp[sb.m.obs_pt[i]], 1)] = i;
+    __syncthreads();
+    for (int q = tid; q < npt; q += SLAM_THREADS) {
+        const int j0 = sb.pt_first[q], j1 = sb.pt_first[q + 1];
+        for (int a = j0 + 1; a < j1; a++) {
+            const int v = sb.idx[a];
+            int b = a - 1;
+            while (b >= j0 && sb.idx[b] > v) { sb.idx[b + 1] = sb.idx[b]; b--; }
+            sb.idx[b + 1] = v;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < nobs; j += SLAM_THREADS) {
+        const int i = sb.idx[j];
+        sb.s_cam[j] = sb.m.obs_cam[i]; sb.s_pt[j] = sb.m.obs_pt[i];
+        sb.s_xy[2 * (size_t)j] = sb.m.obs_xy[2 * (size_t)i]; sb.s_xy[2 * (size_t)j + 1] = sb.m.obs_xy[2 * (size_t)i + 1];
+    }
+    __syncthreads();
+    // pair lists, block after block: a lane owns a point, the points' offsets inside a block are an ordered scan of their counts
+    int base = 0, blk = 0;
+    if (tid == 0) sb.blk_first[0] = 0;
+    for (int a = 0; a < nfree; a++)
+        for (int c = a; c < nfree; c++, blk++) {
+            const int total = slam_scan(npt, s_w,
+                [&](int q) {
+                    int na = 0, nc = 0;
+                    for (int j = sb.pt_first[q]; j < sb.pt_first[q + 1]; j++) { const int k = s_col[sb.s_cam[j]]; na += k == a; nc += k == c; }
+                    return na * nc;
+                },
+                [&](int q, int at, int n) {
+                    if (n == 0) return;
+                    if (base + at + n > sb.pair_cap) { s_over = 1; return; }
+                    int o = base + at;
+                    for (int j1 = sb.pt_first[q]; j1 < sb.pt_first[q + 1]; j1++) {
+                        if (s_col[sb.s_cam[j1]] != a) continue;
+                        for (int j2 = sb.pt_first[q]; j2 < sb.pt_first[q + 1]; j2++)
+                            if (s_col[sb.s_cam[j2]] == c) sb.pairs[o++] = make_int2(j1, j2);
+                    }
+                });
+            base = min(base + total, sb.pair_cap);
+            if (tid == 0) sb.blk_first[blk + 1] = base;
+        }
+    __syncthreads();
+    if (tid == 0) {
+        BaProblem q{};
+        q.ncam = ncam; q.npt = npt; q.nobs = nobs; q.nfree = nfree;
+        q.skip = s_over || nfree > VO_BA_MAX_FREE;            // (a pair list beyond its capacity: a point seen twice by one camera, which one-to-one matches exclude)
+        sb.prob[0] = q;
+    }
+}
+
+void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_ba_prepare, dim3(1), dim3(SLAM_THREADS), 0, s, cb, sb);
+}
+
+__device__ __forceinline__ int slam_slot_of(const PairBuf& pb, int chain_frame)
+{
+    return chain_frame == 0 ? pb.slots[0] : pb.slots[2 * (chain_frame - 1) + 1];
+}
+
+// What optimize_map wrote back (map.py:175-186) reaches the tables the next pair's k_chain_gather / k_chain_pose read; then
+// remove_observations_with_reprojection_errors_above_threshold (map.py:46-70) with k_reprojection's arithmetic, the list
+// compacted in place and in order.  Points are not removed here: one that loses every observation stays usable for PnP.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    __shared__ int s_w[SLAM_WAVES];
+    if (!cb.alive[0]) return;
+    const int tid = threadIdx.x;
+    const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
+    for (int k = tid; k < ncam * 12; k += SLAM_THREADS)
+        cb.cam[(size_t)slam_slot_of(pb, sb.m.cam_frame[k / 12]) * 12 + k % 12] = sb.m.cam_pose[k];
+    for (int q = tid; q < npt; q += SLAM_THREADS)
+        for (int a = 0; a < 3; a++) cb.map_pt[3 * (size_t)sb.m.pt_key[q] + a] = sb.m.pt_xyz[3 * (size_t)q + a];
+    if (!(threshold > 0)) return;
+    int ci = 0, pi = 0; double u = 0, v = 0;
+    const int kept = slam_scan(nobs, s_w,
+        [&](int i) {
+            ci = sb.m.obs_cam[i]; pi = sb.m.obs_pt[i]; u = sb.m.obs_xy[2 * (size_t)i]; v = sb.m.obs_xy[2 * (size_t)i + 1];
+            return reprojection_sqerr_one(sb.m.cam_pose + 12 * (size_t)ci, sb.m.pt_xyz + 3 * (size_t)pi, Kd, u, v) < threshold ? 1 : 0;
+        },
+        [&](int, int at, int keep) {
+            if (!keep) return;
+            sb.m.obs_cam[at] = ci; sb.m.obs_pt[at] = pi; sb.m.obs_xy[2 * (size_t)at] = u; sb.m.obs_xy[2 * (size_t)at + 1] = v;
+        });
+    __syncthreads();
+    if (tid == 0) sb.m.cnt[2] = kept;
+}
+
+void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_filter, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
+}
+
+// limit_number_of_camera_in_map (map.py:299-318): with more than max_cameras cameras, remove_camera_from_map(cameras[0])
+// (:188-232) with the quirk it has — observations are counted per point AMONG POINTS THAT STILL HAVE ONE (a defaultdict), so a
+// point left with one observation goes and a point with none stays.  A removed point leaves mappointdict: its feature id can
+// receive a new point later.  Camera and point indices in the observations are renumbered.  Also the end of a pair: every
+// camera's pose as the map holds it goes to poses_last (an evicted camera keeps its last row), the map's sizes to n_*.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+{
+    __shared__ int s_w[SLAM_WAVES];
+    const int tid = threadIdx.x;
+    int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
+    if (cb.alive[0]) {
+        for (int k = tid; k < ncam * 12; k += SLAM_THREADS) sb.poses_last[(size_t)sb.m.cam_frame[k / 12] * 12 + k % 12] = sb.m.cam_pose[k];
+        if (ncam > max_cameras) {
+            for (int q = tid; q < npt; q += SLAM_THREADS) sb.tmp[q] = 0;
+            __syncthreads();
+            for (int i = tid; i < nobs; i += SLAM_THREADS) if (sb.m.obs_cam[i] != 0) atomicAdd(&sb.tmp[sb.m.obs_pt[i]], 1);
+            __syncthreads();
+            // the points, in order; tmp becomes old index -> new index (-1: removed)
+            int key = 0; double X[3] = {0, 0, 0};
+            const int npt2 = slam_scan(npt, s_w,
+                [&](int q) { key = sb.m.pt_key[q]; for (int a = 0; a < 3; a++) X[a] = sb.m.pt_xyz[3 * (size_t)q + a]; return sb.tmp[q] != 1 ? 1 : 0; },
+                [&](int q, int at, int keep) {
+                    if (!keep) { sb.tmp[q] = -1; sb.pt_of[key] = 0; cb.in_map[key] = 0; return; }
+                    sb.tmp[q] = at; sb.pt_of[key] = at + 1; sb.m.pt_key[at] = key;
+                    for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)at + a] = X[a];
+                });
+            __syncthreads();
+            int ci = 0, pi = 0; double u = 0, v = 0;
+            const int nobs2 = slam_scan(nobs, s_w,
+                [&](int i) {
+                    ci = sb.m.obs_cam[i]; pi = sb.tmp[sb.m.obs_pt[i]]; u = sb.m.obs_xy[2 * (size_t)i]; v = sb.m.obs_xy[2 * (size_t)i + 1];
+                    return ci != 0 && pi >= 0 ? 1 : 0;
+                },
+                [&](int, int at, int keep) {
+                    if (!keep) return;
+                    sb.m.obs_cam[at] = ci - 1; sb.m.obs_pt[at] = pi; sb.m.obs_xy[2 * (size_t)at] = u; sb.m.obs_xy[2 * (size_t)at + 1] = v;
+                });
+            // the camera list moves up by one
+            double T[12]; int fr = 0; uint8_t fx = 0;
+            const bool mv = tid + 1 < ncam;
+            if (mv) { for (int k = 0; k < 12; k++) T[k] = sb.m.cam_pose[(size_t)(tid + 1) * 12 + k]; fr = sb.m.cam_frame[tid + 1]; fx = sb.m.cam_fixed[tid + 1]; }
+            __syncthreads();
+            if (mv) { for (int k = 0; k < 12; k++) sb.m.cam_pose[(size_t)tid * 12 + k] = T[k]; sb.m.cam_frame[tid] = fr; sb.m.cam_fixed[tid] = fx; }
+            ncam--; npt = npt2; nobs = nobs2;
+            __syncthreads();
+            if (tid == 0) { sb.m.cnt[0] = ncam; sb.m.cnt[1] = npt; sb.m.cnt[2] = nobs; }
+        }
+    }
+    if (tid == 0) { sb.n_cam[p] = ncam; sb.n_pts[p] = npt; sb.n_obs[p] = nobs; }
+}
+
+void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_limit, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
+}

@@ -7,9 +7,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
+#include <type_traits>
 #include <algorithm>
 
-#define MAX_EVENTS 160
+#define MAX_EVENTS 384                        // vo_slam_chain brackets five kernel groups per pair
 
 // The device (and pinned host) allocations of one lifetime: each one its own hipMalloc, all freed together by release() or
 // the destructor.  n == 0 allocates one element.
@@ -79,6 +80,14 @@ struct LastRun {
     int pairs = 0;
     std::vector<int32_t> slots;           // its pair slots (host copy)
     int points = 0;                       // ... and whether it triangulated (want_points)
+    int match_mode = 0;                   // ... and its vo_pair_opts.match_mode (vo_slam_chain needs one-to-one matches)
+    // host copies of the maps of the most recent vo_slam_chain: [0] at the end of the chain, [1] the snapshot
+    struct Map {
+        bool valid = false;
+        std::vector<int32_t> cam_frame, pt_feature, obs_cam, obs_pt;
+        std::vector<uint8_t> cam_fixed;
+        std::vector<double> cam_pose, points, obs_xy;
+    } map[2];
 };
 
 struct vo_ctx {
@@ -147,7 +156,8 @@ static const char* k_stage_names[VO_STAGE_COUNT] = {
     "gray", "pyramid_resize", "fast_score_nms", "select_fast", "harris", "select_harris", "ic_angle",
     "gaussian_blur", "rbrief", "match_nn", "match_select", "essential_ransac", "recover_pose",
     "triangulate", "misc", "reserved", "sift_scale_space", "sift_extrema", "sift_refine_orient", "sift_sort_unique",
-    "sift_descriptor", "cv2_keypoint_order", "trajectory_gather", "reserved2"};
+    "sift_descriptor", "cv2_keypoint_order", "trajectory_gather", "reserved2", "slam_ba_prepare", "slam_bundle_adjust", "slam_filter",
+    "slam_camera_limit"};
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -1027,6 +1037,7 @@ static int pairs_enqueue(vo_ctx* ctx, const int32_t* pair_slots, int B, const do
         ctx->last.pairs = B;
         ctx->last.slots.assign(pair_slots, pair_slots + 2 * (size_t)B);
         ctx->last.points = wp;
+        ctx->last.match_mode = opts->match_mode;
         return VO_OK;
     };
     if (B == 0) return done();
@@ -2601,6 +2612,30 @@ extern "C" int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pai
     return VO_OK;
 }
 
+// What vo_tracks_pnp_batch and vo_slam_chain ask of the most recent vo_pairs_run: all its B pairs, triangulated, every slot
+// inside the configuration, the pairs a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference walks a sequence in
+static int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out)
+{
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (B < 1 || B != ctx->last.pairs) FAIL(VO_ERR_INVALID, "%s takes all %d pairs of the most recent vo_pairs_run", who, ctx->last.pairs);
+    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
+    const int F = b.max_frames, cap = b.kp_cap;
+    const int32_t* sl = ctx->last.slots.data();
+    for (int i = 0; i < 2 * B; i++)
+        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
+    std::vector<char> seen((size_t)F, 0);
+    seen[(size_t)sl[0]] = 1;
+    for (int p = 0; p < B; p++) {
+        if ((p > 0 && sl[2 * p] != sl[2 * p - 1]) || seen[(size_t)sl[2 * p + 1]])
+            FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue a chain of distinct frames", p, sl[2 * p], sl[2 * p + 1]);
+        seen[(size_t)sl[2 * p + 1]] = 1;
+    }
+    if (F >= (1 << 20) || cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames or keypoints for the packed track table");
+    *F_out = F; *cap_out = cap;
+    return VO_OK;
+}
+
 // ------------------------------------------------------------------ measurement
 // ------------------------------------------------------------------ the step after the pair path, on resident data
 // VisualSlam.estimate_current_camera_position + add_information_to_map (src/visual_slam.py:183-266, 153-180) for the pairs the
@@ -2611,27 +2646,11 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
                                    double max_point_norm, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_map)
 {
     if (!ctx) return VO_ERR_INVALID;
-    const Batch b = batch(ctx);
-    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (B < 1 || B != ctx->last.pairs || !K || !poses || !n_corr || !n_inl || !status || !n_map)
-        FAIL(VO_ERR_INVALID, "vo_tracks_pnp_batch takes all %d pairs of the most recent vo_pairs_run", ctx->last.pairs);
-    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
-    const int F = b.max_frames, cap = b.kp_cap;
-    const int32_t* sl = ctx->last.slots.data();
-    for (int i = 0; i < 2 * B; i++)
-        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
-    {   // the pairs must be a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference processes a sequence in
-        std::vector<char> seen((size_t)F, 0);
-        seen[(size_t)sl[0]] = 1;
-        for (int p = 0; p < B; p++) {
-            if ((p > 0 && sl[2 * p] != sl[2 * p - 1]) || seen[(size_t)sl[2 * p + 1]])
-                FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue a chain of distinct frames", p, sl[2 * p], sl[2 * p + 1]);
-            seen[(size_t)sl[2 * p + 1]] = 1;
-        }
-    }
-    if (F >= (1 << 20) || cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames or keypoints for the packed track table");
+    if (!K || !poses || !n_corr || !n_inl || !status || !n_map) FAIL(VO_ERR_INVALID, "bad arguments");
+    int F, cap;
+    int rc = chain_check(ctx, B, "vo_tracks_pnp_batch", &F, &cap); if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
-    int rc = ensure_rng(ctx, seed); if (rc) return rc;
+    rc = ensure_rng(ctx, seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
     const size_t fc = (size_t)F * cap;
     ChainBuf cb; double* dK;
@@ -2664,6 +2683,198 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
     HIPCHK(hipMemcpyAsync(n_map, cb.n_map, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
+// ------------------------------------------------------------------ the reference's complete per-frame map step, on resident data
+// vo_tracks_pnp_batch's walk with what ends every frame of VisualSlam.estimate_current_camera_position (src/visual_slam.py:190-266)
+// joined to it: the Observations of add_information_to_map, freeze_nonlast_cameras, Map.optimize_map, the threshold filter and
+// limit_number_of_camera_in_map — on a map that stays in HBM (slam_kernels.hip), pair after pair with no host round trip.
+// The map's three lists, carved from one block so that a snapshot is one device-to-device copy; base == nullptr: the size only
+static size_t slam_map_carve(uint8_t* base, size_t ncam, size_t npt, size_t nobs, SlamMap* m)
+{
+    size_t o = 0;
+    auto put = [&](auto** p, size_t n) {
+        using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
+        if (base) *p = reinterpret_cast<T*>(base + o);
+        o += (n * sizeof(T) + 255) & ~(size_t)255;
+    };
+    put(&m->cnt, 4); put(&m->cam_frame, ncam); put(&m->cam_pose, ncam * 12); put(&m->cam_fixed, ncam); put(&m->pt_key, npt); put(&m->pt_xyz, npt * 3);
+    put(&m->obs_cam, nobs); put(&m->obs_pt, nobs); put(&m->obs_xy, nobs * 2);
+    return o;
+}
+
+static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Map* out)
+{
+    int cnt[4];
+    HIPCHK(hipMemcpy(cnt, m.cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    const size_t nc = cnt[0], np = cnt[1], no = cnt[2];
+    std::vector<int32_t> key(np);
+    out->cam_frame.resize(nc); out->cam_pose.resize(nc * 12); out->cam_fixed.resize(nc); out->points.resize(np * 3);
+    out->obs_cam.resize(no); out->obs_pt.resize(no); out->obs_xy.resize(no * 2); out->pt_feature.resize(np * 2);
+    if (nc) {
+        HIPCHK(hipMemcpy(out->cam_frame.data(), m.cam_frame, nc * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->cam_pose.data(), m.cam_pose, nc * 96, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->cam_fixed.data(), m.cam_fixed, nc, hipMemcpyDeviceToHost));
+    }
+    if (np) {
+        HIPCHK(hipMemcpy(key.data(), m.pt_key, np * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->points.data(), m.pt_xyz, np * 24, hipMemcpyDeviceToHost));
+    }
+    if (no) {
+        HIPCHK(hipMemcpy(out->obs_cam.data(), m.obs_cam, no * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->obs_pt.data(), m.obs_pt, no * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out->obs_xy.data(), m.obs_xy, no * 16, hipMemcpyDeviceToHost));
+    }
+    // feature id (slot, keypoint) -> (index of the frame in the chain, keypoint)
+    const std::vector<int32_t>& sl = ctx->last.slots;
+    for (size_t i = 0; i < np; i++) {
+        const int slot = key[i] / cap;
+        int frame = sl[0] == slot ? 0 : -1;
+        for (size_t p = 0; frame < 0 && 2 * p + 1 < sl.size(); p++) if (sl[2 * p + 1] == slot) frame = (int)p + 1;
+        out->pt_feature[2 * i] = frame; out->pt_feature[2 * i + 1] = key[i] % cap;
+    }
+    out->valid = true;
+    return VO_OK;
+}
+
+extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
+                             int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                             double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
+        FAIL(VO_ERR_INVALID, "bad arguments");
+    int F, cap;
+    int rc = chain_check(ctx, B, "vo_slam_chain", &F, &cap); if (rc) return rc;
+    ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
+    if (ctx->last.match_mode == 1)
+        FAIL(VO_ERR_UNSUPPORTED, "vo_slam_chain needs one-to-one matches (cross-check): with ratio matches two inliers can share a track root");
+    if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
+    if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
+    if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);
+    if (o->max_cameras < 2) FAIL(VO_ERR_INVALID, "max_cameras must be at least 2, got %d", o->max_cameras);
+    if ((int64_t)o->max_cameras + 1 > VO_BA_MAX_CAMERAS)
+        FAIL(VO_ERR_UNSUPPORTED, "the map holds max_cameras + 1 cameras before the limit is applied, bundle adjustment at most %d", VO_BA_MAX_CAMERAS);
+    if (!(o->huber_delta == o->huber_delta) || !(o->filter_threshold == o->filter_threshold) || !(K[0] == K[0]) || !(K[2] == K[2]) || !(K[5] == K[5]))
+        FAIL(VO_ERR_INVALID, "camera parameters and thresholds must be numbers");
+    if ((o->snapshot_pair >= 0) != (o->snapshot_stage >= 1) || o->snapshot_pair >= B || o->snapshot_stage > 4)
+        FAIL(VO_ERR_INVALID, "snapshot_pair must be -1 or a pair of the chain, snapshot_stage 1 .. 4 with it");
+    const size_t fc = (size_t)F * cap;
+    HIPCHK(hipSetDevice(ctx->device));
+    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    // capacities from the configuration: a pair adds at most one point and two observations per match
+    const size_t cm = (size_t)o->max_cameras + 1, np = fc, no = (size_t)2 * B * cap, npair = no * (o->free_cameras + 1) / 2;
+    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
+    if (np >= ((size_t)1 << 31) || npair >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the map's lists would not fit 32-bit indices");
+    ChainBuf cb; SlamBuf sb{}; BaBuf D{}; double* dK; uint8_t *map_mem, *snap_mem;
+    const size_t map_bytes = slam_map_carve(nullptr, cm, np, no, &sb.m);
+    ScratchLayout sc;
+    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
+    sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4); sc.take(&cb.poses, (size_t)(B + 1) * 12);
+    sc.take(&dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
+    sc.take(&cb.alive, 1); sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&cb.map_count, 1);
+    sc.take(&map_mem, map_bytes); sc.take(&snap_mem, map_bytes);
+    sc.take(&sb.pt_of, fc); sc.take(&sb.dec, cap); sc.take(&sb.tmp, np); sc.take(&sb.idx, no); sc.take(&sb.n_pts, B); sc.take(&sb.n_obs, B); sc.take(&sb.n_cam, B);
+    sc.take(&sb.poses_last, (size_t)(B + 1) * 12);
+    sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
+    sc.take(&sb.pairs, npair); sc.take(&sb.blk_first, (size_t)nblk + 1);
+    sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
+    double* dchi2; int *dit, *dtr;
+    sc.take(&dchi2, (size_t)2 * B); sc.take(&dit, B); sc.take(&dtr, B);
+    rc = sc.place(ctx); if (rc) return rc;
+    SlamMap snap{};
+    slam_map_carve(map_mem, cm, np, no, &sb.m); slam_map_carve(snap_mem, cm, np, no, &snap);
+    sb.cam_cap = (int)cm; sb.pt_cap = (int)np; sb.obs_cap = (int)no; sb.pair_cap = (int)npair;
+    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
+    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
+    HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty map, no cameras, zero results
+    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
+    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
+    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
+    auto snapshot = [&](int p, int stage) {
+        if (p == o->snapshot_pair && stage == o->snapshot_stage) (void)hipMemcpyAsync(snap_mem, map_mem, map_bytes, hipMemcpyDeviceToDevice, s);
+    };
+    launch_chain_link(s, ctx->pb, cap, B, cb);
+    for (int p = 0; p < B; p++) {
+        {
+            StageTimer t(ctx, ST_MISC);
+            if (p == 0) launch_chain_init(s, ctx->pb, cap, cb);
+            else {
+                launch_chain_gather(s, ctx->pb, cap, p, F, cb);
+                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
+                launch_chain_pose(s, ctx->pb, p, dK, cb);
+                launch_chain_triangulate(s, ctx->pb, cap, p, cb);
+            }
+            launch_slam_add(s, ctx->pb, cap, p, F, o->max_point_norm, o->free_cameras, cb, sb);
+        }
+        snapshot(p, 1);
+        if (ba) {
+            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare(s, cb, sb); }
+            BaBuf Dp = D;
+            Dp.chi2 = dchi2 + 2 * p; Dp.iterations_run = dit + p; Dp.trials_run = dtr + p;
+            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dp, prm, 1, o->free_cameras); }
+        }
+        snapshot(p, 2);
+        // pair 0 ends with optimize_map (:90); what it wrote back still has to reach the tables the next pair reads
+        if (ba || (filt && p > 0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter(s, ctx->pb, dK, p > 0 ? o->filter_threshold : 0.0, cb, sb); }
+        snapshot(p, 3);
+        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit(s, p, o->max_cameras, cb, sb); }
+        snapshot(p, 4);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(chi2, dchi2, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ba_iterations_run, dit, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ba_trials_run, dtr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    // the scratch buffer belongs to the next call: the two maps are kept as host copies
+    rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
+    if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, snap, cap, &ctx->last.map[1]); if (rc) return rc; }
+    return VO_OK;
+}
+
+static const LastRun::Map* slam_map_of(vo_ctx* ctx, int which)
+{
+    if (which < 0 || which > 1 || !ctx->last.map[which].valid) {
+        snprintf(ctx->err, sizeof(ctx->err), which < 0 || which > 1 ? "which must be 0 (the map at the end of the chain) or 1 (the snapshot)"
+                                                                   : "no such map: vo_slam_chain has not run (or not with a snapshot) since the last configure / vo_pairs_run");
+        return nullptr;
+    }
+    return &ctx->last.map[which];
+}
+
+extern "C" int vo_slam_map_size(vo_ctx* ctx, int which, int32_t* ncam, int32_t* npt, int32_t* nobs)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!ncam || !npt || !nobs) FAIL(VO_ERR_INVALID, "bad arguments");
+    const LastRun::Map* m = slam_map_of(ctx, which);
+    if (!m) return VO_ERR_INVALID;
+    *ncam = (int32_t)m->cam_frame.size(); *npt = (int32_t)(m->points.size() / 3); *nobs = (int32_t)m->obs_cam.size();
+    return VO_OK;
+}
+
+extern "C" int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature, double* points,
+                           int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const LastRun::Map* m = slam_map_of(ctx, which);
+    if (!m) return VO_ERR_INVALID;
+    if ((!m->cam_frame.empty() && (!cam_frame || !cam_pose || !cam_fixed)) || (!m->points.empty() && (!pt_feature || !points)) ||
+        (!m->obs_cam.empty() && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
+    auto copy = [](auto* dst, const auto& v) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    copy(cam_frame, m->cam_frame); copy(cam_pose, m->cam_pose); copy(cam_fixed, m->cam_fixed); copy(pt_feature, m->pt_feature); copy(points, m->points);
+    copy(obs_cam, m->obs_cam); copy(obs_pt, m->obs_pt); copy(obs_xy, m->obs_xy);
     return VO_OK;
 }
 

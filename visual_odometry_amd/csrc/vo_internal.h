@@ -8,7 +8,8 @@
 enum {
     ST_GRAY = 0, ST_RESIZE, ST_FAST, ST_SELECT_FAST, ST_HARRIS, ST_SELECT_HARRIS, ST_ANGLE,
     ST_BLUR, ST_BRIEF, ST_MATCH_NN, ST_MATCH_SELECT, ST_RANSAC, ST_POSE, ST_TRIANGULATE,
-    ST_MISC, ST_RESERVED, ST_SIFT_SCALE, ST_SIFT_EXTREMA, ST_SIFT_ORIENT, ST_SIFT_SORT, ST_SIFT_DESC, ST_CV2_ORDER, ST_GATHER, ST_RESERVED2
+    ST_MISC, ST_RESERVED, ST_SIFT_SCALE, ST_SIFT_EXTREMA, ST_SIFT_ORIENT, ST_SIFT_SORT, ST_SIFT_DESC, ST_CV2_ORDER, ST_GATHER, ST_RESERVED2,
+    ST_SLAM_PREPARE, ST_SLAM_BA, ST_SLAM_FILTER, ST_SLAM_LIMIT
 };
 
 // ---- pyramid / work geometry, passed to kernels by value ------------------------------------
@@ -298,5 +299,32 @@ struct BaBuf {
 };
 struct BaParams { double focal, cx, cy, delta; int iterations; };
 void launch_bundle_adjust(hipStream_t s, const BaBuf& D, const BaParams& P, int B, int max_free);
+// ---- the resident map of vo_slam_chain (slam_kernels.hip): src/map.py's three lists, dense, in the reference's append order
+struct SlamMap {
+    int*     cnt;                       // [4] cameras, points, observations, unused
+    int*     cam_frame;                 // [cameras] index of the camera's frame in the chain (0 = pair 0's first frame, p + 1 = pair p's second)
+    double*  cam_pose;                  // [cameras][12] world -> camera [R | t]
+    uint8_t* cam_fixed;                 // [cameras]
+    int*     pt_key;                    // [points] owning feature id: slot * kp_cap + keypoint (TrackedPoint.feature_id)
+    double*  pt_xyz;                    // [points][3]
+    int*     obs_cam; int* obs_pt;      // [observations] indices into the two lists above
+    double*  obs_xy;                    // [observations][2]
+};
+struct SlamBuf {
+    SlamMap  m;
+    int      cam_cap, pt_cap, obs_cap, pair_cap;   // entries the map's three lists and `pairs` can hold
+    int*     pt_of;                     // [F][cap] 1 + index of the map point keyed by this feature id, 0 = none (mappointdict)
+    int*     dec;                       // [cap] add_information_to_map's decision per match, taken against the pre-loop snapshot
+    int*     tmp;                       // [points] per-point counts / cursors / new indices
+    int*     idx;                       // [observations] input index of every observation sorted by point
+    int*     n_pts; int* n_obs; int* n_cam;   // [P] the map's sizes after every pair
+    double*  poses_last;                // [P + 1][12] every camera as the map last held it
+    // what k_slam_ba_prepare hands k_bundle_adjust (BaBuf's const members)
+    BaProblem* prob; int* cam_col; int* pt_first; int* s_cam; int* s_pt; double* s_xy; int2* pairs; int* blk_first;
+};
+void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
+void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb);
+void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb);
+void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

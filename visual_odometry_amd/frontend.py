@@ -173,6 +173,43 @@ class FrontEnd:
                                           float(max_point_norm), poses.ctypes.data, nc.ctypes.data, ni.ctypes.data, st.ctypes.data, nm.ctypes.data))
         return dict(poses=poses.reshape(B + 1, 3, 4), n_corr=nc, n_inl=ni, status=st, n_map=nm)
 
+    def slam_chain(self, n_pairs, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
+                   ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """The reference's complete per-frame map step on resident data (vo_slam_chain; src/visual_slam.py:190-266 and :311):
+        localize_chain's walk with the Observation list, freeze_nonlast_cameras, Map.optimize_map, the reprojection filter and
+        limit_number_of_camera_in_map after every pair, on a map that stays on the device.  snapshot=(pair, stage): keep a copy
+        of the map as it was at that pair after stage 1 add_information_to_map, 2 bundle adjustment, 3 filter, 4 camera limit
+        (slam_map(1)).  Returns dict(poses_pnp, poses [n_pairs + 1, 3, 4], n_corr, n_inl, status, n_pts, n_obs, n_cam,
+        ba_iterations, ba_trials [n_pairs], chi2 [n_pairs, 2])."""
+        B = int(n_pairs)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        sp, ss = (-1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]))
+        opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
+                             float(huber_delta), int(free_cameras), float(filter_threshold), int(max_cameras), sp, ss)
+        pp = np.zeros((B + 1, 12)); pl = np.zeros((B + 1, 12)); chi2 = np.zeros((B, 2))
+        i32 = {k: np.zeros(B, np.int32) for k in ("n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")}
+        c = self.ctx
+        c.check(c.lib.vo_slam_chain(c.handle, B, K.ctypes.data, C.addressof(opts), pp.ctypes.data, pl.ctypes.data, i32["n_corr"].ctypes.data,
+                                    i32["n_inl"].ctypes.data, i32["status"].ctypes.data, i32["n_pts"].ctypes.data, i32["n_obs"].ctypes.data,
+                                    i32["n_cam"].ctypes.data, chi2.ctypes.data, i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data))
+        return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, **i32)
+
+    def slam_map(self, which=0):
+        """The map of the latest slam_chain: which=0 at the end of the chain, 1 the snapshot.  dict(cam_frame [ncam] index of the
+        camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool, pt_feature [npt, 2] (chain frame, keypoint),
+        points [npt, 3], obs_cam, obs_pt [nobs], obs_xy [nobs, 2])."""
+        c = self.ctx
+        n = [C.c_int32(0) for _ in range(3)]
+        c.check(c.lib.vo_slam_map_size(c.handle, int(which), *[C.addressof(v) for v in n]))
+        nc, npt, no = (v.value for v in n)
+        m = dict(cam_frame=np.zeros(nc, np.int32), cam_pose=np.zeros((nc, 3, 4)), cam_fixed=np.zeros(nc, np.uint8),
+                 pt_feature=np.zeros((npt, 2), np.int32), points=np.zeros((npt, 3)), obs_cam=np.zeros(no, np.int32),
+                 obs_pt=np.zeros(no, np.int32), obs_xy=np.zeros((no, 2)))
+        c.check(c.lib.vo_slam_map(c.handle, int(which), *[_lib.ptr(m[k]) for k in ("cam_frame", "cam_pose", "cam_fixed", "pt_feature", "points",
+                                                                                  "obs_cam", "obs_pt", "obs_xy")]))
+        m["cam_fixed"] = m["cam_fixed"].astype(bool)
+        return m
+
     def gather_records(self, B, world=1, wait=True):
         """All-gather the [R|t] + counts records (16 float64 per pair) of the first B pairs of the latest run_pairs
         over the context's RCCL communicator (ctx.comm_init; without one: the local records).  Returns a
