@@ -20,8 +20,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ba_reference as BA  # noqa: E402
 from test_gpu_chain import _KP, _inv_pose  # noqa: E402
 
-DEFAULTS = dict(iterations=100, reproj_err=8.0, confidence=0.99, max_point_norm=50.0, ba_iterations=40, huber_delta=1.0,
-                free_cameras=2, filter_threshold=1.0, max_cameras=18)
+DEFAULTS = dict(iterations=100, reproj_err=8.0, confidence=0.99, seed=0xFFFFFFFFFFFFFFFF,
+                max_point_norm=50.0, ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18)
 MAP_KEYS = ("cam_frame", "cam_pose", "cam_fixed", "pt_feature", "points", "obs_cam", "obs_pt", "obs_xy")
 
 
@@ -174,7 +174,7 @@ def step(O, state, pr, K, opts=None, follow=None, stages=False):
                 obj.append(s["points"][mappointdict[fid]]); img.append(kp2)
         out["n_corr"] = len(obj)
         obj, img = np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2)
-        rc, rvec, tvec, _, ninl = O.solve_pnp_ransac(obj, img, K, o["iterations"], o["reproj_err"], o["confidence"]) if len(obj) >= 4 else (-3, None, None, None, 0)
+        rc, rvec, tvec, _, ninl = O.solve_pnp_ransac(obj, img, K, o["iterations"], o["reproj_err"], o["confidence"], o["seed"]) if len(obj) >= 4 else (-3, None, None, None, 0)
         out["n_inl"] = int(ninl)
         if rc != 0:
             out["status"] = rc; out["state"] = s

@@ -22,11 +22,12 @@ def _inv_pose(R, t):
     return np.array([[R[0, r], R[1, r], R[2, r], -(R[0, r] * t[0] + R[1, r] * t[1] + R[2, r] * t[2])] for r in range(3)])
 
 
-def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None):
+def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None, pnp=None):
     """The reference's loop over a sequence, on the oracle's stage outputs.  feats[f] = dict(xy, desc).
     follow = the device's poses [n, 3, 4]: every solvePnPRansac result is reported as computed, but the chain then continues from
     the DEVICE's camera, so that every step is compared on identical inputs (a RANSAC over points near its 8-pixel threshold turns
-    a 1e-9 difference of the previous pose into a different winner: the free-running chains agree only while the geometry is good)."""
+    a 1e-9 difference of the previous pose into a different winner: the free-running chains agree only while the geometry is good).
+    pnp = solvePnPRansac's options (iterations, reproj_err, confidence, seed) where they are not the defaults."""
     feature_mapper, mappoints, cameras = {}, {}, {}
     out = dict(poses=[], n_corr=[], n_inl=[], status=[], n_map=[], E_inl=[], corr=[None])
     alive = True
@@ -62,7 +63,7 @@ def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None):
             if feature_id in mappoints:
                 obj.append(mappoints[feature_id]); img.append(kp2)
         out["n_corr"].append(len(obj)); out["corr"].append((np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2)))
-        rc, rvec, tvec, pmask, ninl = O.solve_pnp_ransac(np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2), K) if len(obj) >= 4 else (-1, None, None, None, 0)
+        rc, rvec, tvec, pmask, ninl = O.solve_pnp_ransac(np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2), K, **(pnp or {})) if len(obj) >= 4 else (-1, None, None, None, 0)
         out["n_inl"].append(int(ninl))
         if rc != 0:                                                    # cv2 raises / retval False: no camera is added (:253-261)
             alive = False

@@ -52,11 +52,12 @@ def update_num_iters(prob, ep, max_iters):
     return max_iters if denom >= 0 or -num >= max_iters * (-denom) else int(np.rint(num / denom))
 
 
-def oracle_iterations(oracle, p1, p2, K, prob, thresh, max_iters):
-    """Iterations the oracle's RANSAC loop ran, from its results alone (see the module docstring)."""
+def oracle_last_change(oracle, p1, p2, K, prob, thresh, max_iters):
+    """(sample at which the oracle's RANSAC loop took its final model, its inlier count), from its results alone (see the
+    module docstring); (None, 0) where no model was ever accepted."""
     rc, E, mask, ninl = oracle.find_essential_ransac(p1, p2, K, prob=prob, thresh=thresh, max_iters=max_iters)
     if rc != 0:
-        return max(max_iters, 1)                     # no model was ever accepted: the bound never moved
+        return None, 0
     lo, hi = 1, max(max_iters, 1)                    # smallest budget that already ends with the final model
     while lo < hi:
         mid = (lo + hi) // 2
@@ -65,7 +66,15 @@ def oracle_iterations(oracle, p1, p2, K, prob, thresh, max_iters):
             hi = mid
         else:
             lo = mid + 1
-    return max(lo, update_num_iters(prob, (len(p1) - ninl) / len(p1), max(max_iters, 1)))
+    return lo, ninl
+
+
+def oracle_iterations(oracle, p1, p2, K, prob, thresh, max_iters):
+    """Iterations the oracle's RANSAC loop ran, from its results alone (see the module docstring)."""
+    last, ninl = oracle_last_change(oracle, p1, p2, K, prob, thresh, max_iters)
+    if last is None:
+        return max(max_iters, 1)                     # no model was ever accepted: the bound never moved
+    return max(last, update_num_iters(prob, (len(p1) - ninl) / len(p1), max(max_iters, 1)))
 
 
 # ---------------------------------------------------------------------------------------------- five-point samples
@@ -162,6 +171,20 @@ def _problem(seed, n, outl, take=None):
     return K, p1[:take], p2[:take]
 
 
+def _unrelated(seed, n):
+    """n correspondences without a two-view geometry behind them, the second point up to 400 px from the first: few models
+    gather a sixth and a seventh inlier by chance, so the final model comes late."""
+    rng = np.random.default_rng(seed)
+    p1 = rng.uniform([0, 0], [640, 480], (n, 2))
+    return np.array([[800, 0, 320], [0, 800, 240], [0, 0, 1.0]]), p1, p1 + rng.uniform(-400.0, 400.0, (n, 2))
+
+
+def case_problem(name):
+    """(K, p1, p2) of a RANSAC case: a scene, or for the cases in UNRELATED (seed, n) of _unrelated."""
+    _, seed, n, outl, take, _, _ = _ransac_case(name)
+    return _unrelated(seed, n) if name in UNRELATED else _problem(seed, n, outl, take)
+
+
 RANSAC_CASES = [
     # name,                 seed, n,   outl, take, prob,  max_iters
     ("one_wave",            60,   800, 0.1,  None, 0.99,  1000),
@@ -181,12 +204,18 @@ RANSAC_CASES = [
     ("M_6_outliers",        66,   200, 0.5,  6,    0.999, 1000),
     ("M_7_outliers",        66,   200, 0.5,  7,    0.999, 1000),
     ("M_8_outliers",        66,   200, 0.5,  8,    0.999, 1000),
+    ("past_the_table",      76,   13,  None, None, 1 - 2.0 ** -53, 2000),       # unrelated points, not a scene
 ]
+UNRELATED = {"past_the_table"}
+# Which of these cases take their final model from a sample drawn past the table is asserted on the CPU, where the CPU suite
+# runs it: tests/test_pnp_control_reference.py::test_which_essential_cases_draw_past_the_table (only `past_the_table`).
+
 # what each case has to reach, as a range of the oracle's iteration count (inclusive)
 RANSAC_REACH = {
     "one_wave": (2, ROUND), "over_16": (ROUND + 1, 2 * ROUND), "over_32": (2 * ROUND + 1, 4 * ROUND),
     "over_64_by_little": (4 * ROUND + 1, 6 * ROUND), "over_64": (4 * ROUND + 1, 1000), "several_rounds": (5 * 4 * ROUND, 1000), "budget_exhausted": (1000, 1000),
     "max_iters_1": (1, 1), "max_iters_17": (17, 17), "max_iters_33": (33, 33), "max_iters_33_hard": (33, 33),
+    "past_the_table": (1509, 1509),
 }
 
 
@@ -197,8 +226,8 @@ def _ransac_case(name):
 @pytest.mark.parametrize("name", [c[0] for c in RANSAC_CASES])
 def test_ransac_300_sweeps_bit_identical(oracle, ctx300, name):
     from visual_odometry_amd import geometry
-    _, seed, n, outl, take, prob, max_iters = _ransac_case(name)
-    K, p1, p2 = _problem(seed, n, outl, take)
+    _, _, _, _, _, prob, max_iters = _ransac_case(name)
+    K, p1, p2 = case_problem(name)
     rc, Er, mr, nr = oracle.find_essential_ransac(p1, p2, K, prob=prob, max_iters=max_iters)
     iters = oracle_iterations(oracle, p1, p2, K, prob, 1.0, max_iters) if len(p1) > 5 else 0
     if name in RANSAC_REACH:
@@ -227,8 +256,8 @@ def test_ransac_300_sweeps_bit_identical(oracle, ctx300, name):
 def test_ransac_default_solver_vs_faithful_oracle(oracle, ctx, name):
     from visual_odometry_amd import geometry
     assert not oracle.get_dk_early_exit()
-    _, seed, n, outl, take, prob, max_iters = _ransac_case(name)
-    K, p1, p2 = _problem(seed, n, outl, take)
+    _, _, _, _, _, prob, max_iters = _ransac_case(name)
+    K, p1, p2 = case_problem(name)
     rc, Er, mr, nr = oracle.find_essential_ransac(p1, p2, K, prob=prob, max_iters=max_iters)
     E, mask = geometry.findEssentialMat(p1, p2, K, geometry.FM_RANSAC, prob, 1.0, max_iters)
     if rc != 0:

@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ba_reference as BA  # noqa: E402
 import slam_reference as S  # noqa: E402
 from test_gpu_chain import _advances_along_a_line  # noqa: E402
+from test_pnp_control_reference import CHAIN_PNP  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -141,6 +142,25 @@ def test_map_building_follows_the_reference(run, oracle, kernel_dk_rule):
         # both kinds of inlier occur: observations of existing points (one each) and new points (two each)
         added = len(cur["obs_cam"]) - len(prev["obs_cam"])
         assert added > 2 * (len(cur["points"]) - n_old) > 0
+
+
+def test_pnp_options_reach_the_kernel(run, oracle, kernel_dk_rule):
+    """iterations / reproj_err / confidence / seed none of which is a default (bundle adjustment, filter and camera limit on):
+    every pair localises, and the checker's step with the same options from the device's map after pair p - 1 localises pair p
+    as the device did, by the rule of the test above."""
+    K = run.K
+    opts = dict(max_cameras=MAX_CAMERAS, **CHAIN_PNP)
+    default, got = run.chain()[0], run.chain(**CHAIN_PNP)[0]
+    assert got["status"].tolist() == [0] * (N - 1)
+    assert got["n_inl"].tolist() != default["n_inl"].tolist()              # the options reached the kernel
+    for p in range(1, N - 1):
+        prev = run.snap(p - 1, 4, **CHAIN_PNP)
+        out, cur = run.chain(snapshot=(p, 1), **CHAIN_PNP)
+        state = S.to_lists(prev, mapper=run.mapper(p))
+        r = S.step(oracle, state, run.pin[p], K, opts, follow=out["poses_pnp"][p + 1], stages=True)
+        assert r["status"] == 0 == out["status"][p] and (r["n_corr"], r["n_inl"]) == (out["n_corr"][p], out["n_inl"][p]), p
+        assert np.abs(r["pose_pnp"] - out["poses_pnp"][p + 1]).max() < 1e-6, p
+        _same_map(r["stage"][1], cur, ("cam_frame", "cam_fixed", "pt_feature", "obs_cam", "obs_pt", "obs_xy"))
 
 
 def test_filter_is_the_reprojection_oracle(run, oracle):
