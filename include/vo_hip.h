@@ -464,6 +464,33 @@ int vo_slam_map_size(vo_ctx* ctx, int which, int32_t* ncam, int32_t* npt, int32_
 int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[ncam][12]*/, uint8_t* cam_fixed, int32_t* pt_feature /*[npt][2]*/,
                 double* points /*[npt][3]*/, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy /*[nobs][2]*/);
 
+/* ------------------------------------------------------------------ the same map step for S independent sequences in one call
+ * vo_slam_chain is sequential by nature — frame k + 1 is localised against the map frame k left — and runs as one workgroup
+ * per kernel; several sequences (several flights, or one flight cut into shards) are what runs in parallel.  vo_slam_chains
+ * walks S of them at once, one workgroup per sequence and kernel: the launches per call stay those of the longest sequence.
+ *   B = seq_off[S] is all the pairs of the most recent vo_pairs_run (want_points); sequence s is its pairs seq_off[s] ..
+ *   seq_off[s + 1] - 1 (seq_off[0] = 0, strictly increasing, S >= 1) and must by itself be a chain of distinct frames, as
+ *   vo_slam_chain asks of its one chain.  NO FRAME SLOT MAY BELONG TO TWO SEQUENCES (VO_ERR_INVALID): the slot-keyed
+ *   tables are shared between the sequences exactly because their slots are disjoint.  A frame two shards share (a halo
+ *   frame) is uploaded into two slots; sequences that share a slot are out of scope.
+ * Every option, check and code of vo_slam_chain applies (ratio matches: VO_ERR_UNSUPPORTED).  opts->snapshot_pair counts
+ * along sequence snapshot_seq (0 .. S - 1, and snapshot_pair < its pair count); snapshot_seq is ignored when snapshot_pair < 0.
+ * Per-pair outputs are indexed by the pair's position in the run; sequence s owns the pose rows seq_off[s] + s ..
+ * seq_off[s + 1] + s (its B_s + 1 cameras).  Every sequence computes exactly what vo_slam_chain computes for it alone: the
+ * sequences are independent, a pair that cannot be localised ends ITS sequence (the failing status at that pair,
+ * VO_ERR_NOT_CONFIGURED after it) and the others run to their end.
+ * vo_slam_chains_map_size / vo_slam_chains_map: the map of sequence seq, which = 0 at its end, 1 the snapshot (valid only
+ * for seq == snapshot_seq); cam_frame and pt_feature[:, 0] are indices along the sequence's own chain.  After a
+ * vo_slam_chains call vo_slam_map_size / vo_slam_map report sequence 0 (and the snapshot only if snapshot_seq == 0).  A
+ * configure call, a vo_pairs_run, a vo_slam_chain or a later vo_slam_chains forgets these maps; a refused call leaves none. */
+int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/, const double* K, const vo_slam_opts* opts, int snapshot_seq,
+                   double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
+                   int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam /*[B] each*/,
+                   double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run /*[B] each*/);
+int vo_slam_chains_map_size(vo_ctx* ctx, int seq, int which, int32_t* ncam, int32_t* npt, int32_t* nobs);
+int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, double* cam_pose /*[ncam][12]*/, uint8_t* cam_fixed,
+                       int32_t* pt_feature /*[npt][2]*/, double* points /*[npt][3]*/, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy /*[nobs][2]*/);
+
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since

@@ -26,6 +26,18 @@ __device__ __forceinline__ void chain_root(const unsigned long long* parent, int
     }
 }
 
+// The pair buffers as one sequence of a run sees them: its pair 0 is pair `first` of the run.  Only the members the chain and map
+// kernels read are moved (slots, res, m_count, m_q, m_t, mask, px1, px2, ipx1, ipx2, X).
+__device__ __forceinline__ PairBuf chain_pairs_from(PairBuf pb, int first, int kp_cap)
+{
+    const size_t c = (size_t)first * kp_cap;
+    pb.slots += 2 * (size_t)first; pb.res += first; pb.m_count += first;
+    pb.m_q += c; pb.m_t += c; pb.mask += c;
+    pb.px1 += 2 * c; pb.px2 += 2 * c; pb.ipx1 += 2 * c; pb.ipx2 += 2 * c;
+    pb.X += 4 * c;
+    return pb;
+}
+
 // the j-th inlier's match index: inliers are numbered in match order, as k_pose compacts them (and as X's columns run)
 template <typename F>
 __device__ __forceinline__ void chain_for_each_inlier(const PairBuf& pb, int kp_cap, int p, int* s_w, F&& body)

@@ -1339,7 +1339,7 @@ void launch_chain_link(hipStream_t s, PairBuf pb, int kp_cap, int P, ChainBuf cb
 // [deviation, documented in DESIGN.md] the reference stores camera 1 = (I, 0) and camera 2 = (R, t) but its first points in
 // camera-2 coordinates (reconstruct_3d_points' default matrices) and lets the bundle adjustment reconcile them; without BA the
 // cameras are stored consistently with the points: camera 2 = (I, 0), camera 1 = (R^T, -R^T t).
-__global__ __launch_bounds__(256) void k_chain_init(PairBuf pb, int kp_cap, ChainBuf cb)
+__device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf cb)
 {
     __shared__ int s_w[4];
     const int tid = threadIdx.x;
@@ -1374,6 +1374,20 @@ __global__ __launch_bounds__(256) void k_chain_init(PairBuf pb, int kp_cap, Chai
     if (tid == 0) { cb.map_count[0] = s_added; cb.n_map[0] = s_added; }
 }
 
+__global__ __launch_bounds__(256) void k_chain_init(PairBuf pb, int kp_cap, ChainBuf cb) { chain_init_wg(pb, kp_cap, cb); }
+
+// vo_slam_chains: workgroup = sequence (blockIdx.x); the sequence's pair 0 is pair `first` of the run
+__global__ __launch_bounds__(256) void k_chain_init_seqs(PairBuf pb, int kp_cap, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    chain_init_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, q.cb);
+}
+
+void launch_chain_init_seqs(hipStream_t s, PairBuf pb, int kp_cap, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_chain_init_seqs, dim3(S), dim3(256), 0, s, pb, kp_cap, seqs);
+}
+
 void launch_chain_init(hipStream_t s, PairBuf pb, int kp_cap, ChainBuf cb)
 {
     hipLaunchKernelGGL(k_chain_init, dim3(1), dim3(256), 0, s, pb, kp_cap, cb);
@@ -1381,7 +1395,7 @@ void launch_chain_init(hipStream_t s, PairBuf pb, int kp_cap, ChainBuf cb)
 
 // matches_with_map (:201-218): for every match with 3-D information of the current pair, in order — trace featureid2 back, keep
 // the match if the root feature owns a map point: (imagecoord = keypoint2, mapcoord = the point)
-__global__ __launch_bounds__(256) void k_chain_gather(PairBuf pb, int kp_cap, int p, int F, ChainBuf cb)
+__device__ __forceinline__ void chain_gather_wg(PairBuf pb, int kp_cap, int p, int F, ChainBuf cb)
 {
     __shared__ int s_w[4];
     __shared__ int s_base;
@@ -1391,7 +1405,7 @@ __global__ __launch_bounds__(256) void k_chain_gather(PairBuf pb, int kp_cap, in
     const bool ok = cb.alive[0] && r.status == VO_OK && cb.cam_ok[f1];
     if (!ok) {
         if (tid == 0) {
-            cb.off[0] = 0; cb.off[1] = 0; cb.n_corr[p] = 0;
+            cb.off[0] = cb.obj0; cb.off[1] = cb.obj0; cb.n_corr[p] = 0;
             cb.status[p] = !cb.alive[0] ? VO_ERR_NOT_CONFIGURED : r.status != VO_OK ? r.status : VO_ERR_INVALID;   // the chain broke earlier / this pair failed / no camera for frame 1
             cb.alive[0] = 0;
         }
@@ -1425,7 +1439,25 @@ __global__ __launch_bounds__(256) void k_chain_gather(PairBuf pb, int kp_cap, in
         if (tid == 0) s_base += tot;
         __syncthreads();
     }
-    if (tid == 0) { cb.off[0] = 0; cb.off[1] = s_base; cb.n_corr[p] = s_base; }
+    if (tid == 0) { cb.off[0] = cb.obj0; cb.off[1] = cb.obj0 + s_base; cb.n_corr[p] = s_base; }
+}
+
+__global__ __launch_bounds__(256) void k_chain_gather(PairBuf pb, int kp_cap, int p, int F, ChainBuf cb) { chain_gather_wg(pb, kp_cap, p, F, cb); }
+
+// vo_slam_chains, step j: workgroup = sequence (blockIdx.x).  A sequence that has ended hands k_pnp_ransac an empty problem.
+__global__ __launch_bounds__(256) void k_chain_gather_seqs(PairBuf pb, int kp_cap, int j, int F, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) {
+        if (threadIdx.x == 0) { q.cb.off[0] = q.cb.obj0; q.cb.off[1] = q.cb.obj0; }
+        return;
+    }
+    chain_gather_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, F, q.cb);
+}
+
+void launch_chain_gather_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_chain_gather_seqs, dim3(S), dim3(256), 0, s, pb, kp_cap, j, F, seqs);
 }
 
 void launch_chain_gather(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, ChainBuf cb)
@@ -1435,10 +1467,10 @@ void launch_chain_gather(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, Ch
 
 // add_information_to_map's reconstruct_3d_points(essential_matches, pose(frame2)[0:3], pose(frame1)[0:3]) (:164-172):
 // cv2.triangulatePoints(K pose(frame1), K pose(frame2), pts1, pts2), X /= w, for every E inlier of the pair
-__global__ void k_chain_triangulate(PairBuf pb, int kp_cap, int p, ChainBuf cb)
+__device__ __forceinline__ void chain_triangulate_one(PairBuf pb, int kp_cap, int p, ChainBuf cb)
 {
     if (!cb.alive[0]) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;    // keypoint tiles on x, in both kernels
     if (i >= pb.res[p].n_inl) return;
     double P1[12], P2[12], q[4];
     for (int k = 0; k < 12; k++) { P1[k] = cb.P1[k]; P2[k] = cb.P2[k]; }
@@ -1447,6 +1479,21 @@ __global__ void k_chain_triangulate(PairBuf pb, int kp_cap, int p, ChainBuf cb)
     triangulate_one(P1, P2, a[0], a[1], b[0], b[1], q);
     const double w = q[3];
     for (int k = 0; k < 4; k++) cb.Xw[4 * (size_t)i + k] = q[k] / w;
+}
+
+__global__ void k_chain_triangulate(PairBuf pb, int kp_cap, int p, ChainBuf cb) { chain_triangulate_one(pb, kp_cap, p, cb); }
+
+// vo_slam_chains, step j: the keypoint tiles stay on x, the sequence is blockIdx.y
+__global__ void k_chain_triangulate_seqs(PairBuf pb, int kp_cap, int j, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.y];
+    if (j >= q.count) return;
+    chain_triangulate_one(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, q.cb);
+}
+
+void launch_chain_triangulate_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_chain_triangulate_seqs, dim3((kp_cap + 63) / 64, S), dim3(64), 0, s, pb, kp_cap, j, seqs);
 }
 
 void launch_chain_triangulate(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb)

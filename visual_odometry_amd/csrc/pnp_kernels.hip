@@ -1578,12 +1578,12 @@ __device__ static void dp_reduce(PnpShared& sh, int tid)
 __global__ __launch_bounds__(256) void k_pnp_ransac(const double* obj_all, const double* img_all, const int* offsets, const double* Kd,
                                                     int iterations, double reproj_err, double confidence, uint64_t seed,
                                                     const uint32_t* rng_tab, int rng_n, int refine_cv2, PnpLambdaTab lam,
-                                                    double* rvec_out, double* tvec_out, uint8_t* mask_all, int* ninl_out, int* status_out)
+                                                    double* rvec_out, double* tvec_out, uint8_t* mask_all, int* ninl_out, int* status_out, int off_stride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn_pnp[];   // 160 KB: more than the static limit
     PnpShared& sh = *(PnpShared*)s_dyn_pnp;
     const int pb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int o0 = offsets[pb], n = offsets[pb + 1] - o0;
+    const int o0 = offsets[pb * off_stride], n = offsets[pb * off_stride + 1] - o0;
     const double* obj = obj_all + (size_t)o0 * 3; const double* img = img_all + (size_t)o0 * 2;
     uint8_t* mask = mask_all + o0;
     const dp_cam K = {Kd[0], Kd[4], Kd[2], Kd[5]};
@@ -1823,7 +1823,7 @@ __global__ __launch_bounds__(256) void k_pnp_ransac(const double* obj_all, const
 
 void launch_pnp_ransac(hipStream_t s, const double* obj, const double* img, const int* offsets, int B, const double* Kd,
                        int iterations, double reproj_err, double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n,
-                       int refine_cv2, double* rvec, double* tvec, uint8_t* mask, int* ninl, int* status)
+                       int refine_cv2, double* rvec, double* tvec, uint8_t* mask, int* ninl, int* status, int off_stride)
 {
     if (B <= 0) return;
     PnpLambdaTab lam;                                        // CvLevMarq::step: lambda = exp(lambdaLg10 * log(10.)), from the host's libm
@@ -1833,7 +1833,7 @@ void launch_pnp_ransac(hipStream_t s, const double* obj, const double* img, cons
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)k_pnp_ransac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PnpShared)); attr = true; }
     hipLaunchKernelGGL(k_pnp_ransac, dim3(B), dim3(256), sizeof(PnpShared), s, obj, img, offsets, Kd, iterations, reproj_err, confidence, seed,
-                       rng_tab, rng_n, refine_cv2, lam, rvec, tvec, mask, ninl, status);
+                       rng_tab, rng_n, refine_cv2, lam, rvec, tvec, mask, ninl, status, off_stride);
 }
 
 // cv2.Rodrigues for the Python shim (a 3-vector or a 3x3 matrix in, the other out): one thread
@@ -1855,9 +1855,9 @@ void launch_rodrigues(hipStream_t s, const double* in, int in_is_matrix, double*
 // ------------------------------------------------------------------ the localisation chain: the camera of a localised frame
 // src/visual_slam.py:237-251: retval -> R, _ = cv2.Rodrigues(rvec); TrackedCamera(R, tvec, ...).  Also the two projection
 // matrices add_information_to_map hands to reconstruct_3d_points (:166-172): K pose(frame1)[0:3] and K pose(frame2)[0:3].
-__global__ void k_chain_pose(PairBuf pb, int p, const double* Kd, ChainBuf cb)
+// (one lane works; the workgroup's other lanes have returned)
+__device__ __forceinline__ void chain_pose_one(PairBuf pb, int p, const double* Kd, ChainBuf cb)
 {
-    if (threadIdx.x | blockIdx.x) return;
     if (!cb.alive[0]) { cb.n_inl[p] = 0; for (int k = 0; k < 12; k++) cb.poses[(size_t)(p + 1) * 12 + k] = 0.0; return; }   // (status set by k_chain_gather)
     const int st = cb.pstatus[0];
     cb.n_inl[p] = cb.pninl[0];
@@ -1882,7 +1882,28 @@ __global__ void k_chain_pose(PairBuf pb, int p, const double* Kd, ChainBuf cb)
         }
 }
 
+__global__ void k_chain_pose(PairBuf pb, int p, const double* Kd, ChainBuf cb)
+{
+    if (threadIdx.x | blockIdx.x) return;
+    chain_pose_one(pb, p, Kd, cb);
+}
+
 void launch_chain_pose(hipStream_t s, PairBuf pb, int p, const double* Kd, ChainBuf cb)
 {
     hipLaunchKernelGGL(k_chain_pose, dim3(1), dim3(64), 0, s, pb, p, Kd, cb);
+}
+
+// step j of every sequence: workgroup = sequence (blockIdx.x), its lane 0 works
+__global__ void k_chain_pose_seqs(PairBuf pb, int j, const double* Kd, const SlamSeq* __restrict__ seqs)
+{
+    if (threadIdx.x) return;
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    pb.slots += 2 * (size_t)q.first;                        // the only member of pb read here: the sequence's pair 0 is pair `first` of the run
+    chain_pose_one(pb, j, Kd, q.cb);
+}
+
+void launch_chain_pose_seqs(hipStream_t s, PairBuf pb, int j, const double* Kd, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_chain_pose_seqs, dim3(S), dim3(64), 0, s, pb, j, Kd, seqs);
 }

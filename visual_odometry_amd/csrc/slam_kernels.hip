@@ -5,6 +5,9 @@
 //   remove_observations_with_reprojection_errors_above_threshold (:46-70)     -> k_slam_filter
 //   limit_number_of_camera_in_map / remove_camera_from_map (:188-232, 299-318)-> k_slam_limit
 // One workgroup of 256 lanes per map and kernel: the walk is sequential by nature and the maps are the reference's size.
+// Every step is written once, as a workgroup-wide device function, and has two kernels: k_slam_* for the one chain of vo_slam_chain
+// (its buffers by value) and k_slam_*_seqs for the S independent sequences of vo_slam_chains — workgroup = sequence (blockIdx.x),
+// which reads its SlamSeq descriptor and does step j of its own chain, or returns at once when its chain has fewer steps.
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
 // order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
 #include "chain_common.h"
@@ -40,8 +43,8 @@ __device__ __forceinline__ int slam_scan(int n, int* s_w, G&& get, W&& put)
 // camera list, and every E inlier in match order appends what the reference appends — a new point under featureid1 with its
 // observations on camera 1 and camera 2, or one observation of the point its track root owns.  Pass 1 takes every decision
 // against the map as it was before the loop (the snapshot of :154-156) and stores it; pass 2 writes, after a barrier.
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
-                                                           ChainBuf cb, SlamBuf sb)
+__device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
+                                            ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES], s_cnt[3][SLAM_WAVES];
     if (!cb.alive[0]) return;
@@ -121,22 +124,47 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add(PairBuf pb, int kp_ca
     if (tid == 0) { sb.m.cnt[0] = newn; sb.m.cnt[1] = min(npt0 + pbase, sb.pt_cap); sb.m.cnt[2] = min(nobs0 + obase, sb.obs_cap); }
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
+                                                           ChainBuf cb, SlamBuf sb)
+{
+    slam_add_wg(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_seqs(PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras,
+                                                                const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_add_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, F, max_norm, free_cameras, q.cb, q.sb);
+}
+
+void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_add_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, F, max_norm, free_cameras, seqs);
+}
+
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_add, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+// the problem k_bundle_adjust is handed: the map's place in the lists (all 0 for a single chain), its sizes, skip or not
+__device__ __forceinline__ BaProblem slam_problem(const BaProblem& at, int ncam, int npt, int nobs, int nfree, int skip)
+{
+    return BaProblem{at.cam0, at.pt0, at.obs0, at.pair0, at.blk0, ncam, npt, nobs, nfree, skip};
 }
 
 // g2o's graph bookkeeping for the resident map — the lists the host loop of vo_bundle_adjust_batch builds, entry for entry:
 // camera -> column of S, the observations sorted by point (stable in input order) with pt_first, and per block (c1 <= c2) of
 // free cameras the (observation of c1, observation of c2) that share a point: blocks (0,0) (0,1) .. (F-1,F-1), within a block
 // by point, then input order.
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_ba_prepare(ChainBuf cb, SlamBuf sb)
+__device__ __forceinline__ void slam_ba_prepare_wg(ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES], s_col[VO_BA_MAX_CAMERAS], s_nfree, s_over;
     const int tid = threadIdx.x;
     const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
     if (!cb.alive[0] || ncam > VO_BA_MAX_CAMERAS) {
-        if (tid == 0) { BaProblem q{}; q.skip = 1; sb.prob[0] = q; }
+        if (tid == 0) sb.prob[0] = slam_problem(sb.base, 0, 0, 0, 0, 1);
         return;
     }
     if (tid == 0) {
@@ -198,11 +226,27 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_ba_prepare(ChainBuf cb, S
         }
     __syncthreads();
     if (tid == 0) {
-        BaProblem q{};
-        q.ncam = ncam; q.npt = npt; q.nobs = nobs; q.nfree = nfree;
-        q.skip = s_over || nfree > VO_BA_MAX_FREE;            // (a pair list beyond its capacity: a point seen twice by one camera, which one-to-one matches exclude)
-        sb.prob[0] = q;
+        // (skipped: a pair list beyond its capacity — a point seen twice by one camera, which one-to-one matches exclude)
+        sb.prob[0] = slam_problem(sb.base, ncam, npt, nobs, nfree, s_over || nfree > VO_BA_MAX_FREE);
     }
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_ba_prepare(ChainBuf cb, SlamBuf sb) { slam_ba_prepare_wg(cb, sb); }
+
+// a sequence that has ended marks its problem skipped: k_bundle_adjust is launched for all S and must leave its map as it is
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_ba_prepare_seqs(int j, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) {
+        if (threadIdx.x == 0) q.sb.prob[0] = slam_problem(q.sb.base, 0, 0, 0, 0, 1);
+        return;
+    }
+    slam_ba_prepare_wg(q.cb, q.sb);
+}
+
+void launch_slam_ba_prepare_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_ba_prepare_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, j, seqs);
 }
 
 void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb)
@@ -218,7 +262,7 @@ __device__ __forceinline__ int slam_slot_of(const PairBuf& pb, int chain_frame)
 // What optimize_map wrote back (map.py:175-186) reaches the tables the next pair's k_chain_gather / k_chain_pose read; then
 // remove_observations_with_reprojection_errors_above_threshold (map.py:46-70) with k_reprojection's arithmetic, the list
 // compacted in place and in order.  Points are not removed here: one that loses every observation stays usable for PnP.
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+__device__ __forceinline__ void slam_filter_wg(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES];
     if (!cb.alive[0]) return;
@@ -243,6 +287,25 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter(PairBuf pb, const 
     if (tid == 0) sb.m.cnt[2] = kept;
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    slam_filter_wg(pb, Kd, threshold, cb, sb);
+}
+
+// (threshold is the step's: 0 at step 0, where initialize_map's optimize_map is only written back)
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_seqs(PairBuf pb, int kp_cap, int j, const double* Kd, double threshold,
+                                                                   const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_filter_wg(chain_pairs_from(pb, q.first, kp_cap), Kd, threshold, q.cb, q.sb);
+}
+
+void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_filter_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, Kd, threshold, seqs);
+}
+
 void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_filter, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
@@ -253,7 +316,7 @@ void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double thre
 // point left with one observation goes and a point with none stays.  A removed point leaves mappointdict: its feature id can
 // receive a new point later.  Camera and point indices in the observations are renumbered.  Also the end of a pair: every
 // camera's pose as the map holds it goes to poses_last (an evicted camera keeps its last row), the map's sizes to n_*.
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+__device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES];
     const int tid = threadIdx.x;
@@ -297,6 +360,20 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_came
         }
     }
     if (tid == 0) { sb.n_cam[p] = ncam; sb.n_pts[p] = npt; sb.n_obs[p] = nobs; }
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg(p, max_cameras, cb, sb); }
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_seqs(int j, int max_cameras, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_limit_wg(j, max_cameras, q.cb, q.sb);
+}
+
+void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_limit_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, j, max_cameras, seqs);
 }
 
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)

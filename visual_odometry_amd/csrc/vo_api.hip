@@ -88,6 +88,10 @@ struct LastRun {
         std::vector<uint8_t> cam_fixed;
         std::vector<double> cam_pose, points, obs_xy;
     } map[2];
+    // ... of the most recent vo_slam_chains: every sequence's map at its end, and the snapshot of sequence snap_seq (-1: none)
+    std::vector<Map> seq_map;
+    Map snap_map;
+    int snap_seq = -1;
 };
 
 struct vo_ctx {
@@ -2653,7 +2657,7 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
     rc = ensure_rng(ctx, seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
     const size_t fc = (size_t)F * cap;
-    ChainBuf cb; double* dK;
+    ChainBuf cb{}; double* dK;
     ScratchLayout sc;
     sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
     sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4); sc.take(&cb.poses, (size_t)(B + 1) * 12);
@@ -2704,7 +2708,8 @@ static size_t slam_map_carve(uint8_t* base, size_t ncam, size_t npt, size_t nobs
     return o;
 }
 
-static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Map* out)
+// first, count: the pairs of the run that are the map's chain (pt_feature names a frame by its index along that chain)
+static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Map* out, int first = 0, int count = -1)
 {
     int cnt[4];
     HIPCHK(hipMemcpy(cnt, m.cnt, sizeof(cnt), hipMemcpyDeviceToHost));
@@ -2727,14 +2732,39 @@ static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Ma
         HIPCHK(hipMemcpy(out->obs_xy.data(), m.obs_xy, no * 16, hipMemcpyDeviceToHost));
     }
     // feature id (slot, keypoint) -> (index of the frame in the chain, keypoint)
-    const std::vector<int32_t>& sl = ctx->last.slots;
+    const int32_t* sl = ctx->last.slots.data() + 2 * (size_t)first;
+    const size_t npairs = count < 0 ? ctx->last.slots.size() / 2 : (size_t)count;
     for (size_t i = 0; i < np; i++) {
         const int slot = key[i] / cap;
         int frame = sl[0] == slot ? 0 : -1;
-        for (size_t p = 0; frame < 0 && 2 * p + 1 < sl.size(); p++) if (sl[2 * p + 1] == slot) frame = (int)p + 1;
+        for (size_t p = 0; frame < 0 && p < npairs; p++) if (sl[2 * p + 1] == slot) frame = (int)p + 1;
         out->pt_feature[2 * i] = frame; out->pt_feature[2 * i + 1] = key[i] % cap;
     }
     out->valid = true;
+    return VO_OK;
+}
+
+static void forget_slam_maps(vo_ctx* ctx)
+{
+    ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
+    ctx->last.seq_map.clear(); ctx->last.snap_map = LastRun::Map(); ctx->last.snap_seq = -1;
+}
+
+// the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
+static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, int B_snap, const char* who)
+{
+    if (ctx->last.match_mode == 1)
+        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio matches two inliers can share a track root", who);
+    if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
+    if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
+    if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);
+    if (o->max_cameras < 2) FAIL(VO_ERR_INVALID, "max_cameras must be at least 2, got %d", o->max_cameras);
+    if ((int64_t)o->max_cameras + 1 > VO_BA_MAX_CAMERAS)
+        FAIL(VO_ERR_UNSUPPORTED, "the map holds max_cameras + 1 cameras before the limit is applied, bundle adjustment at most %d", VO_BA_MAX_CAMERAS);
+    if (!(o->huber_delta == o->huber_delta) || !(o->filter_threshold == o->filter_threshold) || !(K[0] == K[0]) || !(K[2] == K[2]) || !(K[5] == K[5]))
+        FAIL(VO_ERR_INVALID, "camera parameters and thresholds must be numbers");
+    if ((o->snapshot_pair >= 0) != (o->snapshot_stage >= 1) || o->snapshot_pair >= B_snap || o->snapshot_stage > 4)
+        FAIL(VO_ERR_INVALID, "snapshot_pair must be -1 or a pair of the chain, snapshot_stage 1 .. 4 with it");
     return VO_OK;
 }
 
@@ -2747,19 +2777,8 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
         FAIL(VO_ERR_INVALID, "bad arguments");
     int F, cap;
     int rc = chain_check(ctx, B, "vo_slam_chain", &F, &cap); if (rc) return rc;
-    ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
-    if (ctx->last.match_mode == 1)
-        FAIL(VO_ERR_UNSUPPORTED, "vo_slam_chain needs one-to-one matches (cross-check): with ratio matches two inliers can share a track root");
-    if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
-    if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
-    if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);
-    if (o->max_cameras < 2) FAIL(VO_ERR_INVALID, "max_cameras must be at least 2, got %d", o->max_cameras);
-    if ((int64_t)o->max_cameras + 1 > VO_BA_MAX_CAMERAS)
-        FAIL(VO_ERR_UNSUPPORTED, "the map holds max_cameras + 1 cameras before the limit is applied, bundle adjustment at most %d", VO_BA_MAX_CAMERAS);
-    if (!(o->huber_delta == o->huber_delta) || !(o->filter_threshold == o->filter_threshold) || !(K[0] == K[0]) || !(K[2] == K[2]) || !(K[5] == K[5]))
-        FAIL(VO_ERR_INVALID, "camera parameters and thresholds must be numbers");
-    if ((o->snapshot_pair >= 0) != (o->snapshot_stage >= 1) || o->snapshot_pair >= B || o->snapshot_stage > 4)
-        FAIL(VO_ERR_INVALID, "snapshot_pair must be -1 or a pair of the chain, snapshot_stage 1 .. 4 with it");
+    forget_slam_maps(ctx);
+    rc = slam_opts_check(ctx, o, K, B, "vo_slam_chain"); if (rc) return rc;
     const size_t fc = (size_t)F * cap;
     HIPCHK(hipSetDevice(ctx->device));
     rc = ensure_rng(ctx, o->seed); if (rc) return rc;
@@ -2768,7 +2787,7 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
     const size_t cm = (size_t)o->max_cameras + 1, np = fc, no = (size_t)2 * B * cap, npair = no * (o->free_cameras + 1) / 2;
     const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
     if (np >= ((size_t)1 << 31) || npair >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the map's lists would not fit 32-bit indices");
-    ChainBuf cb; SlamBuf sb{}; BaBuf D{}; double* dK; uint8_t *map_mem, *snap_mem;
+    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; double* dK; uint8_t *map_mem, *snap_mem;
     const size_t map_bytes = slam_map_carve(nullptr, cm, np, no, &sb.m);
     ScratchLayout sc;
     sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
@@ -2844,6 +2863,17 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
     return VO_OK;
 }
 
+static int slam_map_copy_out(vo_ctx* ctx, const LastRun::Map* m, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature, double* points,
+                             int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
+{
+    if ((!m->cam_frame.empty() && (!cam_frame || !cam_pose || !cam_fixed)) || (!m->points.empty() && (!pt_feature || !points)) ||
+        (!m->obs_cam.empty() && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
+    auto copy = [](auto* dst, const auto& v) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    copy(cam_frame, m->cam_frame); copy(cam_pose, m->cam_pose); copy(cam_fixed, m->cam_fixed); copy(pt_feature, m->pt_feature); copy(points, m->points);
+    copy(obs_cam, m->obs_cam); copy(obs_pt, m->obs_pt); copy(obs_xy, m->obs_xy);
+    return VO_OK;
+}
+
 static const LastRun::Map* slam_map_of(vo_ctx* ctx, int which)
 {
     if (which < 0 || which > 1 || !ctx->last.map[which].valid) {
@@ -2870,12 +2900,226 @@ extern "C" int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* c
     if (!ctx) return VO_ERR_INVALID;
     const LastRun::Map* m = slam_map_of(ctx, which);
     if (!m) return VO_ERR_INVALID;
-    if ((!m->cam_frame.empty() && (!cam_frame || !cam_pose || !cam_fixed)) || (!m->points.empty() && (!pt_feature || !points)) ||
-        (!m->obs_cam.empty() && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
-    auto copy = [](auto* dst, const auto& v) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-    copy(cam_frame, m->cam_frame); copy(cam_pose, m->cam_pose); copy(cam_fixed, m->cam_fixed); copy(pt_feature, m->pt_feature); copy(points, m->points);
-    copy(obs_cam, m->obs_cam); copy(obs_pt, m->obs_pt); copy(obs_xy, m->obs_xy);
+    return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
+}
+
+// ------------------------------------------------------------------ the map step for S independent sequences in one call
+// vo_slam_chain's walk, every kernel of a step launched once with the sequence on a grid axis (k_*_seqs): the host loop runs over
+// the step j = 0 .. max B_s - 1, a workgroup does step j of its own sequence on pair seq_off[s] + j.  The slot-keyed tables are
+// shared (the sequences' slots are disjoint: checked here); every list is carved once for all sequences and a sequence owns the
+// range its capacities give it — cameras max_cameras + 1, points (B_s + 1) kp_cap, observations 2 B_s kp_cap — so k_bundle_adjust
+// runs the S problems through BaProblem's offsets unchanged and the scratch grows with B, not with S * B.
+static int chains_check(vo_ctx* ctx, int S, const int32_t* seq_off, int* F_out, int* cap_out)
+{
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (S < 1) FAIL(VO_ERR_INVALID, "vo_slam_chains takes at least one sequence, got %d", S);
+    if (seq_off[0] != 0) FAIL(VO_ERR_INVALID, "seq_off[0] must be 0, got %d", seq_off[0]);
+    for (int s = 0; s < S; s++)
+        if (seq_off[s + 1] <= seq_off[s]) FAIL(VO_ERR_INVALID, "seq_off must be strictly increasing: sequence %d has %d pairs", s, seq_off[s + 1] - seq_off[s]);
+    if (ctx->last.pairs < 1 || seq_off[S] != ctx->last.pairs)
+        FAIL(VO_ERR_INVALID, "vo_slam_chains takes all %d pairs of the most recent vo_pairs_run, seq_off ends at %d", ctx->last.pairs, seq_off[S]);
+    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
+    const int F = b.max_frames, cap = b.kp_cap, B = seq_off[S];
+    const int32_t* sl = ctx->last.slots.data();
+    for (int i = 0; i < 2 * B; i++)
+        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
+    std::vector<int> owner((size_t)F, -1);                  // the sequence a slot's frame belongs to
+    for (int s = 0; s < S; s++)
+        for (int p = seq_off[s]; p < seq_off[s + 1]; p++) {
+            const bool head = p == seq_off[s];
+            const int a = sl[2 * p], c = sl[2 * p + 1];
+            const int other = head && owner[(size_t)a] >= 0 ? owner[(size_t)a] : owner[(size_t)c];
+            if (other >= 0 && other != s)
+                FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", other, s, p, a, c);
+            if ((!head && a != sl[2 * p - 1]) || (head && a == c) || owner[(size_t)c] == s)
+                FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue sequence %d as a chain of distinct frames", p, a, c, s);
+            owner[(size_t)a] = s; owner[(size_t)c] = s;
+        }
+    if (F >= (1 << 20) || cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames or keypoints for the packed track table");
+    *F_out = F; *cap_out = cap;
     return VO_OK;
+}
+
+extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
+                              double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
+                              int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    forget_slam_maps(ctx);
+    if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
+        FAIL(VO_ERR_INVALID, "bad arguments");
+    int F, cap;
+    int rc = chains_check(ctx, S, seq_off, &F, &cap); if (rc) return rc;
+    const bool snap_on = o->snapshot_pair >= 0;        // (snapshot_seq is ignored otherwise)
+    if (snap_on && (snapshot_seq < 0 || snapshot_seq >= S)) FAIL(VO_ERR_INVALID, "snapshot_seq must be a sequence of the call (0 .. %d), got %d", S - 1, snapshot_seq);
+    const int ss = snap_on ? snapshot_seq : 0;
+    const int B = seq_off[S], Bss = seq_off[ss + 1] - seq_off[ss];
+    rc = slam_opts_check(ctx, o, K, Bss, "vo_slam_chains"); if (rc) return rc;
+    int maxB = 0;
+    for (int q = 0; q < S; q++) maxB = std::max(maxB, seq_off[q + 1] - seq_off[q]);
+    const size_t fc = (size_t)F * cap;
+    HIPCHK(hipSetDevice(ctx->device));
+    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    // capacities from the configuration: a pair adds at most one point and two observations per match
+    const size_t cm = (size_t)o->max_cameras + 1, NC = cm * S, NP = (size_t)(B + S) * cap, NO = (size_t)2 * B * cap;
+    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
+    std::vector<size_t> pair0((size_t)S + 1, 0);
+    for (int q = 0; q < S; q++) pair0[q + 1] = pair0[q] + (size_t)2 * (seq_off[q + 1] - seq_off[q]) * cap * (o->free_cameras + 1) / 2;
+    const size_t NPAIR = pair0[S];
+    if (NP >= ((size_t)1 << 31) || NPAIR >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the maps' lists would not fit 32-bit indices");
+    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; SlamMap snap{}; double* dK; uint8_t* snap_mem; SlamSeq* dseq;
+    const size_t snap_np = (size_t)(Bss + 1) * cap, snap_no = (size_t)2 * Bss * cap;
+    ScratchLayout sc;
+    // shared, keyed by slot
+    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&sb.pt_of, fc);
+    sc.take(&dK, 9);
+    // per sequence: the current problem and the step's state
+    sc.take(&cb.obj, (size_t)S * cap * 3); sc.take(&cb.img, (size_t)S * cap * 2); sc.take(&cb.Xw, (size_t)S * cap * 4); sc.take(&cb.pmask, (size_t)S * cap);
+    sc.take(&sb.dec, (size_t)S * cap); sc.take(&cb.off, (size_t)2 * S); sc.take(&cb.rvec, (size_t)3 * S); sc.take(&cb.tvec, (size_t)3 * S);
+    sc.take(&cb.pninl, S); sc.take(&cb.pstatus, S); sc.take(&cb.P1, (size_t)12 * S); sc.take(&cb.P2, (size_t)12 * S); sc.take(&cb.alive, S); sc.take(&cb.map_count, S);
+    // per pair, in the run's order; sequence s owns the pose rows seq_off[s] + s .. seq_off[s + 1] + s
+    sc.take(&cb.poses, (size_t)(B + S) * 12); sc.take(&sb.poses_last, (size_t)(B + S) * 12);
+    sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&sb.n_pts, B); sc.take(&sb.n_obs, B); sc.take(&sb.n_cam, B);
+    // the maps' lists and the bundle adjustment's, each carved once: a sequence's range starts at its BaProblem offsets
+    sc.take(&sb.m.cnt, (size_t)4 * S); sc.take(&sb.m.cam_frame, NC); sc.take(&sb.m.cam_pose, NC * 12); sc.take(&sb.m.cam_fixed, NC);
+    sc.take(&sb.m.pt_key, NP); sc.take(&sb.m.pt_xyz, NP * 3); sc.take(&sb.m.obs_cam, NO); sc.take(&sb.m.obs_pt, NO); sc.take(&sb.m.obs_xy, NO * 2);
+    sc.take(&sb.tmp, NP); sc.take(&sb.idx, NO); sc.take(&sb.prob, S); sc.take(&sb.cam_col, NC); sc.take(&sb.pt_first, NP + S);
+    sc.take(&sb.s_cam, NO); sc.take(&sb.s_pt, NO); sc.take(&sb.s_xy, NO * 2); sc.take(&sb.pairs, NPAIR); sc.take(&sb.blk_first, (size_t)S * (nblk + 1));
+    sc.take(&D.X2, NP * 3); sc.take(&D.W, NO * 18); sc.take(&D.Hpp, NP * 6); sc.take(&D.bp, NP * 3); sc.take(&D.Hpi, NP * 6);
+    // k_bundle_adjust writes problem s of step j at [j][s]
+    double* dchi2; int *dit, *dtr;
+    sc.take(&dchi2, (size_t)2 * maxB * S); sc.take(&dit, (size_t)maxB * S); sc.take(&dtr, (size_t)maxB * S);
+    sc.take(&snap_mem, snap_on ? slam_map_carve(nullptr, cm, snap_np, snap_no, &snap) : 0);
+    sc.take(&dseq, S);
+    rc = sc.place(ctx); if (rc) return rc;
+    if (snap_on) slam_map_carve(snap_mem, cm, snap_np, snap_no, &snap);
+    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
+    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
+    std::vector<SlamSeq> seq((size_t)S);
+    for (int q = 0; q < S; q++) {
+        const int first = seq_off[q], Bq = seq_off[q + 1] - first;
+        SlamSeq& e = seq[(size_t)q];
+        e.first = first; e.count = Bq;
+        BaProblem at{};
+        at.cam0 = (int)(cm * q); at.pt0 = (int)((size_t)(first + q) * cap); at.obs0 = (int)((size_t)2 * first * cap); at.pair0 = (int)pair0[q]; at.blk0 = q * (nblk + 1);
+        ChainBuf& c = e.cb; c = cb;
+        c.obj0 = q * cap;                                    // k_pnp_ransac indexes the whole arrays by the sequence's {first, end}
+        c.off += 2 * q; c.rvec += 3 * q; c.tvec += 3 * q; c.pmask += (size_t)q * cap; c.pninl += q; c.pstatus += q; c.P1 += 12 * q; c.P2 += 12 * q;
+        c.obj += (size_t)q * cap * 3; c.img += (size_t)q * cap * 2; c.Xw += (size_t)q * cap * 4; c.alive += q; c.map_count += q;
+        c.n_corr += first; c.n_inl += first; c.status += first; c.n_map += first; c.poses += (size_t)(first + q) * 12;
+        SlamBuf& m = e.sb; m = sb;
+        m.base = at;
+        m.cam_cap = (int)cm; m.pt_cap = (Bq + 1) * cap; m.obs_cap = 2 * Bq * cap; m.pair_cap = (int)(pair0[q + 1] - pair0[q]);
+        m.m.cnt += 4 * q; m.m.cam_frame += at.cam0; m.m.cam_pose += (size_t)at.cam0 * 12; m.m.cam_fixed += at.cam0;
+        m.m.pt_key += at.pt0; m.m.pt_xyz += (size_t)at.pt0 * 3; m.m.obs_cam += at.obs0; m.m.obs_pt += at.obs0; m.m.obs_xy += (size_t)at.obs0 * 2;
+        m.dec += (size_t)q * cap; m.tmp += at.pt0; m.idx += at.obs0; m.n_pts += first; m.n_obs += first; m.n_cam += first; m.poses_last += (size_t)(first + q) * 12;
+        m.prob += q; m.cam_col += at.cam0; m.pt_first += at.pt0 + q; m.s_cam += at.obs0; m.s_pt += at.obs0; m.s_xy += (size_t)at.obs0 * 2;
+        m.pairs += at.pair0; m.blk_first += at.blk0;
+    }
+    HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty maps, no cameras, zero results
+    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dseq, seq.data(), (size_t)S * sizeof(SlamSeq), hipMemcpyHostToDevice, s));
+    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
+    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
+    const SlamMap live = seq[(size_t)ss].sb.m;
+    auto snapshot = [&](int j, int stage) {                          // the sequence's ranges of the lists: a few device-to-device copies
+        if (!snap_on || j != o->snapshot_pair || stage != o->snapshot_stage) return;
+        auto cp = [&](auto* dst, const auto* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * sizeof(*src), hipMemcpyDeviceToDevice, s); };
+        cp(snap.cnt, live.cnt, 4); cp(snap.cam_frame, live.cam_frame, cm); cp(snap.cam_pose, live.cam_pose, cm * 12); cp(snap.cam_fixed, live.cam_fixed, cm);
+        cp(snap.pt_key, live.pt_key, snap_np); cp(snap.pt_xyz, live.pt_xyz, snap_np * 3);
+        cp(snap.obs_cam, live.obs_cam, snap_no); cp(snap.obs_pt, live.obs_pt, snap_no); cp(snap.obs_xy, live.obs_xy, snap_no * 2);
+    };
+    launch_chain_link(s, ctx->pb, cap, B, cb);
+    for (int j = 0; j < maxB; j++) {
+        {
+            StageTimer t(ctx, ST_MISC);
+            if (j == 0) launch_chain_init_seqs(s, ctx->pb, cap, dseq, S);
+            else {
+                launch_chain_gather_seqs(s, ctx->pb, cap, j, F, dseq, S);
+                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
+                launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
+                launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
+            }
+            launch_slam_add_seqs(s, ctx->pb, cap, j, F, o->max_point_norm, o->free_cameras, dseq, S);
+        }
+        snapshot(j, 1);
+        if (ba) {
+            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare_seqs(s, j, dseq, S); }
+            BaBuf Dj = D;
+            Dj.chi2 = dchi2 + (size_t)2 * j * S; Dj.iterations_run = dit + (size_t)j * S; Dj.trials_run = dtr + (size_t)j * S;
+            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dj, prm, S, o->free_cameras); }
+        }
+        snapshot(j, 2);
+        // step 0 ends with optimize_map (:90); what it wrote back still has to reach the tables the next pair reads
+        if (ba || (filt && j > 0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter_seqs(s, ctx->pb, cap, j, dK, j > 0 ? o->filter_threshold : 0.0, dseq, S); }
+        snapshot(j, 3);
+        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_seqs(s, j, o->max_cameras, dseq, S); }
+        snapshot(j, 4);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<double> hchi((size_t)2 * maxB * S); std::vector<int32_t> hit((size_t)maxB * S), htr((size_t)maxB * S);
+    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hchi.data(), dchi2, hchi.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hit.data(), dit, hit.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(htr.data(), dtr, htr.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    for (int q = 0; q < S; q++)                                       // [step][sequence] -> the pair's position in the run
+        for (int j = 0; j < seq_off[q + 1] - seq_off[q]; j++) {
+            const size_t at = (size_t)j * S + q, p = (size_t)seq_off[q] + j;
+            chi2[2 * p] = hchi[2 * at]; chi2[2 * p + 1] = hchi[2 * at + 1]; ba_iterations_run[p] = hit[at]; ba_trials_run[p] = htr[at];
+        }
+    // the scratch buffer belongs to the next call: the maps are kept as host copies
+    std::vector<LastRun::Map> maps((size_t)S);
+    for (int q = 0; q < S; q++) { rc = slam_map_download(ctx, seq[(size_t)q].sb.m, cap, &maps[(size_t)q], seq_off[q], seq_off[q + 1] - seq_off[q]); if (rc) return rc; }
+    LastRun::Map smap;
+    if (snap_on) { rc = slam_map_download(ctx, snap, cap, &smap, seq_off[ss], Bss); if (rc) return rc; }
+    ctx->last.map[0] = maps[0];                                       // what vo_slam_map reports: sequence 0, and its snapshot if it has one
+    if (snap_on && ss == 0) ctx->last.map[1] = smap;
+    ctx->last.seq_map = std::move(maps);
+    if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
+    return VO_OK;
+}
+
+static const LastRun::Map* slam_chains_map_of(vo_ctx* ctx, int seq, int which)
+{
+    const LastRun& l = ctx->last;
+    const char* why = nullptr;
+    if (which < 0 || which > 1) why = "which must be 0 (the map at the end of the sequence) or 1 (the snapshot)";
+    else if (l.seq_map.empty()) why = "no such map: vo_slam_chains has not run since the last configure / vo_pairs_run / chain call";
+    else if (seq < 0 || seq >= (int)l.seq_map.size()) why = "no such sequence in the most recent vo_slam_chains";
+    else if (which == 1 && seq != l.snap_seq) why = "no such map: the most recent vo_slam_chains took no snapshot of this sequence";
+    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); return nullptr; }
+    return which == 1 ? &l.snap_map : &l.seq_map[(size_t)seq];
+}
+
+extern "C" int vo_slam_chains_map_size(vo_ctx* ctx, int seq, int which, int32_t* ncam, int32_t* npt, int32_t* nobs)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!ncam || !npt || !nobs) FAIL(VO_ERR_INVALID, "bad arguments");
+    const LastRun::Map* m = slam_chains_map_of(ctx, seq, which);
+    if (!m) return VO_ERR_INVALID;
+    *ncam = (int32_t)m->cam_frame.size(); *npt = (int32_t)(m->points.size() / 3); *nobs = (int32_t)m->obs_cam.size();
+    return VO_OK;
+}
+
+extern "C" int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature,
+                                  double* points, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const LastRun::Map* m = slam_chains_map_of(ctx, seq, which);
+    if (!m) return VO_ERR_INVALID;
+    return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
 }
 
 extern "C" int vo_profile_enable(vo_ctx* ctx, int on)

@@ -208,9 +208,11 @@ void launch_jpeg_decode(hipStream_t s, const uint8_t* blob, JpegImage* imgs, con
                         bool packed_tables = false /* no file of the batch names more than four Huffman tables */,
                         hipEvent_t coef_cleared = nullptr /* the coefficient buffer is cleared on another stream: k_jpeg_huffman waits for this */);
 
+// problem b is rows offsets[b * off_stride] .. offsets[b * off_stride + 1] - 1: off_stride 1 = problems packed back to back,
+// 2 = a {first, end} pair per problem (vo_slam_chains: every sequence's rows sit in its own range)
 void launch_pnp_ransac(hipStream_t s, const double* obj, const double* img, const int* offsets, int B, const double* Kd,
                        int iterations, double reproj_err, double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n,
-                       int refine_cv2, double* rvec, double* tvec, uint8_t* mask, int* ninl, int* status);
+                       int refine_cv2, double* rvec, double* tvec, uint8_t* mask, int* ninl, int* status, int off_stride = 1);
 void launch_rodrigues(hipStream_t s, const double* in, int in_is_matrix, double* out);
 void launch_blur(hipStream_t s, const uint8_t* pyr, uint8_t* blur, const PyrGeom& g, int F);
 void launch_brief(hipStream_t s, const uint8_t* blur, const PyrGeom& g, FrameFeat ff, int F, uint8_t* desc_x, int cap_x, int fp4);
@@ -260,7 +262,8 @@ struct ChainBuf {
     int*     cam_ok;              // [F]
     double*  obj;                 // [cap][3] the current problem's map coordinates
     double*  img;                 // [cap][2] ... image coordinates
-    int*     off;                 // [2] {0, n}: the offsets k_pnp_ransac reads
+    int*     off;                 // [2] {obj0, obj0 + n}: the offsets k_pnp_ransac reads
+    int      obj0;                // first row of this chain's problem in the arrays k_pnp_ransac is handed (0 unless several chains share them)
     double*  rvec; double* tvec;  // [3] each: solvePnPRansac's result for the current pair
     uint8_t* pmask;               // [cap]
     int*     pninl; int* pstatus; // [1] each
@@ -321,10 +324,24 @@ struct SlamBuf {
     double*  poses_last;                // [P + 1][12] every camera as the map last held it
     // what k_slam_ba_prepare hands k_bundle_adjust (BaBuf's const members)
     BaProblem* prob; int* cam_col; int* pt_first; int* s_cam; int* s_pt; double* s_xy; int2* pairs; int* blk_first;
+    BaProblem base;                     // where this map's lists start in the arrays BaBuf names: cam0 .. blk0 (all 0 for a single chain)
 };
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
 void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb);
 void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb);
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb);
+// ---- the same step for S independent sequences at once (vo_slam_chains): one workgroup per sequence and kernel, the sequence on a
+// grid axis.  A workgroup reads its sequence's descriptor from a device array — its pairs inside the run, and a ChainBuf / SlamBuf
+// whose slot-keyed tables (parent, in_map, map_pt, cam, cam_ok, pt_of) are the shared ones (the sequences' slots are disjoint) and
+// whose other members are the sequence's own — and does step j of its chain on pair first + j; with j >= count it returns at once.
+struct SlamSeq { int first, count; ChainBuf cb; SlamBuf sb; };
+void launch_chain_init_seqs(hipStream_t s, PairBuf pb, int kp_cap, const SlamSeq* seqs, int S);
+void launch_chain_gather_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, const SlamSeq* seqs, int S);
+void launch_chain_pose_seqs(hipStream_t s, PairBuf pb, int j, const double* Kd, const SlamSeq* seqs, int S);
+void launch_chain_triangulate_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S);
+void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S);
+void launch_slam_ba_prepare_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S);
+void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);
+void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

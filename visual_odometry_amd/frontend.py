@@ -194,10 +194,33 @@ class FrontEnd:
                                     i32["n_cam"].ctypes.data, chi2.ctypes.data, i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data))
         return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, **i32)
 
-    def slam_map(self, which=0):
-        """The map of the latest slam_chain: which=0 at the end of the chain, 1 the snapshot.  dict(cam_frame [ncam] index of the
-        camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool, pt_feature [npt, 2] (chain frame, keypoint),
-        points [npt, 3], obs_cam, obs_pt [nobs], obs_xy [nobs, 2])."""
+    def slam_chains(self, seq_lengths, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
+                    ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """slam_chain for several independent sequences in one call (vo_slam_chains), one workgroup per sequence and kernel: the
+        pairs of the latest run_pairs(..., want_points=True) are sequence 0's seq_lengths[0] pairs, then sequence 1's, ...; every
+        sequence is a chain of its own and no frame slot belongs to two of them (a frame two sequences share is uploaded into
+        two slots).  snapshot=(seq, pair, stage), the pair counted along that sequence (slam_map(1, seq=seq)).  Returns a list of
+        len(seq_lengths) dicts, each what slam_chain returns for that sequence alone: a pair that cannot be localised ends its
+        own sequence only."""
+        off = sequence_offsets(seq_lengths, len(self._keep[0]) if getattr(self, "_keep", None) else 0)
+        S, B = len(off) - 1, int(off[-1])
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        sq, sp, ss = (0, -1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]), int(snapshot[2]))
+        opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
+                             float(huber_delta), int(free_cameras), float(filter_threshold), int(max_cameras), sp, ss)
+        flat = dict(poses_pnp=np.zeros((B + S, 12)), poses=np.zeros((B + S, 12)), chi2=np.zeros((B, 2)))
+        flat.update({k: np.zeros(B, np.int32) for k in ("n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")})
+        c = self.ctx
+        c.check(c.lib.vo_slam_chains(c.handle, S, off.ctypes.data, K.ctypes.data, C.addressof(opts), sq, *[flat[k].ctypes.data for k in (
+            "poses_pnp", "poses", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "chi2", "ba_iterations", "ba_trials")]))
+        return split_sequences(flat, off)
+
+    def slam_map(self, which=0, seq=0):
+        """The map of the latest slam_chain, or of sequence `seq` of the latest slam_chains: which=0 at the end of the chain, 1 the
+        snapshot.  dict(cam_frame [ncam] index of the camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool,
+        pt_feature [npt, 2] (chain frame, keypoint), points [npt, 3], obs_cam, obs_pt [nobs], obs_xy [nobs, 2])."""
+        if seq:
+            return self._slam_chains_map(int(seq), int(which))
         c = self.ctx
         n = [C.c_int32(0) for _ in range(3)]
         c.check(c.lib.vo_slam_map_size(c.handle, int(which), *[C.addressof(v) for v in n]))
@@ -207,6 +230,19 @@ class FrontEnd:
                  obs_pt=np.zeros(no, np.int32), obs_xy=np.zeros((no, 2)))
         c.check(c.lib.vo_slam_map(c.handle, int(which), *[_lib.ptr(m[k]) for k in ("cam_frame", "cam_pose", "cam_fixed", "pt_feature", "points",
                                                                                   "obs_cam", "obs_pt", "obs_xy")]))
+        m["cam_fixed"] = m["cam_fixed"].astype(bool)
+        return m
+
+    def _slam_chains_map(self, seq, which):
+        c = self.ctx
+        n = [C.c_int32(0) for _ in range(3)]
+        c.check(c.lib.vo_slam_chains_map_size(c.handle, seq, which, *[C.addressof(v) for v in n]))
+        nc, npt, no = (v.value for v in n)
+        m = dict(cam_frame=np.zeros(nc, np.int32), cam_pose=np.zeros((nc, 3, 4)), cam_fixed=np.zeros(nc, np.uint8),
+                 pt_feature=np.zeros((npt, 2), np.int32), points=np.zeros((npt, 3)), obs_cam=np.zeros(no, np.int32),
+                 obs_pt=np.zeros(no, np.int32), obs_xy=np.zeros((no, 2)))
+        c.check(c.lib.vo_slam_chains_map(c.handle, seq, which, *[_lib.ptr(m[k]) for k in ("cam_frame", "cam_pose", "cam_fixed", "pt_feature", "points",
+                                                                                          "obs_cam", "obs_pt", "obs_xy")]))
         m["cam_fixed"] = m["cam_fixed"].astype(bool)
         return m
 
@@ -250,6 +286,30 @@ class FrontEnd:
             if c.lib.vo_stage_name(i).decode() == stage_name:
                 return float(c.lib.vo_stage_bytes(c.handle, i, int(frames)))
         raise KeyError(stage_name)
+
+
+def sequence_offsets(seq_lengths, n_pairs):
+    """slam_chains' seq_off: [0, l0, l0 + l1, ...] as int32 for the pair counts `seq_lengths` of the sequences that make up a
+    run of `n_pairs` pairs.  ValueError on an empty list, a length < 1 or a sum different from n_pairs."""
+    lengths = [int(v) for v in seq_lengths]
+    if not lengths:
+        raise ValueError("seq_lengths is empty: slam_chains takes at least one sequence")
+    if min(lengths) < 1:
+        raise ValueError(f"every sequence has at least one pair, got {lengths}")
+    if sum(lengths) != int(n_pairs):
+        raise ValueError(f"the sequences' {sum(lengths)} pairs are not the {int(n_pairs)} pairs of the latest run_pairs")
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+
+
+def split_sequences(flat, seq_off):
+    """vo_slam_chains' flat outputs -> one slam_chain dict per sequence (copies): per-pair arrays are rows seq_off[s] ..
+    seq_off[s + 1] - 1, the pose arrays rows seq_off[s] + s .. seq_off[s + 1] + s (a sequence of B_s pairs has B_s + 1 cameras)."""
+    out = []
+    for s in range(len(seq_off) - 1):
+        a, b = int(seq_off[s]), int(seq_off[s + 1])
+        d = {k: (v[a + s:b + s + 1].reshape(-1, 3, 4) if k in ("poses_pnp", "poses") else v[a:b]).copy() for k, v in flat.items()}
+        out.append(d)
+    return out
 
 
 def chain_poses(R, t):
