@@ -164,7 +164,8 @@ int vo_stage_five_point(vo_ctx* ctx, const double* x1, const double* x2, double*
  * estimate_camera_movement -> reconstruct_3d_points). */
 typedef struct {
     int32_t match_mode;     /* 0 = BFMatcher(crossCheck=True).match (strict mutual NN), 1 = knnMatch(k=2) + ratio,
-                               2 = the legacy cross-check rule (vo_match_hamming cross_check = 1) */
+                               2 = the legacy cross-check rule (vo_match_hamming cross_check = 1),
+                               3 = BFMatcher(crossCheck=False).match: every query's nearest train row, not one-to-one */
     double  ratio;          /* ratio for match_mode 1 */
     double  ransac_prob;    /* 0.99  src/image_pair.py:278 */
     double  ransac_thresh;  /* 1.0   src/image_pair.py:279 */
@@ -215,7 +216,11 @@ int vo_pairs_run_async(vo_ctx* ctx, const int32_t* pair_slots, int B, const doub
 /* The synchronous forms (vo_frames_detect, vo_pairs_run) return VO_WARN_CAPACITY (> 0, results valid) when a keypoint list of an
  * involved slot hit its capacity: the batched SIFT path cuts such a frame at kp_cap in cv2's list order — x ascending, i.e. the
  * right edge of the image goes first — so E-RANSAC would run on a one-sided set; raise kp_cap.  The asynchronous forms cannot
- * know: vo_frame_features[_sift] reports the flag per slot. */
+ * know: vo_frame_features[_sift] reports the flag per slot.
+ * SIFT: vo_pairs_run returns VO_ERR_INVALID when a slot of the pair list holds a descriptor row with |row|^2 > 2^20 (the bound
+ * under which the integer matcher's order is cv2's; SIFT's normalisation gives ~2^18).  Like the capacity warning the error is
+ * reported AFTER the run — the results of the other pairs are in `results`, those of a pair with such a slot are not to be
+ * used — and the asynchronous form cannot know: vo_frame_features_sift reports the slot. */
 int vo_sync(vo_ctx* ctx);
 /* Orders ctx's next enqueued work after `other`'s most recent vo_frames_detect_async (same device).  Chaining the
  * detections of two contexts keeps them out of phase: one's RANSAC / pose always runs beside the other's ORB. */
@@ -321,6 +326,12 @@ int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_params* par
 /* like vo_frame_features; desc: cap x 128 bytes = the descriptor values cv2 hands out as float32 */
 int vo_frame_features_sift(vo_ctx* ctx, int slot, float* kp_xy, float* kp_size, float* kp_angle, float* kp_response,
                            int32_t* kp_octave, uint8_t* desc /*cap x 128*/, int cap, int32_t* n_out);
+
+/* Parity seam of the SIFT matcher: rows[n][128] (values 0..255; 0 <= n <= vo_batch_kp_capacity) become slot `slot` as if they
+ * had been detected: descriptors, the matcher's int8 operand image and norms, the keypoint count, the flags (the norm-bound bit
+ * by the descriptor kernel's rule, the capacity bit clear), kp_xy = xy[n][2] (zeros when NULL), size / angle / response / octave
+ * zero.  Operand rows past n keep what an earlier frame left in the slot.  Needs vo_batch_configure_sift; synchronous. */
+int vo_stage_sift_rows(vo_ctx* ctx, int slot, const uint8_t* rows /*[n][128]*/, int n, const float* xy /*[n][2] or NULL*/);
 
 /* cv2.imread(filename) for a .jpg — /root/reference/src/visual_slam.py:346 (also triangulate_points_from_images.py:14-15,
  * feature_detection.py:5,10).  What cv2 does with such a file is libjpeg-turbo's default decompression: baseline Huffman

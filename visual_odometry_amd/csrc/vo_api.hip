@@ -814,6 +814,8 @@ extern "C" int vo_detect_after(vo_ctx* ctx, vo_ctx* other)
     return VO_OK;
 }
 
+#define SIFT_NORM_BOUND_MSG "a SIFT descriptor row broke the norm bound of the integer matcher (slot %d)"
+// VO_ERR_INVALID if a slot of the pair list `slots` holds a flagged SIFT row (flags bit 1), else
 // VO_WARN_CAPACITY if a keypoint / candidate list of one of the given slots overflowed (flags bit 0) — after a stream sync.
 // SIFT cuts an over-full frame at kp_cap in cv2's list order (x ascending after removeDuplicatedSorted): the keypoints at the
 // right edge of the image are the ones lost, so a caller should know before it trusts the pose of such a pair.
@@ -823,6 +825,11 @@ static int capacity_warning(vo_ctx* ctx, const int32_t* slots, int n, int first_
     if (!b.ready || b.max_frames <= 0) return VO_OK;
     std::vector<int> fl((size_t)b.max_frames);
     HIPCHK(hipMemcpy(fl.data(), b.flags, (size_t)b.max_frames * sizeof(int), hipMemcpyDeviceToHost));
+    // (SIFT, flags bit 1: a descriptor row of a pair's slot broke the norm bound under which k_nn_l2i8's integer order is cv2's
+    // float order — the matches of that pair cannot be trusted, which is an error and not a warning)
+    if (b.sift)
+        for (int i = 0; i < n; i++)
+            if (fl[(size_t)slots[i]] & 2) FAIL(VO_ERR_INVALID, SIFT_NORM_BOUND_MSG, (int)slots[i]);
     for (int i = 0; i < F; i++) if (fl[(size_t)first_slot + i] & 1) return VO_WARN_CAPACITY;
     for (int i = 0; i < n; i++) if (fl[(size_t)slots[i]] & 1) return VO_WARN_CAPACITY;
     return VO_OK;
@@ -999,8 +1006,8 @@ static int ensure_rng(vo_ctx* ctx, uint64_t seed)
 
 // vo_pair_opts.match_mode -> k_match_select mode.  BFMatcher(crossCheck=True) of OpenCV 4.x is the strict mutual
 // nearest neighbour (batchDistance compares the forward result too: `d < d0 && sidx[idx] == i`); the older
-// reverse-NN-only update rule stays selectable as match_mode 2.
-static int map_select_mode(int match_mode) { return match_mode == 0 ? 2 : match_mode == 2 ? 1 : 3; }
+// reverse-NN-only update rule stays selectable as match_mode 2; 3 is BFMatcher(crossCheck=False).match, every query's nearest.
+static int map_select_mode(int match_mode) { return match_mode == 0 ? 2 : match_mode == 2 ? 1 : match_mode == 3 ? 0 : 3; }
 
 static int run_pairs(vo_ctx* ctx, PairBuf pb, const uint8_t* desc, const uint8_t* desc_x, const float* kp_xy, const int* kp_count, int cap,
                      int P, int select_mode, double ratio, const RansacParams& rp, bool do_geometry, bool want_points, int descx_fp4,
@@ -1030,7 +1037,7 @@ static int pairs_enqueue(vo_ctx* ctx, const int32_t* pair_slots, int B, const do
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (!pair_slots || !K || !opts || !results || B < 0 || B > b.max_pairs) FAIL(VO_ERR_INVALID, "bad pair batch arguments");
-    if (opts->match_mode < 0 || opts->match_mode > 2) FAIL(VO_ERR_INVALID, "match_mode must be 0, 1 or 2");
+    if (opts->match_mode < 0 || opts->match_mode > 3) FAIL(VO_ERR_INVALID, "match_mode must be 0, 1, 2 or 3");
     if (!(opts->ransac_prob > 0 && opts->ransac_prob < 1)) FAIL(VO_ERR_INVALID, "ransac_prob must be in (0, 1)");
     for (int i = 0; i < 2 * B; i++)
         if (pair_slots[i] < 0 || pair_slots[i] >= b.max_frames) FAIL(VO_ERR_INVALID, "pair slot %d out of range", pair_slots[i]);
@@ -2350,8 +2357,39 @@ extern "C" int vo_frame_features_sift(vo_ctx* ctx, int slot, float* kp_xy, float
     const int rc = download_keypoints(ctx, {S.kp_xy, S.kp_size, S.kp_angle, S.kp_resp, S.kp_oct, S.desc, 128}, (size_t)slot * S.kp_cap, n,
                                       kp_xy, kp_size, kp_angle, kp_response, kp_octave, desc);
     if (rc) return rc;
-    if (flags & 2) FAIL(VO_ERR_INVALID, "a SIFT descriptor row broke the norm bound of the integer matcher (slot %d)", slot);
+    if (flags & 2) FAIL(VO_ERR_INVALID, SIFT_NORM_BOUND_MSG, slot);
     return warn;
+}
+
+// Parity seam of the SIFT matcher: n descriptor rows the caller chose become slot `slot`, written as if they had been detected —
+// desc, the int8 operand image and the norms through the function k_sb_descriptor ends in, kp_count = n, flags recomputed (bit 1
+// by the descriptor's rule, bit 0 clear), kp_xy = xy (zeros without), the other keypoint arrays zero for n rows.  The operand
+// image and the norms past row n keep whatever an earlier, fuller frame left there: k_nn_l2i8 has to mask them.
+extern "C" int vo_stage_sift_rows(vo_ctx* ctx, int slot, const uint8_t* rows, int n, const float* xy)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    SiftState& S = ctx->sift;
+    if (ctx->detector != 1 || !S.configured || !S.with_operands) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure_sift has not been called");
+    if (slot < 0 || slot >= S.max_frames) FAIL(VO_ERR_INVALID, "bad slot");
+    if (n < 0 || n > S.kp_cap || (n > 0 && !rows)) FAIL(VO_ERR_INVALID, "0 <= n <= kp_cap rows are needed");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));                        // an asynchronous detection may still be writing the slot; the staging buffer may be in use
+    if (n > 0) { int rc = ctx->staging.grow(ctx, (size_t)n * 128); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(S.flags + slot, 0, sizeof(int), s));
+    HIPCHK(hipMemcpyAsync(S.kp_count + slot, &n, sizeof(int), hipMemcpyHostToDevice, s));
+    if (n > 0) {
+        const size_t o = (size_t)slot * S.kp_cap;
+        HIPCHK(hipMemcpyAsync(ctx->staging.p, rows, (size_t)n * 128, hipMemcpyHostToDevice, s));
+        if (xy) HIPCHK(hipMemcpyAsync(S.kp_xy + o * 2, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+        else HIPCHK(hipMemsetAsync(S.kp_xy + o * 2, 0, (size_t)n * 2 * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(S.kp_size + o, 0, (size_t)n * sizeof(float), s)); HIPCHK(hipMemsetAsync(S.kp_angle + o, 0, (size_t)n * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(S.kp_resp + o, 0, (size_t)n * sizeof(float), s)); HIPCHK(hipMemsetAsync(S.kp_oct + o, 0, (size_t)n * sizeof(int), s));
+        launch_sb_pack_rows(s, ctx->staging.p, n, slot, S.kp_cap, S.desc, S.desc_x, S.cap_x, S.norms, S.flags);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(s));                        // (the caller's rows, xy and n have been read)
+    return VO_OK;
 }
 
 // (frames_upload_enqueue has checked the arguments)
@@ -2753,8 +2791,8 @@ static void forget_slam_maps(vo_ctx* ctx)
 // the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
 static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, int B_snap, const char* who)
 {
-    if (ctx->last.match_mode == 1)
-        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio matches two inliers can share a track root", who);
+    if (ctx->last.match_mode == 1 || ctx->last.match_mode == 3)
+        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio or nearest-neighbour matches two inliers can share a track root", who);
     if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
     if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
     if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);

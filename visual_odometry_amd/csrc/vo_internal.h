@@ -195,6 +195,8 @@ void launch_sb_sort_emit(hipStream_t s, const SiftKp* kps, int kp_cap, int* coun
                          SiftKp* out, int out_cap, int* out_count, int* out_flags, int cand_cap, int surv_cap, int F);
 void launch_sb_descriptor(hipStream_t s, const SiftGeom& P, const float* gauss, const SiftKp* kps, int kp_cap, const int* counts, const SiftExpTab& E,
                           uint8_t* desc, uint8_t* desc_x, int cap_x, int* norms, int* flags, int first_slot, int F, int waves);
+// n chosen descriptor rows (device, [n][128] values 0..255) into a slot exactly as launch_sb_descriptor leaves detected ones
+void launch_sb_pack_rows(hipStream_t s, const uint8_t* rows, int n, int slot, int kp_cap, uint8_t* desc, uint8_t* desc_x, int cap_x, int* norms, int* flags);
 void launch_sb_unpack(hipStream_t s, const SiftKp* kps, int kp_cap, const int* counts, int first_slot, float* kp_xy, float* kp_size, float* kp_angle,
                       float* kp_resp, int* kp_oct, int* kp_count, const int* fin_count, const int* fin_flags, int* flags, int F);
 // L2 nearest neighbours of integer-valued (0..255) 128-element descriptors on the matrix cores (match_kernels.hip)

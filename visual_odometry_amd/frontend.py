@@ -13,7 +13,7 @@ from . import _lib
 from .detector import make_params
 from .geometry import OPENCV_RNG_SEED
 
-MATCH_CROSSCHECK, MATCH_RATIO, MATCH_CROSSCHECK_LEGACY = 0, 1, 2
+MATCH_CROSSCHECK, MATCH_RATIO, MATCH_CROSSCHECK_LEGACY, MATCH_NEAREST = 0, 1, 2, 3
 
 
 class FrontEnd:
@@ -122,6 +122,24 @@ class FrontEnd:
         fn = c.lib.vo_frame_features_sift if sift else c.lib.vo_frame_features
         rc = c.check(fn(c.handle, int(slot), *kp.args()))
         return kp.result(rc, np.float32 if sift else None)
+
+    def set_sift_rows(self, slot, rows, xy=None):
+        """SIFT mode's parity seam (vo_stage_sift_rows): rows [n, 128] uint8 become the slot's descriptors as if they had been
+        detected (desc, the matcher's operand image and norms, count, flags); xy [n, 2] float32 pixel positions, zeros when None.
+        Operand rows past n keep what the slot held before."""
+        if self.detector != "sift":
+            raise ValueError("set_sift_rows needs detector='sift'")
+        r = np.asarray(rows)
+        if r.dtype != np.uint8 or r.ndim != 2 or r.shape[1] != 128:
+            raise ValueError("rows must be [n, 128] uint8")
+        r = np.ascontiguousarray(r)
+        p = None
+        if xy is not None:
+            p = np.ascontiguousarray(xy, dtype=np.float32)
+            if p.shape != (len(r), 2):
+                raise ValueError("xy must be [n, 2]")
+        c = self.ctx
+        c.check(c.lib.vo_stage_sift_rows(c.handle, int(slot), r.ctypes.data, len(r), _lib.ptr(p)))
 
     def make_opts(self, match_mode=MATCH_CROSSCHECK, ratio=0.75, prob=0.99, thresh=1.0, max_iters=1000,
                   seed=OPENCV_RNG_SEED, dist_thresh=50.0, want_points=False):
