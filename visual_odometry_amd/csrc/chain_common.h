@@ -38,7 +38,7 @@ __device__ __forceinline__ PairBuf chain_pairs_from(PairBuf pb, int first, int k
     return pb;
 }
 
-// the j-th inlier's match index: inliers are numbered in match order, as k_pose compacts them (and as X's columns run)
+// the j-th inlier's match index: inliers are numbered in match order, as k_pose_prepare compacts them (and as X's columns run)
 template <typename F>
 __device__ __forceinline__ void chain_for_each_inlier(const PairBuf& pb, int kp_cap, int p, int* s_w, F&& body)
 {

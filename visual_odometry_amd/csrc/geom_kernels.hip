@@ -1102,23 +1102,26 @@ __device__ __forceinline__ void cheirality2(const double* P0, const double* P, c
     neg = w < 0 && -q2 < dist && -z > 0 && -z < dist;
 }
 
-// 1024 threads: the inlier compaction uses the first 256; then the two rotations are tested in parallel, eight wavefronts
-// each, every triangulation serving both signs of t, so every SIMD holds four waves of independent f64 Jacobi sweeps
-// (the kernel is bound by the dependent-issue latency of those sweeps).
-__global__ __launch_bounds__(1024) void k_pose(PairBuf pb, int kp_cap, RansacParams rp)
+// recoverPose in three launches, none with a workgroup over 256 threads (a 1024-thread workgroup at 128 registers is the
+// register file of a whole CU and waits for an empty one):
+//  k_pose_prepare  one workgroup per pair: the in-order inlier compaction and decomposeEssentialMat (one wavefront) -> pb.pose_state
+//  k_pose          (pair, block of 256 inliers, rotation): one triangulation per thread serves both signs of t; wavefront
+//                  ballots, one integer atomicAdd per wave and candidate into the pair's four counts (bound by the
+//                  dependent-issue latency of the f64 Jacobi sweeps, so it wants many independent waves, not large groups)
+//  k_pose_finish   the best of the four counts in recoverPose's tie order -> R, t, n_good, n_inl (+ the single-call mask)
+__global__ __launch_bounds__(256) void k_pose_prepare(PairBuf pb, int kp_cap)
 {
     __shared__ int s_w[4];
-    __shared__ int s_good[4];
-    const int p = blockIdx.x, tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6, cand = threadIdx.x >> 8;
-    const bool first = cand == 0;                       // the 256 threads that compact and write
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     vo_pair_result* res = pb.res + p;
+    PoseState* ps = pb.pose_state + p;
     if (res->status != VO_OK) {
-        if (first && tid == 0) res->n_good = 0;
+        if (tid == 0) { res->n_good = 0; ps->active = 0; }
         return;
     }
     if (res->reserved != 1) {           // M == 5: stacked solutions; decomposeEssentialMat needs a single 3x3 matrix
-        __syncthreads();
-        if (first && tid == 0) { res->status = VO_ERR_AMBIGUOUS; res->n_good = 0; }
+        __syncthreads();                // every thread has read the status before it changes
+        if (tid == 0) { res->status = VO_ERR_AMBIGUOUS; res->n_good = 0; ps->active = 0; }
         return;
     }
     const int M = pb.m_count[p];
@@ -1126,14 +1129,13 @@ __global__ __launch_bounds__(1024) void k_pose(PairBuf pb, int kp_cap, RansacPar
     const uint8_t* mask = pb.mask + (size_t)p * kp_cap;
     double* in1 = pb.in1 + base2; double* in2 = pb.in2 + base2;
     double* ip1 = pb.ipx1 + base2; double* ip2 = pb.ipx2 + base2;
-    if (first && tid < 4) s_good[tid] = 0;
     int ninl = 0;
     for (int b = 0; b < M; b += 256) {
         const int i = b + tid;
-        const bool f = first && i < M && mask[i] != 0;
+        const bool f = i < M && mask[i] != 0;
         const unsigned long long bal = __ballot(f);
         __syncthreads();
-        if (first && lane == 0) s_w[wave] = __popcll(bal);
+        if (lane == 0) s_w[wave] = __popcll(bal);
         __syncthreads();
         int off = 0, tot = 0;
 #pragma unroll
@@ -1147,77 +1149,87 @@ __global__ __launch_bounds__(1024) void k_pose(PairBuf pb, int kp_cap, RansacPar
         }
         ninl += tot;
     }
-    __syncthreads();
-    // decomposeEssentialMat once (the first wavefront; sixteen waves doing it side by side took three times as long), shared through LDS
-    __shared__ double s_dec[21];
-    double R1[9], R2[9], tt[3];
-    if (threadIdx.x < 64) {
-        double E[9];
+    if (tid < 64) {                     // decomposeEssentialMat once, by the first wavefront
+        double E[9], R1[9], R2[9], tt[3];
 #pragma unroll
         for (int k = 0; k < 9; k++) E[k] = res->E[k];
         decompose_essential(E, R1, R2, tt);
-        if (threadIdx.x == 0) {
+        if (tid == 0) {
 #pragma unroll
-            for (int k = 0; k < 9; k++) { s_dec[k] = R1[k]; s_dec[9 + k] = R2[k]; }
+            for (int k = 0; k < 9; k++) { ps->R1[k] = R1[k]; ps->R2[k] = R2[k]; }
 #pragma unroll
-            for (int k = 0; k < 3; k++) s_dec[18 + k] = tt[k];
+            for (int k = 0; k < 3; k++) ps->t[k] = tt[k];
+#pragma unroll
+            for (int k = 0; k < 4; k++) ps->good[k] = 0;
+            ps->ninl = ninl; ps->active = 1;
         }
     }
-    __syncthreads();
+}
+
+// P = [R | t] of candidate rotation c (R1 / R2) from the pair's record
+__device__ __forceinline__ void pose_candidate(const PoseState* ps, int c, double* P)
+{
+    const double* Rc = c ? ps->R2 : ps->R1;
 #pragma unroll
-    for (int k = 0; k < 9; k++) { R1[k] = s_dec[k]; R2[k] = s_dec[9 + k]; }
+    for (int r = 0; r < 3; r++) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) tt[k] = s_dec[18 + k];
+        for (int k = 0; k < 3; k++) P[r * 4 + k] = Rc[r * 3 + k];
+        P[r * 4 + 3] = ps->t[r];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pose(PairBuf pb, int kp_cap, RansacParams rp)
+{
+    const int p = blockIdx.x, blk = blockIdx.y, c = blockIdx.z, lane = threadIdx.x & 63;      // candidates c (R, t) and c + 2 (R, -t), R = R1 / R2
+    PoseState* ps = pb.pose_state + p;
+    if (!ps->active) return;
+    const int ninl = ps->ninl, i = blk * 256 + threadIdx.x;
+    if (blk * 256 >= ninl) return;
+    const size_t base2 = (size_t)p * kp_cap * 2;
+    const double* in1 = pb.in1 + base2; const double* in2 = pb.in2 + base2;
     const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    {
-        const int c = threadIdx.x >> 9, t512 = threadIdx.x & 511;        // wave-uniform: candidates c (R, t) and c + 2 (R, -t), R = R1 / R2
-        const double* Rc = c ? R2 : R1;
-        double P[12];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) P[r * 4 + k] = Rc[r * 3 + k];
-            P[r * 4 + 3] = tt[r];
-        }
-        int gp = 0, gn = 0;
-        for (int b = 0; b < ninl; b += 512) {
-            const int i = b + t512;
-            bool mp = false, mn = false;
-            if (i < ninl) cheirality2(P0, P, in1 + 2 * i, in2 + 2 * i, rp.dist_thresh, mp, mn);
-            gp += __popcll(__ballot(mp)); gn += __popcll(__ballot(mn));
-        }
-        if (lane == 0 && gp) atomicAdd(&s_good[c], gp);
-        if (lane == 0 && gn) atomicAdd(&s_good[c + 2], gn);
-    }
-    __syncthreads();
-    const int g0 = s_good[0], g1 = s_good[1], g2 = s_good[2], g3 = s_good[3];
+    double P[12];
+    pose_candidate(ps, c, P);
+    bool mp = false, mn = false;
+    if (i < ninl) cheirality2(P0, P, in1 + 2 * i, in2 + 2 * i, rp.dist_thresh, mp, mn);
+    const int gp = __popcll(__ballot(mp)), gn = __popcll(__ballot(mn));
+    if (lane == 0 && gp) atomicAdd(&ps->good[c], gp);
+    if (lane == 0 && gn) atomicAdd(&ps->good[c + 2], gn);
+}
+
+// 64 threads per pair; 256 where the single-call mask is wanted (the winning candidate's test again)
+__global__ __launch_bounds__(256) void k_pose_finish(PairBuf pb, int kp_cap, RansacParams rp)
+{
+    const int p = blockIdx.x;
+    const PoseState* ps = pb.pose_state + p;
+    if (!ps->active) return;
+    vo_pair_result* res = pb.res + p;
+    const int ninl = ps->ninl;
+    const int g0 = ps->good[0], g1 = ps->good[1], g2 = ps->good[2], g3 = ps->good[3];
     int best;
     if (g0 >= g1 && g0 >= g2 && g0 >= g3) best = 0;
     else if (g1 >= g0 && g1 >= g2 && g1 >= g3) best = 1;
     else if (g2 >= g0 && g2 >= g1 && g2 >= g3) best = 2;
     else best = 3;
-    if (pb.pose_mask) {      // single-call cv2.recoverPose mask: the winning candidate's test again
-        const double* Rc = (best & 1) ? R2 : R1;
+    if (pb.pose_mask) {      // single-call cv2.recoverPose mask
+        const size_t base2 = (size_t)p * kp_cap * 2;
+        const double* in1 = pb.in1 + base2; const double* in2 = pb.in2 + base2;
+        const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
         double P[12];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) P[r * 4 + k] = Rc[r * 3 + k];
-            P[r * 4 + 3] = tt[r];
-        }
+        pose_candidate(ps, best & 1, P);
         uint8_t* pm = pb.pose_mask + (size_t)p * kp_cap;
-        for (int i = threadIdx.x; i < ninl; i += 1024) {
+        for (int i = threadIdx.x; i < ninl; i += blockDim.x) {
             bool mp, mn;
             cheirality2(P0, P, in1 + 2 * i, in2 + 2 * i, rp.dist_thresh, mp, mn);
             pm[i] = (best >= 2 ? mn : mp) ? 255 : 0;
         }
     }
-    if (first && tid == 0) {
-        const double* Rb = (best & 1) ? R2 : R1;
+    if (threadIdx.x == 0) {
+        const double* Rb = (best & 1) ? ps->R2 : ps->R1;
 #pragma unroll
         for (int k = 0; k < 9; k++) res->R[k] = Rb[k];
 #pragma unroll
-        for (int k = 0; k < 3; k++) res->t[k] = best >= 2 ? -tt[k] : tt[k];
+        for (int k = 0; k < 3; k++) res->t[k] = best >= 2 ? -ps->t[k] : ps->t[k];
         res->n_good = best == 0 ? g0 : best == 1 ? g1 : best == 2 ? g2 : g3;
         res->n_inl = ninl;
     }
@@ -1225,7 +1237,9 @@ __global__ __launch_bounds__(1024) void k_pose(PairBuf pb, int kp_cap, RansacPar
 
 void launch_pose(hipStream_t s, PairBuf pb, int kp_cap, int P, RansacParams rp)
 {
-    hipLaunchKernelGGL(k_pose, dim3(P), dim3(1024), 0, s, pb, kp_cap, rp);
+    hipLaunchKernelGGL(k_pose_prepare, dim3(P), dim3(256), 0, s, pb, kp_cap);
+    hipLaunchKernelGGL(k_pose, dim3(P, (kp_cap + 255) / 256, 2), dim3(256), 0, s, pb, kp_cap, rp);
+    hipLaunchKernelGGL(k_pose_finish, dim3(P), dim3(pb.pose_mask ? 256 : 64), 0, s, pb, kp_cap, rp);
 }
 
 // ------------------------------------------------------------------ single five-point sample (stage test)

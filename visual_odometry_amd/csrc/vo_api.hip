@@ -345,7 +345,7 @@ static hipError_t alloc_pairbuf(DevList& mem, PairBuf& pb, int P, int cap, bool 
     A_(slots, (size_t)P * 2); A_(nn_idx, pc * 2); A_(nn_dist, pc * 2); A_(nn_idx2, pc); A_(nn_dist2, pc);
     A_(m_q, pc); A_(m_t, pc); A_(m_d, pc); A_(m_count, (size_t)P);
     A_(px1, pc * 2); A_(px2, pc * 2); A_(xn1, pc * 2); A_(xn2, pc * 2);
-    A_(mask, pc); A_(models, (size_t)P * 64 * 90);
+    A_(mask, pc); A_(models, (size_t)P * 64 * 90); A_(pose_state, (size_t)P);
     A_(in1, pc * 2); A_(in2, pc * 2); A_(ipx1, pc * 2); A_(ipx2, pc * 2);
     A_(res, (size_t)P); A_(X, pc * 4);
     if (with_pose_mask) { A_(pose_mask, pc); }

@@ -96,6 +96,14 @@ struct Cv2Buf {
     int all_off[VO_MAX_LEVELS], all_cap[VO_MAX_LEVELS], all_total;
 };
 
+// recoverPose between its launches: k_pose_prepare writes it, k_pose adds the candidates' counts, k_pose_finish reads it
+struct PoseState {
+    int active;           // 0: the pair failed or is ambiguous (k_pose_prepare has written its result)
+    int ninl;
+    int good[4];          // points in front of both cameras: (R1, t), (R2, t), (R1, -t), (R2, -t)
+    double R1[9], R2[9], t[3];
+};
+
 // per-pair arrays (device), P = number of pairs
 struct PairBuf {
     int*      slots;      // [P][2]
@@ -114,6 +122,7 @@ struct PairBuf {
     double*   xn2;
     uint8_t*  mask;       // [P][kp_cap] E-RANSAC inlier mask
     double*   models;     // [P][64][90] workspace: five-point models of one RANSAC round
+    PoseState* pose_state; // [P]
     double*   in1;        // [P][kp_cap][2] normalised inliers
     double*   in2;
     double*   ipx1;       // [P][kp_cap][2] pixel inliers
