@@ -432,13 +432,15 @@ __global__ __launch_bounds__(CV_THREADS) void k_cv2_order(PyrGeom g, FrameFeat f
         const int nc = min(ff.cand_count[f * VO_MAX_LEVELS + l], lv.cand_cap);
         const uint32_t* cpos = ff.cand_pos + (size_t)f * g.cand_total + lv.cand_off;
         const float* cresp = ff.cand_resp + (size_t)f * g.cand_total + lv.cand_off;
+        // k_sel_rows<emit> left every kept winner's place in that list at its place in the all-winner list.  Places of winners
+        // it did not keep hold whatever was there before (an earlier frame's entry, or nothing ever written): an entry is
+        // believed only if the candidate it names is this very pixel (positions are unique within a list)
+        const uint32_t* all_cand = cb.all_cand + abase;
         for (int i = tid; i < n; i += CV_THREADS) {
-            const uint32_t pos = all_pos[a[i].y];
-            int lo = 0, hi = nc;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (cpos[mid] < pos) lo = mid + 1; else hi = mid; }
-            const bool hit = lo < nc && cpos[lo] == pos;
+            const uint32_t ai = a[i].y, pos = all_pos[ai], idx = all_cand[ai];
+            const bool hit = idx < (uint32_t)nc && cpos[idx] == pos;
             bad |= !hit;
-            a[i].x = __float_as_uint(hit ? cresp[lo] : -FLT_MAX);
+            a[i].x = __float_as_uint(hit ? cresp[idx] : -FLT_MAX);
         }
         __syncthreads();
         n = retain_best_cv2(a, n, lv.quota, lpos, rpos, s_a, s_l, s_r, sh);

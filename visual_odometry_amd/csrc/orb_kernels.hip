@@ -858,7 +858,8 @@ void launch_fast(hipStream_t s, const uint8_t* pyr, uint8_t* score, uint32_t* hi
 //     raster order with no sort, no workgroup barrier and no pass over a score map.
 // In cv2 keypoint order the same two launches also produce the raster-ordered list of ALL listed winners (the list cv2's
 // first retainBest permutes, cv2order_kernels.hip): its tile-row counts are sums of tile_count, its ranks come from a second
-// bitmap filled in the same pass over the tile lists, and the one write loop stores into both lists.
+// bitmap filled in the same pass over the tile lists, and the one write loop stores into both lists and into the map from
+// a kept winner's place in the one to its place in the other.
 
 // The n-th largest score of a (frame, level) from its histogram `h`, by one wavefront; every lane returns it.  1: fewer than
 // n winners, keep them all; 256: keep nothing.
@@ -888,12 +889,63 @@ __device__ __forceinline__ int sel_threshold(const PyrGeom& g, const LevelGeom& 
     return __builtin_amdgcn_readfirstlane(result);    // the same in every lane: hand it out as a scalar
 }
 
+// The flat walk over the winners of a row of FAST tiles (at most 64 tiles at a time: one tile count per lane).  The counts are
+// read with ONE vector load and scanned across the wave; entry e of the row then lives in the tile whose scanned range holds
+// e, found by comparing e with the scanned counts (read out of the scan's register lane by lane: scalar operands, no memory),
+// so every list load of the walk depends on the count load alone and any number of them can be in flight.  (The walk used to
+// go tile by tile: a wave-uniform count load, then the list load that depends on it, once per tile and pass.)
+__device__ __forceinline__ int sel_load_counts(const int* tile_count, size_t tile_first, int nt, int lane)
+{
+    // lanes behind the block's last tile repeat its count: nobody reads their part of the scan, and a load under a condition
+    // becomes a branch with a wait of its own
+    return min(tile_count[tile_first + min(lane, max(nt - 1, 0))], FT_LISTCAP);
+}
+__device__ __forceinline__ int sel_scan_counts(int cnt, int nt, int lane, int& total)
+{
+    int inc = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d, 64); if (lane >= d) inc += v; }
+    total = __builtin_amdgcn_readlane(inc, max(nt - 1, 0));
+    return inc;                                       // lane t < nt: the listed winners of tiles 0 .. t of the block
+}
+
+// Entries e, e + 64, .. of the walk (SEL_TRIPS of them: one trip each, all loads independent): the list word (0 behind the
+// row's last entry: no winner scores 0) and the tile it came from.  lists: the block's first tile list; inc: sel_scan_counts.
+// A lane without an entry loads the first word of the block instead (allocated whatever the counts are): a load under a
+// condition becomes a branch with its own wait, and the trips would queue up behind one another again.
+#define SEL_TRIPS 4
+__device__ __forceinline__ void sel_flat_entries(const uint32_t* lists, int nt, int inc, int e, int total,
+                                                 uint32_t (&ent)[SEL_TRIPS], int (&tile)[SEL_TRIPS])
+{
+    int st[SEL_TRIPS];
+#pragma unroll
+    for (int u = 0; u < SEL_TRIPS; u++) { tile[u] = 0; st[u] = 0; }
+    for (int k = 0; k + 1 < nt; k++) {                // the last tile's scanned count is the total: every e is below it
+        const int v = __builtin_amdgcn_readlane(inc, k);
+#pragma unroll
+        for (int u = 0; u < SEL_TRIPS; u++) if (e + 64 * u >= v) { tile[u] = k + 1; st[u] = v; }
+    }
+#pragma unroll
+    for (int u = 0; u < SEL_TRIPS; u++) ent[u] = lists[e + 64 * u < total ? tile[u] * FT_LISTCAP + (e + 64 * u - st[u]) : 0];
+#pragma unroll
+    for (int u = 0; u < SEL_TRIPS; u++) ent[u] = e + 64 * u < total ? ent[u] : 0u;
+}
+
+// the scanned word counts of k_sel_rows<emit>: a tile row has fewer than 65 536 pixels at any supported width, so 16 bits
+// would do (9.6 instead of 12.8 KB of LDS per wave at 1280 pixels); measured apart, see DESIGN section 10
+#ifdef SEL_PF16
+typedef uint16_t sel_pf_t;
+#else
+typedef uint32_t sel_pf_t;
+#endif
+
 // One wavefront per (frame, level, row of FAST tiles).  COUNT: how many listed winners reach the threshold (ALL: and how many
-// are listed at all).  EMIT: every kept winner of the tile row sets the bit of its pixel in a bitmap of the tile row
-// (FAST_TH rows x level width), the words' population counts are scanned, a winner's rank in (y, x) order is the number of
-// set bits in front of its own (keys are unique), and it is written at base + rank, base = the kept counts of the tile rows
-// above: canonical raster order without sorting, without comparing winners with one another and without touching a score
-// map.  ALL keeps a second bitmap with every listed winner and writes each one into the all-winner list as well.
+// are listed at all: the total of the scanned tile counts).  EMIT: every kept winner of the tile row sets the bit of its pixel
+// in a bitmap of the tile row (FAST_TH rows x level width), the words' population counts are scanned, a winner's rank in
+// (y, x) order is the number of set bits in front of its own (keys are unique), and it is written at base + rank, base = the
+// kept counts of the tile rows above: canonical raster order without sorting, without comparing winners with one another and
+// without touching a score map.  ALL keeps a second bitmap with every listed winner, writes each one into the all-winner list
+// as well, and leaves at a kept winner's place in the all-winner list its place in the candidate list (Cv2Buf::all_cand).
 template <bool EMIT, bool ALL>
 __device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* tile_count, const PyrGeom& g, const FrameFeat& ff,
                                          int* thr, int* chunk_count, const Cv2Buf& cb, uint32_t* s_sel)
@@ -907,21 +959,26 @@ __device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* t
     const size_t cslot = (size_t)f * g.sel_chunks_total + blockIdx.x;
     const size_t tile0 = (size_t)f * g.ftiles_total + lv.ftile_base + (size_t)chunk * lv.ftiles_x;
     if (!EMIT) {
+        int cnt = sel_load_counts(tile_count, tile0, min(lv.ftiles_x, 64), lane);        // in flight with the histogram
         const int T = sel_threshold(g, lv, ff.hist + ((size_t)f * VO_MAX_LEVELS + l) * 256, lane);
         int n = 0, na = 0;                            // wave-uniform: kept / listed winners of this tile row
         if (ALL || T <= 255)
-            for (int t = 0; t < lv.ftiles_x; t++) {
-                const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
-                const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
-                na += cnt;
-                for (int j0 = 0; j0 < cnt; j0 += 64) {
-                    const int j = j0 + lane;
-                    const uint32_t e = j < cnt ? lst[j] : 0u;
-                    n += (int)__popcll(__ballot(j < cnt && (int)(e >> 16) >= T));
+            for (int tb = 0; tb < lv.ftiles_x; tb += 64) {
+                const int nt = min(lv.ftiles_x - tb, 64);
+                if (tb) cnt = sel_load_counts(tile_count, tile0 + tb, nt, lane);
+                int total;
+                const int inc = sel_scan_counts(cnt, nt, lane, total);
+                const uint32_t* lists = tile_list + (tile0 + tb) * FT_LISTCAP;
+                na += total;
+                for (int e0 = 0; e0 < total; e0 += 64 * SEL_TRIPS) {
+                    uint32_t ent[SEL_TRIPS]; int tile[SEL_TRIPS];
+                    sel_flat_entries(lists, nt, inc, e0 + lane, total, ent, tile);
+#pragma unroll
+                    for (int u = 0; u < SEL_TRIPS; u++) n += (int)__popcll(__ballot((int)(ent[u] >> 16) >= T));      // T >= 1
                 }
             }
-        // every store of the wave comes after its last load: a store in front of them would turn the wave-uniform loads above
-        // (tile counts, list bases) from scalar into vector loads
+        // every store of the wave comes after its last load (a rule from the tile-by-tile walk, whose wave-uniform count loads
+        // a store in front of them turned from scalar into vector loads; kept: nothing here gains from an earlier store)
         if (lane != 0) return;
         chunk_count[cslot] = n;
         if (ALL) cb.chunk_count[cslot] = na;
@@ -938,42 +995,69 @@ __device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* t
         }
         return;
     }
+    const int nt0 = min(lv.ftiles_x, 64);
+    const int cnt0 = sel_load_counts(tile_count, tile0, nt0, lane);
     const int T = thr[f * VO_MAX_LEVELS + l];
     if (!ALL && T > 255) {
         if (chunk == 0 && lane == 0) ff.cand_count[f * VO_MAX_LEVELS + l] = 0;
         return;
     }
-    int base = 0, abase = 0;
+    int base = 0, abase = 0;                          // the tile rows above: these loads travel with the tile counts'
     {
         const size_t c0 = (size_t)f * g.sel_chunks_total + lv.sel_chunk_base;
         for (int c = lane; c < chunk; c += 64) { base += chunk_count[c0 + c]; if (ALL) abase += cb.chunk_count[c0 + c]; }
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { base += __shfl_xor(base, d, 64); if (ALL) abase += __shfl_xor(abase, d, 64); }
     }
-    // Rank of every winner in (y, x) order without comparing winners with one another and without a copy of them: a bit per
-    // pixel of the tile row is set for every kept winner (ALL: in a second bitmap for every listed winner), the words'
-    // population counts are scanned, and a winner's rank is the number of set bits in front of its own.  The tile lists are
-    // read twice (L2).
-    const int W32 = (lv.w + 31) >> 5, NW = FAST_TH * W32;
-    uint32_t* s_bm = s_sel;                           // [NW] kept bitmap, [NW] set bits in front of each word;
-    uint32_t* s_pf = s_sel + NW;
-    uint32_t* s_abm = s_sel + 2 * NW;                 // ALL: the same pair for every listed winner
-    uint32_t* s_apf = s_sel + 3 * NW;
-    for (int i = lane; i < NW; i += 64) { s_bm[i] = 0u; if (ALL) s_abm[i] = 0u; }
-    __syncthreads();
-    for (int t = 0; t < lv.ftiles_x; t++) {
-        const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
-        const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
-        for (int j = lane; j < cnt; j += 64) {
-            const uint32_t e = lst[j];
-            const bool kept = (int)(e >> 16) >= T;
-            if (ALL || kept) {
-                const uint32_t gx = (uint32_t)(lv.fox + t * FAST_TW) + (e & 255u), wd = ((e >> 8) & 255u) * W32 + (gx >> 5), bit = 1u << (gx & 31u);
-                if (ALL) atomicOr(&s_abm[wd], bit);
-                if (kept) atomicOr(&s_bm[wd], bit);
+    // A winner travels as score << 24 | row in the tile row << 16 | x in the level (0: none).  The first SEL_TRIPS entries of
+    // every lane (256 of the tile row: all of them at the flagship's densities) stay in registers from the bitmap pass to the
+    // write pass; only what a denser row lists beyond them is read a second time.
+    auto pack = [&](uint32_t e, int tile) -> uint32_t {
+        return e ? ((e & 0x00ff0000u) << 8) | ((e & 0x0000ff00u) << 8) | ((uint32_t)(lv.fox + tile * FAST_TW) + (e & 255u)) : 0u;
+    };
+    int total0;
+    const int inc0 = sel_scan_counts(cnt0, nt0, lane, total0);
+    uint32_t held[SEL_TRIPS];
+    {
+        uint32_t ent[SEL_TRIPS]; int tile[SEL_TRIPS];
+        sel_flat_entries(tile_list + tile0 * FT_LISTCAP, nt0, inc0, lane, total0, ent, tile);
+#pragma unroll
+        for (int u = 0; u < SEL_TRIPS; u++) held[u] = pack(ent[u], tile[u]);
+    }
+    auto beyond_held = [&](auto&& visit) {
+        for (int tb = 0; tb < lv.ftiles_x; tb += 64) {
+            const int nt = min(lv.ftiles_x - tb, 64);
+            int total = total0, inc = inc0;
+            if (tb) inc = sel_scan_counts(sel_load_counts(tile_count, tile0 + tb, nt, lane), nt, lane, total);
+            for (int e0 = tb ? 0 : 64 * SEL_TRIPS; e0 < total; e0 += 64 * SEL_TRIPS) {
+                uint32_t ent[SEL_TRIPS]; int tile[SEL_TRIPS];
+                sel_flat_entries(tile_list + (tile0 + tb) * FT_LISTCAP, nt, inc, e0 + lane, total, ent, tile);
+#pragma unroll
+                for (int u = 0; u < SEL_TRIPS; u++) visit(pack(ent[u], tb + tile[u]));
             }
         }
-    }
+    };
+    // Rank of every winner in (y, x) order without comparing winners with one another and without a copy of them: a bit per
+    // pixel of the tile row is set for every kept winner (ALL: in a second bitmap for every listed winner), the words'
+    // population counts are scanned, and a winner's rank is the number of set bits in front of its own.
+    const int W32 = (lv.w + 31) >> 5, NW = FAST_TH * W32;
+    uint32_t* s_bm = s_sel;                           // [NW] kept bitmap; ALL: [NW] the same for every listed winner;
+    uint32_t* s_abm = s_sel + NW;
+    sel_pf_t* s_pf = (sel_pf_t*)(s_sel + (ALL ? 2 : 1) * NW);         // [NW] set bits in front of each word (ALL: [NW] again)
+    sel_pf_t* s_apf = s_pf + NW;
+    for (int i = lane; i < NW; i += 64) { s_bm[i] = 0u; if (ALL) s_abm[i] = 0u; }
+    __syncthreads();
+    auto mark = [&](uint32_t p) {
+        const bool kept = (int)(p >> 24) >= T;        // T >= 1: never an empty entry
+        if (ALL ? p != 0u : kept) {
+            const uint32_t gx = p & 0xffffu, wd = ((p >> 16) & 255u) * W32 + (gx >> 5), bit = 1u << (gx & 31u);
+            if (ALL) atomicOr(&s_abm[wd], bit);
+            if (kept) atomicOr(&s_bm[wd], bit);
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < SEL_TRIPS; u++) mark(held[u]);
+    beyond_held(mark);
     __syncthreads();
     int n, na = 0;
     {
@@ -990,8 +1074,8 @@ __device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* t
         if (ALL) na = __shfl(ainc, 63, 64);
         int acc = inc - own, aacc = ainc - aown;
         for (int wd = w0; wd < w1; wd++) {
-            s_pf[wd] = (uint32_t)acc; acc += __popc(s_bm[wd]);
-            if (ALL) { s_apf[wd] = (uint32_t)aacc; aacc += __popc(s_abm[wd]); }
+            s_pf[wd] = (sel_pf_t)acc; acc += __popc(s_bm[wd]);
+            if (ALL) { s_apf[wd] = (sel_pf_t)aacc; aacc += __popc(s_abm[wd]); }
         }
     }
     __syncthreads();
@@ -1000,31 +1084,36 @@ __device__ __forceinline__ void sel_rows(const uint32_t* tile_list, const int* t
     float* out_resp = ff.cand_resp + (size_t)f * g.cand_total + lv.cand_off;
     uint32_t* all_pos = ALL ? cb.all_pos + (size_t)f * cb.all_total + cb.all_off[l] : nullptr;
     float* all_resp = ALL ? cb.all_resp + (size_t)f * cb.all_total + cb.all_off[l] : nullptr;
+    uint32_t* all_cand = ALL ? cb.all_cand + (size_t)f * cb.all_total + cb.all_off[l] : nullptr;
     const int all_cap = ALL ? cb.all_cap[l] : 0;
-    for (int t = 0; t < lv.ftiles_x; t++) {
-        const int cnt = min(tile_count[tile0 + t], FT_LISTCAP);
-        const uint32_t* lst = tile_list + (tile0 + t) * FT_LISTCAP;
-        for (int j = lane; j < cnt; j += 64) {
-            const uint32_t e = lst[j];
-            const bool kept = (int)(e >> 16) >= T;
-            if (ALL || kept) {
-                const uint32_t ly = (e >> 8) & 255u, gx = (uint32_t)(lv.fox + t * FAST_TW) + (e & 255u);
-                const int wd = (int)(ly * W32 + (gx >> 5));
-                const uint32_t below = (1u << (gx & 31u)) - 1u, key = (((uint32_t)(lv.foy + chunk * FAST_TH) + ly) << 16) | gx;
-                const float score = (float)(e >> 16);
-                if (ALL) {
-                    const int apos = abase + (int)s_apf[wd] + __popc(s_abm[wd] & below);
-                    if (apos < all_cap) { all_pos[apos] = key; all_resp[apos] = score; }
-                    else overflow = true;
+    auto emit = [&](uint32_t p) {
+        const bool kept = (int)(p >> 24) >= T;
+        if (ALL ? p != 0u : kept) {
+            const uint32_t ly = (p >> 16) & 255u, gx = p & 0xffffu;
+            const int wd = (int)(ly * W32 + (gx >> 5));
+            const uint32_t below = (1u << (gx & 31u)) - 1u, key = (((uint32_t)(lv.foy + chunk * FAST_TH) + ly) << 16) | gx;
+            const float score = (float)(p >> 24);
+            int pos = 0;
+            if (kept) {
+                pos = base + (int)s_pf[wd] + __popc(s_bm[wd] & below);
+                if (pos < lv.cand_cap) { out_pos[pos] = key; out_resp[pos] = score; }
+                else overflow = true;
+            }
+            if (ALL) {
+                const int apos = abase + (int)s_apf[wd] + __popc(s_abm[wd] & below);
+                if (apos < all_cap) {
+                    all_pos[apos] = key; all_resp[apos] = score;
+                    // where k_cv2_order finds this survivor's Harris response; the places of winners that are not kept are
+                    // never written: the reader checks what it finds there against the candidate list
+                    if (kept) all_cand[apos] = (uint32_t)pos;
                 }
-                if (kept) {
-                    const int pos = base + (int)s_pf[wd] + __popc(s_bm[wd] & below);
-                    if (pos < lv.cand_cap) { out_pos[pos] = key; out_resp[pos] = score; }
-                    else overflow = true;
-                }
+                else overflow = true;
             }
         }
-    }
+    };
+#pragma unroll
+    for (int u = 0; u < SEL_TRIPS; u++) emit(held[u]);
+    beyond_held(emit);
     if (overflow) atomicOr(&ff.flags[f], 1);
     if (chunk == nchunks - 1 && lane == 0) {
         ff.cand_count[f * VO_MAX_LEVELS + l] = min(base + n, lv.cand_cap);
@@ -1048,12 +1137,13 @@ __global__ __launch_bounds__(64) void k_sel_rows(const uint32_t* tile_list, cons
     sel_rows<EMIT, true>(tile_list, tile_count, g, ff, thr, chunk_count, cb, s_sel);
 }
 
-// LDS of k_sel_rows<emit>: per list one bit per pixel of a row of FAST tiles + the scanned word counts
+// LDS of k_sel_rows<emit>: per list one bit per pixel of a row of FAST tiles + the scanned word counts (the bitmaps first:
+// FAST_TH is even, so the 16-bit counts behind them stay aligned)
 static size_t sel_bitmap_bytes(const PyrGeom& g, bool all)
 {
     int w = 0;
     for (int l = 0; l < g.nlevels; l++) w = g.lv[l].w > w ? g.lv[l].w : w;
-    return (size_t)(all ? 4 : 2) * FAST_TH * ((w + 31) / 32) * 4;
+    return (size_t)(all ? 2 : 1) * FAST_TH * ((w + 31) / 32) * (sizeof(uint32_t) + sizeof(sel_pf_t));
 }
 
 // cb: the all-winner arrays of the cv2 keypoint order, offset to the first frame like ff; nullptr = canonical order

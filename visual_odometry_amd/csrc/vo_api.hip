@@ -372,7 +372,7 @@ static int alloc_cv2(vo_ctx* ctx)
     const size_t F = (size_t)ctx->max_frames, n = F * off;
     DevList& m = ctx->orb_mem;
     HIPCHK(m.alloc(&cb.all_pos, n)); HIPCHK(m.alloc(&cb.all_resp, n)); HIPCHK(m.alloc(&cb.work, n));
-    HIPCHK(m.alloc(&cb.lpos, n)); HIPCHK(m.alloc(&cb.rpos, n));
+    HIPCHK(m.alloc(&cb.all_cand, n)); HIPCHK(m.alloc(&cb.lpos, n)); HIPCHK(m.alloc(&cb.rpos, n));
     HIPCHK(m.alloc(&cb.all_count, F * VO_MAX_LEVELS));
     HIPCHK(m.alloc(&cb.chunk_count, F * (size_t)(g.sel_chunks_total + 1)));
     HIPCHK(hipMemset(cb.all_count, 0, F * VO_MAX_LEVELS * sizeof(int)));
@@ -721,7 +721,7 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
     if (cv2) {
         const size_t fo = (size_t)first_slot;
         cb.all_pos += fo * cb.all_total; cb.all_resp += fo * cb.all_total; cb.work += fo * cb.all_total;
-        cb.lpos += fo * cb.all_total; cb.rpos += fo * cb.all_total;
+        cb.all_cand += fo * cb.all_total; cb.lpos += fo * cb.all_total; cb.rpos += fo * cb.all_total;
         cb.all_count += fo * VO_MAX_LEVELS; cb.chunk_count += fo * g.sel_chunks_total;
     }
     {

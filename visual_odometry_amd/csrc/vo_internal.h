@@ -88,6 +88,7 @@ struct FrameFeat {
 struct Cv2Buf {
     uint32_t* all_pos;    // [F][all_total]  (y << 16 | x)
     float*    all_resp;   // [F][all_total]  FAST score
+    uint32_t* all_cand;   // [F][all_total]  kept winners only: index into the level's candidate list; the rest is never written
     int*      all_count;  // [F][VO_MAX_LEVELS]
     int*      chunk_count;// [F][sel_chunks_total + 1] listed winners per row of FAST tiles
     uint2*    work;       // [F][all_total]  (response bits, index into the all-list)
