@@ -6,7 +6,9 @@
     -> update_feature_mapper / estimate_current_camera_position (solvePnPRansac) / add_information_to_map   (:183-266, :153-180)
 
 Only the compressed file bytes cross PCIe; every stage after that reads what the previous one left in HBM.
-    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0]"""
+    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart]
+--restart: afterwards the complete map step (bundle adjustment, filter, camera limit) on the same resident pairs with restart=True — a lost frame
+starts a new map instead of ending the chain — and one track per segment, each in its own gauge."""
 import argparse
 import io
 import os
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--scale", type=float, default=0.3, help="the reference's scale_percent / 100")
     ap.add_argument("--detector", choices=["sift", "orb"], default="sift")
     ap.add_argument("--step", type=float, default=4.0, help="flight distance per frame (the camera is 30 units above the ground)")
+    ap.add_argument("--restart", action="store_true", help="also run slam_chain(restart=True) and print one track per segment")
     a = ap.parse_args()
     from PIL import Image
     n = a.frames
@@ -53,6 +56,13 @@ def main():
     for k in range(n - 1):
         print(f"pair {k}->{k + 1}: keypoints {res['n_kp1'][k]}/{res['n_kp2'][k]} matches {res['n_match'][k]} E-inliers {res['n_inl'][k]} | "
               f"PnP {out['n_inl'][k]}/{out['n_corr'][k]} status {out['status'][k]} map {out['n_map'][k]} | camera {k + 1} at {np.round(centres[k + 1], 2)}")
+    if a.restart:
+        out = fe.slam_chain(n - 1, K, restart=True)             # the map step; tracking lost -> a new map from the next usable pair
+        print(f"slam_chain(restart=True): status {out['status'].tolist()} segment {out['segment'].tolist()} cause {out['cause'].tolist()}")
+        for i, sg in enumerate(out["segments"]):
+            track = np.array([-P[:, :3].T @ P[:, 3] for P in sg["poses"]])
+            print(f"segment {i}: frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']}, camera centres in its own gauge:")
+            print(np.round(track, 2))
 
 
 if __name__ == "__main__":

@@ -446,7 +446,8 @@ int vo_bundle_adjust(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int n
  *     (map.py:188-232) — its observations go, then every point that is left with exactly ONE observation and that
  *     observation (a point with none is not counted by the defaultdict and stays); a removed point's feature id can
  *     receive a new point later.
- * A pair whose localisation fails does none of this and ends the chain [deviation, as vo_tracks_pnp_batch].
+ * A pair whose localisation fails does none of this and ends the chain [deviation, as vo_tracks_pnp_batch; vo_slam_chains_restart
+ * starts a new map instead].
  * ba_iterations = 0, filter_threshold <= 0 and max_cameras >= B + 1 give vo_tracks_pnp_batch's poses and counts, byte for
  * byte.  max_cameras + 1 must not exceed VO_BA_MAX_CAMERAS (VO_ERR_UNSUPPORTED); max_cameras >= 2.
  * poses_pnp: every camera as it entered the map (rows 0, 1: the initial pair; then solvePnPRansac's result); poses: every
@@ -501,6 +502,44 @@ int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/, const d
 int vo_slam_chains_map_size(vo_ctx* ctx, int seq, int which, int32_t* ncam, int32_t* npt, int32_t* nobs);
 int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, double* cam_pose /*[ncam][12]*/, uint8_t* cam_fixed,
                        int32_t* pt_feature /*[npt][2]*/, double* points /*[npt][3]*/, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy /*[nobs][2]*/);
+
+/* ------------------------------------------------------------------ ... that starts a new map after a lost frame and goes on
+ * vo_slam_chains ends a sequence at its first lost frame [deviation]; the reference prints "Failed to estimate the camera
+ * position" (src/visual_slam.py:254), adds no camera, and dies at the next frame on camera_dict[ip.frame1.id] (:167, inside the
+ * try of :258).  The recovery it names but never wires up: initialize_map begins with self.map.clean() (:43-45) and can be
+ * called again.  vo_slam_chains_restart is vo_slam_chains — same arguments, checks, options and outputs — with that
+ * recovery, decided and done on the device, per sequence, inside the step loop:
+ *   1 A pair that failed in vo_pairs_run (its own status != VO_OK) gets that status; the map is left as it stands and the
+ *     sequence is LOST until rule 3 applies.  No pair ever gets VO_ERR_NOT_CONFIGURED.
+ *   2 A pair whose own result is VO_OK but whose solvePnPRansac fails (VO_ERR_TOO_FEW, VO_ERR_NO_MODEL) starts a new
+ *     SEGMENT in the same step: the map is cleaned and initialize_map (:43-92) runs on this pair exactly as on pair 0 —
+ *     second camera = identity, first = (R^T, -R^T t), first fixed, second free; one point per E inlier under featureid1
+ *     with its two observations, in match order (:56-87); optimize_map (:90); no filter; the camera limit (:311).  Nothing
+ *     of the failed localisation reaches the new map.
+ *   3 A lost sequence that meets a pair whose own result is VO_OK starts a new segment from it, as in rule 2.
+ *   4 A new segment forgets the old one: the map's lists restart at length 0, no feature id of the old map stays in
+ *     mappointdict (:154-156), and every feature track (feature_mapper, :183-188; track_feature_back_in_time, :94-99) is cut
+ *     at the segment's first frame.
+ *   5 cam_frame and pt_feature[:, 0] stay indices along the sequence's whole chain; they do not restart with the segment.
+ *   6 The map a call leaves (vo_slam_chains_map, vo_slam_map) is the last segment's; if the sequence ends lost, the one it
+ *     had when it was lost.  snapshot_pair still counts along the sequence.
+ * A pair that starts a segment reports status, n_corr, n_inl, n_pts, n_obs, n_cam, chi2 and the bundle adjustment's counts
+ * as pair 0 of a chain does.  segment [B]: index of the pair's segment within its sequence, 0, 1, ... in order of start;
+ * -1 for a pair in no segment (rule 1).  cause [B]: 0 for a pair that continues its segment, or starts segment 0 at the
+ * sequence's first pair; otherwise, at a pair that starts a segment, the status that ended tracking before it — the
+ * solvePnPRansac status of rule 2, or the status of the FIRST failed pair of the lost stretch (rule 3).  seg_poses_pnp,
+ * seg_poses [B][12]: at a pair p that starts a segment, the segment's first camera (frame 1 of the pair) as it entered
+ * the map and as the map last held it; zeros elsewhere.  Row p + 1 of poses_pnp / poses holds the pair's second frame as
+ * always; row p belongs to the previous segment's gauge (or is zero) — except row 0 of a sequence whose first pair starts
+ * segment 0, which holds that first camera as it does in vo_slam_chains.  A sequence that never loses a frame gets
+ * vo_slam_chains' bytes in every output and map, segment = 0, cause = 0.
+ * Out of scope: joining segments into one gauge (tracking was lost: there is nothing to join them with), relocalisation
+ * against the old map, a restart form of vo_tracks_pnp_batch, ratio matches (VO_ERR_UNSUPPORTED as before). */
+int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/, const double* K, const vo_slam_opts* opts, int snapshot_seq,
+                           double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
+                           int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam /*[B] each*/,
+                           double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run /*[B] each*/,
+                           int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/);
 
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the

@@ -59,3 +59,45 @@ __device__ __forceinline__ void chain_for_each_inlier(const PairBuf& pb, int kp_
         base += tot;
     }
 }
+
+// [deviation, documented in DESIGN.md] the reference stores camera 1 = (I, 0) and camera 2 = (R, t) but its first points in
+// camera-2 coordinates (reconstruct_3d_points' default matrices) and lets the bundle adjustment reconcile them; without BA the
+// cameras are stored consistently with the points: camera 2 = (I, 0), camera 1 = (R^T, -R^T t).
+// initialize_map (:43-92) on pair p of the chain: p = 0 for k_chain_init, the pair that starts a new segment for
+// k_slam_restart_seqs — there the first camera goes to seg_poses[p], since pose row p belongs to the segment before (p > 0).
+__device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf cb, int p = 0)
+{
+    __shared__ int s_w[4];
+    const int tid = threadIdx.x;
+    const vo_pair_result& r = pb.res[p];
+    const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
+    if (r.status != VO_OK) {
+        if (tid == 0) { cb.alive[0] = 0; cb.status[p] = r.status; cb.n_corr[p] = 0; cb.n_inl[p] = 0; cb.n_map[p] = 0; }
+        return;
+    }
+    if (tid < 12) {
+        const int rr = tid / 4, c = tid % 4;
+        const double a = c < 3 ? r.R[c * 3 + rr] : -(r.R[0 * 3 + rr] * r.t[0] + r.R[1 * 3 + rr] * r.t[1] + r.R[2 * 3 + rr] * r.t[2]);
+        const double b = c < 3 ? (rr == c ? 1.0 : 0.0) : 0.0;
+        cb.cam[(size_t)f1 * 12 + tid] = a; cb.cam[(size_t)f2 * 12 + tid] = b;
+        if (p == 0) cb.poses[tid] = a;
+        if (cb.rs.st) cb.rs.seg_poses[(size_t)p * 12 + tid] = a;
+        cb.poses[(size_t)(p + 1) * 12 + tid] = b;
+    }
+    if (tid == 0) { cb.cam_ok[f1] = 1; cb.cam_ok[f2] = 1; cb.alive[0] = 1; cb.status[p] = VO_OK; cb.n_corr[p] = 0; cb.n_inl[p] = 0; }
+    const double* X = pb.X + (size_t)4 * p * kp_cap;         // the pair's [4][kp_cap], w = 1
+    __shared__ int s_added;
+    if (tid == 0) s_added = 0;
+    int added = 0;
+    chain_for_each_inlier(pb, kp_cap, p, s_w, [&](bool f, int i, int pos) {
+        if (!f) return;
+        const size_t k = chain_key(f1, pb.m_q[(size_t)p * kp_cap + i], kp_cap);   // TrackedPoint(match.point, ..., match.featureid1)  (:70-75)
+        cb.in_map[k] = 1;
+        for (int d = 0; d < 3; d++) cb.map_pt[3 * k + d] = X[(size_t)d * kp_cap + pos];
+        added++;
+    });
+    __syncthreads();
+    atomicAdd(&s_added, added);
+    __syncthreads();
+    if (tid == 0) { cb.map_count[0] = s_added; cb.n_map[p] = s_added; }
+}

@@ -1350,44 +1350,7 @@ void launch_chain_link(hipStream_t s, PairBuf pb, int kp_cap, int P, ChainBuf cb
     hipLaunchKernelGGL(k_chain_link, dim3((kp_cap + 255) / 256, P), dim3(256), 0, s, pb, kp_cap, cb);
 }
 
-// [deviation, documented in DESIGN.md] the reference stores camera 1 = (I, 0) and camera 2 = (R, t) but its first points in
-// camera-2 coordinates (reconstruct_3d_points' default matrices) and lets the bundle adjustment reconcile them; without BA the
-// cameras are stored consistently with the points: camera 2 = (I, 0), camera 1 = (R^T, -R^T t).
-__device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf cb)
-{
-    __shared__ int s_w[4];
-    const int tid = threadIdx.x;
-    const vo_pair_result& r = pb.res[0];
-    const int f1 = pb.slots[0], f2 = pb.slots[1];
-    if (r.status != VO_OK) {
-        if (tid == 0) { cb.alive[0] = 0; cb.status[0] = r.status; cb.n_corr[0] = 0; cb.n_inl[0] = 0; cb.n_map[0] = 0; }
-        return;
-    }
-    if (tid < 12) {
-        const int rr = tid / 4, c = tid % 4;
-        const double a = c < 3 ? r.R[c * 3 + rr] : -(r.R[0 * 3 + rr] * r.t[0] + r.R[1 * 3 + rr] * r.t[1] + r.R[2 * 3 + rr] * r.t[2]);
-        const double b = c < 3 ? (rr == c ? 1.0 : 0.0) : 0.0;
-        cb.cam[(size_t)f1 * 12 + tid] = a; cb.cam[(size_t)f2 * 12 + tid] = b;
-        cb.poses[tid] = a; cb.poses[12 + tid] = b;
-    }
-    if (tid == 0) { cb.cam_ok[f1] = 1; cb.cam_ok[f2] = 1; cb.alive[0] = 1; cb.status[0] = VO_OK; cb.n_corr[0] = 0; cb.n_inl[0] = 0; }
-    const double* X = pb.X;                                  // pair 0: [4][kp_cap], w = 1
-    __shared__ int s_added;
-    if (tid == 0) s_added = 0;
-    int added = 0;
-    chain_for_each_inlier(pb, kp_cap, 0, s_w, [&](bool f, int i, int pos) {
-        if (!f) return;
-        const size_t k = chain_key(f1, pb.m_q[i], kp_cap);   // TrackedPoint(match.point, ..., match.featureid1)  (:70-75)
-        cb.in_map[k] = 1;
-        for (int d = 0; d < 3; d++) cb.map_pt[3 * k + d] = X[(size_t)d * kp_cap + pos];
-        added++;
-    });
-    __syncthreads();
-    atomicAdd(&s_added, added);
-    __syncthreads();
-    if (tid == 0) { cb.map_count[0] = s_added; cb.n_map[0] = s_added; }
-}
-
+// (chain_init_wg: chain_common.h — k_slam_restart_seqs starts a new map with it)
 __global__ __launch_bounds__(256) void k_chain_init(PairBuf pb, int kp_cap, ChainBuf cb) { chain_init_wg(pb, kp_cap, cb); }
 
 // vo_slam_chains: workgroup = sequence (blockIdx.x); the sequence's pair 0 is pair `first` of the run
@@ -1416,12 +1379,29 @@ __device__ __forceinline__ void chain_gather_wg(PairBuf pb, int kp_cap, int p, i
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const vo_pair_result& r = pb.res[p];
     const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
+    if (cb.rs.st) {
+        // vo_slam_chains_restart: a failed pair keeps its status and leaves the sequence lost (the first such status is the cause
+        // the next segment reports); a lost sequence that meets a good pair starts a new map from it — no PnP, an initial step
+        const bool lost = !cb.alive[0];
+        if (r.status != VO_OK || lost) {
+            if (tid == 0) {
+                cb.off[0] = cb.obj0; cb.off[1] = cb.obj0; cb.n_corr[p] = 0;
+                if (r.status != VO_OK) {
+                    cb.status[p] = r.status; cb.alive[0] = 0; cb.rs.st[SEG_INIT] = 0;
+                    if (cb.rs.st[SEG_CAUSE] == 0) cb.rs.st[SEG_CAUSE] = r.status;
+                } else cb.rs.st[SEG_INIT] = 1;
+            }
+            return;
+        }
+        if (tid == 0) cb.rs.st[SEG_INIT] = 0;
+    }
     const bool ok = cb.alive[0] && r.status == VO_OK && cb.cam_ok[f1];
     if (!ok) {
         if (tid == 0) {
             cb.off[0] = cb.obj0; cb.off[1] = cb.obj0; cb.n_corr[p] = 0;
             cb.status[p] = !cb.alive[0] ? VO_ERR_NOT_CONFIGURED : r.status != VO_OK ? r.status : VO_ERR_INVALID;   // the chain broke earlier / this pair failed / no camera for frame 1
             cb.alive[0] = 0;
+            if (cb.rs.st && cb.rs.st[SEG_CAUSE] == 0) cb.rs.st[SEG_CAUSE] = cb.status[p];
         }
         return;
     }
@@ -1483,7 +1463,7 @@ void launch_chain_gather(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, Ch
 // cv2.triangulatePoints(K pose(frame1), K pose(frame2), pts1, pts2), X /= w, for every E inlier of the pair
 __device__ __forceinline__ void chain_triangulate_one(PairBuf pb, int kp_cap, int p, ChainBuf cb)
 {
-    if (!cb.alive[0]) return;
+    if (!cb.alive[0] || (cb.rs.st && cb.rs.st[SEG_INIT])) return;   // (an initial step takes pair 0's points, not these)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;    // keypoint tiles on x, in both kernels
     if (i >= pb.res[p].n_inl) return;
     double P1[12], P2[12], q[4];

@@ -1858,8 +1858,10 @@ void launch_rodrigues(hipStream_t s, const double* in, int in_is_matrix, double*
 // (one lane works; the workgroup's other lanes have returned)
 __device__ __forceinline__ void chain_pose_one(PairBuf pb, int p, const double* Kd, ChainBuf cb)
 {
+    if (cb.rs.st && cb.rs.st[SEG_INIT]) return;              // an initial step: k_pnp_ransac was handed an empty problem, nothing of it counts
     if (!cb.alive[0]) { cb.n_inl[p] = 0; for (int k = 0; k < 12; k++) cb.poses[(size_t)(p + 1) * 12 + k] = 0.0; return; }   // (status set by k_chain_gather)
     const int st = cb.pstatus[0];
+    if (cb.rs.st && st != VO_OK) { cb.rs.st[SEG_INIT] = 1; cb.rs.st[SEG_CAUSE] = st; return; }   // vo_slam_chains_restart: this pair starts a new map
     cb.n_inl[p] = cb.pninl[0];
     if (st != VO_OK) {                 // fewer than 4 correspondences (cv2 raises) or no model (retval False): the reference adds no camera
         cb.status[p] = st; cb.alive[0] = 0;

@@ -4,6 +4,7 @@
 //   Map.optimize_map's graph bookkeeping (src/map.py:121-164)                 -> k_slam_ba_prepare, then k_bundle_adjust (ba_kernels.hip)
 //   remove_observations_with_reprojection_errors_above_threshold (:46-70)     -> k_slam_filter
 //   limit_number_of_camera_in_map / remove_camera_from_map (:188-232, 299-318)-> k_slam_limit
+//   initialize_map's self.map.clean() (src/visual_slam.py:43-45), called again  -> k_slam_restart_seqs (vo_slam_chains_restart only)
 // One workgroup of 256 lanes per map and kernel: the walk is sequential by nature and the maps are the reference's size.
 // Every step is written once, as a workgroup-wide device function, and has two kernels: k_slam_* for the one chain of vo_slam_chain
 // (its buffers by value) and k_slam_*_seqs for the S independent sequences of vo_slam_chains — workgroup = sequence (blockIdx.x),
@@ -51,23 +52,25 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
     const int ncam0 = sb.m.cnt[0], npt0 = sb.m.cnt[1], nobs0 = sb.m.cnt[2];
-    const int newn = ncam0 + (p == 0 ? 2 : 1);
-    if (newn > sb.cam_cap || (p > 0 && ncam0 < 1)) return;   // cannot happen: the host sizes the list from max_cameras
+    const bool first = p == 0 || (cb.rs.st && cb.rs.st[SEG_INIT]);   // pair 0, or the pair that starts a new segment on a cleaned map
+    const int newn = ncam0 + (first ? 2 : 1);
+    if (newn > sb.cam_cap || (!first && ncam0 < 1)) return;   // cannot happen: the host sizes the list from max_cameras
     const int c1 = newn - 2, c2 = newn - 1;
-    if (p == 0) {
-        if (tid < 24) sb.m.cam_pose[tid] = cb.poses[tid];
-        if (tid < 2) sb.m.cam_frame[tid] = tid;
+    if (first) {
+        if (tid < 12) sb.m.cam_pose[tid] = p == 0 ? cb.poses[tid] : cb.rs.seg_poses[(size_t)p * 12 + tid];
+        else if (tid < 24) sb.m.cam_pose[tid] = cb.poses[(size_t)p * 12 + tid];
+        if (tid < 2) sb.m.cam_frame[tid] = p + tid;
     } else {
         if (tid < 12) sb.m.cam_pose[(size_t)c2 * 12 + tid] = cb.cam[(size_t)f2 * 12 + tid];
         if (tid == 0) sb.m.cam_frame[c2] = p + 1;
     }
     // initialize_map: first camera fixed, second free; afterwards freeze_nonlast_cameras: all fixed but the last free_cameras
-    for (int c = tid; c < newn; c += SLAM_THREADS) sb.m.cam_fixed[c] = p == 0 ? (c == 0) : (c < newn - free_cameras);
+    for (int c = tid; c < newn; c += SLAM_THREADS) sb.m.cam_fixed[c] = first ? (c == 0) : (c < newn - free_cameras);
 
     chain_for_each_inlier(pb, kp_cap, p, s_w, [&](bool f, int i, int pos) {
         if (!f) return;
         int d = -1;                                            // -1: new point, -2: skipped, >= 0: observation of that point
-        if (p > 0) {
+        if (!first) {
             const double x = cb.Xw[4 * (size_t)pos], y = cb.Xw[4 * (size_t)pos + 1], z = cb.Xw[4 * (size_t)pos + 2];
             if (!(sqrt(x * x + y * y + z * z) <= max_norm)) d = -2;   // np.linalg.norm(match.point) > 50: continue (NaN: kept out)
             else {
@@ -104,8 +107,8 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
         if (is_new && pi < sb.pt_cap && oi + 2 <= sb.obs_cap) {     // add_new_match_to_map / initialize_map's loop
             const size_t k = chain_key(f1, pb.m_q[(size_t)p * kp_cap + i], kp_cap);
             double X[3];
-            for (int a = 0; a < 3; a++) X[a] = p == 0 ? cb.map_pt[3 * k + a] : cb.Xw[4 * (size_t)ipos + a];
-            if (p > 0) { cb.in_map[k] = 1; for (int a = 0; a < 3; a++) cb.map_pt[3 * k + a] = X[a]; }
+            for (int a = 0; a < 3; a++) X[a] = first ? cb.map_pt[3 * k + a] : cb.Xw[4 * (size_t)ipos + a];
+            if (!first) { cb.in_map[k] = 1; for (int a = 0; a < 3; a++) cb.map_pt[3 * k + a] = X[a]; }
             sb.pt_of[k] = pi + 1;
             sb.m.pt_key[pi] = (int)k;
             for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)pi + a] = X[a];
@@ -298,6 +301,7 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_seqs(PairBuf pb, i
 {
     const SlamSeq& q = seqs[blockIdx.x];
     if (j >= q.count) return;
+    if (q.cb.rs.st && q.cb.rs.st[SEG_INIT]) threshold = 0.0;       // (a pair that starts a new segment is step 0 of it)
     slam_filter_wg(chain_pairs_from(pb, q.first, kp_cap), Kd, threshold, q.cb, q.sb);
 }
 
@@ -322,7 +326,13 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
     const int tid = threadIdx.x;
     int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
     if (cb.alive[0]) {
-        for (int k = tid; k < ncam * 12; k += SLAM_THREADS) sb.poses_last[(size_t)sb.m.cam_frame[k / 12] * 12 + k % 12] = sb.m.cam_pose[k];
+        // (vo_slam_chains_restart: pose row `first pair of the segment` belongs to the segment before; the first camera has its own)
+        const int seg0 = cb.rs.st ? cb.rs.st[SEG_FIRST] : -1;
+        for (int k = tid; k < ncam * 12; k += SLAM_THREADS) {
+            const int fr = sb.m.cam_frame[k / 12];
+            if (fr == seg0) cb.rs.seg_poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
+            if (fr != seg0 || fr == 0) sb.poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
+        }
         if (ncam > max_cameras) {
             for (int q = tid; q < npt; q += SLAM_THREADS) sb.tmp[q] = 0;
             __syncthreads();
@@ -379,4 +389,41 @@ void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_limit, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
+}
+
+// vo_slam_chains_restart, between k_chain_pose and k_chain_triangulate of every step: the end of the step's decision.  On an
+// initial step (SEG_INIT: k_chain_gather met a good pair while the sequence was lost, or k_chain_pose a failed solvePnPRansac)
+// the pair starts a new segment — initialize_map's self.map.clean() (src/visual_slam.py:43-45): the lists restart at length 0
+// and every point's feature id leaves mappointdict (pt_of, in_map); the first frame's feature_mapper row is cleared, so no
+// track reaches behind the segment; then initialize_map on this pair (chain_init_wg).  Every pair gets its segment here.
+__device__ __forceinline__ void slam_restart_wg(PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb)
+{
+    const int tid = threadIdx.x;
+    const int init = cb.rs.st[SEG_INIT], nseg = cb.rs.st[SEG_COUNT], cause = cb.rs.st[SEG_CAUSE], npt = sb.m.cnt[1];
+    if (!init) {
+        if (tid == 0) cb.rs.segment[p] = cb.alive[0] ? nseg - 1 : -1;
+        return;
+    }
+    for (int q = tid; q < npt; q += SLAM_THREADS) { const int key = sb.m.pt_key[q]; sb.pt_of[key] = 0; cb.in_map[key] = 0; }
+    unsigned long long* row = cb.parent + chain_key(pb.slots[2 * p], 0, kp_cap);
+    for (int i = tid; i < kp_cap; i += SLAM_THREADS) row[i] = 0;
+    __syncthreads();                                           // every lane has read the state words and the old point count
+    if (tid == 0) {
+        sb.m.cnt[0] = 0; sb.m.cnt[1] = 0; sb.m.cnt[2] = 0;
+        cb.rs.st[SEG_FIRST] = p; cb.rs.st[SEG_COUNT] = nseg + 1; cb.rs.st[SEG_CAUSE] = 0;
+        cb.rs.segment[p] = nseg; cb.rs.cause[p] = cause;
+    }
+    chain_init_wg(pb, kp_cap, cb, p);
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_restart_seqs(PairBuf pb, int kp_cap, int j, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_restart_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, q.cb, q.sb);
+}
+
+void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, seqs);
 }

@@ -2979,14 +2979,20 @@ static int chains_check(vo_ctx* ctx, int S, const int32_t* seq_off, int* F_out, 
     return VO_OK;
 }
 
-extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
-                              double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
-                              int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
+// The walk of vo_slam_chains and vo_slam_chains_restart.  restart: a sequence that loses tracking starts a new map from the next
+// usable pair, decided on the device (k_chain_gather, k_chain_pose) and done by k_slam_restart_seqs, which joins every step;
+// step 0 is then an initial step like any other (k_chain_gather meets a sequence that has no map yet).  Without it the stream
+// carries vo_slam_chains' launches and nothing else.
+static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
+                           double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
+                           int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                           int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
 {
     if (!ctx) return VO_ERR_INVALID;
     forget_slam_maps(ctx);
     if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
         FAIL(VO_ERR_INVALID, "bad arguments");
+    if (restart && (!segment || !cause || !seg_poses_pnp || !seg_poses)) FAIL(VO_ERR_INVALID, "bad arguments");
     int F, cap;
     int rc = chains_check(ctx, S, seq_off, &F, &cap); if (rc) return rc;
     const bool snap_on = o->snapshot_pair >= 0;        // (snapshot_seq is ignored otherwise)
@@ -3031,7 +3037,10 @@ extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const 
     sc.take(&dchi2, (size_t)2 * maxB * S); sc.take(&dit, (size_t)maxB * S); sc.take(&dtr, (size_t)maxB * S);
     sc.take(&snap_mem, snap_on ? slam_map_carve(nullptr, cm, snap_np, snap_no, &snap) : 0);
     sc.take(&dseq, S);
+    sc.take(&cb.rs.st, restart ? (size_t)4 * S : 0); sc.take(&cb.rs.segment, restart ? B : 0); sc.take(&cb.rs.cause, restart ? B : 0);
+    sc.take(&cb.rs.seg_poses, restart ? (size_t)B * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? (size_t)B * 12 : 0);
     rc = sc.place(ctx); if (rc) return rc;
+    if (!restart) cb.rs = RestartBuf{};
     if (snap_on) slam_map_carve(snap_mem, cm, snap_np, snap_no, &snap);
     D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
     D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
@@ -3047,6 +3056,7 @@ extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const 
         c.off += 2 * q; c.rvec += 3 * q; c.tvec += 3 * q; c.pmask += (size_t)q * cap; c.pninl += q; c.pstatus += q; c.P1 += 12 * q; c.P2 += 12 * q;
         c.obj += (size_t)q * cap * 3; c.img += (size_t)q * cap * 2; c.Xw += (size_t)q * cap * 4; c.alive += q; c.map_count += q;
         c.n_corr += first; c.n_inl += first; c.status += first; c.n_map += first; c.poses += (size_t)(first + q) * 12;
+        if (restart) { c.rs.st += 4 * q; c.rs.segment += first; c.rs.cause += first; c.rs.seg_poses += (size_t)first * 12; c.rs.seg_poses_last += (size_t)first * 12; }
         SlamBuf& m = e.sb; m = sb;
         m.base = at;
         m.cam_cap = (int)cm; m.pt_cap = (Bq + 1) * cap; m.obs_cap = 2 * Bq * cap; m.pair_cap = (int)(pair0[q + 1] - pair0[q]);
@@ -3073,7 +3083,17 @@ extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const 
     for (int j = 0; j < maxB; j++) {
         {
             StageTimer t(ctx, ST_MISC);
-            if (j == 0) launch_chain_init_seqs(s, ctx->pb, cap, dseq, S);
+            if (restart) {
+                launch_chain_gather_seqs(s, ctx->pb, cap, j, F, dseq, S);
+                if (j > 0) {
+                    launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                      ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
+                    launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
+                }
+                launch_slam_restart_seqs(s, ctx->pb, cap, j, dseq, S);
+                if (j > 0) launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
+            }
+            else if (j == 0) launch_chain_init_seqs(s, ctx->pb, cap, dseq, S);
             else {
                 launch_chain_gather_seqs(s, ctx->pb, cap, j, F, dseq, S);
                 launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
@@ -3110,6 +3130,12 @@ extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const 
     HIPCHK(hipMemcpyAsync(hchi.data(), dchi2, hchi.size() * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(hit.data(), dit, hit.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(htr.data(), dtr, htr.size() * 4, hipMemcpyDeviceToHost, s));
+    if (restart) {
+        HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
     for (int q = 0; q < S; q++)                                       // [step][sequence] -> the pair's position in the run
@@ -3127,6 +3153,23 @@ extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const 
     ctx->last.seq_map = std::move(maps);
     if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
     return VO_OK;
+}
+
+extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
+                              double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
+                              int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
+{
+    return slam_chains_run(ctx, false, S, seq_off, K, o, snapshot_seq, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2,
+                           ba_iterations_run, ba_trials_run, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
+                                      double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
+                                      int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                                      int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
+{
+    return slam_chains_run(ctx, true, S, seq_off, K, o, snapshot_seq, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2,
+                           ba_iterations_run, ba_trials_run, segment, cause, seg_poses_pnp, seg_poses);
 }
 
 static const LastRun::Map* slam_chains_map_of(vo_ctx* ctx, int seq, int which)

@@ -266,6 +266,18 @@ void launch_reprojection(hipStream_t s, const double* poses, int ncam, const dou
                          const int* obs_pt, const double* obs_xy, int nobs, const double* Kd, double threshold,
                          double* sqerr, uint8_t* keep, int* bad);
 // ---- the localisation chain on resident pair results (geom_kernels.hip / pnp_kernels.hip): src/visual_slam.py:183-266
+// vo_slam_chains_restart: what a sequence needs to start a new map after a lost frame (initialize_map's self.map.clean(),
+// src/visual_slam.py:43-45).  st == nullptr everywhere else: the chain stops at the first lost frame.
+enum { SEG_INIT = 0,    // 1: this step is an initial step of the sequence — its pair starts a segment as pair 0 starts a chain
+       SEG_FIRST = 1,   // the pair that started the current segment
+       SEG_COUNT = 2,    // segments started so far
+       SEG_CAUSE = 3 }; // the status that ended tracking and has not been reported yet (0: none)
+struct RestartBuf {
+    int*    st;                   // [4] the SEG_* words
+    int*    segment; int* cause;  // [P] per-pair outputs
+    double* seg_poses;            // [P][12] at a pair that starts a segment: its first camera as it entered the map
+    double* seg_poses_last;       // [P][12] ... as the map last held it
+};
 struct ChainBuf {
     unsigned long long* parent;   // [F][cap] packed feature_mapper entry (k_track_link's format), 0 = no entry
     uint8_t* in_map;              // [F][cap] 1: a map point is keyed by this feature id (mappointdict)
@@ -285,6 +297,7 @@ struct ChainBuf {
     int*     n_corr; int* n_inl; int* status; int* n_map;   // [P] per-pair outputs
     double*  poses;               // [P + 1][12]: camera of pair 0's first frame, then of every pair's second frame
     int*     map_count;           // [1]
+    RestartBuf rs;                // vo_slam_chains_restart only
 };
 void launch_chain_link(hipStream_t s, PairBuf pb, int kp_cap, int P, ChainBuf cb);
 void launch_chain_init(hipStream_t s, PairBuf pb, int kp_cap, ChainBuf cb);
@@ -355,5 +368,6 @@ void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, d
 void launch_slam_ba_prepare_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S);
 void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);
 void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S);
+void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

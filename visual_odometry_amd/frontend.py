@@ -192,14 +192,17 @@ class FrontEnd:
         return dict(poses=poses.reshape(B + 1, 3, 4), n_corr=nc, n_inl=ni, status=st, n_map=nm)
 
     def slam_chain(self, n_pairs, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
-                   ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+                   ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None, restart=False):
         """The reference's complete per-frame map step on resident data (vo_slam_chain; src/visual_slam.py:190-266 and :311):
         localize_chain's walk with the Observation list, freeze_nonlast_cameras, Map.optimize_map, the reprojection filter and
         limit_number_of_camera_in_map after every pair, on a map that stays on the device.  snapshot=(pair, stage): keep a copy
         of the map as it was at that pair after stage 1 add_information_to_map, 2 bundle adjustment, 3 filter, 4 camera limit
         (slam_map(1)).  Returns dict(poses_pnp, poses [n_pairs + 1, 3, 4], n_corr, n_inl, status, n_pts, n_obs, n_cam,
-        ba_iterations, ba_trials [n_pairs], chi2 [n_pairs, 2])."""
+        ba_iterations, ba_trials [n_pairs], chi2 [n_pairs, 2]).  restart=True: slam_chains(restart=True) on this one chain."""
         B = int(n_pairs)
+        if restart:
+            return self.slam_chains([B], K, iterations, reproj_err, confidence, seed, max_point_norm, ba_iterations, huber_delta, free_cameras,
+                                    filter_threshold, max_cameras, None if snapshot is None else (0, snapshot[0], snapshot[1]), restart=True)[0]
         K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
         sp, ss = (-1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]))
         opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
@@ -213,13 +216,20 @@ class FrontEnd:
         return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, **i32)
 
     def slam_chains(self, seq_lengths, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
-                    ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+                    ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None, restart=False):
         """slam_chain for several independent sequences in one call (vo_slam_chains), one workgroup per sequence and kernel: the
         pairs of the latest run_pairs(..., want_points=True) are sequence 0's seq_lengths[0] pairs, then sequence 1's, ...; every
         sequence is a chain of its own and no frame slot belongs to two of them (a frame two sequences share is uploaded into
         two slots).  snapshot=(seq, pair, stage), the pair counted along that sequence (slam_map(1, seq=seq)).  Returns a list of
         len(seq_lengths) dicts, each what slam_chain returns for that sequence alone: a pair that cannot be localised ends its
-        own sequence only."""
+        own sequence only.
+        restart=True (vo_slam_chains_restart): a sequence that loses tracking — a pair that failed in run_pairs, or a solvePnPRansac
+        that finds no camera — starts a new map from the next usable pair and goes on, on the device (initialize_map's
+        self.map.clean(), src/visual_slam.py:43-45).  A failed pair keeps its own status and none gets VO_ERR_NOT_CONFIGURED.  Every
+        dict then also has segment [n_pairs] (index of the pair's segment, -1: in none), cause [n_pairs] (at a pair that starts a
+        segment after a loss: the status that ended tracking) and segments, a list of dict(first_pair, n_pairs, poses_pnp, poses
+        [n + 1, 3, 4]): each segment's trajectory in its own gauge (split_segments).  Segments are not joined, and the map a
+        sequence leaves is its last segment's; cam_frame and pt_feature[:, 0] still count along the whole sequence."""
         off = sequence_offsets(seq_lengths, len(self._keep[0]) if getattr(self, "_keep", None) else 0)
         S, B = len(off) - 1, int(off[-1])
         K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
@@ -229,9 +239,19 @@ class FrontEnd:
         flat = dict(poses_pnp=np.zeros((B + S, 12)), poses=np.zeros((B + S, 12)), chi2=np.zeros((B, 2)))
         flat.update({k: np.zeros(B, np.int32) for k in ("n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")})
         c = self.ctx
-        c.check(c.lib.vo_slam_chains(c.handle, S, off.ctypes.data, K.ctypes.data, C.addressof(opts), sq, *[flat[k].ctypes.data for k in (
-            "poses_pnp", "poses", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "chi2", "ba_iterations", "ba_trials")]))
-        return split_sequences(flat, off)
+        keys = ("poses_pnp", "poses", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "chi2", "ba_iterations", "ba_trials")
+        if not restart:
+            c.check(c.lib.vo_slam_chains(c.handle, S, off.ctypes.data, K.ctypes.data, C.addressof(opts), sq, *[flat[k].ctypes.data for k in keys]))
+            return split_sequences(flat, off)
+        seg = dict(segment=np.zeros(B, np.int32), cause=np.zeros(B, np.int32), seg_poses_pnp=np.zeros((B, 12)), seg_poses=np.zeros((B, 12)))
+        c.check(c.lib.vo_slam_chains_restart(c.handle, S, off.ctypes.data, K.ctypes.data, C.addressof(opts), sq, *[flat[k].ctypes.data for k in keys],
+                                             *[seg[k].ctypes.data for k in ("segment", "cause", "seg_poses_pnp", "seg_poses")]))
+        out = split_sequences(flat, off)
+        for s, d in enumerate(out):
+            a, b = int(off[s]), int(off[s + 1])
+            d["segment"] = seg["segment"][a:b].copy(); d["cause"] = seg["cause"][a:b].copy()
+            d["segments"] = split_segments(d["segment"], d["poses_pnp"], d["poses"], seg["seg_poses_pnp"][a:b], seg["seg_poses"][a:b])
+        return out
 
     def slam_map(self, which=0, seq=0):
         """The map of the latest slam_chain, or of sequence `seq` of the latest slam_chains: which=0 at the end of the chain, 1 the
@@ -327,6 +347,35 @@ def split_sequences(flat, seq_off):
         a, b = int(seq_off[s]), int(seq_off[s + 1])
         d = {k: (v[a + s:b + s + 1].reshape(-1, 3, 4) if k in ("poses_pnp", "poses") else v[a:b]).copy() for k, v in flat.items()}
         out.append(d)
+    return out
+
+
+def split_segments(segment, poses_pnp, poses, seg_poses_pnp, seg_poses):
+    """One sequence's outputs of vo_slam_chains_restart -> its segments, in order of start: a list of dict(first_pair, n_pairs,
+    poses_pnp, poses [n_pairs + 1, 3, 4]) (copies).  segment [P]: the pairs' segment indices (-1: in none; a segment's pairs are
+    consecutive); poses_pnp / poses [P + 1, ...]: row p + 1 = the second frame of pair p; seg_poses_pnp / seg_poses [P, ...]: at the
+    pair that starts a segment, the segment's first camera.  That row goes in front of the rows of the segment's pairs, so every
+    segment is a trajectory in one gauge: camera k of the segment is row k, the frame first_pair + k of the sequence."""
+    segment = np.asarray(segment).ravel()
+    pp, pl = np.asarray(poses_pnp, np.float64).reshape(-1, 3, 4), np.asarray(poses, np.float64).reshape(-1, 3, 4)
+    sp, sl = np.asarray(seg_poses_pnp, np.float64).reshape(-1, 3, 4), np.asarray(seg_poses, np.float64).reshape(-1, 3, 4)
+    P = len(segment)
+    if len(pp) != P + 1 or len(pl) != P + 1 or len(sp) != P or len(sl) != P:
+        raise ValueError(f"{P} pairs take {P + 1} pose rows and {P} first-camera rows, got {len(pp)}, {len(pl)}, {len(sp)}, {len(sl)}")
+    out, p = [], 0
+    while p < P:
+        k = int(segment[p])
+        if k < 0:
+            p += 1
+            continue
+        if k != len(out):
+            raise ValueError(f"pair {p} is in segment {k}, expected segment {len(out)}: segments are numbered in order of start")
+        n = 1
+        while p + n < P and segment[p + n] == k:
+            n += 1
+        out.append(dict(first_pair=p, n_pairs=n, poses_pnp=np.concatenate([sp[p:p + 1], pp[p + 1:p + n + 1]]),
+                        poses=np.concatenate([sl[p:p + 1], pl[p + 1:p + n + 1]])))
+        p += n
     return out
 
 
