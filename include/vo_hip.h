@@ -57,8 +57,28 @@ int         vo_version(void);
 
 /* ------------------------------------------------------------------ single-call operators */
 
+/* IMAGE LAYOUT CONTRACT — holds for every entry point that takes row_stride, frame_stride or dst_stride (all in bytes):
+ * vo_orb_detect_and_compute, vo_stage_pyramid / _fast_scores / _blur, vo_frames_upload[_async], vo_frames_upload_color,
+ * vo_frames_ingest, vo_sift_detect_and_compute, vo_resize_linear, vo_resize_area.  A cv::Mat ROI (data, step) or a decoder's
+ * padded frame is passed as it is.
+ *   Source image: h rows of w * channels bytes, row y at img + y * row_stride.  The library reads only inside
+ *     [img, img + (h - 1) * row_stride + w * channels): nothing after the last row's last pixel, nothing before img.
+ *   Source frame stack: frame f at frames + f * frame_stride; for F frames the span is
+ *     (F - 1) * frame_stride + (h - 1) * row_stride + w * channels bytes.  The bytes between rows and between frames may be read
+ *     (a padded stack crosses the bus in one copy) but never influence a result.
+ *   Destination (vo_resize_*): dh rows at dst_stride; the library writes only the dw * channels bytes of each row — never the
+ *     bytes between the rows, never anything after the last row's last pixel.
+ *   Alignment: none is required of img, dst or any stride; rows may start on any byte.
+ *   row_stride < w * channels and dst_stride < dw * channels are refused (VO_ERR_INVALID).
+ *   frame_stride: vo_frames_upload[_async] take any value, 0 included (every slot then receives frame 0; the single-image calls
+ *     pass 0 themselves); vo_frames_upload_color (channels 3, 4) and vo_frames_ingest require
+ *     frame_stride >= (h - 1) * row_stride + w * channels — a frame may begin where the previous one's last row ends, which a
+ *     stack of ROI views needs — and refuse less (VO_ERR_INVALID).
+ * Tight strides (row_stride == w * channels, frame_stride == h * row_stride, dst_stride == dw * channels) are the fast path: one
+ * linear copy each way. */
+
 /* detector.detectAndCompute(image, None) — src/frame_generator.py:25-26, src/image_and_keypoints.py:46.
- * img: h x w x channels u8 (1 = gray, 3 = BGR, 4 = BGRA).  Outputs hold up to cap keypoints in
+ * img: h x w x channels u8 (1 = gray, 3 = BGR, 4 = BGRA), laid out as the contract above says.  Outputs hold up to cap keypoints in
  * canonical order (octave, y, x); desc is cap x 32 bytes. */
 int vo_orb_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h, int w, int channels, int row_stride,
                               const vo_orb_params* params,
@@ -143,7 +163,7 @@ int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, const double
 /* ------------------------------------------------------------------ stage outputs (parity tests) */
 /* size in bytes of the packed outputs below (sum over levels of w_l * h_l); < 0 for invalid parameters */
 int64_t vo_packed_pyramid_bytes(int h, int w, const vo_orb_params* params);
-/* gray + INTER_LINEAR_EXACT pyramid, levels packed tightly one after the other */
+/* gray + INTER_LINEAR_EXACT pyramid, levels packed tightly one after the other (img: see IMAGE LAYOUT CONTRACT; out_packed is dense) */
 int vo_stage_pyramid(vo_ctx* ctx, const uint8_t* img, int h, int w, int channels, int row_stride,
                      const vo_orb_params* params, uint8_t* out_packed);
 /* per level: FAST-9/16 score after 3x3 NMS (dense, packed like the pyramid) and the 7x7 blur */
@@ -183,12 +203,13 @@ typedef struct {
 /* (re)allocate device buffers for frames of h x w, up to max_frames resident frames and
  * max_pairs pairs per vo_pair_batch call */
 int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params* params, int max_frames, int max_pairs);
-/* copy F gray frames (u8, row_stride/frame_stride in bytes) into slots [first_slot, first_slot+F) */
+/* copy F gray frames (u8, row_stride / frame_stride in bytes: IMAGE LAYOUT CONTRACT, any frame_stride) into slots [first_slot, first_slot+F) */
 int vo_frames_upload(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 /* Same, enqueue only: `frames` should be page-locked (vo_host_alloc) and must stay unchanged until vo_sync(ctx).
  * Streaming drivers alternate two contexts: one's upload (DMA) runs beside the other's kernels. */
 int vo_frames_upload_async(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
-/* same for BGR (channels 3) / BGRA (4) frames: converted to gray on the device (cv2's BGR2GRAY, as ORB does) */
+/* same for BGR (channels 3) / BGRA (4) frames: converted to gray on the device (cv2's BGR2GRAY, as ORB does); strides per the
+ * IMAGE LAYOUT CONTRACT, frame_stride >= (h - 1) * row_stride + w * channels */
 int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F, int channels, int row_stride,
                            int64_t frame_stride, int first_slot);
 /* detect + describe slots [first_slot, first_slot+F); results stay on the device */
@@ -286,11 +307,12 @@ int vo_solve_pnp_ransac_batch(vo_ctx* ctx, const double* obj, const double* img,
 int vo_rodrigues(vo_ctx* ctx, const double* in, int in_is_matrix, double* out);
 
 /* cv2.resize(img, dim) with the default INTER_LINEAR, 8-bit, 1 / 3 / 4 channels — src/visual_slam.py:346-352
- * (cv2.imread's JPEG decode stays on the host).  Host image in, host image out. */
+ * (cv2.imread's JPEG decode stays on the host).  Host image in, host image out; src and dst may be strided
+ * views (IMAGE LAYOUT CONTRACT): the padding of dst is never written. */
 int vo_resize_linear(vo_ctx* ctx, const uint8_t* src, int sh, int sw, int channels, int row_stride,
                      uint8_t* dst, int dh, int dw, int dst_stride);
 /* cv2.resize(img, dim, interpolation=cv2.INTER_AREA) for an image that shrinks on both axes —
- * src/image_and_keypoints.py:42 (ImageAndKeypoints.set_image).  VO_ERR_UNSUPPORTED: enlargement. */
+ * src/image_and_keypoints.py:42 (ImageAndKeypoints.set_image).  VO_ERR_UNSUPPORTED: enlargement.  Layout as vo_resize_linear. */
 int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, int channels, int row_stride,
                    uint8_t* dst, int dh, int dw, int dst_stride);
 /* cv2.SIFT_create(...).detectAndCompute(img, None) — the reference's LIVE detector, /root/reference/src/visual_slam.py:17
@@ -301,7 +323,8 @@ int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, int channels
  * KeyPointsFilter::retainBest (libstdc++'s nth_element + partition, ties kept) as cv2 does.  VO_WARN_CAPACITY: more than `cap` keypoints (n_out = the number found).
  * Keypoints and descriptors are bit-identical to the ORACLE (oracle/voo_sift.c: the scalar code paths of sift.simd.hpp, one rounding
  * per operation); a cv2 wheel accumulates the descriptor norm in SIMD lanes, so its uint8 bins can differ by +-1 where value * scale
- * lands near .5 — parity with cv2 itself is unpinned (tests/test_cv2_crosscheck.py carries the tolerance for machines that have cv2). */
+ * lands near .5 — parity with cv2 itself is unpinned (tests/test_cv2_crosscheck.py carries the tolerance for machines that have cv2).
+ * img / row_stride: IMAGE LAYOUT CONTRACT (above vo_orb_detect_and_compute). */
 typedef struct {
     int32_t nfeatures;            /* 0 = keep every keypoint */
     int32_t n_octave_layers;      /* 3 */
@@ -355,7 +378,8 @@ int vo_frames_ingest_jpeg(vo_ctx* ctx, const uint8_t* blob, const int64_t* offse
 
 /* The batched form of the same step: F full-resolution host frames are resized on the device to the configured
  * (w, h), converted to gray as ORB does, and become level 0 of slots first_slot..; resized_out (optional, host,
- * [F][h][w][channels] dense) receives the resized frames (the reference keeps them as Frame.image). */
+ * [F][h][w][channels] dense) receives the resized frames (the reference keeps them as Frame.image).  Source strides per the
+ * IMAGE LAYOUT CONTRACT, frame_stride >= (sh - 1) * row_stride + sw * channels. */
 int vo_frames_ingest(vo_ctx* ctx, const uint8_t* frames, int F, int sh, int sw, int channels, int row_stride,
                      int64_t frame_stride, int first_slot, uint8_t* resized_out);
 

@@ -604,6 +604,14 @@ static Batch batch(const vo_ctx* ctx)
             ctx->ff.kp_count, ctx->ff.flags, nullptr, ctx->descx_fp4, ctx->pyr + g.lv[0].off, g.lv[0].stride, (size_t)g.frame_bytes};
 }
 
+// Bytes from the first byte of a host image (stack) to the last byte of its last row: n frames at frame_stride, h rows of row_bytes
+// at row_stride.  The layout contract of include/vo_hip.h: no host-to-device image copy reads beyond it.  Tight strides
+// (row_stride == row_bytes, frame_stride == h * row_stride) give n * h * row_bytes.
+static inline size_t image_span(int n, int64_t frame_stride, int h, int row_stride, int row_bytes)
+{
+    return (size_t)(n - 1) * (size_t)frame_stride + (size_t)(h - 1) * (size_t)row_stride + (size_t)row_bytes;
+}
+
 // cvtColor(BGR2GRAY) (or a copy of gray input) of n device frames into slots first_slot..
 static void gray_into_slots(vo_ctx* ctx, hipStream_t s, const uint8_t* src, int channels, int row_stride, int64_t frame_stride, int first_slot, int n)
 {
@@ -672,7 +680,7 @@ extern "C" int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F,
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (channels != 3 && channels != 4) FAIL(VO_ERR_INVALID, "channels must be 1, 3 or 4");
     if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
-    if (row_stride < b.w * channels || frame_stride < (int64_t)row_stride * b.h) FAIL(VO_ERR_INVALID, "strides too small");
+    if (row_stride < b.w * channels || frame_stride < (int64_t)image_span(1, 0, b.h, row_stride, b.w * channels)) FAIL(VO_ERR_INVALID, "strides too small");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t per = (size_t)frame_stride;
@@ -683,7 +691,8 @@ extern "C" int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F,
     int rc = ctx->staging.grow(ctx, per * chunk); if (rc) return rc;
     for (int f0 = 0; f0 < F; f0 += chunk) {
         const int n = F - f0 < chunk ? F - f0 : chunk;
-        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, image_span(n, frame_stride, b.h, row_stride, b.w * channels),
+                              hipMemcpyHostToDevice, ctx->stream));
         StageTimer t(ctx, ST_GRAY);
         gray_into_slots(ctx, ctx->stream, ctx->staging.p, channels, row_stride, frame_stride, first_slot + f0, n);
     }
@@ -892,7 +901,7 @@ static int load_single(vo_ctx* ctx, const uint8_t* img, int h, int w, int channe
     int rc = vo_batch_configure(ctx, h, w, params, mf, mp);
     if (rc) return rc;
     if (channels == 1) return vo_frames_upload(ctx, img, 1, row_stride, 0, 0);
-    const size_t bytes = (size_t)row_stride * h;
+    const size_t bytes = image_span(1, 0, h, row_stride, w * channels);
     rc = ctx->staging.grow(ctx, bytes); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ctx->staging.p, img, bytes, hipMemcpyHostToDevice, ctx->stream));
     { StageTimer t(ctx, ST_GRAY); launch_gray(ctx->stream, ctx->staging.p, channels, row_stride, 0, ctx->pyr, ctx->g, 1); }
@@ -1935,6 +1944,15 @@ static int ingest_tables(vo_ctx* ctx, int sw, int sh, int dw, int dh, const int*
     return VO_OK;
 }
 
+// The resized image (ctx->ingest_out, rows at dst_stride) back to the caller's dst, enqueued: a dense destination is one linear copy;
+// otherwise a 2-D copy of the rows' row_bytes, so that the bytes between the caller's rows and after its last row are never written.
+static int resized_to_host(vo_ctx* ctx, uint8_t* dst, int dh, int row_bytes, int dst_stride)
+{
+    if (dst_stride == row_bytes) HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out.p, (size_t)dst_stride * dh, hipMemcpyDeviceToHost, ctx->stream));
+    else HIPCHK(hipMemcpy2DAsync(dst, (size_t)dst_stride, ctx->ingest_out.p, (size_t)dst_stride, (size_t)row_bytes, (size_t)dh, hipMemcpyDeviceToHost, ctx->stream));
+    return VO_OK;
+}
+
 extern "C" int vo_resize_linear(vo_ctx* ctx, const uint8_t* src, int sh, int sw, int channels, int row_stride,
                                 uint8_t* dst, int dh, int dw, int dst_stride)
 {
@@ -1942,7 +1960,7 @@ extern "C" int vo_resize_linear(vo_ctx* ctx, const uint8_t* src, int sh, int sw,
     if (!src || !dst || sh < 1 || sw < 1 || dh < 1 || dw < 1 || (channels != 1 && channels != 3 && channels != 4) ||
         row_stride < sw * channels || dst_stride < dw * channels) FAIL(VO_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t sbytes = (size_t)row_stride * sh, dbytes = (size_t)dst_stride * dh;
+    const size_t sbytes = image_span(1, 0, sh, row_stride, sw * channels), dbytes = (size_t)dst_stride * dh;
     int rc = ctx->staging.grow(ctx, sbytes); if (rc) return rc;
     rc = ctx->ingest_out.grow(ctx, dbytes); if (rc) return rc;
     const int* xofs; const void* xa; const int* yofs; const void* yb;
@@ -1952,7 +1970,7 @@ extern "C" int vo_resize_linear(vo_ctx* ctx, const uint8_t* src, int sh, int sw,
     { StageTimer t(ctx, ST_MISC); launch_resize_linear(s, ctx->staging.p, sw, sh, channels, row_stride, 0, ctx->ingest_out.p, dw, dh, dst_stride, 0,
                                                        xofs, xa, yofs, yb, sw == 2 * dw && sh == 2 * dh, 1); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out.p, dbytes, hipMemcpyDeviceToHost, s));
+    rc = resized_to_host(ctx, dst, dh, dw * channels, dst_stride); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
     return VO_OK;
@@ -1988,7 +2006,7 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
         row_stride < sw * channels || dst_stride < dw * channels) FAIL(VO_ERR_INVALID, "bad arguments");
     if (dw > sw || dh > sh) FAIL(VO_ERR_UNSUPPORTED, "INTER_AREA enlargement (a bilinear variant in OpenCV) is not built");
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t sbytes = (size_t)row_stride * sh, dbytes = (size_t)dst_stride * dh;
+    const size_t sbytes = image_span(1, 0, sh, row_stride, sw * channels), dbytes = (size_t)dst_stride * dh;
     int rc = ctx->staging.grow(ctx, sbytes); if (rc) return rc;
     rc = ctx->ingest_out.grow(ctx, dbytes); if (rc) return rc;
     const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);     // as resize() forms them
@@ -2015,7 +2033,7 @@ extern "C" int vo_resize_area(vo_ctx* ctx, const uint8_t* src, int sh, int sw, i
     { StageTimer t(ctx, ST_MISC); launch_resize_area(s, ctx->staging.p, channels, row_stride, ctx->ingest_out.p, dw, dh, dst_stride,
                                                      fast ? isx : 0, fast ? isy : 0, xsi, xal, xst, ysi, yal, yst); }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst, ctx->ingest_out.p, dbytes, hipMemcpyDeviceToHost, s));
+    rc = resized_to_host(ctx, dst, dh, dw * channels, dst_stride); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));                                 // also keeps the host tables alive until copied
     if (ctx->prof) prof_collect(ctx);
     return VO_OK;
@@ -2070,7 +2088,7 @@ extern "C" int vo_frames_ingest(vo_ctx* ctx, const uint8_t* frames, int F, int s
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
     if (sh < 1 || sw < 1 || (channels != 1 && channels != 3 && channels != 4) || row_stride < sw * channels ||
-        frame_stride < (int64_t)row_stride * sh) FAIL(VO_ERR_INVALID, "bad source geometry");
+        frame_stride < (int64_t)image_span(1, 0, sh, row_stride, sw * channels)) FAIL(VO_ERR_INVALID, "bad source geometry");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t per = (size_t)frame_stride, dper = (size_t)b.w * b.h * channels;
@@ -2079,7 +2097,7 @@ extern "C" int vo_frames_ingest(vo_ctx* ctx, const uint8_t* frames, int F, int s
     hipStream_t s = ctx->stream;
     for (int f0 = 0; f0 < F; f0 += (int)chunk) {
         const int n = F - f0 < (int)chunk ? F - f0 : (int)chunk;
-        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, per * n, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->staging.p, frames + (size_t)f0 * per, image_span(n, frame_stride, sh, row_stride, sw * channels), hipMemcpyHostToDevice, s));
         rc = ingest_from_device(ctx, ctx->staging.p, n, sh, sw, channels, row_stride, (int64_t)per, first_slot + f0,
                                 resized_out ? resized_out + (size_t)f0 * dper : nullptr);
         if (rc) return rc;
@@ -2247,7 +2265,7 @@ extern "C" int vo_sift_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h
     int rc = sift_setup(ctx, S, h, w, p, 1, 1 << 18, 1 << 18, (int)cand_all, 1 << 18, 1, false);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    const size_t img_bytes = (size_t)row_stride * h;
+    const size_t img_bytes = image_span(1, 0, h, row_stride, w * channels);
     rc = ctx->sift_img.grow(ctx, img_bytes); if (rc) return rc;
     HIPCHK(hipMemcpyAsync(ctx->sift_img.p, img, img_bytes, hipMemcpyHostToDevice, s));
     rc = sift_detect_enqueue(ctx, S, ctx->sift_img.p, channels, row_stride, 0, 1); if (rc) return rc;
