@@ -6,9 +6,12 @@
     -> update_feature_mapper / estimate_current_camera_position (solvePnPRansac) / add_information_to_map   (:183-266, :153-180)
 
 Only the compressed file bytes cross PCIe; every stage after that reads what the previous one left in HBM.
-    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart]
+    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart] [--stream N]
 --restart: afterwards the complete map step (bundle adjustment, filter, camera limit) on the same resident pairs with restart=True — a lost frame
-starts a new map instead of ending the chain — and one track per segment, each in its own gauge."""
+starts a new map instead of ending the chain — and one track per segment, each in its own gauge.
+--stream N: the same files once more in chunks of N pairs through slam_stream on a front end with only N + 1 frame slots — the map stays on the
+device between the chunks, every chunk's files are decoded into the slots the chunk before freed — and the track, which is the track of one
+slam_chain call on all the files."""
 import argparse
 import io
 import os
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--detector", choices=["sift", "orb"], default="sift")
     ap.add_argument("--step", type=float, default=4.0, help="flight distance per frame (the camera is 30 units above the ground)")
     ap.add_argument("--restart", action="store_true", help="also run slam_chain(restart=True) and print one track per segment")
+    ap.add_argument("--stream", type=int, default=0, metavar="N", help="also walk the files in chunks of N pairs through slam_stream (N + 1 frame slots)")
     a = ap.parse_args()
     from PIL import Image
     n = a.frames
@@ -63,6 +67,26 @@ def main():
             track = np.array([-P[:, :3].T @ P[:, 3] for P in sg["poses"]])
             print(f"segment {i}: frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']}, camera centres in its own gauge:")
             print(np.round(track, 2))
+    if a.stream > 0:
+        whole = fe.slam_chain(n - 1, K)                         # the yardstick: one call, every frame resident
+        N = min(a.stream, n - 1)
+        st = FrontEnd(dh, dw, max_frames=N + 1, max_pairs=N, detector=a.detector, **({} if a.detector == "sift" else {"nfeatures": 2000}))
+        slots, last = list(range(N + 1)), np.zeros((n, 3, 4))
+        for c, first in enumerate(range(0, n - 1, N)):          # the chunk's pairs: first .. first + b - 1
+            b = min(N, n - 1 - first)
+            new = slots[:b + 1] if c == 0 else slots[1:b + 1]
+            for slot, f in zip(new, range(first + (c > 0), first + b + 1)):
+                st.ingest_jpeg([files[f]], first_slot=slot); st.detect(slot, 1)
+            st.run_pairs([[slots[j], slots[j + 1]] for j in range(b)], K, want_points=True)
+            out = st.slam_stream(b, K, resume=c > 0, total_pairs=n - 1)
+            for f, T in zip(out["carried_frame"], out["carried_poses"]):
+                last[f] = T                                     # a camera of an earlier chunk, as the map last held it in this call
+            last[first:first + b + 1] = out["poses"]
+            print(f"slam_stream chunk {c}: frames {first}..{first + b} in slots {slots[:b + 1]}, status {out['status'].tolist()}, map {out['n_cam'][-1]} cameras "
+                  f"{out['n_pts'][-1]} points, carried {out['carried_frame'].tolist()}")
+            slots = [slots[b]] + slots[:b] + slots[b + 1:]      # the chunk's last frame stays where it is
+        print(f"slam_stream in chunks of {N}: the track {'equals' if np.array_equal(last, whole['poses']) else 'DIFFERS from'} slam_chain's on all {n} files; camera centres:")
+        print(np.round(np.array([-P[:, :3].T @ P[:, 3] for P in last]), 2))
 
 
 if __name__ == "__main__":

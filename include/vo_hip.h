@@ -500,6 +500,48 @@ int vo_slam_map_size(vo_ctx* ctx, int which, int32_t* ncam, int32_t* npt, int32_
 int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[ncam][12]*/, uint8_t* cam_fixed, int32_t* pt_feature /*[npt][2]*/,
                 double* points /*[npt][3]*/, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy /*[nobs][2]*/);
 
+/* ------------------------------------------------------------------ the map step as a stream: one map, one call after another
+ * vo_slam_chain walks one vo_pairs_run and its map ends with the call; a flight longer than one batch configuration needs the
+ * reference's loop (src/visual_slam.py:333-374): one frame after another into one Map.  vo_slam_stream keeps the map, the
+ * feature tracks and every table of the walk on the device when it returns, in an allocation of their own, and a later call
+ * continues them.  The contract: the calls of a stream together compute the bytes one vo_slam_chain on the whole flight computes.
+ *   resume = 0 starts a stream: vo_slam_chain's checks, options, statuses and bytes (outputs and vo_slam_map) for the B pairs of
+ *     the most recent vo_pairs_run; n_carried = 0.  total_pairs >= B is the number of pairs the whole stream may reach; it sizes
+ *     the lists once — points (total_pairs + 1) kp_cap; observations 2 kp_cap min(max_cameras + 1, total_pairs) (a camera is
+ *     observed at most kp_cap times as a pair's second frame and kp_cap times as the next pair's first) and the bundle
+ *     adjustment's pair list from those — and nothing grows afterwards.  A call that would pass it: VO_ERR_INVALID.
+ *   Between calls the caller uploads and detects the next frames into any slot EXCEPT THE ANCHOR SLOT, the slot of the stream's
+ *     last frame, and runs vo_pairs_run (want_points) on a chain that starts there.  vo_pairs_run forgets vo_slam_map's host
+ *     copies as always but leaves the stream alone.  An upload, ingest, detection or vo_stage_sift_rows that covers the anchor
+ *     slot ends the stream's use: a later resume = 1 is refused.
+ *   resume = 1 continues it.  VO_ERR_INVALID, with the stream left as it is: no live stream; its last call ended lost; pair 0
+ *     does not start at the anchor slot; the run is not a chain of distinct frames (so no later pair can use the anchor slot);
+ *     K or an option other than snapshot_pair / snapshot_stage differs from the stream's; total_pairs would be passed.  Ratio
+ *     matches: VO_ERR_UNSUPPORTED.  total_pairs is ignored.  Every pair is a p >= 1 step of vo_slam_chain; there is no
+ *     initial step.  Per-pair outputs [B] as vo_slam_chain reports them for these pairs; snapshot_pair counts along the call.
+ *     poses_pnp row 0: the anchor camera as it entered the map (the previous call's last row), rows 1 .. B the new cameras; poses:
+ *     the same cameras as the map last held them, in this call or when evicted.  The cameras the map held at the start of the
+ *     call beside the anchor have no row: carried_frame [n_carried] names them by their index along the whole stream, in map
+ *     order, and carried_poses [n_carried][12] is each one as the map last held it during this call (with free_cameras >= 3
+ *     one of them is still free in the first steps and changes).  Both arrays take max_cameras rows.
+ *   vo_slam_map after either: cam_frame and pt_feature[:, 0] count along the whole stream.
+ * The stream ends — its memory is released — with vo_destroy, vo_batch_configure[_sift], a new resume = 0 or any vo_slam_chain*
+ * call.  A call that ends lost (vo_slam_chain's stop rule and statuses) leaves the map for vo_slam_map; it cannot be continued.
+ * How a call continues a map whose frames have lost their slots (k_slam_carry): the slot-keyed tables get two ghost rows behind
+ * the max_frames slots (max_frames + 2 < 2^20).  Every keypoint of the anchor frame whose track root lies in an older frame is
+ * linked to an entry of a ghost row that takes over the root's map point — also a root that owns no point, which must stay
+ * one: the reference finds nothing under it at every later frame and adds a new point each time (:139-146).  A point no track
+ * can reach any more keeps its place in the lists and in the bundle adjustment, as in the reference, but has no key.
+ * [deviation] none in the results; the per-call cost is one k_slam_carry launch and the download of the map for vo_slam_map.
+ * Out of scope: several sequences per call, restart (vo_slam_chains_restart) inside a stream, pruning points that have lost every
+ * observation (the reference keeps them: the lists and k_bundle_adjust's cost grow with the flight), relocalisation against an
+ * earlier map, and any change to the entries above. */
+int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
+                   double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
+                   int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                   double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                   int32_t* n_carried, int32_t* carried_frame /*[max_cameras]*/, double* carried_poses /*[max_cameras][12]*/);
+
 /* ------------------------------------------------------------------ the same map step for S independent sequences in one call
  * vo_slam_chain is sequential by nature — frame k + 1 is localised against the map frame k left — and runs as one workgroup
  * per kernel; several sequences (several flights, or one flight cut into shards) are what runs in parallel.  vo_slam_chains

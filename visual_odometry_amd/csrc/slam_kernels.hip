@@ -9,6 +9,9 @@
 // Every step is written once, as a workgroup-wide device function, and has two kernels: k_slam_* for the one chain of vo_slam_chain
 // (its buffers by value) and k_slam_*_seqs for the S independent sequences of vo_slam_chains — workgroup = sequence (blockIdx.x),
 // which reads its SlamSeq descriptor and does step j of its own chain, or returns at once when its chain has fewer steps.
+// vo_slam_stream continues a map an earlier call left: k_slam_carry restates its keys at the start of such a call, and the three
+// steps that name a frame or a key have a third kernel, k_slam_*_stream — the same device function compiled with ST = true; the
+// other kernels are compiled with ST = false and carry none of it.
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
 // order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
 #include "chain_common.h"
@@ -44,6 +47,7 @@ __device__ __forceinline__ int slam_scan(int n, int* s_w, G&& get, W&& put)
 // camera list, and every E inlier in match order appends what the reference appends — a new point under featureid1 with its
 // observations on camera 1 and camera 2, or one observation of the point its track root owns.  Pass 1 takes every decision
 // against the map as it was before the loop (the snapshot of :154-156) and stores it; pass 2 writes, after a barrier.
+template <bool ST>
 __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
                                             ChainBuf cb, SlamBuf sb)
 {
@@ -52,17 +56,18 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
     const int ncam0 = sb.m.cnt[0], npt0 = sb.m.cnt[1], nobs0 = sb.m.cnt[2];
-    const bool first = p == 0 || (cb.rs.st && cb.rs.st[SEG_INIT]);   // pair 0, or the pair that starts a new segment on a cleaned map
+    const int frame0 = ST ? sb.st.frame0 : 0;                  // vo_slam_stream: the call's pair 0 is pair frame0 of the stream
+    const bool first = (p == 0 && frame0 == 0) || (cb.rs.st && cb.rs.st[SEG_INIT]);   // pair 0, or the pair that starts a new segment on a cleaned map
     const int newn = ncam0 + (first ? 2 : 1);
     if (newn > sb.cam_cap || (!first && ncam0 < 1)) return;   // cannot happen: the host sizes the list from max_cameras
     const int c1 = newn - 2, c2 = newn - 1;
     if (first) {
         if (tid < 12) sb.m.cam_pose[tid] = p == 0 ? cb.poses[tid] : cb.rs.seg_poses[(size_t)p * 12 + tid];
         else if (tid < 24) sb.m.cam_pose[tid] = cb.poses[(size_t)p * 12 + tid];
-        if (tid < 2) sb.m.cam_frame[tid] = p + tid;
+        if (tid < 2) sb.m.cam_frame[tid] = frame0 + p + tid;
     } else {
         if (tid < 12) sb.m.cam_pose[(size_t)c2 * 12 + tid] = cb.cam[(size_t)f2 * 12 + tid];
-        if (tid == 0) sb.m.cam_frame[c2] = p + 1;
+        if (tid == 0) sb.m.cam_frame[c2] = frame0 + p + 1;
     }
     // initialize_map: first camera fixed, second free; afterwards freeze_nonlast_cameras: all fixed but the last free_cameras
     for (int c = tid; c < newn; c += SLAM_THREADS) sb.m.cam_fixed[c] = first ? (c == 0) : (c < newn - free_cameras);
@@ -111,6 +116,7 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
             if (!first) { cb.in_map[k] = 1; for (int a = 0; a < 3; a++) cb.map_pt[3 * k + a] = X[a]; }
             sb.pt_of[k] = pi + 1;
             sb.m.pt_key[pi] = (int)k;
+            if (ST) { sb.m.pt_feat[2 * (size_t)pi] = frame0 + p; sb.m.pt_feat[2 * (size_t)pi + 1] = pb.m_q[(size_t)p * kp_cap + i]; }
             for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)pi + a] = X[a];
             sb.m.obs_cam[oi] = c1; sb.m.obs_pt[oi] = pi;
             sb.m.obs_xy[2 * (size_t)oi] = px1[2 * i]; sb.m.obs_xy[2 * (size_t)oi + 1] = px1[2 * i + 1];
@@ -130,7 +136,13 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
                                                            ChainBuf cb, SlamBuf sb)
 {
-    slam_add_wg(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+    slam_add_wg<false>(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_stream(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
+                                                                  ChainBuf cb, SlamBuf sb)
+{
+    slam_add_wg<true>(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
 }
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_seqs(PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras,
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_seqs(PairBuf pb, int 
 {
     const SlamSeq& q = seqs[blockIdx.x];
     if (j >= q.count) return;
-    slam_add_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, F, max_norm, free_cameras, q.cb, q.sb);
+    slam_add_wg<false>(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, F, max_norm, free_cameras, q.cb, q.sb);
 }
 
 void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S)
@@ -149,6 +161,11 @@ void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, d
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_add, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+void launch_slam_add_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_add_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
 }
 
 // the problem k_bundle_adjust is handed: the map's place in the lists (all 0 for a single chain), its sizes, skip or not
@@ -265,16 +282,25 @@ __device__ __forceinline__ int slam_slot_of(const PairBuf& pb, int chain_frame)
 // What optimize_map wrote back (map.py:175-186) reaches the tables the next pair's k_chain_gather / k_chain_pose read; then
 // remove_observations_with_reprojection_errors_above_threshold (map.py:46-70) with k_reprojection's arithmetic, the list
 // compacted in place and in order.  Points are not removed here: one that loses every observation stays usable for PnP.
+// vo_slam_stream: a camera of an earlier call has no slot any more (its frame lies before frame0), and a point whose key was
+// marked none by k_slam_carry has no row in the slot-keyed tables: neither is written back.
+template <bool ST>
 __device__ __forceinline__ void slam_filter_wg(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES];
     if (!cb.alive[0]) return;
     const int tid = threadIdx.x;
     const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1], nobs = sb.m.cnt[2];
-    for (int k = tid; k < ncam * 12; k += SLAM_THREADS)
-        cb.cam[(size_t)slam_slot_of(pb, sb.m.cam_frame[k / 12]) * 12 + k % 12] = sb.m.cam_pose[k];
-    for (int q = tid; q < npt; q += SLAM_THREADS)
-        for (int a = 0; a < 3; a++) cb.map_pt[3 * (size_t)sb.m.pt_key[q] + a] = sb.m.pt_xyz[3 * (size_t)q + a];
+    for (int k = tid; k < ncam * 12; k += SLAM_THREADS) {
+        const int fr = sb.m.cam_frame[k / 12] - (ST ? sb.st.frame0 : 0);
+        if (ST && fr < 0) continue;
+        cb.cam[(size_t)slam_slot_of(pb, fr) * 12 + k % 12] = sb.m.cam_pose[k];
+    }
+    for (int q = tid; q < npt; q += SLAM_THREADS) {
+        const int key = sb.m.pt_key[q];
+        if (ST && key < 0) continue;
+        for (int a = 0; a < 3; a++) cb.map_pt[3 * (size_t)key + a] = sb.m.pt_xyz[3 * (size_t)q + a];
+    }
     if (!(threshold > 0)) return;
     int ci = 0, pi = 0; double u = 0, v = 0;
     const int kept = slam_scan(nobs, s_w,
@@ -292,7 +318,12 @@ __device__ __forceinline__ void slam_filter_wg(PairBuf pb, const double* Kd, dou
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
 {
-    slam_filter_wg(pb, Kd, threshold, cb, sb);
+    slam_filter_wg<false>(pb, Kd, threshold, cb, sb);
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_stream(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    slam_filter_wg<true>(pb, Kd, threshold, cb, sb);
 }
 
 // (threshold is the step's: 0 at step 0, where initialize_map's optimize_map is only written back)
@@ -302,7 +333,7 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_seqs(PairBuf pb, i
     const SlamSeq& q = seqs[blockIdx.x];
     if (j >= q.count) return;
     if (q.cb.rs.st && q.cb.rs.st[SEG_INIT]) threshold = 0.0;       // (a pair that starts a new segment is step 0 of it)
-    slam_filter_wg(chain_pairs_from(pb, q.first, kp_cap), Kd, threshold, q.cb, q.sb);
+    slam_filter_wg<false>(chain_pairs_from(pb, q.first, kp_cap), Kd, threshold, q.cb, q.sb);
 }
 
 void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S)
@@ -315,11 +346,19 @@ void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double thre
     hipLaunchKernelGGL(k_slam_filter, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
 }
 
+void launch_slam_filter_stream(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_filter_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
+}
+
 // limit_number_of_camera_in_map (map.py:299-318): with more than max_cameras cameras, remove_camera_from_map(cameras[0])
 // (:188-232) with the quirk it has — observations are counted per point AMONG POINTS THAT STILL HAVE ONE (a defaultdict), so a
 // point left with one observation goes and a point with none stays.  A removed point leaves mappointdict: its feature id can
 // receive a new point later.  Camera and point indices in the observations are renumbered.  Also the end of a pair: every
 // camera's pose as the map holds it goes to poses_last (an evicted camera keeps its last row), the map's sizes to n_*.
+// vo_slam_stream: poses_last has the call's rows only; a camera of an earlier call reports to its carried row instead.  A point
+// whose key is none (k_slam_carry) has no entry in pt_of / in_map; pt_feat moves with pt_key.
+template <bool ST>
 __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES];
@@ -329,7 +368,15 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
         // (vo_slam_chains_restart: pose row `first pair of the segment` belongs to the segment before; the first camera has its own)
         const int seg0 = cb.rs.st ? cb.rs.st[SEG_FIRST] : -1;
         for (int k = tid; k < ncam * 12; k += SLAM_THREADS) {
-            const int fr = sb.m.cam_frame[k / 12];
+            int fr = sb.m.cam_frame[k / 12];
+            if (ST) {
+                fr -= sb.st.frame0;
+                if (fr < 0) {
+                    for (int j = 0; j < sb.st.n_carried; j++)
+                        if (sb.st.carried_frame[j] == fr + sb.st.frame0) sb.st.carried_poses[(size_t)j * 12 + k % 12] = sb.m.cam_pose[k];
+                    continue;
+                }
+            }
             if (fr == seg0) cb.rs.seg_poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
             if (fr != seg0 || fr == 0) sb.poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
         }
@@ -339,12 +386,18 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
             for (int i = tid; i < nobs; i += SLAM_THREADS) if (sb.m.obs_cam[i] != 0) atomicAdd(&sb.tmp[sb.m.obs_pt[i]], 1);
             __syncthreads();
             // the points, in order; tmp becomes old index -> new index (-1: removed)
-            int key = 0; double X[3] = {0, 0, 0};
+            int key = 0, ff = 0, fk = 0; double X[3] = {0, 0, 0};
             const int npt2 = slam_scan(npt, s_w,
-                [&](int q) { key = sb.m.pt_key[q]; for (int a = 0; a < 3; a++) X[a] = sb.m.pt_xyz[3 * (size_t)q + a]; return sb.tmp[q] != 1 ? 1 : 0; },
+                [&](int q) {
+                    key = sb.m.pt_key[q]; for (int a = 0; a < 3; a++) X[a] = sb.m.pt_xyz[3 * (size_t)q + a];
+                    if (ST) { ff = sb.m.pt_feat[2 * (size_t)q]; fk = sb.m.pt_feat[2 * (size_t)q + 1]; }
+                    return sb.tmp[q] != 1 ? 1 : 0;
+                },
                 [&](int q, int at, int keep) {
-                    if (!keep) { sb.tmp[q] = -1; sb.pt_of[key] = 0; cb.in_map[key] = 0; return; }
-                    sb.tmp[q] = at; sb.pt_of[key] = at + 1; sb.m.pt_key[at] = key;
+                    const bool keyed = !ST || key >= 0;
+                    if (!keep) { sb.tmp[q] = -1; if (keyed) { sb.pt_of[key] = 0; cb.in_map[key] = 0; } return; }
+                    sb.tmp[q] = at; if (keyed) sb.pt_of[key] = at + 1; sb.m.pt_key[at] = key;
+                    if (ST) { sb.m.pt_feat[2 * (size_t)at] = ff; sb.m.pt_feat[2 * (size_t)at + 1] = fk; }
                     for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)at + a] = X[a];
                 });
             __syncthreads();
@@ -372,13 +425,15 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
     if (tid == 0) { sb.n_cam[p] = ncam; sb.n_pts[p] = npt; sb.n_obs[p] = nobs; }
 }
 
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg(p, max_cameras, cb, sb); }
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<false>(p, max_cameras, cb, sb); }
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<true>(p, max_cameras, cb, sb); }
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_seqs(int j, int max_cameras, const SlamSeq* __restrict__ seqs)
 {
     const SlamSeq& q = seqs[blockIdx.x];
     if (j >= q.count) return;
-    slam_limit_wg(j, max_cameras, q.cb, q.sb);
+    slam_limit_wg<false>(j, max_cameras, q.cb, q.sb);
 }
 
 void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S)
@@ -389,6 +444,11 @@ void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_limit, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
+}
+
+void launch_slam_limit_stream(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_limit_stream, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
 }
 
 // vo_slam_chains_restart, between k_chain_pose and k_chain_triangulate of every step: the end of the step's decision.  On an
@@ -426,4 +486,62 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_restart_seqs(PairBuf pb, 
 void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S)
 {
     hipLaunchKernelGGL(k_slam_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, seqs);
+}
+
+// vo_slam_stream, at the start of a call that continues the map of the call before (before k_chain_link): the frames of that call
+// lose their slots, so every key that still matters is restated in rows that stay.  Integers and copies only; one workgroup, its
+// phases separated by barriers; the result is a function of the tables alone (a lane owns a keypoint, a point or a table entry).
+//   A  every keypoint k of the anchor row — the stream's last frame, the only one a later track can pass through — walks to its
+//      track root on the old table.  A root other than (anchor, k) itself moves to entry k of the new ghost row: parent[(anchor, k)]
+//      names it, it takes the root's pt_of / in_map / map_pt, and the point the root owns is re-keyed.  A root that owns no point
+//      moves as well: left as its own root, the anchor keypoint would own the first point a later pair keys there and later
+//      pairs would find it, where the one-call walk finds the old, empty root every time and adds a new point (:139-146).
+//      The old ghost row is read here (a root of the call before last), the new one written: two rows, alternating.
+//   B  a point keyed neither in the anchor row nor in the new ghost row can never be reached again: its key becomes none (-1).
+//      (Its feature id for vo_slam_map was stored in pt_feat when it was added.)  The cameras beside the anchor go to the carried rows.
+//   C  every row but the anchor's and the new ghost's is cleared in parent, in_map, map_pt, pt_of, cam and cam_ok: a reused slot
+//      starts empty, as every slot does in a single call.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry(SlamCarry c, ChainBuf cb, SlamBuf sb)
+{
+    const int tid = threadIdx.x, cap = c.kp_cap;
+    const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1];
+    for (int k = tid; k < cap; k += SLAM_THREADS) {
+        int rf = c.anchor, ri = k;
+        chain_root(cb.parent, cap, c.F + 2, rf, ri);
+        const size_t g = chain_key(c.ghost_new, k, cap);
+        int own = 0; uint8_t in = 0; double X[3] = {0, 0, 0};
+        if (rf != c.anchor) {                                   // (a root in the anchor row is the keypoint itself: tracks are one-to-one)
+            const size_t r = chain_key(rf, ri, cap);
+            own = sb.pt_of[r]; in = cb.in_map[r];
+            for (int a = 0; a < 3; a++) X[a] = cb.map_pt[3 * r + a];
+            if (own) sb.m.pt_key[own - 1] = (int)g;
+            cb.parent[chain_key(c.anchor, k, cap)] = (1ULL << 40) | ((unsigned long long)(unsigned)c.ghost_new << 20) | (unsigned)k;
+        }
+        sb.pt_of[g] = own; cb.in_map[g] = in; cb.parent[g] = 0;
+        for (int a = 0; a < 3; a++) cb.map_pt[3 * g + a] = X[a];
+    }
+    if (tid < 12) cb.poses[tid] = c.keep[tid];
+    else if (tid < 24) sb.poses_last[tid - 12] = c.keep[tid];
+    for (int k = tid; k < (ncam - 1) * 12; k += SLAM_THREADS) sb.st.carried_poses[k] = sb.m.cam_pose[k];
+    for (int i = tid; i < ncam - 1; i += SLAM_THREADS) sb.st.carried_frame[i] = sb.m.cam_frame[i];
+    __syncthreads();
+    for (int q = tid; q < npt; q += SLAM_THREADS) {
+        const int key = sb.m.pt_key[q];
+        if (key < 0) continue;
+        const int row = key / cap;
+        if (row != c.anchor && row != c.ghost_new) sb.m.pt_key[q] = -1;
+    }
+    for (int r = 0; r < c.F + 2; r++) {
+        if (r == c.anchor || r == c.ghost_new) continue;
+        const size_t at = chain_key(r, 0, cap);
+        for (int k = tid; k < cap; k += SLAM_THREADS) { cb.parent[at + k] = 0; cb.in_map[at + k] = 0; sb.pt_of[at + k] = 0; }
+        for (int k = tid; k < 3 * cap; k += SLAM_THREADS) cb.map_pt[3 * at + k] = 0.0;
+    }
+    for (int k = tid; k < c.F * 12; k += SLAM_THREADS) if (k / 12 != c.anchor) cb.cam[k] = 0.0;
+    for (int r = tid; r < c.F; r += SLAM_THREADS) if (r != c.anchor) cb.cam_ok[r] = 0;
+}
+
+void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_carry, dim3(1), dim3(SLAM_THREADS), 0, s, c, cb, sb);
 }

@@ -94,6 +94,26 @@ struct LastRun {
     int snap_seq = -1;
 };
 
+// vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one
+// allocation that lives from the call that starts the stream (resume = 0) until the stream is dropped.
+struct SlamStream {
+    DevList mem;
+    bool live = false;                    // a resume = 0 call has run and nothing has dropped the stream since
+    bool lost = false;                    // its last call ended with a pair that was not localised
+    bool touched = false;                 // the anchor slot was uploaded to or detected again: the stream's last frame is gone
+    int anchor = -1;                      // slot of the stream's last frame
+    int done = 0, total = 0;              // pairs so far, pairs the stream may reach (what the lists were sized for)
+    int carries = 0, last_ncam = 0;       // resumed calls so far; cameras the map held at the end of the last call
+    int F = 0, cap = 0, max_pairs = 0;    // the configuration it was sized for
+    vo_slam_opts opts{};
+    double K[9] = {0};
+    uint8_t* base = nullptr; size_t bytes = 0;
+    uint8_t* call_mem = nullptr; size_t call_bytes = 0;     // the per-pair outputs: cleared at the start of every call
+    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; SlamMap snap{};
+    double *dK = nullptr, *dchi2 = nullptr, *keep = nullptr; int *dit = nullptr, *dtr = nullptr;
+    uint8_t *map_mem = nullptr, *snap_mem = nullptr; size_t map_bytes = 0;
+};
+
 struct vo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;         // non-blocking: no implicit ordering with the NULL stream (PyTorch / RCCL use it)
@@ -127,6 +147,7 @@ struct vo_ctx {
     int pb_pairs = 0, pb_cap = 0;
     double* dK = nullptr;
     LastRun last;
+    SlamStream stream_map;                // vo_slam_stream's resident map (its own lifetime: see drop_slam_stream)
 
     // scratch for the single-call operators
     DevList raw_mem;                      // the single-call matcher: raw_desc, raw_desc_x, raw_xy, raw_count, raw_pb.*
@@ -191,6 +212,17 @@ template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
 
 static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
 
+// The end of a stream: vo_destroy (the context's destructor), a configure call, a vo_slam_stream that starts a new one and every
+// vo_slam_chain* call come here.  (Every call that uses the allocation has waited for the context's stream before it returned.)
+static void drop_slam_stream(vo_ctx* ctx) { ctx->stream_map = SlamStream(); }
+
+// An upload, ingest or detection into slots first .. first + n - 1: if the stream's last frame is among them, no call can continue it.
+static void slam_stream_slots_written(vo_ctx* ctx, int first, int n)
+{
+    SlamStream& st = ctx->stream_map;
+    if (st.live && st.anchor >= first && st.anchor < first + n) st.touched = true;
+}
+
 // The device memory of one call: typed sub-buffers of ctx->scratch, each on a 256-byte boundary.  take() names a pointer
 // and its element count; place() grows the buffer to what was taken and sets the pointers, so size and offsets agree.
 struct ScratchLayout {
@@ -200,6 +232,7 @@ struct ScratchLayout {
         slots.push_back({p, bytes, [](void* dst, uint8_t* at) { *static_cast<T**>(dst) = reinterpret_cast<T*>(at); }});
         bytes += (n * sizeof(T) + 255) & ~(size_t)255;
     }
+    void place_at(uint8_t* base) { for (const Slot& s : slots) s.set(s.dst, base + s.off); }   // (an allocation of the caller's, `bytes` long)
     int place(vo_ctx* ctx)
     {
         int rc = ctx->scratch.grow(ctx, bytes, bytes + bytes / 4 + 64); if (rc) return rc;
@@ -389,6 +422,7 @@ static void free_config(vo_ctx* c)
     c->pb_mem.release();
     c->pb_pairs = c->pb_cap = 0;
     clear_last_run(c);
+    drop_slam_stream(c);
 }
 
 static void comm_release(vo_ctx* ctx);
@@ -501,6 +535,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
         ctx->max_frames >= max_frames && ctx->max_pairs >= max_pairs && ctx->pb_cap == ctx->g.kp_cap) {
         ctx->detector = 0;
         clear_last_run(ctx);
+        drop_slam_stream(ctx);
         return VO_OK;
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -625,6 +660,7 @@ static int frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int 
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    slam_stream_slots_written(ctx, first_slot, F);
     if (row_stride < b.w) FAIL(VO_ERR_INVALID, "row_stride < width");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
@@ -680,6 +716,7 @@ extern "C" int vo_frames_upload_color(vo_ctx* ctx, const uint8_t* frames, int F,
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (channels != 3 && channels != 4) FAIL(VO_ERR_INVALID, "channels must be 1, 3 or 4");
     if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    slam_stream_slots_written(ctx, first_slot, F);
     if (row_stride < b.w * channels || frame_stride < (int64_t)image_span(1, 0, b.h, row_stride, b.w * channels)) FAIL(VO_ERR_INVALID, "strides too small");
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
@@ -790,6 +827,7 @@ static int detect_enqueue(vo_ctx* ctx, int first_slot, int F)
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    slam_stream_slots_written(ctx, first_slot, F);
     HIPCHK(hipSetDevice(ctx->device));
     if (F == 0) return VO_OK;
     if (b.sift) return sift_frames_detect_enqueue(ctx, first_slot, F);
@@ -2087,6 +2125,7 @@ extern "C" int vo_frames_ingest(vo_ctx* ctx, const uint8_t* frames, int F, int s
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (!frames || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    slam_stream_slots_written(ctx, first_slot, F);
     if (sh < 1 || sw < 1 || (channels != 1 && channels != 3 && channels != 4) || row_stride < sw * channels ||
         frame_stride < (int64_t)image_span(1, 0, sh, row_stride, sw * channels)) FAIL(VO_ERR_INVALID, "bad source geometry");
     if (F == 0) return VO_OK;
@@ -2325,6 +2364,7 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     clear_last_run(ctx);                                        // the pair buffers may be replaced below
+    drop_slam_stream(ctx);
     // frames per launch chain: the small octaves' launches are latency-bound (a dependent chain of ~50 launches per sub-batch)
     // and the wave-per-keypoint kernels like long grids, so the more frames share a chain the better (1280 x 720, pairs/s with
     // 64 / 96 / 128 / 192 / 256 frames: 4.59 / 4.68 / 4.79 / 4.94 / 4.94 k): up to 192 frames, within 48 GB of scale-space scratch
@@ -2390,6 +2430,7 @@ extern "C" int vo_stage_sift_rows(vo_ctx* ctx, int slot, const uint8_t* rows, in
     if (ctx->detector != 1 || !S.configured || !S.with_operands) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure_sift has not been called");
     if (slot < 0 || slot >= S.max_frames) FAIL(VO_ERR_INVALID, "bad slot");
     if (n < 0 || n > S.kp_cap || (n > 0 && !rows)) FAIL(VO_ERR_INVALID, "0 <= n <= kp_cap rows are needed");
+    slam_stream_slots_written(ctx, slot, 1);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     HIPCHK(hipStreamSynchronize(s));                        // an asynchronous detection may still be writing the slot; the staging buffer may be in use
@@ -2592,6 +2633,7 @@ extern "C" int vo_frames_ingest_jpeg(vo_ctx* ctx, const uint8_t* blob, const int
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
     if (!blob || !offsets || F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    slam_stream_slots_written(ctx, first_slot, F);
     for (int f = 0; f < F; f++) if (offsets[f + 1] < offsets[f] + 4) FAIL(VO_ERR_INVALID, "file %d is empty", f);
     if (F == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
@@ -2787,6 +2829,11 @@ static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Ma
         HIPCHK(hipMemcpy(out->obs_pt.data(), m.obs_pt, no * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out->obs_xy.data(), m.obs_xy, no * 16, hipMemcpyDeviceToHost));
     }
+    if (m.pt_feat) {                                                  // vo_slam_stream keeps the feature ids as (frame, keypoint) on the device
+        if (np) HIPCHK(hipMemcpy(out->pt_feature.data(), m.pt_feat, np * 8, hipMemcpyDeviceToHost));
+        out->valid = true;
+        return VO_OK;
+    }
     // feature id (slot, keypoint) -> (index of the frame in the chain, keypoint)
     const int32_t* sl = ctx->last.slots.data() + 2 * (size_t)first;
     const size_t npairs = count < 0 ? ctx->last.slots.size() / 2 : (size_t)count;
@@ -2832,6 +2879,7 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
     if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
         FAIL(VO_ERR_INVALID, "bad arguments");
     int F, cap;
+    drop_slam_stream(ctx);
     int rc = chain_check(ctx, B, "vo_slam_chain", &F, &cap); if (rc) return rc;
     forget_slam_maps(ctx);
     rc = slam_opts_check(ctx, o, K, B, "vo_slam_chain"); if (rc) return rc;
@@ -2959,6 +3007,165 @@ extern "C" int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* c
     return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
 }
 
+// ------------------------------------------------------------------ the map step, one call after another on one resident map
+// vo_slam_chain's walk on buffers of their own lifetime (SlamStream): the first call of a stream clears them as vo_slam_chain
+// clears the scratch buffer and runs vo_slam_chain's steps; a call that continues it clears the per-pair outputs only, lets
+// k_slam_carry restate the keys (slam_kernels.hip) and runs a p >= 1 step for every pair.  The work buffers keep what the last
+// step left in them, as they do between two steps of one call.
+static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, int F, int cap, int max_pairs, int total, const vo_slam_opts* o, const double* K)
+{
+    // the slot-keyed tables have two ghost rows behind the F slots.  Lists: a pair adds at most one point per match; a camera takes
+    // at most kp_cap observations as a pair's second frame and kp_cap as the next pair's first (one-to-one matches), and the map
+    // holds at most max_cameras + 1 cameras — or every pair's two observations per match, if the stream is shorter than that.
+    const size_t fc = (size_t)(F + 2) * cap, cm = (size_t)o->max_cameras + 1, np = ((size_t)total + 1) * cap;
+    const size_t no = (size_t)2 * cap * std::min(cm, (size_t)total), npair = no * (o->free_cameras + 1) / 2;
+    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
+    const size_t P = (size_t)max_pairs;
+    if (F + 2 >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames for the packed track table");
+    if (np >= ((size_t)1 << 31) || npair >= ((size_t)1 << 31) || fc >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the map's lists would not fit 32-bit indices");
+    ChainBuf& cb = st.cb; SlamBuf& sb = st.sb; BaBuf& D = st.D;
+    size_t o_feat = 0;
+    st.map_bytes = slam_map_carve(nullptr, cm, np, no, &sb.m);
+    o_feat = st.map_bytes; st.map_bytes += (np * 2 * sizeof(int) + 255) & ~(size_t)255;       // pt_feat rides behind the lists: a snapshot takes it along
+    ScratchLayout sc;
+    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
+    sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4);
+    sc.take(&st.dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
+    sc.take(&cb.alive, 1); sc.take(&cb.map_count, 1); sc.take(&st.keep, 24);
+    sc.take(&st.map_mem, st.map_bytes); sc.take(&st.snap_mem, st.map_bytes);
+    sc.take(&sb.pt_of, fc); sc.take(&sb.dec, cap); sc.take(&sb.tmp, np); sc.take(&sb.idx, no);
+    sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
+    sc.take(&sb.pairs, npair); sc.take(&sb.blk_first, (size_t)nblk + 1);
+    sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
+    const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
+    sc.take(&cb.poses, (P + 1) * 12); sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P);
+    sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P); sc.take(&sb.poses_last, (P + 1) * 12);
+    sc.take(&st.dchi2, 2 * P); sc.take(&st.dit, P); sc.take(&st.dtr, P);
+    sc.take(&sb.st.carried_frame, cm); sc.take(&sb.st.carried_poses, cm * 12);
+    HIPCHK(st.mem.alloc(&st.base, sc.bytes));
+    sc.place_at(st.base);
+    st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
+    slam_map_carve(st.map_mem, cm, np, no, &sb.m); slam_map_carve(st.snap_mem, cm, np, no, &st.snap);
+    sb.m.pt_feat = reinterpret_cast<int*>(st.map_mem + o_feat); st.snap.pt_feat = reinterpret_cast<int*>(st.snap_mem + o_feat);
+    sb.cam_cap = (int)cm; sb.pt_cap = (int)np; sb.obs_cap = (int)no; sb.pair_cap = (int)npair;
+    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
+    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
+    st.F = F; st.cap = cap; st.max_pairs = max_pairs; st.total = total; st.opts = *o; memcpy(st.K, K, sizeof(st.K));
+    return VO_OK;
+}
+
+extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
+                              int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                              double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                              int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!resume) drop_slam_stream(ctx);
+    forget_slam_maps(ctx);
+    if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run ||
+        !n_carried || !carried_frame || !carried_poses) FAIL(VO_ERR_INVALID, "bad arguments");
+    SlamStream& st = ctx->stream_map;
+    if (resume) {
+        if (!st.live) FAIL(VO_ERR_INVALID, "vo_slam_stream: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)");
+        if (st.lost) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
+        if (st.touched) FAIL(VO_ERR_INVALID, "vo_slam_stream: slot %d, the stream's last frame, was uploaded to or detected again", st.anchor);
+    }
+    int F, cap;
+    int rc = chain_check(ctx, B, "vo_slam_stream", &F, &cap); if (rc) return rc;
+    rc = slam_opts_check(ctx, o, K, B, "vo_slam_stream"); if (rc) return rc;
+    const int32_t* sl = ctx->last.slots.data();
+    if (resume) {
+        const vo_slam_opts& a = st.opts;
+        if (sl[0] != st.anchor) FAIL(VO_ERR_INVALID, "vo_slam_stream: pair 0 starts at slot %d, the stream's last frame is in slot %d", sl[0], st.anchor);
+        if (memcmp(K, st.K, sizeof(st.K)) != 0 || o->pnp_iterations != a.pnp_iterations || o->reproj_err != a.reproj_err || o->confidence != a.confidence ||
+            o->seed != a.seed || o->max_point_norm != a.max_point_norm || o->ba_iterations != a.ba_iterations || o->huber_delta != a.huber_delta ||
+            o->free_cameras != a.free_cameras || o->filter_threshold != a.filter_threshold || o->max_cameras != a.max_cameras)
+            FAIL(VO_ERR_INVALID, "vo_slam_stream: K and every option but the snapshot's must be those the stream was started with");
+        if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "vo_slam_stream: %d + %d pairs pass the stream's total_pairs = %d", st.done, B, st.total);
+    } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "vo_slam_stream: total_pairs = %d is less than the call's %d pairs", total_pairs, B);
+    HIPCHK(hipSetDevice(ctx->device));
+    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    if (!resume) {
+        rc = slam_stream_allocate(ctx, st, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
+        if (rc) { drop_slam_stream(ctx); return rc; }
+        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));              // empty feature_mapper, empty map, no cameras, zero results
+        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
+    } else HIPCHK(hipMemsetAsync(st.call_mem, 0, st.call_bytes, s));
+    ChainBuf cb = st.cb; SlamBuf sb = st.sb;
+    sb.st.frame0 = resume ? st.done : 0;
+    sb.st.n_carried = resume ? st.last_ncam - 1 : 0;
+    double* dK = st.dK;
+    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
+    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
+    auto snapshot = [&](int p, int stage) {
+        if (p == o->snapshot_pair && stage == o->snapshot_stage) (void)hipMemcpyAsync(st.snap_mem, st.map_mem, st.map_bytes, hipMemcpyDeviceToDevice, s);
+    };
+    st.live = false;                                                  // (until the call has come through)
+    if (resume) {
+        StageTimer t(ctx, ST_MISC);
+        const int gn = F + (st.carries & 1);
+        launch_slam_carry(s, SlamCarry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.keep}, cb, sb);
+    }
+    launch_chain_link(s, ctx->pb, cap, B, cb);
+    for (int p = 0; p < B; p++) {
+        {
+            StageTimer t(ctx, ST_MISC);
+            if (p == 0 && !resume) launch_chain_init(s, ctx->pb, cap, cb);
+            else {
+                launch_chain_gather(s, ctx->pb, cap, p, F + 2, cb);   // (a track may end in a ghost row: two more hops at most)
+                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
+                launch_chain_pose(s, ctx->pb, p, dK, cb);
+                launch_chain_triangulate(s, ctx->pb, cap, p, cb);
+            }
+            launch_slam_add_stream(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
+        }
+        snapshot(p, 1);
+        if (ba) {
+            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare(s, cb, sb); }
+            BaBuf Dp = st.D;
+            Dp.chi2 = st.dchi2 + 2 * p; Dp.iterations_run = st.dit + p; Dp.trials_run = st.dtr + p;
+            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dp, prm, 1, o->free_cameras); }
+        }
+        snapshot(p, 2);
+        const bool step0 = p == 0 && !resume;
+        if (ba || (filt && !step0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter_stream(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb); }
+        snapshot(p, 3);
+        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_stream(s, p, o->max_cameras, cb, sb); }
+        snapshot(p, 4);
+    }
+    HIPCHK(hipGetLastError());
+    // the anchor camera of the next call: this call's last rows
+    HIPCHK(hipMemcpyAsync(st.keep, cb.poses + (size_t)B * 12, 96, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(st.keep + 12, sb.poses_last + (size_t)B * 12, 96, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(chi2, st.dchi2, (size_t)B * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ba_iterations_run, st.dit, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ba_trials_run, st.dtr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    *n_carried = sb.st.n_carried;
+    if (sb.st.n_carried > 0) {
+        HIPCHK(hipMemcpyAsync(carried_frame, sb.st.carried_frame, (size_t)sb.st.n_carried * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(carried_poses, sb.st.carried_poses, (size_t)sb.st.n_carried * 96, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
+    if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, st.snap, cap, &ctx->last.map[1]); if (rc) return rc; }
+    st.lost = false;
+    for (int p = 0; p < B; p++) if (status[p] != VO_OK) st.lost = true;
+    st.anchor = sl[2 * B - 1]; st.done = (resume ? st.done : 0) + B; st.carries = resume ? st.carries + 1 : 0;
+    st.last_ncam = n_cam[B - 1]; st.touched = false; st.live = true;
+    return VO_OK;
+}
+
 // ------------------------------------------------------------------ the map step for S independent sequences in one call
 // vo_slam_chain's walk, every kernel of a step launched once with the sequence on a grid axis (k_*_seqs): the host loop runs over
 // the step j = 0 .. max B_s - 1, a workgroup does step j of its own sequence on pair seq_off[s] + j.  The slot-keyed tables are
@@ -3007,6 +3214,7 @@ static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_
                            int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
 {
     if (!ctx) return VO_ERR_INVALID;
+    drop_slam_stream(ctx);
     forget_slam_maps(ctx);
     if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
         FAIL(VO_ERR_INVALID, "bad arguments");

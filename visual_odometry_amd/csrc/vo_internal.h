@@ -337,6 +337,14 @@ struct SlamMap {
     double*  pt_xyz;                    // [points][3]
     int*     obs_cam; int* obs_pt;      // [observations] indices into the two lists above
     double*  obs_xy;                    // [observations][2]
+    int*     pt_feat;                   // vo_slam_stream only (nullptr elsewhere): [points][2] the owning feature id as (frame along the stream, keypoint)
+};
+// vo_slam_stream: what a call that continues a map needs beside the lists.  All zero / nullptr in every other entry.
+struct StreamBuf {
+    int      frame0;                    // index along the stream of the call's first frame (0: the call that starts the stream)
+    int      n_carried;                 // cameras the map held at the carry beside the anchor: they have no slot in this call
+    int*     carried_frame;             // [n_carried] their frames along the stream, in map order at the carry
+    double*  carried_poses;             // [n_carried][12] ... as the map last held them
 };
 struct SlamBuf {
     SlamMap  m;
@@ -350,11 +358,24 @@ struct SlamBuf {
     // what k_slam_ba_prepare hands k_bundle_adjust (BaBuf's const members)
     BaProblem* prob; int* cam_col; int* pt_first; int* s_cam; int* s_pt; double* s_xy; int2* pairs; int* blk_first;
     BaProblem base;                     // where this map's lists start in the arrays BaBuf names: cam0 .. blk0 (all 0 for a single chain)
+    StreamBuf st;                       // vo_slam_stream only
 };
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
 void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb);
 void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb);
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb);
+// ---- the same step on a map carried from an earlier call (vo_slam_stream): the kernels whose code differs, and the carry.
+// The slot-keyed tables have max_frames + 2 rows there: rows F and F + 1 are the ghost rows (slam_kernels.hip, k_slam_carry).
+void launch_slam_add_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
+void launch_slam_filter_stream(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb);
+void launch_slam_limit_stream(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb);
+struct SlamCarry {
+    int kp_cap, F;                      // rows 0 .. F - 1 are frame slots
+    int anchor;                         // slot of the stream's last frame: pair 0 of the new call starts there
+    int ghost_new, ghost_old;           // F and F + 1, alternating between carries
+    const double* keep;                 // [2][12] the anchor camera as it entered the map / as the map last held it (the previous call's last rows)
+};
+void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb);
 // ---- the same step for S independent sequences at once (vo_slam_chains): one workgroup per sequence and kernel, the sequence on a
 // grid axis.  A workgroup reads its sequence's descriptor from a device array — its pairs inside the run, and a ChainBuf / SlamBuf
 // whose slot-keyed tables (parent, in_map, map_pt, cam, cam_ok, pt_of) are the shared ones (the sequences' slots are disjoint) and

@@ -215,6 +215,36 @@ class FrontEnd:
                                     i32["n_cam"].ctypes.data, chi2.ctypes.data, i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data))
         return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, **i32)
 
+    def slam_stream(self, n_pairs, K, resume=False, total_pairs=None, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED,
+                    max_point_norm=50.0, ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """slam_chain on a map that outlives the call (vo_slam_stream): resume=False starts a stream with the `n_pairs` pairs of the
+        latest run_pairs(..., want_points=True) and computes what slam_chain computes; total_pairs (default n_pairs) is how many
+        pairs the whole stream may reach.  Then, as often as needed: upload and detect the next frames into any slots but the one
+        of the stream's last frame, run_pairs on a chain that starts at that slot, slam_stream(..., resume=True) with the same K and
+        options.  The calls together compute what one slam_chain on the whole flight computes, byte for byte.
+        Returns slam_chain's dict (in a resumed call poses_pnp / poses row 0 is the stream's last frame of the call before, and
+        snapshot=(pair, stage) counts along the call) plus carried_frame [n] and carried_poses [n, 3, 4]: the cameras the map held
+        at the start of a resumed call beside that frame, by their index along the whole stream, as the map last held them
+        during this call.  slam_map()'s cam_frame and pt_feature[:, 0] count along the whole stream."""
+        B = int(n_pairs)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        sp, ss = (-1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]))
+        opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
+                             float(huber_delta), int(free_cameras), float(filter_threshold), int(max_cameras), sp, ss)
+        pp = np.zeros((B + 1, 12)); pl = np.zeros((B + 1, 12)); chi2 = np.zeros((B, 2))
+        i32 = {k: np.zeros(B, np.int32) for k in ("n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")}
+        rows = max(int(max_cameras), 1)
+        nc = C.c_int32(0); cf = np.zeros(rows, np.int32); cp = np.zeros((rows, 12))
+        c = self.ctx
+        rc = c.lib.vo_slam_stream(c.handle, int(bool(resume)), B if total_pairs is None else int(total_pairs), B, K.ctypes.data, C.addressof(opts),
+                                  pp.ctypes.data, pl.ctypes.data, i32["n_corr"].ctypes.data, i32["n_inl"].ctypes.data, i32["status"].ctypes.data,
+                                  i32["n_pts"].ctypes.data, i32["n_obs"].ctypes.data, i32["n_cam"].ctypes.data, chi2.ctypes.data,
+                                  i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data, C.addressof(nc), cf.ctypes.data, cp.ctypes.data)
+        c.check(rc)
+        n = nc.value
+        return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, carried_frame=cf[:n].copy(),
+                    carried_poses=cp[:n].reshape(n, 3, 4).copy(), **i32)
+
     def slam_chains(self, seq_lengths, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
                     ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None, restart=False):
         """slam_chain for several independent sequences in one call (vo_slam_chains), one workgroup per sequence and kernel: the
