@@ -11,7 +11,10 @@ Only the compressed file bytes cross PCIe; every stage after that reads what the
 starts a new map instead of ending the chain — and one track per segment, each in its own gauge.
 --stream N: the same files once more in chunks of N pairs through slam_stream on a front end with only N + 1 frame slots — the map stays on the
 device between the chunks, every chunk's files are decoded into the slots the chunk before freed — and the track, which is the track of one
-slam_chain call on all the files."""
+slam_chain call on all the files.
+--stream N --restart together: the chunks go through slam_stream_restart instead — a lost frame starts a new map in whichever chunk it falls,
+and a chunk that ends lost is continued — and one track per segment is printed from the joined calls (join_stream, split_segments); they are the
+segments of slam_chain(restart=True) on all the files."""
 import argparse
 import io
 import os
@@ -22,7 +25,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visual_odometry_amd import ingest, synth  # noqa: E402
-from visual_odometry_amd.frontend import FrontEnd  # noqa: E402
+from visual_odometry_amd.frontend import FrontEnd, join_stream, split_segments  # noqa: E402
 
 
 def main():
@@ -68,25 +71,37 @@ def main():
             print(f"segment {i}: frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']}, camera centres in its own gauge:")
             print(np.round(track, 2))
     if a.stream > 0:
-        whole = fe.slam_chain(n - 1, K)                         # the yardstick: one call, every frame resident
+        whole = fe.slam_chain(n - 1, K, restart=a.restart)      # the yardstick: one call, every frame resident
         N = min(a.stream, n - 1)
         st = FrontEnd(dh, dw, max_frames=N + 1, max_pairs=N, detector=a.detector, **({} if a.detector == "sift" else {"nfeatures": 2000}))
-        slots, last = list(range(N + 1)), np.zeros((n, 3, 4))
+        slots, last, outs = list(range(N + 1)), np.zeros((n, 3, 4)), []
+        call, name = (st.slam_stream_restart, "slam_stream_restart") if a.restart else (st.slam_stream, "slam_stream")
         for c, first in enumerate(range(0, n - 1, N)):          # the chunk's pairs: first .. first + b - 1
             b = min(N, n - 1 - first)
             new = slots[:b + 1] if c == 0 else slots[1:b + 1]
             for slot, f in zip(new, range(first + (c > 0), first + b + 1)):
                 st.ingest_jpeg([files[f]], first_slot=slot); st.detect(slot, 1)
             st.run_pairs([[slots[j], slots[j + 1]] for j in range(b)], K, want_points=True)
-            out = st.slam_stream(b, K, resume=c > 0, total_pairs=n - 1)
+            out = call(b, K, resume=c > 0, total_pairs=n - 1)
+            outs.append(out)
             for f, T in zip(out["carried_frame"], out["carried_poses"]):
                 last[f] = T                                     # a camera of an earlier chunk, as the map last held it in this call
             last[first:first + b + 1] = out["poses"]
-            print(f"slam_stream chunk {c}: frames {first}..{first + b} in slots {slots[:b + 1]}, status {out['status'].tolist()}, map {out['n_cam'][-1]} cameras "
+            print(f"{name} chunk {c}: frames {first}..{first + b} in slots {slots[:b + 1]}, status {out['status'].tolist()}, map {out['n_cam'][-1]} cameras "
                   f"{out['n_pts'][-1]} points, carried {out['carried_frame'].tolist()}")
             slots = [slots[b]] + slots[:b] + slots[b + 1:]      # the chunk's last frame stays where it is
-        print(f"slam_stream in chunks of {N}: the track {'equals' if np.array_equal(last, whole['poses']) else 'DIFFERS from'} slam_chain's on all {n} files; camera centres:")
-        print(np.round(np.array([-P[:, :3].T @ P[:, 3] for P in last]), 2))
+        if not a.restart:
+            print(f"slam_stream in chunks of {N}: the track {'equals' if np.array_equal(last, whole['poses']) else 'DIFFERS from'} slam_chain's on all {n} files; camera centres:")
+            print(np.round(np.array([-P[:, :3].T @ P[:, 3] for P in last]), 2))
+        else:
+            j = join_stream(outs)                               # the whole flight's arrays from the calls' rows, seg_poses rows and carried rows
+            segs = split_segments(j["segment"], j["poses_pnp"], j["poses"], j["seg_poses_pnp"], j["seg_poses"])
+            same = len(segs) == len(whole["segments"]) and all(np.array_equal(x["poses"], y["poses"]) for x, y in zip(segs, whole["segments"]))
+            print(f"slam_stream_restart in chunks of {N}: segment {j['segment'].tolist()} cause {j['cause'].tolist()}; the segments "
+                  f"{'equal' if same else 'DIFFER from'} slam_chain(restart=True)'s on all {n} files")
+            for i, sg in enumerate(segs):
+                print(f"segment {i}: frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']}, camera centres in its own gauge:")
+                print(np.round(np.array([-P[:, :3].T @ P[:, 3] for P in sg["poses"]]), 2))
 
 
 if __name__ == "__main__":

@@ -526,14 +526,15 @@ int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[
  *     one of them is still free in the first steps and changes).  Both arrays take max_cameras rows.
  *   vo_slam_map after either: cam_frame and pt_feature[:, 0] count along the whole stream.
  * The stream ends — its memory is released — with vo_destroy, vo_batch_configure[_sift], a new resume = 0 or any vo_slam_chain*
- * call.  A call that ends lost (vo_slam_chain's stop rule and statuses) leaves the map for vo_slam_map; it cannot be continued.
+ * call.  A call that ends lost (vo_slam_chain's stop rule and statuses) leaves the map for vo_slam_map; it cannot be continued
+ * (vo_slam_stream_restart, below, is the stream that can).
  * How a call continues a map whose frames have lost their slots (k_slam_carry): the slot-keyed tables get two ghost rows behind
  * the max_frames slots (max_frames + 2 < 2^20).  Every keypoint of the anchor frame whose track root lies in an older frame is
  * linked to an entry of a ghost row that takes over the root's map point — also a root that owns no point, which must stay
  * one: the reference finds nothing under it at every later frame and adds a new point each time (:139-146).  A point no track
  * can reach any more keeps its place in the lists and in the bundle adjustment, as in the reference, but has no key.
  * [deviation] none in the results; the per-call cost is one k_slam_carry launch and the download of the map for vo_slam_map.
- * Out of scope: several sequences per call, restart (vo_slam_chains_restart) inside a stream, pruning points that have lost every
+ * Out of scope: several sequences per call, pruning points that have lost every
  * observation (the reference keeps them: the lists and k_bundle_adjust's cost grow with the flight), relocalisation against an
  * earlier map, and any change to the entries above. */
 int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
@@ -605,6 +606,49 @@ int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/,
                            double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
                            int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam /*[B] each*/,
                            double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run /*[B] each*/,
+                           int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/);
+
+/* ------------------------------------------------------------------ the stream that starts a new map after a lost frame
+ * vo_slam_stream ends at its first lost frame and vo_slam_chains_restart needs the whole flight resident in one vo_pairs_run; a
+ * long flight needs both.  vo_slam_stream_restart is vo_slam_stream — same arguments, sizing, slot rules and carry — with
+ * vo_slam_chains_restart's recovery and its four outputs.  The contract: the calls of a restart stream together compute the
+ * bytes one vo_slam_chains_restart call with S = 1 computes on the whole flight.
+ *   Mode: restart is a property of the stream.  A stream begun by one of the two entry points is continued only by the same
+ *     one; the other returns VO_ERR_INVALID and leaves the stream as it was, still continuable by the right entry point.
+ *     vo_slam_stream itself is unchanged and still refuses to continue after a call that ended lost.
+ *   resume = 0: vo_slam_chains_restart's checks, rules 1-6 and bytes with S = 1 for the B pairs of the most recent
+ *     vo_pairs_run; n_carried = 0.  The lists are sized from total_pairs as for vo_slam_stream; a restart sets their lengths
+ *     back to 0, so nothing can outgrow them.
+ *   resume = 1: vo_slam_stream's refusals — no live stream, the anchor slot was written, pair 0 does not start at the anchor,
+ *     not a chain of distinct frames, K or an option differs, total_pairs would be passed (VO_ERR_INVALID), ratio matches
+ *     (VO_ERR_UNSUPPORTED) — except the one for a lost stream: a call that ended lost IS continued.  The first usable pair then
+ *     starts a new segment by rule 3.  A call whose every pair fails leaves the stream lost, still continuable, and still holding
+ *     the map it had when tracking was lost (rule 6).
+ *   Carried between the calls, on the device: whether the stream is alive, the number of segments started and the status that
+ *     ended tracking and has not been reported yet.  So segment counts along the whole stream, and cause, at a pair that starts
+ *     a segment, is the status of the FIRST failed pair of the lost stretch even when that pair was in an earlier call.
+ *   Pose rows: row 0 of poses_pnp / poses is the previous call's last row — zeros if that frame was never localised — and is
+ *     never the first camera of a segment.  seg_poses_pnp / seg_poses [B][12] are written at a pair of THIS call that starts a
+ *     segment, pair 0 included (its first frame is the anchor).  carried_frame / carried_poses name every camera the map held
+ *     at the start of the call other than the anchor; after a call that ended lost the anchor is not in the map, so they name
+ *     ALL its cameras (n_carried <= max_cameras as before).  A segment's first camera that was started in an earlier call is
+ *     reported through the carried rows like any other carried camera.  A whole-flight row is therefore always the latest
+ *     report of a frame across the calls' own rows, seg_poses rows and carried rows; a carried frame f reports to seg_poses
+ *     row f if pair f started a segment (and to poses row 0 as well for f = 0), to poses row f otherwise.
+ *   vo_slam_map after a call: cam_frame and pt_feature[:, 0] are stream indices; the map is the last segment's, or the one
+ *     held when tracking was lost.
+ *   A flight that never fails gets vo_slam_stream's bytes in every shared output and in the map, segment = 0, cause = 0.
+ * How: k_slam_restart_stream between k_chain_pose and k_chain_triangulate of every step; the step kernels that name a pose row
+ * and k_slam_carry have a restart form (slam_kernels.hip).  A point whose key the carry marked none has nothing to clear at a
+ * restart; a key in a ghost row is cleared like any other.  The ghost rows keep alternating across segments.
+ * [deviation] none in the results; the cost is one more launch per step, and four small downloads and the alive word per call.
+ * Out of scope: several sequences per stream call, joining segments into one gauge, relocalisation against an old map, pruning
+ * points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change to the entries above. */
+int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
+                           double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
+                           int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                           double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                           int32_t* n_carried, int32_t* carried_frame /*[max_cameras]*/, double* carried_poses /*[max_cameras][12]*/,
                            int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/);
 
 /* ------------------------------------------------------------------ measurement

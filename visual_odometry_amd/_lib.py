@@ -98,6 +98,7 @@ _SIGS = {
     "vo_slam_map_size": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "vo_slam_map": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_stream": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vo_slam_stream_restart": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_chains": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_chains_restart": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_chains_map_size": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),

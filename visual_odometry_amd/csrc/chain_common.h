@@ -65,7 +65,8 @@ __device__ __forceinline__ void chain_for_each_inlier(const PairBuf& pb, int kp_
 // cameras are stored consistently with the points: camera 2 = (I, 0), camera 1 = (R^T, -R^T t).
 // initialize_map (:43-92) on pair p of the chain: p = 0 for k_chain_init, the pair that starts a new segment for
 // k_slam_restart_seqs — there the first camera goes to seg_poses[p], since pose row p belongs to the segment before (p > 0).
-__device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf cb, int p = 0)
+// row0 = false (k_slam_restart_stream in a resumed call): pose row 0 is the anchor's row of the call before, also for p = 0.
+__device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf cb, int p = 0, bool row0 = true)
 {
     __shared__ int s_w[4];
     const int tid = threadIdx.x;
@@ -80,7 +81,7 @@ __device__ __forceinline__ void chain_init_wg(PairBuf pb, int kp_cap, ChainBuf c
         const double a = c < 3 ? r.R[c * 3 + rr] : -(r.R[0 * 3 + rr] * r.t[0] + r.R[1 * 3 + rr] * r.t[1] + r.R[2 * 3 + rr] * r.t[2]);
         const double b = c < 3 ? (rr == c ? 1.0 : 0.0) : 0.0;
         cb.cam[(size_t)f1 * 12 + tid] = a; cb.cam[(size_t)f2 * 12 + tid] = b;
-        if (p == 0) cb.poses[tid] = a;
+        if (p == 0 && row0) cb.poses[tid] = a;
         if (cb.rs.st) cb.rs.seg_poses[(size_t)p * 12 + tid] = a;
         cb.poses[(size_t)(p + 1) * 12 + tid] = b;
     }

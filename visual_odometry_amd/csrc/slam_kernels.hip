@@ -11,7 +11,8 @@
 // which reads its SlamSeq descriptor and does step j of its own chain, or returns at once when its chain has fewer steps.
 // vo_slam_stream continues a map an earlier call left: k_slam_carry restates its keys at the start of such a call, and the three
 // steps that name a frame or a key have a third kernel, k_slam_*_stream — the same device function compiled with ST = true; the
-// other kernels are compiled with ST = false and carry none of it.
+// other kernels are compiled with ST = false and carry none of it.  vo_slam_stream_restart is the stream whose map restarts after
+// a lost frame: k_slam_restart_stream, and k_slam_*_stream_restart / k_slam_carry_restart — the stream kernels compiled with RS = true.
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
 // order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
 #include "chain_common.h"
@@ -47,7 +48,9 @@ __device__ __forceinline__ int slam_scan(int n, int* s_w, G&& get, W&& put)
 // camera list, and every E inlier in match order appends what the reference appends — a new point under featureid1 with its
 // observations on camera 1 and camera 2, or one observation of the point its track root owns.  Pass 1 takes every decision
 // against the map as it was before the loop (the snapshot of :154-156) and stores it; pass 2 writes, after a barrier.
-template <bool ST>
+// RS (vo_slam_stream_restart): pose row 0 of a resumed call is the anchor's row of the call before, so a segment that starts at
+// the call's pair 0 takes its first camera from seg_poses[0] like any other.
+template <bool ST, bool RS = false>
 __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
                                             ChainBuf cb, SlamBuf sb)
 {
@@ -62,7 +65,7 @@ __device__ __forceinline__ void slam_add_wg(PairBuf pb, int kp_cap, int p, int F
     if (newn > sb.cam_cap || (!first && ncam0 < 1)) return;   // cannot happen: the host sizes the list from max_cameras
     const int c1 = newn - 2, c2 = newn - 1;
     if (first) {
-        if (tid < 12) sb.m.cam_pose[tid] = p == 0 ? cb.poses[tid] : cb.rs.seg_poses[(size_t)p * 12 + tid];
+        if (tid < 12) sb.m.cam_pose[tid] = !RS && p == 0 ? cb.poses[tid] : cb.rs.seg_poses[(size_t)p * 12 + tid];
         else if (tid < 24) sb.m.cam_pose[tid] = cb.poses[(size_t)p * 12 + tid];
         if (tid < 2) sb.m.cam_frame[tid] = frame0 + p + tid;
     } else {
@@ -145,6 +148,12 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_stream(PairBuf pb, in
     slam_add_wg<true>(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_stream_restart(PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras,
+                                                                          ChainBuf cb, SlamBuf sb)
+{
+    slam_add_wg<true, true>(pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_seqs(PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras,
                                                                 const SlamSeq* __restrict__ seqs)
 {
@@ -166,6 +175,11 @@ void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double
 void launch_slam_add_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_add_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
+}
+
+void launch_slam_add_stream_restart(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_add_stream_restart, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, F, max_norm, free_cameras, cb, sb);
 }
 
 // the problem k_bundle_adjust is handed: the map's place in the lists (all 0 for a single chain), its sizes, skip or not
@@ -326,6 +340,12 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_stream(PairBuf pb,
     slam_filter_wg<true>(pb, Kd, threshold, cb, sb);
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_stream_restart(PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    if (cb.rs.st[SEG_INIT]) threshold = 0.0;                       // (a pair that starts a new segment is step 0 of it)
+    slam_filter_wg<true>(pb, Kd, threshold, cb, sb);
+}
+
 // (threshold is the step's: 0 at step 0, where initialize_map's optimize_map is only written back)
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_seqs(PairBuf pb, int kp_cap, int j, const double* Kd, double threshold,
                                                                    const SlamSeq* __restrict__ seqs)
@@ -351,6 +371,11 @@ void launch_slam_filter_stream(hipStream_t s, PairBuf pb, const double* Kd, doub
     hipLaunchKernelGGL(k_slam_filter_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
 }
 
+void launch_slam_filter_stream_restart(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_filter_stream_restart, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
+}
+
 // limit_number_of_camera_in_map (map.py:299-318): with more than max_cameras cameras, remove_camera_from_map(cameras[0])
 // (:188-232) with the quirk it has — observations are counted per point AMONG POINTS THAT STILL HAVE ONE (a defaultdict), so a
 // point left with one observation goes and a point with none stays.  A removed point leaves mappointdict: its feature id can
@@ -358,7 +383,9 @@ void launch_slam_filter_stream(hipStream_t s, PairBuf pb, const double* Kd, doub
 // camera's pose as the map holds it goes to poses_last (an evicted camera keeps its last row), the map's sizes to n_*.
 // vo_slam_stream: poses_last has the call's rows only; a camera of an earlier call reports to its carried row instead.  A point
 // whose key is none (k_slam_carry) has no entry in pt_of / in_map; pt_feat moves with pt_key.
-template <bool ST>
+// RS (vo_slam_stream_restart): row 0 of a resumed call is the anchor's, never the first camera of a segment that starts at its pair 0;
+// SEG_FIRST names a pair of this call or none (k_slam_carry_restart), so a segment's first camera of an earlier call is a carried one.
+template <bool ST, bool RS = false>
 __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     __shared__ int s_w[SLAM_WAVES];
@@ -378,7 +405,7 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
                 }
             }
             if (fr == seg0) cb.rs.seg_poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
-            if (fr != seg0 || fr == 0) sb.poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
+            if (fr != seg0 || (fr == 0 && (!RS || sb.st.frame0 == 0))) sb.poses_last[(size_t)fr * 12 + k % 12] = sb.m.cam_pose[k];
         }
         if (ncam > max_cameras) {
             for (int q = tid; q < npt; q += SLAM_THREADS) sb.tmp[q] = 0;
@@ -429,6 +456,8 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_came
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<true>(p, max_cameras, cb, sb); }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream_restart(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<true, true>(p, max_cameras, cb, sb); }
+
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_seqs(int j, int max_cameras, const SlamSeq* __restrict__ seqs)
 {
     const SlamSeq& q = seqs[blockIdx.x];
@@ -451,11 +480,20 @@ void launch_slam_limit_stream(hipStream_t s, int p, int max_cameras, ChainBuf cb
     hipLaunchKernelGGL(k_slam_limit_stream, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
 }
 
+void launch_slam_limit_stream_restart(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_limit_stream_restart, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
+}
+
 // vo_slam_chains_restart, between k_chain_pose and k_chain_triangulate of every step: the end of the step's decision.  On an
 // initial step (SEG_INIT: k_chain_gather met a good pair while the sequence was lost, or k_chain_pose a failed solvePnPRansac)
 // the pair starts a new segment — initialize_map's self.map.clean() (src/visual_slam.py:43-45): the lists restart at length 0
 // and every point's feature id leaves mappointdict (pt_of, in_map); the first frame's feature_mapper row is cleared, so no
 // track reaches behind the segment; then initialize_map on this pair (chain_init_wg).  Every pair gets its segment here.
+// ST (vo_slam_stream_restart): a point whose key k_slam_carry marked none (-1) has no entry to clear and is skipped; a key in a
+// ghost row is cleared like any other (pt_of and in_map have the ghost rows).  The state words come from the call before, so the
+// segments count along the stream; in a resumed call pose row 0 stays the anchor's (chain_init_wg, row0).
+template <bool ST>
 __device__ __forceinline__ void slam_restart_wg(PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb)
 {
     const int tid = threadIdx.x;
@@ -464,7 +502,11 @@ __device__ __forceinline__ void slam_restart_wg(PairBuf pb, int kp_cap, int p, C
         if (tid == 0) cb.rs.segment[p] = cb.alive[0] ? nseg - 1 : -1;
         return;
     }
-    for (int q = tid; q < npt; q += SLAM_THREADS) { const int key = sb.m.pt_key[q]; sb.pt_of[key] = 0; cb.in_map[key] = 0; }
+    for (int q = tid; q < npt; q += SLAM_THREADS) {
+        const int key = sb.m.pt_key[q];
+        if (ST && key < 0) continue;
+        sb.pt_of[key] = 0; cb.in_map[key] = 0;
+    }
     unsigned long long* row = cb.parent + chain_key(pb.slots[2 * p], 0, kp_cap);
     for (int i = tid; i < kp_cap; i += SLAM_THREADS) row[i] = 0;
     __syncthreads();                                           // every lane has read the state words and the old point count
@@ -473,19 +515,29 @@ __device__ __forceinline__ void slam_restart_wg(PairBuf pb, int kp_cap, int p, C
         cb.rs.st[SEG_FIRST] = p; cb.rs.st[SEG_COUNT] = nseg + 1; cb.rs.st[SEG_CAUSE] = 0;
         cb.rs.segment[p] = nseg; cb.rs.cause[p] = cause;
     }
-    chain_init_wg(pb, kp_cap, cb, p);
+    chain_init_wg(pb, kp_cap, cb, p, !ST || sb.st.frame0 == 0);
 }
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_restart_seqs(PairBuf pb, int kp_cap, int j, const SlamSeq* __restrict__ seqs)
 {
     const SlamSeq& q = seqs[blockIdx.x];
     if (j >= q.count) return;
-    slam_restart_wg(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, q.cb, q.sb);
+    slam_restart_wg<false>(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, q.cb, q.sb);
 }
 
 void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S)
 {
     hipLaunchKernelGGL(k_slam_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, seqs);
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_restart_stream(PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb)
+{
+    slam_restart_wg<true>(pb, kp_cap, p, cb, sb);
+}
+
+void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_restart_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, cb, sb);
 }
 
 // vo_slam_stream, at the start of a call that continues the map of the call before (before k_chain_link): the frames of that call
@@ -501,10 +553,15 @@ void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, cons
 //      (Its feature id for vo_slam_map was stored in pt_feat when it was added.)  The cameras beside the anchor go to the carried rows.
 //   C  every row but the anchor's and the new ghost's is cleared in parent, in_map, map_pt, pt_of, cam and cam_ok: a reused slot
 //      starts empty, as every slot does in a single call.
-__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry(SlamCarry c, ChainBuf cb, SlamBuf sb)
+// RS (vo_slam_stream_restart): after a call that ended lost the anchor frame is not in the map — every camera is a carried one, no
+// track starts in the anchor row (its pair failed) and every point loses its key, which is all the map needs to be kept for
+// vo_slam_map until a usable pair restarts it.  SEG_FIRST is an index into the pairs of the call before: it becomes none (-1).
+template <bool RS>
+__device__ __forceinline__ void slam_carry_wg(SlamCarry c, ChainBuf cb, SlamBuf sb)
 {
     const int tid = threadIdx.x, cap = c.kp_cap;
     const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1];
+    const int ncar = RS && !cb.alive[0] ? ncam : ncam - 1;
     for (int k = tid; k < cap; k += SLAM_THREADS) {
         int rf = c.anchor, ri = k;
         chain_root(cb.parent, cap, c.F + 2, rf, ri);
@@ -522,8 +579,9 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry(SlamCarry c, ChainB
     }
     if (tid < 12) cb.poses[tid] = c.keep[tid];
     else if (tid < 24) sb.poses_last[tid - 12] = c.keep[tid];
-    for (int k = tid; k < (ncam - 1) * 12; k += SLAM_THREADS) sb.st.carried_poses[k] = sb.m.cam_pose[k];
-    for (int i = tid; i < ncam - 1; i += SLAM_THREADS) sb.st.carried_frame[i] = sb.m.cam_frame[i];
+    for (int k = tid; k < ncar * 12; k += SLAM_THREADS) sb.st.carried_poses[k] = sb.m.cam_pose[k];
+    for (int i = tid; i < ncar; i += SLAM_THREADS) sb.st.carried_frame[i] = sb.m.cam_frame[i];
+    if (RS && tid == 0) cb.rs.st[SEG_FIRST] = -1;
     __syncthreads();
     for (int q = tid; q < npt; q += SLAM_THREADS) {
         const int key = sb.m.pt_key[q];
@@ -541,7 +599,16 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry(SlamCarry c, ChainB
     for (int r = tid; r < c.F; r += SLAM_THREADS) if (r != c.anchor) cb.cam_ok[r] = 0;
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry(SlamCarry c, ChainBuf cb, SlamBuf sb) { slam_carry_wg<false>(c, cb, sb); }
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry_restart(SlamCarry c, ChainBuf cb, SlamBuf sb) { slam_carry_wg<true>(c, cb, sb); }
+
 void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_carry, dim3(1), dim3(SLAM_THREADS), 0, s, c, cb, sb);
+}
+
+void launch_slam_carry_restart(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb)
+{
+    hipLaunchKernelGGL(k_slam_carry_restart, dim3(1), dim3(SLAM_THREADS), 0, s, c, cb, sb);
 }

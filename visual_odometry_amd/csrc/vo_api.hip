@@ -100,6 +100,7 @@ struct SlamStream {
     DevList mem;
     bool live = false;                    // a resume = 0 call has run and nothing has dropped the stream since
     bool lost = false;                    // its last call ended with a pair that was not localised
+    bool restart = false;                 // begun by vo_slam_stream_restart: a lost stream is continued and starts a new map
     bool touched = false;                 // the anchor slot was uploaded to or detected again: the stream's last frame is gone
     int anchor = -1;                      // slot of the stream's last frame
     int done = 0, total = 0;              // pairs so far, pairs the stream may reach (what the lists were sized for)
@@ -3012,7 +3013,7 @@ extern "C" int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* c
 // clears the scratch buffer and runs vo_slam_chain's steps; a call that continues it clears the per-pair outputs only, lets
 // k_slam_carry restate the keys (slam_kernels.hip) and runs a p >= 1 step for every pair.  The work buffers keep what the last
 // step left in them, as they do between two steps of one call.
-static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, int F, int cap, int max_pairs, int total, const vo_slam_opts* o, const double* K)
+static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, bool restart, int F, int cap, int max_pairs, int total, const vo_slam_opts* o, const double* K)
 {
     // the slot-keyed tables have two ghost rows behind the F slots.  Lists: a pair adds at most one point per match; a camera takes
     // at most kp_cap observations as a pair's second frame and kp_cap as the next pair's first (one-to-one matches), and the map
@@ -3032,6 +3033,7 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, int F, int cap, int
     sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4);
     sc.take(&st.dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
     sc.take(&cb.alive, 1); sc.take(&cb.map_count, 1); sc.take(&st.keep, 24);
+    sc.take(&cb.rs.st, restart ? 4 : 0);                              // (the segment state outlives the call, as the alive flag does)
     sc.take(&st.map_mem, st.map_bytes); sc.take(&st.snap_mem, st.map_bytes);
     sc.take(&sb.pt_of, fc); sc.take(&sb.dec, cap); sc.take(&sb.tmp, np); sc.take(&sb.idx, no);
     sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
@@ -3042,8 +3044,12 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, int F, int cap, int
     sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P); sc.take(&sb.poses_last, (P + 1) * 12);
     sc.take(&st.dchi2, 2 * P); sc.take(&st.dit, P); sc.take(&st.dtr, P);
     sc.take(&sb.st.carried_frame, cm); sc.take(&sb.st.carried_poses, cm * 12);
+    sc.take(&cb.rs.segment, restart ? P : 0); sc.take(&cb.rs.cause, restart ? P : 0);
+    sc.take(&cb.rs.seg_poses, restart ? P * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? P * 12 : 0);
     HIPCHK(st.mem.alloc(&st.base, sc.bytes));
     sc.place_at(st.base);
+    if (!restart) cb.rs = RestartBuf{};
+    st.restart = restart;
     st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
     slam_map_carve(st.map_mem, cm, np, no, &sb.m); slam_map_carve(st.snap_mem, cm, np, no, &st.snap);
     sb.m.pt_feat = reinterpret_cast<int*>(st.map_mem + o_feat); st.snap.pt_feat = reinterpret_cast<int*>(st.snap_mem + o_feat);
@@ -3054,47 +3060,57 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, int F, int cap, int
     return VO_OK;
 }
 
-extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
-                              int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
-                              double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                              int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
+// The walk of vo_slam_stream and vo_slam_stream_restart.  restart: vo_slam_chains_restart's step for the one chain of the stream —
+// k_chain_gather / k_chain_pose decide (cb.rs is set), k_slam_restart_stream joins every step, step 0 of the stream is an initial
+// step like any other — and the alive flag and the segment state words stay on the device between the calls.  Without it the
+// stream carries vo_slam_stream's launches and nothing else.
+static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
+                           int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                           double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                           int32_t* n_carried, int32_t* carried_frame, double* carried_poses,
+                           int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
 {
     if (!ctx) return VO_ERR_INVALID;
+    const char* who = restart ? "vo_slam_stream_restart" : "vo_slam_stream";
     if (!resume) drop_slam_stream(ctx);
     forget_slam_maps(ctx);
     if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run ||
         !n_carried || !carried_frame || !carried_poses) FAIL(VO_ERR_INVALID, "bad arguments");
+    if (restart && (!segment || !cause || !seg_poses_pnp || !seg_poses)) FAIL(VO_ERR_INVALID, "bad arguments");
     SlamStream& st = ctx->stream_map;
     if (resume) {
-        if (!st.live) FAIL(VO_ERR_INVALID, "vo_slam_stream: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)");
-        if (st.lost) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
-        if (st.touched) FAIL(VO_ERR_INVALID, "vo_slam_stream: slot %d, the stream's last frame, was uploaded to or detected again", st.anchor);
+        if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
+        if (st.restart != restart)
+            FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
+        if (st.lost && !restart) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
+        if (st.touched) FAIL(VO_ERR_INVALID, "%s: slot %d, the stream's last frame, was uploaded to or detected again", who, st.anchor);
     }
     int F, cap;
-    int rc = chain_check(ctx, B, "vo_slam_stream", &F, &cap); if (rc) return rc;
-    rc = slam_opts_check(ctx, o, K, B, "vo_slam_stream"); if (rc) return rc;
+    int rc = chain_check(ctx, B, who, &F, &cap); if (rc) return rc;
+    rc = slam_opts_check(ctx, o, K, B, who); if (rc) return rc;
     const int32_t* sl = ctx->last.slots.data();
     if (resume) {
         const vo_slam_opts& a = st.opts;
-        if (sl[0] != st.anchor) FAIL(VO_ERR_INVALID, "vo_slam_stream: pair 0 starts at slot %d, the stream's last frame is in slot %d", sl[0], st.anchor);
+        if (sl[0] != st.anchor) FAIL(VO_ERR_INVALID, "%s: pair 0 starts at slot %d, the stream's last frame is in slot %d", who, sl[0], st.anchor);
         if (memcmp(K, st.K, sizeof(st.K)) != 0 || o->pnp_iterations != a.pnp_iterations || o->reproj_err != a.reproj_err || o->confidence != a.confidence ||
             o->seed != a.seed || o->max_point_norm != a.max_point_norm || o->ba_iterations != a.ba_iterations || o->huber_delta != a.huber_delta ||
             o->free_cameras != a.free_cameras || o->filter_threshold != a.filter_threshold || o->max_cameras != a.max_cameras)
-            FAIL(VO_ERR_INVALID, "vo_slam_stream: K and every option but the snapshot's must be those the stream was started with");
-        if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "vo_slam_stream: %d + %d pairs pass the stream's total_pairs = %d", st.done, B, st.total);
-    } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "vo_slam_stream: total_pairs = %d is less than the call's %d pairs", total_pairs, B);
+            FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
+        if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "%s: %d + %d pairs pass the stream's total_pairs = %d", who, st.done, B, st.total);
+    } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "%s: total_pairs = %d is less than the call's %d pairs", who, total_pairs, B);
     HIPCHK(hipSetDevice(ctx->device));
     rc = ensure_rng(ctx, o->seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
     if (!resume) {
-        rc = slam_stream_allocate(ctx, st, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
+        rc = slam_stream_allocate(ctx, st, restart, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
         if (rc) { drop_slam_stream(ctx); return rc; }
         HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));              // empty feature_mapper, empty map, no cameras, zero results
         HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
     } else HIPCHK(hipMemsetAsync(st.call_mem, 0, st.call_bytes, s));
     ChainBuf cb = st.cb; SlamBuf sb = st.sb;
     sb.st.frame0 = resume ? st.done : 0;
-    sb.st.n_carried = resume ? st.last_ncam - 1 : 0;
+    // (after a call that ended lost the anchor frame is not in the map: every camera of the map is a carried one)
+    sb.st.n_carried = !resume ? 0 : restart && st.lost ? st.last_ncam : st.last_ncam - 1;
     double* dK = st.dK;
     const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
     const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
@@ -3105,13 +3121,25 @@ extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, c
     if (resume) {
         StageTimer t(ctx, ST_MISC);
         const int gn = F + (st.carries & 1);
-        launch_slam_carry(s, SlamCarry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.keep}, cb, sb);
+        const SlamCarry carry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.keep};
+        if (restart) launch_slam_carry_restart(s, carry, cb, sb);
+        else launch_slam_carry(s, carry, cb, sb);
     }
     launch_chain_link(s, ctx->pb, cap, B, cb);
     for (int p = 0; p < B; p++) {
         {
             StageTimer t(ctx, ST_MISC);
-            if (p == 0 && !resume) launch_chain_init(s, ctx->pb, cap, cb);
+            if (restart) {
+                launch_chain_gather(s, ctx->pb, cap, p, F + 2, cb);
+                if (p > 0 || resume) {
+                    launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                      ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
+                    launch_chain_pose(s, ctx->pb, p, dK, cb);
+                }
+                launch_slam_restart_stream(s, ctx->pb, cap, p, cb, sb);
+                if (p > 0 || resume) launch_chain_triangulate(s, ctx->pb, cap, p, cb);
+            }
+            else if (p == 0 && !resume) launch_chain_init(s, ctx->pb, cap, cb);
             else {
                 launch_chain_gather(s, ctx->pb, cap, p, F + 2, cb);   // (a track may end in a ghost row: two more hops at most)
                 launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
@@ -3119,7 +3147,8 @@ extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, c
                 launch_chain_pose(s, ctx->pb, p, dK, cb);
                 launch_chain_triangulate(s, ctx->pb, cap, p, cb);
             }
-            launch_slam_add_stream(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
+            if (restart) launch_slam_add_stream_restart(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
+            else launch_slam_add_stream(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
         }
         snapshot(p, 1);
         if (ba) {
@@ -3130,9 +3159,17 @@ extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, c
         }
         snapshot(p, 2);
         const bool step0 = p == 0 && !resume;
-        if (ba || (filt && !step0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter_stream(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb); }
+        if (ba || (filt && !step0)) {
+            StageTimer t(ctx, ST_SLAM_FILTER);
+            if (restart) launch_slam_filter_stream_restart(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb);
+            else launch_slam_filter_stream(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb);
+        }
         snapshot(p, 3);
-        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_stream(s, p, o->max_cameras, cb, sb); }
+        {
+            StageTimer t(ctx, ST_SLAM_LIMIT);
+            if (restart) launch_slam_limit_stream_restart(s, p, o->max_cameras, cb, sb);
+            else launch_slam_limit_stream(s, p, o->max_cameras, cb, sb);
+        }
         snapshot(p, 4);
     }
     HIPCHK(hipGetLastError());
@@ -3155,15 +3192,43 @@ extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, c
         HIPCHK(hipMemcpyAsync(carried_frame, sb.st.carried_frame, (size_t)sb.st.n_carried * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(carried_poses, sb.st.carried_poses, (size_t)sb.st.n_carried * 96, hipMemcpyDeviceToHost, s));
     }
+    int alive = 1;
+    if (restart) {
+        HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&alive, cb.alive, 4, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
     rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
     if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, st.snap, cap, &ctx->last.map[1]); if (rc) return rc; }
-    st.lost = false;
-    for (int p = 0; p < B; p++) if (status[p] != VO_OK) st.lost = true;
+    // (a restart stream is lost when the device says so: a pair that fails and a pair that restarts can share a call)
+    st.lost = restart && !alive;
+    for (int p = 0; p < B && !restart; p++) if (status[p] != VO_OK) st.lost = true;
     st.anchor = sl[2 * B - 1]; st.done = (resume ? st.done : 0) + B; st.carries = resume ? st.carries + 1 : 0;
     st.last_ncam = n_cam[B - 1]; st.touched = false; st.live = true;
     return VO_OK;
+}
+
+extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
+                              int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                              double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                              int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
+{
+    return slam_stream_run(ctx, false, resume, total_pairs, B, K, o, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run,
+                           ba_trials_run, n_carried, carried_frame, carried_poses, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
+                                      int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
+                                      double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                                      int32_t* n_carried, int32_t* carried_frame, double* carried_poses,
+                                      int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
+{
+    return slam_stream_run(ctx, true, resume, total_pairs, B, K, o, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run,
+                           ba_trials_run, n_carried, carried_frame, carried_poses, segment, cause, seg_poses_pnp, seg_poses);
 }
 
 // ------------------------------------------------------------------ the map step for S independent sequences in one call

@@ -266,10 +266,10 @@ void launch_reprojection(hipStream_t s, const double* poses, int ncam, const dou
                          const int* obs_pt, const double* obs_xy, int nobs, const double* Kd, double threshold,
                          double* sqerr, uint8_t* keep, int* bad);
 // ---- the localisation chain on resident pair results (geom_kernels.hip / pnp_kernels.hip): src/visual_slam.py:183-266
-// vo_slam_chains_restart: what a sequence needs to start a new map after a lost frame (initialize_map's self.map.clean(),
-// src/visual_slam.py:43-45).  st == nullptr everywhere else: the chain stops at the first lost frame.
+// vo_slam_chains_restart, vo_slam_stream_restart: what a sequence needs to start a new map after a lost frame (initialize_map's
+// self.map.clean(), src/visual_slam.py:43-45).  st == nullptr everywhere else: the chain stops at the first lost frame.
 enum { SEG_INIT = 0,    // 1: this step is an initial step of the sequence — its pair starts a segment as pair 0 starts a chain
-       SEG_FIRST = 1,   // the pair that started the current segment
+       SEG_FIRST = 1,   // the pair that started the current segment (vo_slam_stream_restart: of this call; -1 if an earlier call's)
        SEG_COUNT = 2,    // segments started so far
        SEG_CAUSE = 3 }; // the status that ended tracking and has not been reported yet (0: none)
 struct RestartBuf {
@@ -376,6 +376,13 @@ struct SlamCarry {
     const double* keep;                 // [2][12] the anchor camera as it entered the map / as the map last held it (the previous call's last rows)
 };
 void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb);
+// ---- ... on a stream that starts a new map after a lost frame (vo_slam_stream_restart): cb.rs is set, its state words and the
+// alive flag outlive the call.  k_slam_restart_stream goes between k_chain_pose and k_chain_triangulate of every step.
+void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb);
+void launch_slam_add_stream_restart(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
+void launch_slam_filter_stream_restart(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb);
+void launch_slam_limit_stream_restart(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb);
+void launch_slam_carry_restart(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb);
 // ---- the same step for S independent sequences at once (vo_slam_chains): one workgroup per sequence and kernel, the sequence on a
 // grid axis.  A workgroup reads its sequence's descriptor from a device array — its pairs inside the run, and a ChainBuf / SlamBuf
 // whose slot-keyed tables (parent, in_map, map_pt, cam, cam_ok, pt_of) are the shared ones (the sequences' slots are disjoint) and

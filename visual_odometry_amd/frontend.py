@@ -225,7 +225,27 @@ class FrontEnd:
         Returns slam_chain's dict (in a resumed call poses_pnp / poses row 0 is the stream's last frame of the call before, and
         snapshot=(pair, stage) counts along the call) plus carried_frame [n] and carried_poses [n, 3, 4]: the cameras the map held
         at the start of a resumed call beside that frame, by their index along the whole stream, as the map last held them
-        during this call.  slam_map()'s cam_frame and pt_feature[:, 0] count along the whole stream."""
+        during this call.  slam_map()'s cam_frame and pt_feature[:, 0] count along the whole stream.  A pair that cannot be localised
+        ends the stream; slam_stream_restart is the stream that starts a new map instead."""
+        return self._slam_stream(False, n_pairs, K, resume, total_pairs, iterations, reproj_err, confidence, seed, max_point_norm, ba_iterations,
+                                 huber_delta, free_cameras, filter_threshold, max_cameras, snapshot)
+
+    def slam_stream_restart(self, n_pairs, K, resume=False, total_pairs=None, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED,
+                            max_point_norm=50.0, ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """slam_stream on a stream that survives a lost frame (vo_slam_stream_restart): slam_chain(restart=True)'s rules on a map
+        that outlives the call.  A pair that failed in run_pairs keeps its status and leaves the stream lost; a lost stream, or one
+        whose solvePnPRansac finds no camera, starts a new map from the next usable pair — in this call or a later one.  Restart is
+        a property of the stream: one begun here is continued here (resume=True), one begun by slam_stream there.  The calls
+        together compute what slam_chain(restart=True) computes on the whole flight, byte for byte (join_stream).
+        Returns slam_stream's dict plus segment, cause [n_pairs] (segments count along the whole stream; cause may name a pair of an
+        earlier call) and seg_poses_pnp, seg_poses [n_pairs, 3, 4]: at a pair of this call that starts a segment, its first camera
+        as it entered the map and as the map last held it during this call.  After a call that ended lost the stream's last frame
+        is not in the map and carried_frame names all of the map's cameras."""
+        return self._slam_stream(True, n_pairs, K, resume, total_pairs, iterations, reproj_err, confidence, seed, max_point_norm, ba_iterations,
+                                 huber_delta, free_cameras, filter_threshold, max_cameras, snapshot)
+
+    def _slam_stream(self, restart, n_pairs, K, resume, total_pairs, iterations, reproj_err, confidence, seed, max_point_norm, ba_iterations,
+                     huber_delta, free_cameras, filter_threshold, max_cameras, snapshot):
         B = int(n_pairs)
         K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
         sp, ss = (-1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]))
@@ -236,14 +256,20 @@ class FrontEnd:
         rows = max(int(max_cameras), 1)
         nc = C.c_int32(0); cf = np.zeros(rows, np.int32); cp = np.zeros((rows, 12))
         c = self.ctx
-        rc = c.lib.vo_slam_stream(c.handle, int(bool(resume)), B if total_pairs is None else int(total_pairs), B, K.ctypes.data, C.addressof(opts),
-                                  pp.ctypes.data, pl.ctypes.data, i32["n_corr"].ctypes.data, i32["n_inl"].ctypes.data, i32["status"].ctypes.data,
-                                  i32["n_pts"].ctypes.data, i32["n_obs"].ctypes.data, i32["n_cam"].ctypes.data, chi2.ctypes.data,
-                                  i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data, C.addressof(nc), cf.ctypes.data, cp.ctypes.data)
-        c.check(rc)
+        args = [c.handle, int(bool(resume)), B if total_pairs is None else int(total_pairs), B, K.ctypes.data, C.addressof(opts),
+                pp.ctypes.data, pl.ctypes.data, i32["n_corr"].ctypes.data, i32["n_inl"].ctypes.data, i32["status"].ctypes.data,
+                i32["n_pts"].ctypes.data, i32["n_obs"].ctypes.data, i32["n_cam"].ctypes.data, chi2.ctypes.data,
+                i32["ba_iterations"].ctypes.data, i32["ba_trials"].ctypes.data, C.addressof(nc), cf.ctypes.data, cp.ctypes.data]
+        seg = {}
+        if restart:
+            seg = dict(segment=np.zeros(B, np.int32), cause=np.zeros(B, np.int32), seg_poses_pnp=np.zeros((B, 12)), seg_poses=np.zeros((B, 12)))
+            c.check(c.lib.vo_slam_stream_restart(*args, *[seg[k].ctypes.data for k in ("segment", "cause", "seg_poses_pnp", "seg_poses")]))
+            seg["seg_poses_pnp"] = seg["seg_poses_pnp"].reshape(B, 3, 4); seg["seg_poses"] = seg["seg_poses"].reshape(B, 3, 4)
+        else:
+            c.check(c.lib.vo_slam_stream(*args))
         n = nc.value
         return dict(poses_pnp=pp.reshape(B + 1, 3, 4), poses=pl.reshape(B + 1, 3, 4), chi2=chi2, carried_frame=cf[:n].copy(),
-                    carried_poses=cp[:n].reshape(n, 3, 4).copy(), **i32)
+                    carried_poses=cp[:n].reshape(n, 3, 4).copy(), **i32, **seg)
 
     def slam_chains(self, seq_lengths, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, max_point_norm=50.0,
                     ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None, restart=False):
@@ -406,6 +432,67 @@ def split_segments(segment, poses_pnp, poses, seg_poses_pnp, seg_poses):
         out.append(dict(first_pair=p, n_pairs=n, poses_pnp=np.concatenate([sp[p:p + 1], pp[p + 1:p + n + 1]]),
                         poses=np.concatenate([sl[p:p + 1], pl[p + 1:p + n + 1]])))
         p += n
+    return out
+
+
+STREAM_PAIR_KEYS = ("chi2", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")
+
+
+def join_stream(outs):
+    """The dicts the calls of one stream returned, in order (slam_stream, or slam_stream_restart) -> the whole flight's dict: what
+    slam_chain, or slam_chain(restart=True) without `segments`, returns for all the pairs at once.  Pure: no GPU, no library.
+    Per-pair arrays are concatenated; poses_pnp joins on the anchor rows (row 0 of a resumed call is the last row of the call
+    before).  poses, and seg_poses of a restart stream, take the LATEST report of every frame: a call's own rows, then its seg_poses
+    rows, then its carried rows — a carried frame that is the first camera of a segment (the frame of the pair that started it)
+    reports to seg_poses, and to poses as well if it is frame 0; any other to poses.  With the restart keys the result has segment,
+    cause, seg_poses_pnp, seg_poses and split_segments works on it unchanged.
+    ValueError on what the library cannot produce: an anchor row of poses_pnp that differs between two calls, segment numbers that
+    go backwards, a carried frame that is not earlier than its call's first frame."""
+    outs = list(outs)
+    if not outs:
+        raise ValueError("join_stream takes at least one call")
+    restart = "segment" in outs[0]
+    if any(("segment" in o) != restart for o in outs):
+        raise ValueError("the calls of one stream all have the restart keys or none has")
+    out = {k: np.concatenate([np.asarray(o[k]) for o in outs]) for k in STREAM_PAIR_KEYS if k in outs[0]}
+    pnp = [np.asarray(o["poses_pnp"], np.float64).reshape(-1, 3, 4) for o in outs]
+    for c in range(1, len(outs)):
+        if not np.array_equal(pnp[c][0], pnp[c - 1][-1]):
+            raise ValueError(f"poses_pnp row 0 of call {c} is not the last row of call {c - 1}: these are not consecutive calls of one stream")
+    out["poses_pnp"] = np.concatenate([pnp[0]] + [a[1:] for a in pnp[1:]])
+    P = len(out["poses_pnp"]) - 1
+    starts = np.zeros(P, bool)
+    if restart:
+        seg = np.concatenate([np.asarray(o["segment"]).ravel() for o in outs])
+        last = -1
+        for p, k in enumerate(seg):
+            if k < 0:
+                continue
+            if k < last or k > last + 1:
+                raise ValueError(f"pair {p} is in segment {int(k)} after segment {last}: segments are numbered in order of start along the stream")
+            starts[p] = k != last
+            last = int(k)
+        out["segment"] = seg
+        out["cause"] = np.concatenate([np.asarray(o["cause"]).ravel() for o in outs])
+        out["seg_poses_pnp"] = np.concatenate([np.asarray(o["seg_poses_pnp"], np.float64).reshape(-1, 3, 4) for o in outs])
+        seg_poses = np.concatenate([np.asarray(o["seg_poses"], np.float64).reshape(-1, 3, 4) for o in outs])
+    poses = np.zeros((P + 1, 3, 4))
+    at = 0
+    for c, o in enumerate(outs):
+        own = np.asarray(o["poses"], np.float64).reshape(-1, 3, 4)
+        poses[at:at + len(own)] = own
+        for f, T in zip(np.asarray(o["carried_frame"]).ravel(), np.asarray(o["carried_poses"], np.float64).reshape(-1, 3, 4)):
+            f = int(f)
+            if f < 0 or f >= at:
+                raise ValueError(f"call {c} carries frame {f}, which is not earlier than its first frame {at}")
+            if restart and starts[f]:
+                seg_poses[f] = T
+            if not (restart and starts[f]) or f == 0:
+                poses[f] = T
+        at += len(own) - 1
+    out["poses"] = poses
+    if restart:
+        out["seg_poses"] = seg_poses
     return out
 
 
