@@ -356,6 +356,15 @@ int vo_frame_features_sift(vo_ctx* ctx, int slot, float* kp_xy, float* kp_size, 
  * zero.  Operand rows past n keep what an earlier frame left in the slot.  Needs vo_batch_configure_sift; synchronous. */
 int vo_stage_sift_rows(vo_ctx* ctx, int slot, const uint8_t* rows /*[n][128]*/, int n, const float* xy /*[n][2] or NULL*/);
 
+/* Parity seam of the Hamming matchers — a TEST seam, the ORB counterpart of vo_stage_sift_rows: rows[n][32] (0 <= n <=
+ * vo_batch_kp_capacity) become slot `slot` exactly as a detection of that one slot would leave them: the descriptors, the keypoint
+ * count, the flags clear, kp_xy = xy[n][2] (zeros when NULL), size / angle / response / octave zero, and the matrix-core matcher's
+ * operand image of the slot in the format the kernel chosen by vo_set_matcher_kernel reads (when that differs from the image the
+ * other slots hold, they are expanded again, as after a detection).  Descriptor rows past n keep what an earlier frame left in
+ * the slot.  vo_frame_features returns what was put in.  Needs vo_batch_configure (VO_ERR_NOT_CONFIGURED without, or in SIFT
+ * mode); VO_ERR_INVALID for a bad slot, n < 0, n > capacity, or rows == NULL with n > 0; synchronous. */
+int vo_stage_orb_rows(vo_ctx* ctx, int slot, const uint8_t* rows /*[n][32]*/, int n, const float* xy /*[n][2] or NULL*/);
+
 /* cv2.imread(filename) for a .jpg — /root/reference/src/visual_slam.py:346 (also triangulate_points_from_images.py:14-15,
  * feature_detection.py:5,10).  What cv2 does with such a file is libjpeg-turbo's default decompression: baseline Huffman
  * decoding, the 13-bit integer IDCT (JDCT_ISLOW), triangle-filter ("fancy") chroma upsampling, fixed-point YCbCr -> RGB,

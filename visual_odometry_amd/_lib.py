@@ -124,6 +124,7 @@ _SIGS = {
     "vo_batch_configure_sift": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "vo_frame_features_sift": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "vo_stage_sift_rows": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "vo_stage_orb_rows": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "vo_jpeg_info": (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, _P]),
     "vo_jpeg_decode": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, _P]),
     "vo_jpeg_decode_batch": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_int]),

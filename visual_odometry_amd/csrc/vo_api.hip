@@ -167,7 +167,7 @@ struct vo_ctx {
     bool ev_ready = false;
     hipEvent_t ev_det = nullptr;          // end of the most recent vo_frames_detect_async (vo_detect_after waits on it)
     bool ev_det_set = false;
-    int descx_fp4 = 0;                    // operand image the resident frames' desc_x currently holds (written at detection)
+    int descx_fp4 = -1;                   // operand image EVERY resident slot's desc_x holds: 1 FP4, 0 int8, -1 none written yet (descx_begin_write)
     int matcher_kernel = 2;               // 2: block-scaled FP4 MFMA (default), 0: int8 MFMA on +127/-127 bytes, 1: XOR + popcount
     CommShared* cs = nullptr;             // RCCL communicator of the trajectory gather: ONE per process, shared by its contexts (vo_comm_share)
     Growable<double> rec_send, rec_recv;  // the gather's packed records: this rank's and every rank's
@@ -419,6 +419,7 @@ static int alloc_cv2(vo_ctx* ctx)
 static void free_config(vo_ctx* c)
 {
     c->configured = c->cv2_ready = false;
+    c->descx_fp4 = -1;
     c->orb_mem.release();
     c->pb_mem.release();
     c->pb_pairs = c->pb_cap = 0;
@@ -483,6 +484,24 @@ static int launch_hamming_nn(const vo_ctx* ctx, const PairBuf& pb, const uint8_t
 {
     if (nn_kernel(ctx, cap) == NN_POPCOUNT) { launch_match_nn_popcount(ctx->stream, desc, kp_count, cap, pb, P, dirs, knn2); return 0; }
     return launch_match_nn(ctx->stream, desc_x, kp_count, cap, desc_x_rows(cap), pb, P, dirs, knn2, fp4);
+}
+
+// Slots first .. first + n - 1 of the ORB configuration are about to get the operand image nn_kernel selects now; returns it (1:
+// FP4).  ONE flag names the image of every resident slot, so when a writer of some slots changes it — the setter was called
+// between two detections — the slots outside its range are expanded again from ff.desc in the new format (a slot never written
+// has count 0: no rows).  A run whose format does not change, and the first writer after a configure, launch nothing.
+static int descx_begin_write(vo_ctx* ctx, int first, int n)
+{
+    const PyrGeom& g = ctx->g;
+    const int fp4 = nn_kernel(ctx, g.kp_cap) == NN_FP4, cx = desc_x_rows(g.kp_cap), F = ctx->max_frames;
+    if (ctx->descx_fp4 >= 0 && ctx->descx_fp4 != fp4) {
+        const FrameFeat& ff = ctx->ff;
+        launch_desc_expand(ctx->stream, ff.desc, ff.kp_count, g.kp_cap, cx, ctx->desc_x, first, fp4);
+        const int a = first + n;
+        launch_desc_expand(ctx->stream, ff.desc + (size_t)a * g.kp_cap * 32, ff.kp_count + a, g.kp_cap, cx, ctx->desc_x + (size_t)a * cx * 256, F - a, fp4);
+    }
+    ctx->descx_fp4 = fp4;
+    return fp4;
 }
 
 extern "C" int vo_set_matcher_kernel(vo_ctx* ctx, int kind)
@@ -637,7 +656,7 @@ static Batch batch(const vo_ctx* ctx)
     }
     const PyrGeom& g = ctx->g;
     return {false, ctx->configured, ctx->w, ctx->h, ctx->max_frames, ctx->max_pairs, g.kp_cap, ctx->ff.desc, ctx->desc_x, ctx->ff.kp_xy,
-            ctx->ff.kp_count, ctx->ff.flags, nullptr, ctx->descx_fp4, ctx->pyr + g.lv[0].off, g.lv[0].stride, (size_t)g.frame_bytes};
+            ctx->ff.kp_count, ctx->ff.flags, nullptr, ctx->descx_fp4 > 0, ctx->pyr + g.lv[0].off, g.lv[0].stride, (size_t)g.frame_bytes};
 }
 
 // Bytes from the first byte of a host image (stack) to the last byte of its last row: n frames at frame_stride, h rows of row_bytes
@@ -797,8 +816,8 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
     {
         StageTimer t(ctx, ST_BRIEF);
         const int cx = desc_x_rows(g.kp_cap);
-        ctx->descx_fp4 = nn_kernel(ctx, g.kp_cap) == NN_FP4;
-        launch_brief(s, blur, g, ff, F, ctx->desc_x + (size_t)first_slot * cx * 256, cx, ctx->descx_fp4);
+        const int fp4 = descx_begin_write(ctx, first_slot, F);
+        launch_brief(s, blur, g, ff, F, ctx->desc_x + (size_t)first_slot * cx * 256, cx, fp4);
     }
     return VO_OK;
 }
@@ -928,6 +947,40 @@ extern "C" int vo_frame_features(vo_ctx* ctx, int slot, float* kp_xy, float* kp_
     const int rc = download_keypoints(ctx, {ff.kp_xy, ff.kp_size, ff.kp_angle, ff.kp_resp, ff.kp_level, ff.desc, 32}, (size_t)slot * ctx->g.kp_cap, n,
                                       kp_xy, kp_size, kp_angle, kp_response, kp_octave, desc);
     return rc ? rc : warn;
+}
+
+// Parity seam of the Hamming matchers (a test seam, not a production entry): n descriptor rows the caller chose become slot `slot`
+// exactly as a detection of that one slot would leave them — ff.desc rows 0 .. n - 1, kp_count = n, kp_xy = xy (zeros without),
+// size / angle / response / octave / level zero for those rows, the flags clear, and the matcher's operand image of the slot
+// written by k_desc_expand in the format nn_kernel selects now.  ff.desc rows past n keep what an earlier, fuller frame left
+// there: k_nn_pairs has to bound its reads by the count alone.
+extern "C" int vo_stage_orb_rows(vo_ctx* ctx, int slot, const uint8_t* rows, int n, const float* xy)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (ctx->detector != 0 || !ctx->configured) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    const PyrGeom& g = ctx->g;
+    if (slot < 0 || slot >= ctx->max_frames) FAIL(VO_ERR_INVALID, "bad slot");
+    if (n < 0 || n > g.kp_cap || (n > 0 && !rows)) FAIL(VO_ERR_INVALID, "0 <= n <= kp_cap rows are needed");
+    slam_stream_slots_written(ctx, slot, 1);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));                        // an asynchronous detection may still be writing the slot
+    const FrameFeat& ff = ctx->ff;
+    const size_t o = (size_t)slot * g.kp_cap;
+    HIPCHK(hipMemsetAsync(ff.flags + slot, 0, sizeof(int), s));
+    HIPCHK(hipMemcpyAsync(ff.kp_count + slot, &n, sizeof(int), hipMemcpyHostToDevice, s));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(ff.desc + o * 32, rows, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        if (xy) HIPCHK(hipMemcpyAsync(ff.kp_xy + o * 2, xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+        else HIPCHK(hipMemsetAsync(ff.kp_xy + o * 2, 0, (size_t)n * 2 * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(ff.kp_size + o, 0, (size_t)n * sizeof(float), s)); HIPCHK(hipMemsetAsync(ff.kp_angle + o, 0, (size_t)n * sizeof(float), s));
+        HIPCHK(hipMemsetAsync(ff.kp_resp + o, 0, (size_t)n * sizeof(float), s)); HIPCHK(hipMemsetAsync(ff.kp_level + o, 0, (size_t)n * sizeof(int), s));
+    }
+    const int cx = desc_x_rows(g.kp_cap), fp4 = descx_begin_write(ctx, slot, 1);
+    launch_desc_expand(s, ff.desc + o * 32, ff.kp_count + slot, g.kp_cap, cx, ctx->desc_x + (size_t)slot * cx * 256, 1, fp4);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));                        // (the caller's rows, xy and n have been read)
+    return VO_OK;
 }
 
 // upload one host image (any channel count) into slot 0 and build its gray level 0

@@ -141,6 +141,24 @@ class FrontEnd:
         c = self.ctx
         c.check(c.lib.vo_stage_sift_rows(c.handle, int(slot), r.ctypes.data, len(r), _lib.ptr(p)))
 
+    def set_orb_rows(self, slot, rows, xy=None):
+        """ORB mode's parity seam (vo_stage_orb_rows): rows [n, 32] uint8 become the slot's descriptors as a detection of that slot
+        would leave them (desc, count, flags, the operand image of the matcher kernel selected now); xy [n, 2] float32 pixel
+        positions, zeros when None.  Descriptor rows past n keep what the slot held before."""
+        if self.detector != "orb":
+            raise ValueError("set_orb_rows needs detector='orb'")
+        r = np.asarray(rows)
+        if r.dtype != np.uint8 or r.ndim != 2 or r.shape[1] != 32:
+            raise ValueError("rows must be [n, 32] uint8")
+        r = np.ascontiguousarray(r)
+        p = None
+        if xy is not None:
+            p = np.ascontiguousarray(xy, dtype=np.float32)
+            if p.shape != (len(r), 2):
+                raise ValueError("xy must be [n, 2]")
+        c = self.ctx
+        c.check(c.lib.vo_stage_orb_rows(c.handle, int(slot), r.ctypes.data, len(r), _lib.ptr(p)))
+
     def make_opts(self, match_mode=MATCH_CROSSCHECK, ratio=0.75, prob=0.99, thresh=1.0, max_iters=1000,
                   seed=OPENCV_RNG_SEED, dist_thresh=50.0, want_points=False):
         return _lib.PairOpts(int(match_mode), float(ratio), float(prob), float(thresh), int(max_iters), int(seed),
