@@ -543,7 +543,7 @@ int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[
  * one: the reference finds nothing under it at every later frame and adds a new point each time (:139-146).  A point no track
  * can reach any more keeps its place in the lists and in the bundle adjustment, as in the reference, but has no key.
  * [deviation] none in the results; the per-call cost is one k_slam_carry launch and the download of the map for vo_slam_map.
- * Out of scope: several sequences per call, pruning points that have lost every
+ * Several sequences per stream call: vo_slam_streams, below.  Out of scope: pruning points that have lost every
  * observation (the reference keeps them: the lists and k_bundle_adjust's cost grow with the flight), relocalisation against an
  * earlier map, and any change to the entries above. */
 int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
@@ -651,14 +651,62 @@ int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/,
  * and k_slam_carry have a restart form (slam_kernels.hip).  A point whose key the carry marked none has nothing to clear at a
  * restart; a key in a ghost row is cleared like any other.  The ghost rows keep alternating across segments.
  * [deviation] none in the results; the cost is one more launch per step, and four small downloads and the alive word per call.
- * Out of scope: several sequences per stream call, joining segments into one gauge, relocalisation against an old map, pruning
- * points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change to the entries above. */
+ * Several sequences per stream call: vo_slam_streams, below.  Out of scope: joining segments into one gauge, relocalisation
+ * against an old map, pruning points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change
+ * to the entries above. */
 int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
                            double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
                            int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
                            double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run,
                            int32_t* n_carried, int32_t* carried_frame /*[max_cameras]*/, double* carried_poses /*[max_cameras][12]*/,
                            int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/);
+
+/* ------------------------------------------------------------------ S restart streams at once, carried from call to call
+ * One stream is one workgroup per kernel; several long flights (several cameras, or one flight cut into shards) are what runs in
+ * parallel, and vo_slam_chains needs every frame of every flight resident in one vo_pairs_run.  vo_slam_streams is
+ * vo_slam_stream_restart for S sequences in one call, laid out as vo_slam_chains_restart lays them out.  The contract is one
+ * equality: for every sequence s the calls together compute the bytes a vo_slam_stream_restart stream computes for that flight
+ * alone with the same chunking (so, by that entry's contract, the bytes of vo_slam_chains_restart with S = 1 on the whole
+ * flight) — whatever the other sequences do, in whatever order they are listed, whichever slots they use.
+ *   B = seq_off[S] is all the pairs of the most recent vo_pairs_run (want_points); sequence s is its pairs seq_off[s] ..
+ *     seq_off[s + 1] - 1, B_s of them.  Per-pair outputs [B] are indexed by the pair's position in the run, sequence s owns the
+ *     pose rows seq_off[s] + s .. seq_off[s + 1] + s, and segment, cause, seg_poses_pnp, seg_poses are vo_slam_chains_restart's
+ *     with vo_slam_stream_restart's meaning in a resumed call.  n_carried [S], carried_frame [S][max_cameras] and carried_poses
+ *     [S][max_cameras][12] are vo_slam_stream_restart's per sequence; carried_frame counts along the sequence's own stream.
+ *     opts->snapshot_pair counts along the call's pairs of sequence snapshot_seq.
+ *   resume = 0 starts the stream and drops the one it replaces: every B_s >= 1; vo_slam_chains_restart's checks (NO FRAME SLOT
+ *     MAY BELONG TO TWO SEQUENCES, every sequence a chain of distinct frames, ratio matches VO_ERR_UNSUPPORTED);
+ *     total_pairs[s] >= B_s sizes sequence s's lists once by vo_slam_stream's formulas.  The slot-keyed tables get two ghost rows
+ *     per sequence behind the max_frames slots, rows max_frames + 2 s and + 2 s + 1 (max_frames + 2 S < 2^20).
+ *   resume = 1 continues it: the same S, K and options (the snapshot's excepted); total_pairs is ignored.  Pair 0 of every
+ *     sequence that advances starts at that sequence's anchor slot, the slot of its last frame.  B_s = 0 IS ALLOWED — seq_off is
+ *     then only non-decreasing — as long as one sequence advances: an idle sequence keeps its anchor, its map and its restart
+ *     state, owns one pose row (its anchor's, unchanged), reports n_carried[s] = 0, and continues in a later call as if the
+ *     idle calls had not happened.
+ *   The slot rule: after any call every slot except the S anchor slots is free for any sequence; an idle sequence holds only
+ *     its anchor.  (Every sequence is carried at the start of every resumed call, advancing or not, and a carry clears the rows
+ *     of the slots its own sequence's frames had and no others.)
+ *   Refusals (VO_ERR_INVALID; the whole stream stays as it was and continuable): no live multi-stream; another S; an
+ *     advancing sequence whose anchor slot was uploaded to or detected again; any anchor slot, an idle sequence's included, among
+ *     another sequence's pairs; a pair 0 that does not start at its anchor; total_pairs[s] would be passed; K or an option
+ *     changed; every sequence idle.  Ratio matches: VO_ERR_UNSUPPORTED.
+ *   Stream kinds: vo_slam_stream and vo_slam_stream_restart refuse to continue a stream begun here and vo_slam_streams refuses
+ *     to continue one of theirs (VO_ERR_INVALID, the stream unharmed); a resume = 0 call of any of the three drops whatever
+ *     stream there is, as a configure call or a vo_slam_chain* call does.
+ *   Maps: vo_slam_chains_map_size / vo_slam_chains_map report sequence seq after every call (which = 1: the snapshot, for seq ==
+ *     snapshot_seq), cam_frame and pt_feature[:, 0] counted along that sequence's own stream; vo_slam_map reports sequence 0.
+ * How: vo_slam_chains_restart's host loop — every kernel once per step j = 0 .. max B_s - 1 with the sequence on a grid axis —
+ * on the stream / restart kernel bodies (k_slam_*_stream_restart_seqs), with one k_slam_carry_restart_seqs launch in front.
+ * [deviation] none in the results.
+ * Out of scope: a multi-stream without restart, sequences that join or leave a live stream, sequences that share a slot, joining
+ * segments or shards into one gauge, relocalisation, pruning, ratio matches. */
+int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs /*[S]*/, const int32_t* seq_off /*[S+1]*/,
+                    const double* K, const vo_slam_opts* opts, int snapshot_seq,
+                    double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
+                    int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam /*[B] each*/,
+                    double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run /*[B] each*/,
+                    int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/,
+                    int32_t* n_carried /*[S]*/, int32_t* carried_frame /*[S][max_cameras]*/, double* carried_poses /*[S][max_cameras][12]*/);
 
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the

@@ -13,6 +13,8 @@
 // steps that name a frame or a key have a third kernel, k_slam_*_stream — the same device function compiled with ST = true; the
 // other kernels are compiled with ST = false and carry none of it.  vo_slam_stream_restart is the stream whose map restarts after
 // a lost frame: k_slam_restart_stream, and k_slam_*_stream_restart / k_slam_carry_restart — the stream kernels compiled with RS = true.
+// vo_slam_streams carries S such maps at once: k_slam_*_stream_restart_seqs, the same bodies with the sequence on the grid axis, and
+// k_slam_carry_restart_seqs, whose workgroups clear the rows their own sequence held and no others (SQ = true).
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
 // order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
 #include "chain_common.h"
@@ -165,6 +167,20 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_seqs(PairBuf pb, int 
 void launch_slam_add_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S)
 {
     hipLaunchKernelGGL(k_slam_add_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, F, max_norm, free_cameras, seqs);
+}
+
+// vo_slam_streams, step j: workgroup = sequence; one that is idle in this call (count = 0) or has ended returns at once
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_add_stream_restart_seqs(PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras,
+                                                                               const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_add_wg<true, true>(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, F, max_norm, free_cameras, q.cb, q.sb);
+}
+
+void launch_slam_add_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_add_stream_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, F, max_norm, free_cameras, seqs);
 }
 
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb)
@@ -361,6 +377,20 @@ void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const
     hipLaunchKernelGGL(k_slam_filter_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, Kd, threshold, seqs);
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_filter_stream_restart_seqs(PairBuf pb, int kp_cap, int j, const double* Kd, double threshold,
+                                                                                  const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    if (q.cb.rs.st[SEG_INIT]) threshold = 0.0;                     // (a pair that starts a new segment is step 0 of it)
+    slam_filter_wg<true>(chain_pairs_from(pb, q.first, kp_cap), Kd, threshold, q.cb, q.sb);
+}
+
+void launch_slam_filter_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_filter_stream_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, Kd, threshold, seqs);
+}
+
 void launch_slam_filter(hipStream_t s, PairBuf pb, const double* Kd, double threshold, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_filter, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
@@ -470,6 +500,18 @@ void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq
     hipLaunchKernelGGL(k_slam_limit_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, j, max_cameras, seqs);
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream_restart_seqs(int j, int max_cameras, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_limit_wg<true, true>(j, max_cameras, q.cb, q.sb);
+}
+
+void launch_slam_limit_stream_restart_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_limit_stream_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, j, max_cameras, seqs);
+}
+
 void launch_slam_limit(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_limit, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb);
@@ -540,6 +582,18 @@ void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, Ch
     hipLaunchKernelGGL(k_slam_restart_stream, dim3(1), dim3(SLAM_THREADS), 0, s, pb, kp_cap, p, cb, sb);
 }
 
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_restart_stream_seqs(PairBuf pb, int kp_cap, int j, const SlamSeq* __restrict__ seqs)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_restart_wg<true>(chain_pairs_from(pb, q.first, kp_cap), kp_cap, j, q.cb, q.sb);
+}
+
+void launch_slam_restart_stream_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S)
+{
+    hipLaunchKernelGGL(k_slam_restart_stream_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, pb, kp_cap, j, seqs);
+}
+
 // vo_slam_stream, at the start of a call that continues the map of the call before (before k_chain_link): the frames of that call
 // lose their slots, so every key that still matters is restated in rows that stay.  Integers and copies only; one workgroup, its
 // phases separated by barriers; the result is a function of the tables alone (a lane owns a keypoint, a point or a table entry).
@@ -556,15 +610,18 @@ void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, Ch
 // RS (vo_slam_stream_restart): after a call that ended lost the anchor frame is not in the map — every camera is a carried one, no
 // track starts in the anchor row (its pair failed) and every point loses its key, which is all the map needs to be kept for
 // vo_slam_map until a usable pair restarts it.  SEG_FIRST is an index into the pairs of the call before: it becomes none (-1).
-template <bool RS>
-__device__ __forceinline__ void slam_carry_wg(SlamCarry c, ChainBuf cb, SlamBuf sb)
+// SQ (vo_slam_streams): the tables are shared with other sequences, whose workgroups carry their own maps in the same launch.  This
+// sequence's tracks and keys live in its anchor row, its two ghost rows and the rows of the slots its last call's frames had; step C
+// clears exactly those of them that are not kept — rows[0 .. n_rows - 1] — and a walk is bounded by all the rows of the table (hops).
+template <bool RS, bool SQ = false>
+__device__ __forceinline__ void slam_carry_wg(SlamCarry c, ChainBuf cb, SlamBuf sb, int hops = 0, const int* rows = nullptr, int n_rows = 0)
 {
     const int tid = threadIdx.x, cap = c.kp_cap;
     const int ncam = sb.m.cnt[0], npt = sb.m.cnt[1];
     const int ncar = RS && !cb.alive[0] ? ncam : ncam - 1;
     for (int k = tid; k < cap; k += SLAM_THREADS) {
         int rf = c.anchor, ri = k;
-        chain_root(cb.parent, cap, c.F + 2, rf, ri);
+        chain_root(cb.parent, cap, SQ ? hops : c.F + 2, rf, ri);
         const size_t g = chain_key(c.ghost_new, k, cap);
         int own = 0; uint8_t in = 0; double X[3] = {0, 0, 0};
         if (rf != c.anchor) {                                   // (a root in the anchor row is the keypoint itself: tracks are one-to-one)
@@ -589,6 +646,19 @@ __device__ __forceinline__ void slam_carry_wg(SlamCarry c, ChainBuf cb, SlamBuf 
         const int row = key / cap;
         if (row != c.anchor && row != c.ghost_new) sb.m.pt_key[q] = -1;
     }
+    if (SQ) {
+        for (int n = 0; n < n_rows; n++) {
+            const int r = rows[n];
+            const size_t at = chain_key(r, 0, cap);
+            for (int k = tid; k < cap; k += SLAM_THREADS) { cb.parent[at + k] = 0; cb.in_map[at + k] = 0; sb.pt_of[at + k] = 0; }
+            for (int k = tid; k < 3 * cap; k += SLAM_THREADS) cb.map_pt[3 * at + k] = 0.0;
+            if (r < c.F) {                                          // a frame slot: its camera goes too; a ghost row has none
+                if (tid < 12) cb.cam[(size_t)r * 12 + tid] = 0.0;
+                if (tid == 0) cb.cam_ok[r] = 0;
+            }
+        }
+        return;
+    }
     for (int r = 0; r < c.F + 2; r++) {
         if (r == c.anchor || r == c.ghost_new) continue;
         const size_t at = chain_key(r, 0, cap);
@@ -611,4 +681,19 @@ void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb)
 void launch_slam_carry_restart(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb)
 {
     hipLaunchKernelGGL(k_slam_carry_restart, dim3(1), dim3(SLAM_THREADS), 0, s, c, cb, sb);
+}
+
+// vo_slam_streams: every sequence of the stream is carried at the start of every resumed call, also one that is idle in it (a
+// carry of a carried map moves the ghost entries to the other ghost row and changes nothing else), so after the launch a
+// sequence holds its anchor row and one ghost row and every other slot is free for any sequence.
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry_restart_seqs(const SlamSeq* __restrict__ seqs, const SlamSeqCarry* __restrict__ car)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    const SlamSeqCarry& c = car[blockIdx.x];
+    slam_carry_wg<true, true>(c.c, q.cb, q.sb, c.hops, c.rows, c.n_rows);
+}
+
+void launch_slam_carry_restart_seqs(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, int S)
+{
+    hipLaunchKernelGGL(k_slam_carry_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, seqs, car);
 }

@@ -113,6 +113,22 @@ struct SlamStream {
     ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; SlamMap snap{};
     double *dK = nullptr, *dchi2 = nullptr, *keep = nullptr; int *dit = nullptr, *dtr = nullptr;
     uint8_t *map_mem = nullptr, *snap_mem = nullptr; size_t map_bytes = 0;
+    // vo_slam_streams: S sequences in the one allocation.  The scalars above that describe the one sequence of vo_slam_stream*
+    // (anchor, done, total, last_ncam, lost, touched) are per sequence here; `carries` counts the resumed calls — every sequence is
+    // carried in each — and cb / sb / D / snap name the whole arrays, of which a sequence's descriptor owns its ranges.
+    struct Seq {
+        int anchor = -1, done = 0, total = 0, last_ncam = 0;
+        bool lost = false, touched = false;
+        int n_rows = 0;                   // slots its last call's frames had, the anchor excepted: rows[s * (max_pairs + 1) ..]
+        SlamSeq at{};                     // its descriptor before a call's offsets: the ranges of the lists that are its own
+        size_t np = 0, no = 0;            // points and observations its lists hold
+    };
+    bool multi = false;                   // begun by vo_slam_streams
+    int S = 0;
+    std::vector<Seq> seq;
+    std::vector<int32_t> rows;
+    SlamSeq* dseq = nullptr; SlamSeqCarry* dcar = nullptr; int* drows = nullptr;
+    size_t snap_np = 0, snap_no = 0;
 };
 
 struct vo_ctx {
@@ -213,15 +229,18 @@ template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
 
 static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
 
-// The end of a stream: vo_destroy (the context's destructor), a configure call, a vo_slam_stream that starts a new one and every
-// vo_slam_chain* call come here.  (Every call that uses the allocation has waited for the context's stream before it returned.)
+// The end of a stream: vo_destroy (the context's destructor), a configure call, a vo_slam_stream[_restart] or vo_slam_streams that
+// starts a new one and every vo_slam_chain* call come here.  (Every call that uses the allocation has waited for the context's stream before it returned.)
 static void drop_slam_stream(vo_ctx* ctx) { ctx->stream_map = SlamStream(); }
 
-// An upload, ingest or detection into slots first .. first + n - 1: if the stream's last frame is among them, no call can continue it.
+// An upload, ingest or detection into slots first .. first + n - 1: if the stream's last frame is among them, no call can continue it
+// (vo_slam_streams: the sequence whose last frame it is cannot advance any more; the others can).
 static void slam_stream_slots_written(vo_ctx* ctx, int first, int n)
 {
     SlamStream& st = ctx->stream_map;
     if (st.live && st.anchor >= first && st.anchor < first + n) st.touched = true;
+    for (SlamStream::Seq& q : st.seq)
+        if (st.live && q.anchor >= first && q.anchor < first + n) q.touched = true;
 }
 
 // The device memory of one call: typed sub-buffers of ctx->scratch, each on a 256-byte boundary.  take() names a pointer
@@ -3113,6 +3132,15 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, bool restart, int F
     return VO_OK;
 }
 
+// K and every option but the snapshot's are those the stream was started with
+static bool slam_stream_same_setup(const SlamStream& st, const double* K, const vo_slam_opts* o)
+{
+    const vo_slam_opts& a = st.opts;
+    return memcmp(K, st.K, sizeof(st.K)) == 0 && o->pnp_iterations == a.pnp_iterations && o->reproj_err == a.reproj_err && o->confidence == a.confidence &&
+           o->seed == a.seed && o->max_point_norm == a.max_point_norm && o->ba_iterations == a.ba_iterations && o->huber_delta == a.huber_delta &&
+           o->free_cameras == a.free_cameras && o->filter_threshold == a.filter_threshold && o->max_cameras == a.max_cameras;
+}
+
 // The walk of vo_slam_stream and vo_slam_stream_restart.  restart: vo_slam_chains_restart's step for the one chain of the stream —
 // k_chain_gather / k_chain_pose decide (cb.rs is set), k_slam_restart_stream joins every step, step 0 of the stream is an initial
 // step like any other — and the alive flag and the segment state words stay on the device between the calls.  Without it the
@@ -3133,6 +3161,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     SlamStream& st = ctx->stream_map;
     if (resume) {
         if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
+        if (st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by vo_slam_streams and is continued only by it", who);
         if (st.restart != restart)
             FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
         if (st.lost && !restart) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
@@ -3143,12 +3172,8 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     rc = slam_opts_check(ctx, o, K, B, who); if (rc) return rc;
     const int32_t* sl = ctx->last.slots.data();
     if (resume) {
-        const vo_slam_opts& a = st.opts;
         if (sl[0] != st.anchor) FAIL(VO_ERR_INVALID, "%s: pair 0 starts at slot %d, the stream's last frame is in slot %d", who, sl[0], st.anchor);
-        if (memcmp(K, st.K, sizeof(st.K)) != 0 || o->pnp_iterations != a.pnp_iterations || o->reproj_err != a.reproj_err || o->confidence != a.confidence ||
-            o->seed != a.seed || o->max_point_norm != a.max_point_norm || o->ba_iterations != a.ba_iterations || o->huber_delta != a.huber_delta ||
-            o->free_cameras != a.free_cameras || o->filter_threshold != a.filter_threshold || o->max_cameras != a.max_cameras)
-            FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
+        if (!slam_stream_same_setup(st, K, o)) FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
         if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "%s: %d + %d pairs pass the stream's total_pairs = %d", who, st.done, B, st.total);
     } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "%s: total_pairs = %d is less than the call's %d pairs", who, total_pairs, B);
     HIPCHK(hipSetDevice(ctx->device));
@@ -3514,6 +3539,323 @@ extern "C" int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off
 {
     return slam_chains_run(ctx, true, S, seq_off, K, o, snapshot_seq, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2,
                            ba_iterations_run, ba_trials_run, segment, cause, seg_poses_pnp, seg_poses);
+}
+
+// ------------------------------------------------------------------ S restart streams in one call, carried from call to call
+// vo_slam_stream_restart's walk with vo_slam_chains_restart's layout: the slot-keyed tables are shared (disjoint slots, and two ghost
+// rows per sequence behind them), every list is carved once for all sequences — a sequence owns the range total_pairs[s] gives it —
+// and the per-pair outputs are laid out per call by seq_off.  One allocation with the stream's lifetime (SlamStream).
+static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int cap, int max_pairs, const int32_t* total, const vo_slam_opts* o, const double* K)
+{
+    const size_t R = (size_t)F + 2 * (size_t)S, fc = R * cap, cm = (size_t)o->max_cameras + 1, NC = cm * S, P = (size_t)max_pairs;
+    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
+    if (R >= ((size_t)1 << 20)) FAIL(VO_ERR_INVALID, "vo_slam_streams: max_frames + 2 S = %zu rows are too many for the packed track table", R);
+    std::vector<size_t> pt0((size_t)S + 1, 0), ob0((size_t)S + 1, 0), pr0((size_t)S + 1, 0);
+    st.seq.assign((size_t)S, SlamStream::Seq());
+    st.rows.assign((size_t)S * (P + 1), 0);
+    st.snap_np = 0; st.snap_no = 0;
+    for (int q = 0; q < S; q++) {
+        SlamStream::Seq& e = st.seq[(size_t)q];
+        e.total = total[q];
+        e.np = ((size_t)total[q] + 1) * cap; e.no = (size_t)2 * cap * std::min(cm, (size_t)total[q]);
+        pt0[q + 1] = pt0[q] + e.np; ob0[q + 1] = ob0[q] + e.no; pr0[q + 1] = pr0[q] + e.no * (o->free_cameras + 1) / 2;
+        st.snap_np = std::max(st.snap_np, e.np); st.snap_no = std::max(st.snap_no, e.no);
+    }
+    const size_t NP = pt0[S], NO = ob0[S], NPAIR = pr0[S];
+    if (NP >= ((size_t)1 << 31) || NPAIR >= ((size_t)1 << 31) || fc >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the maps' lists would not fit 32-bit indices");
+    ChainBuf& cb = st.cb; SlamBuf& sb = st.sb; BaBuf& D = st.D; SlamMap& snap = st.snap;
+    ScratchLayout sc;
+    // shared, keyed by slot (and ghost row)
+    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&sb.pt_of, fc);
+    sc.take(&st.dK, 9);
+    // per sequence: the current problem, the step's state, and what outlives a call — alive, the segment state words, the anchor camera
+    sc.take(&cb.obj, (size_t)S * cap * 3); sc.take(&cb.img, (size_t)S * cap * 2); sc.take(&cb.Xw, (size_t)S * cap * 4); sc.take(&cb.pmask, (size_t)S * cap);
+    sc.take(&sb.dec, (size_t)S * cap); sc.take(&cb.off, (size_t)2 * S); sc.take(&cb.rvec, (size_t)3 * S); sc.take(&cb.tvec, (size_t)3 * S);
+    sc.take(&cb.pninl, S); sc.take(&cb.pstatus, S); sc.take(&cb.P1, (size_t)12 * S); sc.take(&cb.P2, (size_t)12 * S); sc.take(&cb.alive, S); sc.take(&cb.map_count, S);
+    sc.take(&cb.rs.st, (size_t)4 * S); sc.take(&st.keep, (size_t)24 * S);
+    // the maps' lists and the bundle adjustment's, each carved once: a sequence's range starts at its BaProblem offsets
+    sc.take(&sb.m.cnt, (size_t)4 * S); sc.take(&sb.m.cam_frame, NC); sc.take(&sb.m.cam_pose, NC * 12); sc.take(&sb.m.cam_fixed, NC);
+    sc.take(&sb.m.pt_key, NP); sc.take(&sb.m.pt_xyz, NP * 3); sc.take(&sb.m.pt_feat, NP * 2);
+    sc.take(&sb.m.obs_cam, NO); sc.take(&sb.m.obs_pt, NO); sc.take(&sb.m.obs_xy, NO * 2);
+    sc.take(&sb.tmp, NP); sc.take(&sb.idx, NO); sc.take(&sb.prob, S); sc.take(&sb.cam_col, NC); sc.take(&sb.pt_first, NP + S);
+    sc.take(&sb.s_cam, NO); sc.take(&sb.s_pt, NO); sc.take(&sb.s_xy, NO * 2); sc.take(&sb.pairs, NPAIR); sc.take(&sb.blk_first, (size_t)S * (nblk + 1));
+    sc.take(&D.X2, NP * 3); sc.take(&D.W, NO * 18); sc.take(&D.Hpp, NP * 6); sc.take(&D.bp, NP * 3); sc.take(&D.Hpi, NP * 6);
+    // the snapshot: room for the largest sequence
+    sc.take(&snap.cnt, 4); sc.take(&snap.cam_frame, cm); sc.take(&snap.cam_pose, cm * 12); sc.take(&snap.cam_fixed, cm);
+    sc.take(&snap.pt_key, st.snap_np); sc.take(&snap.pt_xyz, st.snap_np * 3); sc.take(&snap.pt_feat, st.snap_np * 2);
+    sc.take(&snap.obs_cam, st.snap_no); sc.take(&snap.obs_pt, st.snap_no); sc.take(&snap.obs_xy, st.snap_no * 2);
+    sc.take(&st.dseq, S); sc.take(&st.dcar, S); sc.take(&st.drows, (size_t)S * (P + 1));
+    const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
+    sc.take(&cb.poses, (P + S) * 12); sc.take(&sb.poses_last, (P + S) * 12);
+    sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P); sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P);
+    sc.take(&st.dchi2, 2 * P * S); sc.take(&st.dit, P * S); sc.take(&st.dtr, P * S);       // k_bundle_adjust writes problem s of step j at [j][s]
+    sc.take(&sb.st.carried_frame, NC); sc.take(&sb.st.carried_poses, NC * 12);
+    sc.take(&cb.rs.segment, P); sc.take(&cb.rs.cause, P); sc.take(&cb.rs.seg_poses, P * 12); sc.take(&cb.rs.seg_poses_last, P * 12);
+    HIPCHK(st.mem.alloc(&st.base, sc.bytes));
+    sc.place_at(st.base);
+    st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
+    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
+    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
+    for (int q = 0; q < S; q++) {
+        SlamStream::Seq& e = st.seq[(size_t)q];
+        BaProblem at{};
+        at.cam0 = (int)(cm * q); at.pt0 = (int)pt0[q]; at.obs0 = (int)ob0[q]; at.pair0 = (int)pr0[q]; at.blk0 = q * (nblk + 1);
+        ChainBuf& c = e.at.cb; c = cb;
+        c.obj0 = q * cap;                                    // k_pnp_ransac indexes the whole arrays by the sequence's {first, end}
+        c.off += 2 * q; c.rvec += 3 * q; c.tvec += 3 * q; c.pmask += (size_t)q * cap; c.pninl += q; c.pstatus += q; c.P1 += 12 * q; c.P2 += 12 * q;
+        c.obj += (size_t)q * cap * 3; c.img += (size_t)q * cap * 2; c.Xw += (size_t)q * cap * 4; c.alive += q; c.map_count += q; c.rs.st += 4 * q;
+        SlamBuf& m = e.at.sb; m = sb;
+        m.base = at;
+        m.cam_cap = (int)cm; m.pt_cap = (int)e.np; m.obs_cap = (int)e.no; m.pair_cap = (int)(pr0[q + 1] - pr0[q]);
+        m.m.cnt += 4 * q; m.m.cam_frame += at.cam0; m.m.cam_pose += (size_t)at.cam0 * 12; m.m.cam_fixed += at.cam0;
+        m.m.pt_key += at.pt0; m.m.pt_xyz += (size_t)at.pt0 * 3; m.m.pt_feat += (size_t)at.pt0 * 2;
+        m.m.obs_cam += at.obs0; m.m.obs_pt += at.obs0; m.m.obs_xy += (size_t)at.obs0 * 2;
+        m.dec += (size_t)q * cap; m.tmp += at.pt0; m.idx += at.obs0;
+        m.prob += q; m.cam_col += at.cam0; m.pt_first += at.pt0 + q; m.s_cam += at.obs0; m.s_pt += at.obs0; m.s_xy += (size_t)at.obs0 * 2;
+        m.pairs += at.pair0; m.blk_first += at.blk0;
+        m.st.carried_frame += at.cam0; m.st.carried_poses += (size_t)at.cam0 * 12;
+    }
+    st.restart = true; st.multi = true; st.S = S;
+    st.F = F; st.cap = cap; st.max_pairs = max_pairs; st.opts = *o; memcpy(st.K, K, sizeof(st.K));
+    return VO_OK;
+}
+
+// What vo_slam_streams asks of the most recent vo_pairs_run: vo_slam_chains' checks, and in a resumed call the stream's — a
+// sequence may be idle, one that advances starts at its anchor slot, and no anchor slot is among another sequence's pairs.
+static int streams_check(vo_ctx* ctx, int resume, int S, const int32_t* seq_off, int* F_out, int* cap_out)
+{
+    const SlamStream& st = ctx->stream_map;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (S < 1) FAIL(VO_ERR_INVALID, "vo_slam_streams takes at least one sequence, got %d", S);
+    if (seq_off[0] != 0) FAIL(VO_ERR_INVALID, "seq_off[0] must be 0, got %d", seq_off[0]);
+    for (int s = 0; s < S; s++) {
+        const int n = seq_off[s + 1] - seq_off[s];
+        if (n < 0 || (n == 0 && !resume))
+            FAIL(VO_ERR_INVALID, "vo_slam_streams: sequence %d has %d pairs (a sequence may be idle, with none, only in a resumed call)", s, n);
+    }
+    if (seq_off[S] < 1) FAIL(VO_ERR_INVALID, "vo_slam_streams: every sequence is idle; at least one must advance");
+    if (seq_off[S] != ctx->last.pairs)
+        FAIL(VO_ERR_INVALID, "vo_slam_streams takes all %d pairs of the most recent vo_pairs_run, seq_off ends at %d", ctx->last.pairs, seq_off[S]);
+    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
+    const int F = b.max_frames, cap = b.kp_cap, B = seq_off[S];
+    const int32_t* sl = ctx->last.slots.data();
+    for (int i = 0; i < 2 * B; i++)
+        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
+    std::vector<int> owner((size_t)F, -1);                  // the sequence a slot's frame belongs to: first of all the anchors
+    if (resume) for (int s = 0; s < S; s++) owner[(size_t)st.seq[(size_t)s].anchor] = s;
+    for (int s = 0; s < S; s++)
+        for (int p = seq_off[s]; p < seq_off[s + 1]; p++) {
+            const bool head = p == seq_off[s];
+            const int a = sl[2 * p], c = sl[2 * p + 1];
+            if (head && resume) {
+                const SlamStream::Seq& e = st.seq[(size_t)s];
+                if (a != e.anchor) FAIL(VO_ERR_INVALID, "vo_slam_streams: pair 0 of sequence %d starts at slot %d, the sequence's last frame is in slot %d", s, a, e.anchor);
+                if (e.touched) FAIL(VO_ERR_INVALID, "vo_slam_streams: slot %d, the last frame of sequence %d, was uploaded to or detected again", e.anchor, s);
+            } else if (head) {
+                if (owner[(size_t)a] >= 0)
+                    FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", owner[(size_t)a], s, p, a, c);
+                owner[(size_t)a] = s;
+            }
+            if ((!head && a != sl[2 * p - 1]) || owner[(size_t)c] == s)
+                FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue sequence %d as a chain of distinct frames", p, a, c, s);
+            if (owner[(size_t)c] >= 0)
+                FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", owner[(size_t)c], s, p, a, c);
+            owner[(size_t)c] = s;
+        }
+    if (cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many keypoints for the packed track table");
+    *F_out = F; *cap_out = cap;
+    return VO_OK;
+}
+
+extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs, const int32_t* seq_off, const double* K, const vo_slam_opts* o,
+                               int snapshot_seq, double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts,
+                               int32_t* n_obs, int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
+                               int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses,
+                               int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const char* who = "vo_slam_streams";
+    if (!resume) drop_slam_stream(ctx);
+    forget_slam_maps(ctx);
+    if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run ||
+        !segment || !cause || !seg_poses_pnp || !seg_poses || !n_carried || !carried_frame || !carried_poses || (!resume && !total_pairs))
+        FAIL(VO_ERR_INVALID, "bad arguments");
+    SlamStream& st = ctx->stream_map;
+    if (resume) {
+        if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
+        if (!st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
+        if (S != st.S) FAIL(VO_ERR_INVALID, "%s: the stream has %d sequences, the call names %d", who, st.S, S);
+    }
+    int F, cap;
+    int rc = streams_check(ctx, resume, S, seq_off, &F, &cap); if (rc) return rc;
+    const bool snap_on = o->snapshot_pair >= 0;        // (snapshot_seq is ignored otherwise)
+    if (snap_on && (snapshot_seq < 0 || snapshot_seq >= S)) FAIL(VO_ERR_INVALID, "snapshot_seq must be a sequence of the call (0 .. %d), got %d", S - 1, snapshot_seq);
+    const int ss = snap_on ? snapshot_seq : 0;
+    const int B = seq_off[S];
+    rc = slam_opts_check(ctx, o, K, snap_on ? seq_off[ss + 1] - seq_off[ss] : 1, who); if (rc) return rc;
+    int maxB = 0;
+    for (int q = 0; q < S; q++) {
+        const int Bq = seq_off[q + 1] - seq_off[q];
+        maxB = std::max(maxB, Bq);
+        if (resume) {
+            const SlamStream::Seq& e = st.seq[(size_t)q];
+            if ((int64_t)e.done + Bq > e.total) FAIL(VO_ERR_INVALID, "%s: sequence %d: %d + %d pairs pass its total_pairs = %d", who, q, e.done, Bq, e.total);
+        } else if (total_pairs[q] < Bq) FAIL(VO_ERR_INVALID, "%s: total_pairs[%d] = %d is less than the sequence's %d pairs in this call", who, q, total_pairs[q], Bq);
+    }
+    if (resume && !slam_stream_same_setup(st, K, o))
+        FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
+    HIPCHK(hipSetDevice(ctx->device));
+    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const int max_pairs = batch(ctx).max_pairs;
+    if (!resume) {
+        rc = slam_streams_allocate(ctx, st, S, F, cap, max_pairs, total_pairs, o, K);
+        if (rc) { drop_slam_stream(ctx); return rc; }
+        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));              // empty feature_mapper, empty maps, no cameras, zero results
+        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
+    } else HIPCHK(hipMemsetAsync(st.call_mem, 0, st.call_bytes, s));
+    const ChainBuf& cb = st.cb; const SlamBuf& sb = st.sb;
+    const size_t cm = (size_t)o->max_cameras + 1, row_cap = (size_t)max_pairs + 1;
+    const int R = F + 2 * S, gpar = st.carries & 1;
+    // the descriptors of this call: a sequence's ranges of the lists, and its rows of the call's outputs
+    std::vector<SlamSeq> seq((size_t)S); std::vector<SlamSeqCarry> car((size_t)S); std::vector<int32_t> hrows(st.rows);
+    for (int q = 0; q < S; q++) {
+        const SlamStream::Seq& h = st.seq[(size_t)q];
+        const int first = seq_off[q];
+        SlamSeq& e = seq[(size_t)q]; e = h.at;
+        e.first = first; e.count = seq_off[q + 1] - first;
+        ChainBuf& c = e.cb;
+        c.n_corr += first; c.n_inl += first; c.status += first; c.n_map += first; c.poses += (size_t)(first + q) * 12;
+        c.rs.segment += first; c.rs.cause += first; c.rs.seg_poses += (size_t)first * 12; c.rs.seg_poses_last += (size_t)first * 12;
+        SlamBuf& m = e.sb;
+        m.n_pts += first; m.n_obs += first; m.n_cam += first; m.poses_last += (size_t)(first + q) * 12;
+        m.st.frame0 = resume ? h.done : 0;
+        // (after a call that ended lost the anchor frame is not in the map: every camera of the map is a carried one)
+        m.st.n_carried = !resume ? 0 : h.lost ? h.last_ncam : h.last_ncam - 1;
+        SlamSeqCarry& k = car[(size_t)q];
+        const int gn = F + 2 * q + gpar, go = F + 2 * q + 1 - gpar;
+        k.c = SlamCarry{cap, F, h.anchor, gn, go, st.keep + (size_t)24 * q};
+        k.hops = R; k.rows = st.drows + (size_t)q * row_cap;
+        hrows[(size_t)q * row_cap + h.n_rows] = go; k.n_rows = h.n_rows + 1;
+    }
+    HIPCHK(hipMemcpyAsync(st.dseq, seq.data(), (size_t)S * sizeof(SlamSeq), hipMemcpyHostToDevice, s));
+    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
+    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
+    const SlamMap live = seq[(size_t)ss].sb.m, snap = st.snap;
+    const size_t snap_np = st.seq[(size_t)ss].np, snap_no = st.seq[(size_t)ss].no;
+    auto snapshot = [&](int j, int stage) {                          // the sequence's ranges of the lists: a few device-to-device copies
+        if (!snap_on || j != o->snapshot_pair || stage != o->snapshot_stage) return;
+        auto cp = [&](auto* dst, const auto* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * sizeof(*src), hipMemcpyDeviceToDevice, s); };
+        cp(snap.cnt, live.cnt, 4); cp(snap.cam_frame, live.cam_frame, cm); cp(snap.cam_pose, live.cam_pose, cm * 12); cp(snap.cam_fixed, live.cam_fixed, cm);
+        cp(snap.pt_key, live.pt_key, snap_np); cp(snap.pt_xyz, live.pt_xyz, snap_np * 3); cp(snap.pt_feat, live.pt_feat, snap_np * 2);
+        cp(snap.obs_cam, live.obs_cam, snap_no); cp(snap.obs_pt, live.obs_pt, snap_no); cp(snap.obs_xy, live.obs_xy, snap_no * 2);
+    };
+    st.live = false;                                                  // (until the call has come through)
+    SlamSeq* dseq = st.dseq; double* dK = st.dK;
+    if (resume) {
+        HIPCHK(hipMemcpyAsync(st.dcar, car.data(), (size_t)S * sizeof(SlamSeqCarry), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(st.drows, hrows.data(), hrows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        StageTimer t(ctx, ST_MISC);
+        launch_slam_carry_restart_seqs(s, dseq, st.dcar, S);
+    }
+    launch_chain_link(s, ctx->pb, cap, B, cb);
+    for (int j = 0; j < maxB; j++) {
+        const bool step0 = j == 0 && !resume;
+        {
+            StageTimer t(ctx, ST_MISC);
+            launch_chain_gather_seqs(s, ctx->pb, cap, j, R, dseq, S);  // (a track may end in a ghost row)
+            if (!step0) {
+                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
+                launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
+            }
+            launch_slam_restart_stream_seqs(s, ctx->pb, cap, j, dseq, S);
+            if (!step0) launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
+            launch_slam_add_stream_restart_seqs(s, ctx->pb, cap, j, R, o->max_point_norm, o->free_cameras, dseq, S);
+        }
+        snapshot(j, 1);
+        if (ba) {
+            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare_seqs(s, j, dseq, S); }
+            BaBuf Dj = st.D;
+            Dj.chi2 = st.dchi2 + (size_t)2 * j * S; Dj.iterations_run = st.dit + (size_t)j * S; Dj.trials_run = st.dtr + (size_t)j * S;
+            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dj, prm, S, o->free_cameras); }
+        }
+        snapshot(j, 2);
+        if (ba || (filt && !step0)) {
+            StageTimer t(ctx, ST_SLAM_FILTER);
+            launch_slam_filter_stream_restart_seqs(s, ctx->pb, cap, j, dK, step0 ? 0.0 : o->filter_threshold, dseq, S);
+        }
+        snapshot(j, 3);
+        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_stream_restart_seqs(s, j, o->max_cameras, dseq, S); }
+        snapshot(j, 4);
+    }
+    HIPCHK(hipGetLastError());
+    // the anchor camera of a sequence's next call: its last rows of this call (an idle sequence keeps the one it has)
+    for (int q = 0; q < S; q++) {
+        const int Bq = seq[(size_t)q].count;
+        if (Bq == 0) continue;
+        HIPCHK(hipMemcpyAsync(st.keep + (size_t)24 * q, seq[(size_t)q].cb.poses + (size_t)Bq * 12, 96, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(st.keep + (size_t)24 * q + 12, seq[(size_t)q].sb.poses_last + (size_t)Bq * 12, 96, hipMemcpyDeviceToDevice, s));
+    }
+    std::vector<double> hchi((size_t)2 * maxB * S); std::vector<int32_t> hit((size_t)maxB * S), htr((size_t)maxB * S), alive((size_t)S, 1);
+    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hchi.data(), st.dchi2, hchi.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hit.data(), st.dit, hit.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(htr.data(), st.dtr, htr.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(alive.data(), cb.alive, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    for (int q = 0; q < S; q++) {
+        const int n = seq[(size_t)q].count > 0 ? seq[(size_t)q].sb.st.n_carried : 0;
+        n_carried[q] = n;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(carried_frame + (size_t)q * o->max_cameras, seq[(size_t)q].sb.st.carried_frame, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(carried_poses + (size_t)q * o->max_cameras * 12, seq[(size_t)q].sb.st.carried_poses, (size_t)n * 96, hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    for (int q = 0; q < S; q++)                                       // [step][sequence] -> the pair's position in the run
+        for (int j = 0; j < seq[(size_t)q].count; j++) {
+            const size_t at = (size_t)j * S + q, p = (size_t)seq_off[q] + j;
+            chi2[2 * p] = hchi[2 * at]; chi2[2 * p + 1] = hchi[2 * at + 1]; ba_iterations_run[p] = hit[at]; ba_trials_run[p] = htr[at];
+        }
+    // host copies of every sequence's map, an idle one's too: vo_pairs_run forgot the ones of the call before
+    std::vector<LastRun::Map> maps((size_t)S);
+    for (int q = 0; q < S; q++) { rc = slam_map_download(ctx, seq[(size_t)q].sb.m, cap, &maps[(size_t)q]); if (rc) return rc; }
+    LastRun::Map smap;
+    if (snap_on) { rc = slam_map_download(ctx, snap, cap, &smap); if (rc) return rc; }
+    ctx->last.map[0] = maps[0];                                       // what vo_slam_map reports: sequence 0, and its snapshot if it has one
+    if (snap_on && ss == 0) ctx->last.map[1] = smap;
+    ctx->last.seq_map = std::move(maps);
+    if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
+    // the stream's state for the next call.  A sequence that advanced gives back every slot but its new anchor's; an idle one has
+    // given back all it had at this call's carry.
+    const int32_t* sl = ctx->last.slots.data();
+    for (int q = 0; q < S; q++) {
+        SlamStream::Seq& h = st.seq[(size_t)q];
+        const int first = seq_off[q], Bq = seq[(size_t)q].count;
+        h.n_rows = 0;
+        if (Bq == 0) continue;
+        int32_t* rows = st.rows.data() + (size_t)q * row_cap;
+        rows[h.n_rows++] = sl[2 * first];
+        for (int j = 0; j + 1 < Bq; j++) rows[h.n_rows++] = sl[2 * (first + j) + 1];
+        h.anchor = sl[2 * (first + Bq) - 1]; h.done = (resume ? h.done : 0) + Bq; h.last_ncam = n_cam[first + Bq - 1];
+        h.lost = !alive[(size_t)q]; h.touched = false;
+    }
+    st.carries = resume ? st.carries + 1 : 0;
+    st.live = true;
+    return VO_OK;
 }
 
 static const LastRun::Map* slam_chains_map_of(vo_ctx* ctx, int seq, int which)

@@ -397,5 +397,18 @@ void launch_slam_ba_prepare_seqs(hipStream_t s, int j, const SlamSeq* seqs, int 
 void launch_slam_filter_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);
 void launch_slam_limit_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S);
 void launch_slam_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S);
+// ---- ... on S maps carried from call to call (vo_slam_streams): the stream / restart kernels with the sequence on the grid axis.
+// The slot-keyed tables have max_frames + 2 S rows: sequence s owns the ghost rows F + 2 s and F + 2 s + 1.  A descriptor's sb.st is
+// the sequence's own (frame0 counts along its stream); a sequence that is idle in a call has count = 0.
+struct SlamSeqCarry {
+    SlamCarry c;                        // the sequence's anchor slot, its ghost rows, its anchor camera; c.F = max_frames
+    int hops;                           // rows of the slot-keyed tables (F + 2 S): the bound of a track walk
+    const int* rows; int n_rows;        // the rows only this sequence holds and does not keep: the slots of its last call's frames, its old ghost row
+};
+void launch_slam_carry_restart_seqs(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, int S);
+void launch_slam_restart_stream_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S);
+void launch_slam_add_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S);
+void launch_slam_filter_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);
+void launch_slam_limit_stream_restart_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

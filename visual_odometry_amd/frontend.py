@@ -327,9 +327,53 @@ class FrontEnd:
             d["segments"] = split_segments(d["segment"], d["poses_pnp"], d["poses"], seg["seg_poses_pnp"][a:b], seg["seg_poses"][a:b])
         return out
 
+    def slam_streams(self, seq_lengths, K, resume=False, total_pairs=None, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED,
+                     max_point_norm=50.0, ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """slam_stream_restart for several sequences at once (vo_slam_streams), one workgroup per sequence and kernel: the pairs of
+        the latest run_pairs(..., want_points=True) are sequence 0's seq_lengths[0] pairs, then sequence 1's, ...  resume=False
+        starts the stream: every sequence has at least one pair, no frame slot belongs to two sequences, total_pairs is a list of
+        len(seq_lengths) — how many pairs each sequence may reach (default: its pairs of this call).  resume=True continues it
+        with the same number of sequences, K and options: a sequence that advances starts at the slot of its last frame, and a
+        sequence may be idle (length 0) as long as one advances — it keeps its last frame's slot, its map and its state, and goes
+        on in a later call as if the idle calls had not happened.  Every slot but the sequences' last frames' is free between calls.
+        For every sequence the calls together compute what slam_stream_restart computes for that flight alone, byte for byte.
+        snapshot=(seq, pair, stage), the pair counted along that sequence's pairs of this call (slam_map(1, seq=seq)).
+        Returns one dict for the call, laid out as vo_slam_chains_restart lays its outputs out: seq_off [S + 1]; poses_pnp, poses
+        [B + S, 3, 4] (sequence s owns rows seq_off[s] + s .. seq_off[s + 1] + s; an idle one its last frame's row); n_corr, n_inl,
+        status, n_pts, n_obs, n_cam, ba_iterations, ba_trials, segment, cause [B]; chi2 [B, 2]; seg_poses_pnp, seg_poses [B, 3, 4];
+        n_carried [S]; carried_frame, carried_poses: lists of S arrays [n_s] / [n_s, 3, 4], frames counted along the sequence's own
+        stream.  stream_slice(out, s) is sequence s's part as slam_stream_restart returns it, join_streams(outs) the whole flights.
+        slam_map(which, seq) reports every sequence after every call, an idle one too."""
+        lengths = [int(v) for v in seq_lengths]
+        if not lengths or min(lengths) < 0:
+            raise ValueError(f"slam_streams takes at least one sequence and no negative length, got {lengths}")
+        off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+        S, B = len(lengths), int(off[-1])
+        total = np.ascontiguousarray(lengths if total_pairs is None else [int(v) for v in total_pairs], dtype=np.int32)
+        if len(total) != S:
+            raise ValueError(f"total_pairs names {len(total)} sequences, seq_lengths {S}")
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        sq, sp, ss = (0, -1, 0) if snapshot is None else (int(snapshot[0]), int(snapshot[1]), int(snapshot[2]))
+        opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
+                             float(huber_delta), int(free_cameras), float(filter_threshold), int(max_cameras), sp, ss)
+        flat = dict(poses_pnp=np.zeros((B + S, 12)), poses=np.zeros((B + S, 12)), chi2=np.zeros((B, 2)))
+        flat.update({k: np.zeros(B, np.int32) for k in ("n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials", "segment", "cause")})
+        flat.update(seg_poses_pnp=np.zeros((B, 12)), seg_poses=np.zeros((B, 12)))
+        rows = max(int(max_cameras), 1)
+        nc = np.zeros(S, np.int32); cf = np.zeros((S, rows), np.int32); cp = np.zeros((S, rows, 12))
+        keys = ("poses_pnp", "poses", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "chi2", "ba_iterations", "ba_trials",
+                "segment", "cause", "seg_poses_pnp", "seg_poses")
+        c = self.ctx
+        c.check(c.lib.vo_slam_streams(c.handle, int(bool(resume)), S, total.ctypes.data, off.ctypes.data, K.ctypes.data, C.addressof(opts), sq,
+                                      *[_lib.ptr(flat[k]) for k in keys], nc.ctypes.data, cf.ctypes.data, cp.ctypes.data))
+        for k in ("poses_pnp", "poses", "seg_poses_pnp", "seg_poses"):
+            flat[k] = flat[k].reshape(-1, 3, 4)
+        return dict(seq_off=off, n_carried=nc, carried_frame=[cf[s, :nc[s]].copy() for s in range(S)],
+                    carried_poses=[cp[s, :nc[s]].reshape(-1, 3, 4).copy() for s in range(S)], **flat)
+
     def slam_map(self, which=0, seq=0):
-        """The map of the latest slam_chain, or of sequence `seq` of the latest slam_chains: which=0 at the end of the chain, 1 the
-        snapshot.  dict(cam_frame [ncam] index of the camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool,
+        """The map of the latest slam_chain, or of sequence `seq` of the latest slam_chains or slam_streams call: which=0 at the end of the
+        chain, 1 the snapshot.  dict(cam_frame [ncam] index of the camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool,
         pt_feature [npt, 2] (chain frame, keypoint), points [npt, 3], obs_cam, obs_pt [nobs], obs_xy [nobs, 2])."""
         if seq:
             return self._slam_chains_map(int(seq), int(which))
@@ -512,6 +556,39 @@ def join_stream(outs):
     if restart:
         out["seg_poses"] = seg_poses
     return out
+
+
+def stream_slice(out, s):
+    """Sequence s's part of the dict one slam_streams call returned, in the shape slam_stream_restart returns (copies): the
+    per-pair arrays' rows seq_off[s] .. seq_off[s + 1] - 1, the pose rows seq_off[s] + s .. seq_off[s + 1] + s, its carried rows.
+    A sequence that was idle in the call has no pairs and one pose row, its last frame's."""
+    off = np.asarray(out["seq_off"]).ravel()
+    s = int(s)
+    if s < 0 or s >= len(off) - 1:
+        raise ValueError(f"no sequence {s} in a call of {len(off) - 1}")
+    a, b = int(off[s]), int(off[s + 1])
+    d = {k: np.array(np.asarray(out[k])[a:b], copy=True) for k in STREAM_PAIR_KEYS + ("segment", "cause", "seg_poses_pnp", "seg_poses")}
+    for k in ("poses_pnp", "poses"):
+        d[k] = np.array(np.asarray(out[k])[a + s:b + s + 1], copy=True)
+    d["carried_frame"] = np.array(out["carried_frame"][s], np.int32, copy=True)
+    d["carried_poses"] = np.array(out["carried_poses"][s], np.float64, copy=True).reshape(-1, 3, 4)
+    return d
+
+
+def join_streams(outs):
+    """The dicts the calls of one slam_streams stream returned, in order -> one whole-flight dict per sequence: join_stream over
+    that sequence's slices of the calls in which it advanced (an idle call adds nothing to a flight).  Pure: no GPU, no library."""
+    outs = list(outs)
+    if not outs:
+        raise ValueError("join_streams takes at least one call")
+    S = len(np.asarray(outs[0]["seq_off"]).ravel()) - 1
+    if any(len(np.asarray(o["seq_off"]).ravel()) - 1 != S for o in outs):
+        raise ValueError("the calls of one stream all have the same number of sequences")
+    joined = []
+    for s in range(S):
+        own = [stream_slice(o, s) for o in outs]
+        joined.append(join_stream([d for d in own if len(d["status"]) > 0]))
+    return joined
 
 
 def chain_poses(R, t):
