@@ -325,6 +325,18 @@ __device__ __forceinline__ void dk_iterate_quad(const double* c, double* rr, dou
 // Degree below 10 (a vanishing leading coefficient, rare): the sequential form, run by every lane of the quad on its copy.
 __device__ __forceinline__ void dk_iterate_low(const double* c, int n, double* rr, double* ri, bool early)
 {
+    // s[k] = c[k - (10 - n)]: the coefficients moved up so that the leading one sits at s[10] and coefficient n - 1 - j at
+    // s[9 - j], by 10 - n one-place moves under a select (c[n - 1 - j] itself would be a dynamic index, i.e. scratch)
+    double s[11];
+#pragma unroll
+    for (int k = 0; k <= 10; k++) s[k] = c[k];
+#pragma unroll
+    for (int step = 0; step < 9; step++) {
+        const bool move = step < 10 - n;
+#pragma unroll
+        for (int k = 10; k >= 1; k--) s[k] = move ? s[k - 1] : s[k];
+        s[0] = move ? 0.0 : s[0];
+    }
     double prev = 1e300;
     int stall = 0;
     const int sweeps = early ? VO_DK_FAST_CAP : VO_DK_ITERS;
@@ -336,16 +348,12 @@ __device__ __forceinline__ void dk_iterate_low(const double* c, int n, double* r
         for (int i = 0; i < 10; i++) {
             if (i < n) {
                 cplx p = {rr[i], ri[i]};
-                double lead = c[10];
-#pragma unroll
-                for (int q = 1; q <= 10; q++) if (q == n) lead = c[q];
+                const double lead = s[10];
                 cplx num = {lead, 0}, denom = {lead, 0};
 #pragma unroll
                 for (int j = 0; j < 10; j++) {
                     if (j < n) {
-                        double cj = c[9 - j];
-#pragma unroll
-                        for (int q = 0; q < 10; q++) if (q == n - j - 1) cj = c[q];
+                        const double cj = s[9 - j];
                         cplx np = cmul(num, p);
                         num.re = np.re + cj; num.im = np.im;
                         if (j != i) {
@@ -368,31 +376,71 @@ __device__ __forceinline__ void dk_iterate_low(const double* c, int n, double* r
     }
 }
 
+// One column of the Gauss-Jordan elimination with partial pivoting, on the quad's 10 x 20 matrix held in registers: lane q
+// has the columns 5q .. 5q+4 in cmr.  COL is a template argument so that every register index is a constant (a loop
+// over the columns is only unrolled in part, which sends the matrix to scratch).  The owner of column COL hands it to
+// the quad; the pivot search runs in all four lanes on the same values, so the pivot row and the singular exit (false)
+// are uniform over the quad.  The pivot row is read and written through selects.
+template <int COL>
+__device__ __forceinline__ bool elim_step(double (&cmr)[10][5])
+{
+    double colv[10];
+#pragma unroll
+    for (int r = 0; r < 10; r++) colv[r] = quad_bcast<COL / 5>(cmr[r][COL % 5]);
+    int piv = COL;
+    double best = fabs(colv[COL]), pv = colv[COL];
+#pragma unroll
+    for (int r = COL + 1; r < 10; r++) { const double v = fabs(colv[r]); if (v > best) { best = v; piv = r; pv = colv[r]; } }
+    if (best < 1e-300) return false;
+    double prow[5];
+    const double inv = 1.0 / pv;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const double b = cmr[COL][j];
+        double a = b;
+#pragma unroll
+        for (int r = COL + 1; r < 10; r++) a = piv == r ? cmr[r][j] : a;
+        prow[j] = a * inv;
+#pragma unroll
+        for (int r = COL + 1; r < 10; r++) cmr[r][j] = piv == r ? b : cmr[r][j];      // row swap (no-op when piv == COL)
+        cmr[COL][j] = prow[j];
+    }
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        if (r == COL) continue;
+        const double f = (r > COL && piv == r) ? colv[COL] : colv[r];       // column COL after the swap
+        const bool skip = f == 0;
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            const double v = cmr[r][j] - f * prow[j];
+            cmr[r][j] = skip ? cmr[r][j] : v;
+        }
+    }
+    return true;
+}
+
 // ------------------------------------------------------------------ five-point solver, one sample per quad
 // x1, x2: 5 normalised correspondences (interleaved x,y). Writes up to 10 row-major 3x3 models
 // (x2^T E x1 = 0, unit Frobenius norm) to Eout and returns their number.  Called by the four lanes of a quad with the
 // same arguments (q = lane & 3); the return value and every early return are uniform over the quad.
-//   null space, constraints, polynomial: every lane computes them (5 % of a solve; the same values in the four lanes)
-//   10x20 elimination: lane q owns the columns 5q .. 5q+4
+//   null space, constraints, polynomial: every lane computes them (the same values in the four lanes)
+//   10x20 elimination: lane q owns the columns 5q .. 5q+4 and keeps them in registers; the pivot column travels by
+//   quad broadcast, the row swap is a select chain over the rows (no LDS, no dynamic register index)
 //   Durand-Kerner: see dk_iterate_quad
 //   models: the real roots are dealt over the lanes in ascending index, four per pass
-// cm: the wave's block of elimination matrices in LDS, 200 doubles per sample: element (r, 5 * qo + j) of the quad's
-// sample is held by lane qo of the quad at cm[(r * 5 + j) * 64 + lane] (consecutive lanes hold consecutive doubles:
-// conflict-free ds_read/write_b64; a pivot-column read is one address per quad).
+// park: the wave's block of LDS, FP_PARK doubles per sample.  What is cold while the roots are found (the null-space
+// basis and B(z), 150 registers) waits there, so that the sweep loop runs in about 120 registers and the kernel fits
+// two waves per SIMD.  Value i of the quad's sample sits at park[i * FP_QUADS + lane / 4]; the four lanes hold the
+// same values, each writes all of them and reads back what it wrote (no exchange, so no barrier).
 #define FP_QUADS 16          // samples a wave solves at once
+#define FP_PARK 75           // 36 basis + 12 Bx + 12 By + 15 Bc
 typedef __attribute__((address_space(3))) double lds_double;
-#define CMQ(r, j) cm[((r) * 5 + (j)) * 64 + lane]                                   // own column j
-#define CMK(r, k) cm[((r) * 5 + (k) % 5) * 64 + (lane & ~3) + (k) / 5]              // column k of the quad's sample
-__device__ __forceinline__ void quad_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+#define PARK(i) park[(i) * FP_QUADS + (lane >> 2)]
 
-__device__ __noinline__ int five_point_solve_quad(const double* x1, const double* x2, double* Eout, lds_double* cm, bool dk_early)
+__device__ __forceinline__ int five_point_solve_quad(const double* x1, const double* x2, double* Eout, lds_double* park, bool dk_early)
 {
     const int lane = threadIdx.x & 63, q = lane & 3;
+    double cmr[10][5];       // element (r, 5q + j) of the 10 x 20 constraint matrix
     double basis[36];
     {
         // Householder QR of Q^T (9 x 5); null space = last 4 columns of the orthogonal factor
@@ -475,79 +523,68 @@ __device__ __noinline__ int five_point_solve_quad(const double* x1, const double
                 mul21_acc(m, E[0][c], 1.0, row);
             }
 #pragma unroll
-            for (int j = 0; j < 5; j++) CMQ(0, j) = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
+            for (int j = 0; j < 5; j++) cmr[0][j] = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
         }
-        double L[3][3][10];
+        // E E^T - 0.5 tr(E E^T) I: the diagonal first (the trace needs all of it), then one row of off-diagonal entries
+        // at a time, so that three of the nine products are alive at once
+        double D[3][10], tr[10];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int i = 0; i < 10; i++) D[r][i] = 0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) mul11_acc(E[r][k], E[r][k], 1.0, D[r]);
+        }
+#pragma unroll
+        for (int i = 0; i < 10; i++) tr[i] = D[0][i] + D[1][i] + D[2][i];
 #pragma unroll
         for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int i = 0; i < 10; i++) D[r][i] -= 0.5 * tr[i];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            double L[3][10];
 #pragma unroll
             for (int c = 0; c < 3; c++) {
+                if (c == r) {
 #pragma unroll
-                for (int i = 0; i < 10; i++) L[r][c][i] = 0;
+                    for (int i = 0; i < 10; i++) L[c][i] = D[r][i];
+                } else {
 #pragma unroll
-                for (int k = 0; k < 3; k++) mul11_acc(E[r][k], E[c][k], 1.0, L[r][c]);
+                    for (int i = 0; i < 10; i++) L[c][i] = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) mul11_acc(E[r][k], E[c][k], 1.0, L[c]);
+                }
             }
-        double tr[10];
-#pragma unroll
-        for (int i = 0; i < 10; i++) tr[i] = L[0][0][i] + L[1][1][i] + L[2][2][i];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int i = 0; i < 10; i++) L[r][r][i] -= 0.5 * tr[i];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 double row[20];
 #pragma unroll
                 for (int i = 0; i < 20; i++) row[i] = 0;
 #pragma unroll
-                for (int k = 0; k < 3; k++) mul21_acc(L[r][k], E[k][c], 1.0, row);
+                for (int k = 0; k < 3; k++) mul21_acc(L[k], E[k][c], 1.0, row);
 #pragma unroll
-                for (int j = 0; j < 5; j++) CMQ(1 + r * 3 + c, j) = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
+                for (int j = 0; j < 5; j++) cmr[1 + r * 3 + c][j] = sel4(q, row[j], row[5 + j], row[10 + j], row[15 + j]);
             }
-    }
-    quad_lds_sync();
-
-    // Gauss-Jordan with partial pivoting on the left 10 columns.  Pivot search and the multipliers read column `col`,
-    // which every lane of the quad loads before its owner overwrites it; the row updates are element-wise.
-#pragma unroll 1
-    for (int col = 0; col < 10; col++) {
-        int piv = col;
-        double best = fabs(CMK(col, col));
-#pragma unroll 1
-        for (int r = col + 1; r < 10; r++) { double v = fabs(CMK(r, col)); if (v > best) { best = v; piv = r; } }
-        if (best < 1e-300) return 0;
-        double prow[5], f[10];
-        const double inv = 1.0 / CMK(piv, col);
-        quad_lds_sync();
-#pragma unroll
-        for (int j = 0; j < 5; j++) {
-            const double a = CMQ(piv, j), b = CMQ(col, j);
-            prow[j] = a * inv;
-            CMQ(piv, j) = b;                      // row swap (no-op when piv == col)
-            CMQ(col, j) = prow[j];
         }
-        quad_lds_sync();
-#pragma unroll
-        for (int r = 0; r < 10; r++) f[r] = CMK(r, col);
-        quad_lds_sync();
-#pragma unroll
-        for (int r = 0; r < 10; r++) {
-            if (r == col || f[r] == 0) continue;
-#pragma unroll
-            for (int j = 0; j < 5; j++) CMQ(r, j) -= f[r] * prow[j];
-        }
-        quad_lds_sync();
     }
+#pragma unroll
+    for (int i = 0; i < 36; i++) PARK(i) = basis[i];
 
-    // B(z) [x y 1]^T = 0
+    // Gauss-Jordan with partial pivoting on the left 10 columns, one instance of the step per column
+    if (!elim_step<0>(cmr) || !elim_step<1>(cmr) || !elim_step<2>(cmr) || !elim_step<3>(cmr) || !elim_step<4>(cmr) ||
+        !elim_step<5>(cmr) || !elim_step<6>(cmr) || !elim_step<7>(cmr) || !elim_step<8>(cmr) || !elim_step<9>(cmr)) return 0;
+
+    // B(z) [x y 1]^T = 0, from the rows 4..9 of the right half (the columns of lanes 2 and 3)
     double Bx[3][4], By[3][4], Bc[3][5];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         double r1[10], r2[10];
 #pragma unroll
-        for (int k = 0; k < 10; k++) { r1[k] = CMK(2 * i + 4, 10 + k); r2[k] = CMK(2 * i + 5, 10 + k); }
+        for (int k = 0; k < 10; k++) {
+            r1[k] = quad_bcast_from(2 + k / 5, cmr[2 * i + 4][k % 5]);
+            r2[k] = quad_bcast_from(2 + k / 5, cmr[2 * i + 5][k % 5]);
+        }
         Bx[i][3] = -r2[0]; Bx[i][2] = r1[0] - r2[1]; Bx[i][1] = r1[1] - r2[2]; Bx[i][0] = r1[2];
         By[i][3] = -r2[3]; By[i][2] = r1[3] - r2[4]; By[i][1] = r1[4] - r2[5]; By[i][0] = r1[5];
         Bc[i][4] = -r2[6]; Bc[i][3] = r1[6] - r2[7]; Bc[i][2] = r1[7] - r2[8]; Bc[i][1] = r1[8] - r2[9]; Bc[i][0] = r1[9];
@@ -577,9 +614,20 @@ __device__ __noinline__ int five_point_solve_quad(const double* x1, const double
         for (int i = 0; i < 11; i++) c[i] += t3[i];
     }
 
+    // B(z) waits in LDS for the model stage; the compiler barrier keeps it from carrying the values over in registers
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) { PARK(36 + i * 4 + k) = Bx[i][k]; PARK(48 + i * 4 + k) = By[i][k]; }
+#pragma unroll
+        for (int k = 0; k < 5; k++) PARK(60 + i * 5 + k) = Bc[i][k];
+    }
+    __asm__ volatile("" ::: "memory");
+
     // cv::solvePoly: Durand-Kerner from the starting points (1+i)^k, Gauss-Seidel updates
     int n = 10;
-    while (n > 1 && !(fabs(c[n]) > DBL_EPSILON)) n--;
+#pragma unroll
+    for (int k = 10; k > 1; k--) if (n == k && !(fabs(c[k]) > DBL_EPSILON)) n = k - 1;      // a select chain, not c[n]
     double rr[10], ri[10];
     {
         cplx p = {1, 0}, r = {1, 1};
@@ -622,16 +670,17 @@ __device__ __noinline__ int five_point_solve_quad(const double* x1, const double
             double bz[9], xy1[3];
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                bz[j * 3 + 0] = Bx[j][3] * z3 + Bx[j][2] * z2 + Bx[j][1] * z1 + Bx[j][0];
-                bz[j * 3 + 1] = By[j][3] * z3 + By[j][2] * z2 + By[j][1] * z1 + By[j][0];
-                bz[j * 3 + 2] = Bc[j][4] * z4 + Bc[j][3] * z3 + Bc[j][2] * z2 + Bc[j][1] * z1 + Bc[j][0];
+                const int bx = 36 + j * 4, by = 48 + j * 4, bc = 60 + j * 5;      // B(z) and the basis come back from LDS
+                bz[j * 3 + 0] = PARK(bx + 3) * z3 + PARK(bx + 2) * z2 + PARK(bx + 1) * z1 + PARK(bx);
+                bz[j * 3 + 1] = PARK(by + 3) * z3 + PARK(by + 2) * z2 + PARK(by + 1) * z1 + PARK(by);
+                bz[j * 3 + 2] = PARK(bc + 4) * z4 + PARK(bc + 3) * z3 + PARK(bc + 2) * z2 + PARK(bc + 1) * z1 + PARK(bc);
             }
             solve_z<3>(bz, xy1);
             if (!(fabs(xy1[2]) < 1e-10)) {
                 double x = xy1[0] / xy1[2], y = xy1[1] / xy1[2], nrm = 0, e[9];
 #pragma unroll
                 for (int k = 0; k < 9; k++) {
-                    e[k] = basis[k] * x + basis[9 + k] * y + basis[18 + k] * z1 + basis[27 + k];
+                    e[k] = PARK(k) * x + PARK(9 + k) * y + PARK(18 + k) * z1 + PARK(27 + k);
                     nrm += e[k] * e[k];
                 }
                 nrm = sqrt(nrm);
@@ -704,12 +753,13 @@ __device__ __forceinline__ int count_inliers(const double* E, const double* x1, 
 
 // ------------------------------------------------------------------ RANSACPointSetRegistrator::run, one workgroup (4 waves) per pair
 // Round = RS_ROUND minimal samples, 16 per solver wave (one per quad) — the adaptive count ends at 9..30 on textured
-// pairs (one round), 50..1000 on wide-baseline or low-inlier pairs; the elimination matrices (25.6 KB per solver wave)
-// are the only large LDS user and the models live in global memory (L2).  E, mask and inlier count do not depend on the
+// pairs (one round), 50..1000 on wide-baseline or low-inlier pairs; the solver parks 9.6 KB per solver wave in LDS, the
+// elimination runs in registers and the models live in global memory (L2).  The kernel is held to RS_OCC waves per SIMD
+// (256 registers) and 43 KB of LDS, so two workgroups, or another context's kernels, fit on a CU beside it.  E, mask and inlier count do not depend on the
 // round size; the reported iteration count can, where a sample without models sits at the end of a round.
 // (1) sample indices: the RNG stream (OpenCV's MWC, data independent) is read
 // from a table, `% M` is taken by all threads in parallel, thread 0 only applies the repeat rejection;
-// (2) the first RS_SOLVERS waves solve the samples, one per quad, elimination matrices in LDS; (3) the models
+// (2) the first RS_SOLVERS waves solve the samples, one per quad, elimination matrices in registers; (3) the models
 // are scored four at a time (one per wave, ballot + popcount over the correspondences) and consumed strictly
 // in OpenCV's order, so the adaptive iteration count and the strict `>` rule behave as in the serial loop.
 #define RS_STREAM 512                     // RNG numbers staged per round (up to 64 subsets x 5 + rejections)
@@ -718,14 +768,17 @@ __device__ __forceinline__ int count_inliers(const double* E, const double* x1, 
 #define RS_WAVES 4                         // wavefronts of the workgroup: the first RS_SOLVERS solve, all of them score
 #endif
 #ifndef RS_SOLVERS
-#define RS_SOLVERS 4                       // solver waves: 1, 2 or 4 -> 16, 32 or 64 samples and 26, 51 or 102 KB of LDS per round
+#define RS_SOLVERS 4                       // solver waves: 1, 2 or 4 -> 16, 32 or 64 samples and 10, 19 or 38 KB of LDS per round
 #endif                                     // (measured: 2 and 4 tie while one round serves every pair, 4 wins beyond; docs/experiments.md)
+#ifndef RS_OCC
+#define RS_OCC 2                           // waves per SIMD the register allocation is held to: 2 -> at most 256 registers
+#endif
 #define RS_ROUND (FP_QUADS * RS_SOLVERS)
 #define RS_THREADS (64 * RS_WAVES)
 static_assert(RS_SOLVERS >= 1 && RS_SOLVERS <= RS_WAVES && RS_ROUND <= 64, "the sampler and the model list hold at most 64 samples per round");
 
 struct RansacShared {
-    double cm[200 * RS_ROUND];
+    double park[FP_PARK * RS_ROUND];
     uint32_t stream[RS_STREAM];
     int sub[64][5];
     int nm[64];
@@ -735,9 +788,9 @@ struct RansacShared {
     int used;
 };
 
-__global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap, RansacParams rp, const uint32_t* rng_tab, int rng_n)
+__global__ __launch_bounds__(RS_THREADS) __attribute__((amdgpu_waves_per_eu(RS_OCC, RS_OCC))) void k_ransac(PairBuf pb, int kp_cap, RansacParams rp, const uint32_t* rng_tab, int rng_n)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];   // dynamic: RS_SOLVERS = 4 needs more than the static 64 KB
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     RansacShared& sh = *(RansacShared*)s_dyn;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int M = pb.m_count[p];
@@ -757,7 +810,7 @@ __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap
     if (M == 5) {       // ptsetreg.cpp: count == modelPoints -> all solutions, every point an inlier
         if (tid < 4) {                   // one quad
             double* models = pb.models + (size_t)p * 64 * 90;
-            const int nm = five_point_solve_quad(x1, x2, models, (lds_double*)sh.cm, rp.dk_early != 0);
+            const int nm = five_point_solve_quad(x1, x2, models, (lds_double*)sh.park, rp.dk_early != 0);
             __threadfence_block();       // lane 0 reads what the quad stored
             if (tid == 0) {
                 for (int k = 0; k < 9; k++) res->E[k] = nm > 0 ? models[k] : 0.0;
@@ -846,7 +899,7 @@ __global__ __launch_bounds__(RS_THREADS, 1) void k_ransac(PairBuf pb, int kp_cap
                     s1[2 * i] = x1[2 * v]; s1[2 * i + 1] = x1[2 * v + 1];
                     s2[2 * i] = x2[2 * v]; s2[2 * i + 1] = x2[2 * v + 1];
                 }
-                const int nm = five_point_solve_quad(s1, s2, gmodels + h * 90, (lds_double*)sh.cm + wave * (200 * FP_QUADS), rp.dk_early != 0);
+                const int nm = five_point_solve_quad(s1, s2, gmodels + h * 90, (lds_double*)sh.park + wave * (FP_PARK * FP_QUADS), rp.dk_early != 0);
                 if ((lane & 3) == 0) sh.nm[h] = nm;
             }
         }
@@ -1255,8 +1308,8 @@ __global__ __launch_bounds__(64) void k_five_point_raw(const double* x1, const d
 void launch_five_point_raw(hipStream_t s, const double* x1, const double* x2, double* E, int* nm, int dk_early)
 {
     static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_five_point_raw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(200 * FP_QUADS * sizeof(double))); attr = true; }
-    hipLaunchKernelGGL(k_five_point_raw, dim3(1), dim3(64), 200 * FP_QUADS * sizeof(double), s, x1, x2, E, nm, dk_early);
+    if (!attr) { (void)hipFuncSetAttribute((const void*)k_five_point_raw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FP_PARK * FP_QUADS * sizeof(double))); attr = true; }
+    hipLaunchKernelGGL(k_five_point_raw, dim3(1), dim3(64), FP_PARK * FP_QUADS * sizeof(double), s, x1, x2, E, nm, dk_early);
 }
 
 // ------------------------------------------------------------------ reprojection-error filter
