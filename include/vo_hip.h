@@ -226,7 +226,15 @@ int vo_frame_features(vo_ctx* ctx, int slot, float* kp_xy, float* kp_size, float
                       int32_t* kp_octave, uint8_t* desc, int cap, int32_t* n_out);
 /* run match + E-RANSAC + pose (+ triangulation) for B pairs of already detected slots.
  * pair_slots: B x 2 int32.  results: B entries.  X (optional, may be NULL): B x 4 x x_cap
- * doubles, w normalised to 1; the first n_inl columns of each are valid. */
+ * doubles, w normalised to 1; X is valid only for VO_OK pairs, in their first n_inl columns (the inliers in match order).
+ * A pair's record is zeroed before the run; n_kp1, n_kp2 and n_match are always written.  What else a pair holds, by status
+ * (tests/test_gpu_pairs_chosen.py asserts it field for field):
+ *   VO_OK             every field; a pair of exactly 5 matches whose five-point solve has ONE solution is such a pair
+ *                     (n_inl = 5, ransac_iters = 0, recoverPose and X on the five points)
+ *   VO_ERR_TOO_FEW    n_match < 5: nothing else; n_inl, n_good, ransac_iters, E, R, t stay 0
+ *   VO_ERR_NO_MODEL   ransac_iters (the whole budget max(ransac_max_iters, 1) when n_match > 5; 0 for n_match == 5); the rest stays 0
+ *   VO_ERR_AMBIGUOUS  n_match == 5 with several stacked solutions: n_inl = 5, E = the first of them, n_good = 0, R and t stay 0
+ * vo_pair_matches' inlier mask has no byte set for TOO_FEW and NO_MODEL pairs and all five set for an AMBIGUOUS one. */
 int vo_pairs_run(vo_ctx* ctx, const int32_t* pair_slots, int B, const double* K, const vo_pair_opts* opts,
                  vo_pair_result* results, double* X, int32_t x_cap);
 /* enqueue-only form: results / X must be page-locked (vo_host_alloc), X needs x_cap == vo_batch_kp_capacity();

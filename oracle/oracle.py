@@ -256,6 +256,23 @@ def recover_pose(E, p1, p2, K, dist_thresh=50.0):
     return ng.value, R, t, mask[:M].copy()
 
 
+def recover_pose_counts(E, p1, p2, K, dist_thresh=50.0):
+    """recover_pose with what decides it: (good[4] of the candidates (R1,t) (R2,t) (R1,-t) (R2,-t), best, R, t, mask)."""
+    E = np.ascontiguousarray(E, np.float64).reshape(3, 3)
+    p1 = np.ascontiguousarray(p1, np.float64).reshape(-1, 2); p2 = np.ascontiguousarray(p2, np.float64).reshape(-1, 2)
+    K = np.ascontiguousarray(K, np.float64)
+    M = len(p1)
+    R = np.zeros((3, 3)); t = np.zeros((3, 1)); mask = np.zeros(max(M, 1), np.uint8)
+    good = np.zeros(4, np.int32); best = C.c_int32(0)
+    f = lib().voo_recover_pose_counts
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = f(E.ctypes.data, p1.ctypes.data, p2.ctypes.data, M, K.ctypes.data, dist_thresh, R.ctypes.data,
+           t.ctypes.data, mask.ctypes.data, good.ctypes.data, C.addressof(best))
+    assert rc == 0
+    return good, best.value, R, t, mask[:M].copy()
+
+
 def triangulate(P1, P2, x1, x2):
     P1 = np.ascontiguousarray(P1, np.float64).reshape(3, 4); P2 = np.ascontiguousarray(P2, np.float64).reshape(3, 4)
     x1 = np.ascontiguousarray(x1, np.float64).reshape(2, -1); x2 = np.ascontiguousarray(x2, np.float64).reshape(2, -1)

@@ -91,6 +91,9 @@ int voo_five_point(const double* x1 /*5x2 normalised*/, const double* x2, double
                    int32_t* n_models);
 int voo_recover_pose(const double* E, const double* p1, const double* p2, int M, const double* K,
                      double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* n_good);
+/* voo_recover_pose with the four candidates' counts, (R1,t) (R2,t) (R1,-t) (R2,-t), and the index of the one taken */
+int voo_recover_pose_counts(const double* E, const double* p1, const double* p2, int M, const double* K,
+                            double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* good /*4*/, int32_t* best);
 int voo_triangulate(const double* P1, const double* P2, const double* x1 /*2xM*/,
                     const double* x2 /*2xM*/, int M, double* X /*4xM*/);
 

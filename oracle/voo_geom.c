@@ -547,10 +547,11 @@ static void decompose_essential(const double* E, double* R1, double* R2, double*
     t[0] = U[2]; t[1] = U[5]; t[2] = U[8];
 }
 
-int voo_recover_pose(const double* E, const double* p1, const double* p2, int M, const double* K,
-                     double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* n_good)
+static int recover_pose_body(const double* E, const double* p1, const double* p2, int M, const double* K,
+                             double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* good_out, int32_t* best_out)
 {
-    *n_good = 0;
+    for (int c = 0; c < 4; c++) good_out[c] = 0;
+    *best_out = 0;
     if (M < 0) return -1;
     double* x1 = (double*)malloc(sizeof(double) * 4 * (size_t)(M + 1));
     double* x2 = x1 + 2 * (size_t)M;
@@ -584,7 +585,25 @@ int voo_recover_pose(const double* E, const double* p1, const double* p2, int M,
     memcpy(R, (best & 1) ? R2 : R1, sizeof(double) * 9);
     for (int k = 0; k < 3; k++) t[k] = best >= 2 ? -tt[k] : tt[k];
     if (mask) for (int i = 0; i < M; i++) mask[i] = masks[(size_t)best * M + i] ? 255 : 0;
-    *n_good = good[best];
+    for (int c = 0; c < 4; c++) good_out[c] = good[c];
+    *best_out = best;
     free(masks); free(x1);
     return 0;
+}
+
+int voo_recover_pose(const double* E, const double* p1, const double* p2, int M, const double* K,
+                     double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* n_good)
+{
+    int32_t good[4], best;
+    int rc = recover_pose_body(E, p1, p2, M, K, dist_thresh, R, t, mask, good, &best);
+    *n_good = good[best];
+    return rc;
+}
+
+/* the same call, returning what decides the winner: the four candidates' counts in the order (R1, t), (R2, t), (R1, -t),
+ * (R2, -t) and the index taken (ties go to the lowest index) */
+int voo_recover_pose_counts(const double* E, const double* p1, const double* p2, int M, const double* K,
+                            double dist_thresh, double* R, double* t, uint8_t* mask, int32_t* good /*4*/, int32_t* best)
+{
+    return recover_pose_body(E, p1, p2, M, K, dist_thresh, R, t, mask, good, best);
 }

@@ -280,7 +280,7 @@ def test_fewer_than_five_points_python_guard(ctx):
 
 def test_batched_pair_with_too_few_matches(oracle, seq_small):
     """The kernel's M < 5 branch, through the batched path: a frame without a keypoint gives pairs without a match
-    (M = 0; pairs of 1..4 matches are not covered), beside a normal pair in the same launch."""
+    (M = 0; pairs of 1..4 matches: tests/test_gpu_pairs_chosen.py), beside a normal pair in the same launch."""
     from visual_odometry_amd import _lib
     from visual_odometry_amd.frontend import FrontEnd
     frames, K = seq_small["frames"], seq_small["K"]

@@ -818,9 +818,9 @@ __global__ __launch_bounds__(RS_THREADS) __attribute__((amdgpu_waves_per_eu(RS_O
                 res->n_inl = nm > 0 ? 5 : 0;
                 res->reserved = nm;      // number of stacked models left in pb.models
                 res->ransac_iters = 0;
+                for (int k = 0; k < 5; k++) mask[k] = nm > 0 ? 1 : 0;      // no model: no inlier, as for M > 5
             }
         }
-        if (tid < 5) mask[tid] = 1;
         return;
     }
 
