@@ -716,11 +716,51 @@ int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs /
                     int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/,
                     int32_t* n_carried /*[S]*/, int32_t* carried_frame /*[S][max_cameras]*/, double* carried_poses /*[S][max_cameras][12]*/);
 
+/* ------------------------------------------------------------------ Map.show_map_statistics (src/map.py:234-297) on the device
+ * The second thing VisualSlam.run() does per frame (src/visual_slam.py:354), as numbers (nothing is printed).  For a map given as
+ * its three dense lists in the reference's append order:
+ *   total_sqerr  calculate_reprojection_error() (:72-97): the observations' squared reprojection errors — the value
+ *                vo_reprojection_filter reports for each — ADDED IN OBSERVATION ORDER STARTING FROM 0.0, one after the other, as
+ *                the reference's loop does: the bytes are those of that sequential sum.  (The mean of :240-241 is total / nobs.)
+ *   max_sqerr    the largest of them: m = 0.0; if (e > m) m = e — a NaN never becomes the maximum.
+ *   n_high       how many have sqerr > high_threshold (the "high reprojection error" lines of :92; the reference's threshold is 10).
+ *   obs_hist     [VO_STATS_HIST]: bin k = points of the list with exactly k observations, the last bin = points with
+ *                VO_STATS_HIST - 1 or more (:245-254).  Bin 0, points that have no observation, is an addition: the reference's
+ *                defaultdict does not see them.
+ *   obs_matrix   [ncam][ncam], indices = positions in the camera list (:267-297): for every point, every pair of its observations
+ *                whose cameras differ adds 1 at [min(c1, c2)][max(c1, c2)].  Two observations of one point in one camera pair with
+ *                nothing between themselves and each with every observation in other cameras.  Diagonal and lower triangle: 0.
+ * vo_map_statistics: one map from host arrays, arguments as vo_reprojection_filter (poses ncam x 16).  More than VO_BA_MAX_CAMERAS
+ * cameras: VO_ERR_UNSUPPORTED; an observation of a missing camera or point: VO_ERR_INVALID.  An empty map is legal: all zeros.
+ *
+ * vo_set_slam_stats(ctx, on): a switch of the context, off by default.  While it is off no vo_slam_* entry launches or allocates
+ * anything for statistics.  While it is on, every vo_slam_chain / vo_slam_chains[_restart] / vo_slam_stream[_restart] /
+ * vo_slam_streams call runs one more kernel per step, after the camera limit (after snapshot stage 4), with high_threshold = 10:
+ * row p describes the map state that n_pts[p], n_obs[p], n_cam[p] describe (zeros wherever those are zero; a pair that was not
+ * localised reports the map it left untouched).  A stream keeps the setting it was started with: a resume = 1 call under the
+ * other setting is refused (VO_ERR_INVALID, the stream unharmed).
+ * vo_slam_stats: the rows of sequence seq (0 for the single-sequence entries) of the most recent vo_slam_* call.  B = that
+ * sequence's pairs in the call, C >= the call's max_cameras.  cam_frame [B][C]: the map's camera list at that pair, -1 past
+ * n_cam[p], counted as vo_slam_map counts it (along the stream in the stream forms).  VO_ERR_INVALID when the call ran with
+ * statistics off, when the sizes do not fit, or after anything that forgets the maps.  vo_slam_stats_size reports B and
+ * max_cameras of such a sequence, vo_slam_stats_counts the three list lengths the rows were computed on (show_map_statistics'
+ * first three lines; n_obs is the divisor of the mean). */
+#define VO_STATS_HIST 64
+int vo_map_statistics(vo_ctx* ctx, const double* poses /*[ncam][16]*/, int ncam, const double* points, int npt,
+                      const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs, const double* K, double high_threshold,
+                      double* total_sqerr, double* max_sqerr, int32_t* n_high, int32_t* obs_hist /*[VO_STATS_HIST]*/,
+                      int32_t* obs_matrix /*[ncam][ncam]*/);
+int vo_set_slam_stats(vo_ctx* ctx, int on);
+int vo_slam_stats_size(vo_ctx* ctx, int seq, int32_t* B, int32_t* max_cameras);
+int vo_slam_stats_counts(vo_ctx* ctx, int seq, int B, int32_t* n_cam /*[B]*/, int32_t* n_pts /*[B]*/, int32_t* n_obs /*[B]*/);
+int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*/, double* max_sqerr /*[B]*/, int32_t* n_high /*[B]*/,
+                  int32_t* obs_hist /*[B][VO_STATS_HIST]*/, int32_t* obs_matrix /*[B][C][C]*/, int32_t* cam_frame /*[B][C]*/);
+
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since
  * the last vo_profile_reset. */
-#define VO_STAGE_COUNT 28
+#define VO_STAGE_COUNT 29
 int vo_profile_enable(vo_ctx* ctx, int on);
 int vo_profile_reset(vo_ctx* ctx);
 int vo_profile_read(vo_ctx* ctx, float* ms /*VO_STAGE_COUNT*/, int32_t* launches /*VO_STAGE_COUNT*/);

@@ -16,9 +16,10 @@ LIB_PATH = os.environ.get("VO_HIP_LIBRARY") or os.path.join(_HERE, "libvo_hip.so
 VO_OK, VO_WARN_CAPACITY = 0, 1
 VO_ERR_INVALID, VO_ERR_HIP, VO_ERR_TOO_FEW, VO_ERR_NO_MODEL, VO_ERR_NOT_CONFIGURED, VO_ERR_AMBIGUOUS = -1, -2, -3, -4, -5, -6
 VO_ERR_UNSUPPORTED = -7
-VO_STAGE_COUNT = 28
+VO_STAGE_COUNT = 29
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
 VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
+VO_STATS_HIST = 64
 
 
 class OrbParams(C.Structure):
@@ -104,6 +105,11 @@ _SIGS = {
     "vo_slam_streams": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_chains_map_size": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vo_slam_chains_map": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vo_map_statistics": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P]),
+    "vo_set_slam_stats": (C.c_int, [_P, C.c_int]),
+    "vo_slam_stats_size": (C.c_int, [_P, C.c_int, _P, _P]),
+    "vo_slam_stats_counts": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "vo_slam_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_comm_unique_id": (C.c_int, [_P]),
     "vo_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "vo_comm_destroy": (C.c_int, [_P]),

@@ -5,6 +5,7 @@
 //   remove_observations_with_reprojection_errors_above_threshold (:46-70)     -> k_slam_filter
 //   limit_number_of_camera_in_map / remove_camera_from_map (:188-232, 299-318)-> k_slam_limit
 //   initialize_map's self.map.clean() (src/visual_slam.py:43-45), called again  -> k_slam_restart_seqs (vo_slam_chains_restart only)
+//   Map.show_map_statistics (src/map.py:234-297; src/visual_slam.py:354)       -> k_slam_stats (vo_set_slam_stats on, and vo_map_statistics)
 // One workgroup of 256 lanes per map and kernel: the walk is sequential by nature and the maps are the reference's size.
 // Every step is written once, as a workgroup-wide device function, and has two kernels: k_slam_* for the one chain of vo_slam_chain
 // (its buffers by value) and k_slam_*_seqs for the S independent sequences of vo_slam_chains — workgroup = sequence (blockIdx.x),
@@ -16,7 +17,9 @@
 // vo_slam_streams carries S such maps at once: k_slam_*_stream_restart_seqs, the same bodies with the sequence on the grid axis, and
 // k_slam_carry_restart_seqs, whose workgroups clear the rows their own sequence held and no others (SQ = true).
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
-// order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums.
+// order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums — but one:
+// k_slam_stats' total reprojection error, which one lane adds in observation order because that order is its contract.  That kernel
+// only reads the map and writes a statistics row of its own (StatsBuf); it is launched behind a switch that is off by default.
 #include "chain_common.h"
 
 #define SLAM_THREADS 256
@@ -696,4 +699,146 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry_restart_seqs(const 
 void launch_slam_carry_restart_seqs(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, int S)
 {
     hipLaunchKernelGGL(k_slam_carry_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, seqs, car);
+}
+
+// show_map_statistics (src/map.py:234-297) of the map as it stands: calculate_reprojection_error's total (:72-97), the largest term
+// and the number of "high" ones (:92), the points by number of observations (:245-254, with bin 0 for the points the reference's
+// defaultdict never sees) and show_observation_matrix (:267-297).  The map is only read; one row of out is written.
+// The total is the one floating-point sum of this file and its order is the contract: the terms are added one after the other in
+// observation order, from 0.0, by lane 0 — all lanes put a round's 256 terms (reprojection_sqerr_one, the expression k_slam_filter
+// uses) into one of two LDS buffers, and after the barrier lane 0 adds that round while every lane fills the other buffer with the
+// next one.  Everything else is free of order: the maximum (a NaN never wins: e > m) and the count per lane, then per wave
+// (shuffles), then over the waves in wave order; the grouping by point as k_slam_ba_prepare does it — integer atomics count,
+// an ordered scan turns the counts into cursors, an atomic cursor hands out slots — but unsorted and in scratch of the kernel's
+// own: what a slot holds is its observation's camera, and the histogram and the matrix do not depend on the order of a point's slots.
+// The lane that owns a point adds it to its bin (LDS atomic); every pair of its slots with two different cameras adds 1 to the matrix.
+// An observation that names no camera or point of the lists is not dereferenced: it is skipped and flagged (vo_map_statistics
+// reports it; a resident map has none).  pt0, obs0: where the map's ranges of the scratch start.
+__device__ __forceinline__ void slam_stats_wg(SlamMap m, int pt0, int obs0, int row, StatsBuf out)
+{
+    __shared__ int s_mat[VO_BA_MAX_CAMERAS * VO_BA_MAX_CAMERAS], s_hist[VO_STATS_HIST], s_w[SLAM_WAVES], s_nh[SLAM_WAVES];
+    __shared__ double s_err[2][SLAM_THREADS], s_mx[SLAM_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ncam = m.cnt[0], npt = m.cnt[1], nobs = m.cnt[2], C = out.C;
+    if (ncam > C || C > VO_BA_MAX_CAMERAS) {                    // cannot happen: the host sizes the rows from max_cameras
+        if (tid == 0) out.bad[0] = 1;
+        return;
+    }
+    int* cur = out.pt_cur + pt0;
+    int* slot = out.slot + obs0;
+    for (int k = tid; k < VO_BA_MAX_CAMERAS * VO_BA_MAX_CAMERAS; k += SLAM_THREADS) s_mat[k] = 0;
+    if (tid < VO_STATS_HIST) s_hist[tid] = 0;
+    for (int q = tid; q < npt; q += SLAM_THREADS) cur[q] = 0;
+    __syncthreads();
+
+    double total = 0.0, mx = 0.0;                               // (total: lane 0's)
+    int nh = 0;
+    const int rounds = (nobs + SLAM_THREADS - 1) / SLAM_THREADS;
+    for (int b = 0; b <= rounds; b++) {
+        if (b < rounds) {
+            const int i = b * SLAM_THREADS + tid;
+            double e = 0.0;
+            if (i < nobs) {
+                const int ci = m.obs_cam[i], pi = m.obs_pt[i];
+                if ((unsigned)ci < (unsigned)ncam && (unsigned)pi < (unsigned)npt) {
+                    e = reprojection_sqerr_one(m.cam_pose + 12 * (size_t)ci, m.pt_xyz + 3 * (size_t)pi, out.Kd, m.obs_xy[2 * (size_t)i], m.obs_xy[2 * (size_t)i + 1]);
+                    if (e > mx) mx = e;
+                    nh += e > out.high ? 1 : 0;
+                    atomicAdd(&cur[pi], 1);
+                } else out.bad[0] = 1;
+            }
+            s_err[b & 1][tid] = e;
+        }
+        if (tid == 0 && b > 0) {
+            const double* v = s_err[(b - 1) & 1];
+            const int n = min(SLAM_THREADS, nobs - (b - 1) * SLAM_THREADS);
+            // 16 terms at a time: their LDS reads are issued together, so that the add chain waits for one read latency per 16
+            // terms and not per term; the adds stay one after the other, in index order
+            int k = 0;
+            for (; k + 16 <= n; k += 16) {
+                double r[16];
+#pragma unroll
+                for (int j = 0; j < 16; j++) r[j] = v[k + j];
+#pragma unroll
+                for (int j = 0; j < 16; j++) total += r[j];
+            }
+            for (; k < n; k++) total += v[k];
+        }
+        __syncthreads();
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        nh += __shfl_down(nh, d);
+        const double o = __shfl_down(mx, d);
+        if (o > mx) mx = o;
+    }
+    if (lane == 0) { s_nh[wave] = nh; s_mx[wave] = mx; }
+
+    // counts -> cursors; after the slots are handed out a point's cursor is the end of its slots, the point before it gives the start
+    slam_scan(npt, s_w, [&](int q) { return cur[q]; }, [&](int q, int at, int) { cur[q] = at; });
+    __syncthreads();
+    for (int i = tid; i < nobs; i += SLAM_THREADS) {
+        const int ci = m.obs_cam[i], pi = m.obs_pt[i];
+        if ((unsigned)ci < (unsigned)ncam && (unsigned)pi < (unsigned)npt) slot[atomicAdd(&cur[pi], 1)] = ci;
+    }
+    __syncthreads();
+    // A lane owns a point and reads its slots once, into a mask of the cameras that see it.  A point no camera sees twice adds 1 at
+    // every pair of its cameras: such a cell is counted over the wave's 64 points at once (a ballot per cell, one LDS add by lane
+    // 0).  A point some camera sees twice (the dead-rooted track) walks the pairs of its slots on its own and leaves the ballots.
+    for (int b = 0; b < npt; b += SLAM_THREADS) {               // (uniform trip count: there are ballots inside)
+        const int q = b + tid;
+        unsigned long long seen = 0;
+        bool twice = false;
+        int j0 = 0, j1 = 0;
+        if (q < npt) {
+            j0 = q > 0 ? cur[q - 1] : 0; j1 = cur[q];
+            for (int a = j0; a < j1; a++) { const unsigned long long bit = 1ULL << slot[a]; twice |= (seen & bit) != 0; seen |= bit; }
+            atomicAdd(&s_hist[min(j1 - j0, VO_STATS_HIST - 1)], 1);
+        }
+        if (twice) {
+            for (int a = j0; a < j1; a++) {
+                const int c1 = slot[a];
+                for (int k = a + 1; k < j1; k++) {
+                    const int c2 = slot[k];
+                    if (c1 != c2) atomicAdd(&s_mat[min(c1, c2) * VO_BA_MAX_CAMERAS + max(c1, c2)], 1);
+                }
+            }
+            seen = 0;
+        }
+        for (int c1 = 0; c1 + 1 < ncam; c1++) {
+            if (__ballot((int)((seen >> c1) & 1)) == 0) continue;  // (wave-uniform)
+            for (int c2 = c1 + 1; c2 < ncam; c2++) {
+                const unsigned long long w = __ballot((int)((seen >> c1) & (seen >> c2) & 1));
+                if (w != 0 && lane == 0) atomicAdd(&s_mat[c1 * VO_BA_MAX_CAMERAS + c2], (int)__popcll(w));
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < SLAM_WAVES; w++) { nh += s_nh[w]; if (s_mx[w] > mx) mx = s_mx[w]; }
+        out.total_sqerr[row] = total; out.max_sqerr[row] = mx; out.n_high[row] = nh;
+        out.counts[3 * (size_t)row] = ncam; out.counts[3 * (size_t)row + 1] = npt; out.counts[3 * (size_t)row + 2] = nobs;
+    }
+    if (tid < VO_STATS_HIST) out.obs_hist[(size_t)row * VO_STATS_HIST + tid] = s_hist[tid];
+    for (int k = tid; k < C * C; k += SLAM_THREADS) out.obs_matrix[(size_t)row * C * C + k] = s_mat[(k / C) * VO_BA_MAX_CAMERAS + k % C];
+    if (out.cam_frame && tid < C) out.cam_frame[(size_t)row * C + tid] = tid < ncam ? m.cam_frame[tid] : -1;
+}
+
+// (sb.base: where this map's ranges start — all 0 for a single chain, as for k_bundle_adjust)
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_stats(int p, SlamBuf sb, StatsBuf out) { slam_stats_wg(sb.m, sb.base.pt0, sb.base.obs0, p, out); }
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_stats_seqs(int j, const SlamSeq* __restrict__ seqs, StatsBuf out)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    if (j >= q.count) return;
+    slam_stats_wg(q.sb.m, q.sb.base.pt0, q.sb.base.obs0, q.first + j, out);
+}
+
+void launch_slam_stats(hipStream_t s, int p, SlamBuf sb, StatsBuf out)
+{
+    hipLaunchKernelGGL(k_slam_stats, dim3(1), dim3(SLAM_THREADS), 0, s, p, sb, out);
+}
+
+void launch_slam_stats_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S, StatsBuf out)
+{
+    hipLaunchKernelGGL(k_slam_stats_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, j, seqs, out);
 }

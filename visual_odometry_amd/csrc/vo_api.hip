@@ -10,7 +10,7 @@
 #include <type_traits>
 #include <algorithm>
 
-#define MAX_EVENTS 384                        // vo_slam_chain brackets five kernel groups per pair
+#define MAX_EVENTS 384                        // vo_slam_chain brackets five kernel groups per pair, six with vo_set_slam_stats on
 
 // The device (and pinned host) allocations of one lifetime: each one its own hipMalloc, all freed together by release() or
 // the destructor.  n == 0 allocates one element.
@@ -92,6 +92,13 @@ struct LastRun {
     std::vector<Map> seq_map;
     Map snap_map;
     int snap_seq = -1;
+    // ... and, if it ran with vo_set_slam_stats on, its statistics rows: sequence s owns rows seq_off[s] .. seq_off[s + 1] - 1
+    struct Stats {
+        bool valid = false;
+        int C = 0;                        // cameras a row holds: the call's max_cameras + 1
+        std::vector<int32_t> seq_off, n_high, counts, obs_hist, obs_matrix, cam_frame;
+        std::vector<double> total_sqerr, max_sqerr;
+    } stats;
 };
 
 // vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one
@@ -129,6 +136,8 @@ struct SlamStream {
     std::vector<int32_t> rows;
     SlamSeq* dseq = nullptr; SlamSeqCarry* dcar = nullptr; int* drows = nullptr;
     size_t snap_np = 0, snap_no = 0;
+    bool stats = false;                   // started with vo_set_slam_stats on: the rows and the kernel's scratch are part of the allocation
+    StatsBuf sbuf{};
 };
 
 struct vo_ctx {
@@ -192,6 +201,7 @@ struct vo_ctx {
     bool cv2_ready = false;
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
+    int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it
 };
 
 static const char* k_stage_names[VO_STAGE_COUNT] = {
@@ -199,7 +209,7 @@ static const char* k_stage_names[VO_STAGE_COUNT] = {
     "gaussian_blur", "rbrief", "match_nn", "match_select", "essential_ransac", "recover_pose",
     "triangulate", "misc", "reserved", "sift_scale_space", "sift_extrema", "sift_refine_orient", "sift_sort_unique",
     "sift_descriptor", "cv2_keypoint_order", "trajectory_gather", "reserved2", "slam_ba_prepare", "slam_bundle_adjust", "slam_filter",
-    "slam_camera_limit"};
+    "slam_camera_limit", "slam_map_statistics"};
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -262,6 +272,22 @@ struct ScratchLayout {
     struct Slot { void* dst; size_t off; void (*set)(void*, uint8_t*); };
     std::vector<Slot> slots;
 };
+
+// vo_set_slam_stats: the statistics rows of P pairs with room for cm cameras, and k_slam_stats' scratch for np points and no
+// observations, as sub-buffers of a call's layout.  Off: nothing is taken, the layout is byte for byte what it was.
+static void slam_stats_take_scratch(ScratchLayout& sc, StatsBuf& d, bool on, size_t np, size_t no)
+{
+    if (!on) return;
+    sc.take(&d.pt_cur, np); sc.take(&d.slot, no); sc.take(&d.bad, 1);
+}
+
+static void slam_stats_take_rows(ScratchLayout& sc, StatsBuf& d, bool on, size_t P, size_t cm)
+{
+    if (!on) return;
+    sc.take(&d.total_sqerr, P); sc.take(&d.max_sqerr, P); sc.take(&d.n_high, P); sc.take(&d.counts, P * 3); sc.take(&d.obs_hist, P * VO_STATS_HIST);
+    sc.take(&d.obs_matrix, P * cm * cm); sc.take(&d.cam_frame, P * cm);
+    d.C = (int)cm; d.high = 10.0;
+}
 
 // ------------------------------------------------------------------ profiling brackets
 struct StageTimer {
@@ -557,6 +583,14 @@ extern "C" int vo_set_pnp_refine(vo_ctx* ctx, int kind)
     if (!ctx) return VO_ERR_INVALID;
     if (kind != 0 && kind != 1) FAIL(VO_ERR_INVALID, "pnp refine must be 1 (cv2's solvePnP(ITERATIVE) on the inliers) or 0 (fast minimiser from the RANSAC model)");
     ctx->pnp_refine = kind;
+    return VO_OK;
+}
+
+extern "C" int vo_set_slam_stats(vo_ctx* ctx, int on)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (on != 0 && on != 1) FAIL(VO_ERR_INVALID, "slam stats must be 0 (off) or 1 (one k_slam_stats launch per step of every vo_slam_* call)");
+    ctx->slam_stats = on;
     return VO_OK;
 }
 
@@ -1804,6 +1838,53 @@ extern "C" int vo_reprojection_filter(vo_ctx* ctx, const double* poses, int ncam
     return VO_OK;
 }
 
+// ------------------------------------------------------------------ Map.show_map_statistics, src/map.py:234-297
+// The host arrays as a SlamMap (counts, [R | t] rows at stride 12) and one launch of the resident maps' k_slam_stats on it.
+extern "C" int vo_map_statistics(vo_ctx* ctx, const double* poses, int ncam, const double* points, int npt,
+                                 const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs, const double* K, double high_threshold,
+                                 double* total_sqerr, double* max_sqerr, int32_t* n_high, int32_t* obs_hist, int32_t* obs_matrix)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (ncam < 0 || npt < 0 || nobs < 0 || !K || !total_sqerr || !max_sqerr || !n_high || !obs_hist || (ncam > 0 && (!poses || !obs_matrix)) || (npt > 0 && !points) ||
+        (nobs > 0 && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
+    if (ncam > VO_BA_MAX_CAMERAS) FAIL(VO_ERR_UNSUPPORTED, "the observation matrix holds at most %d cameras, got %d", VO_BA_MAX_CAMERAS, ncam);
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<double> rt((size_t)12 * ncam);
+    for (int c = 0; c < ncam; c++) memcpy(rt.data() + (size_t)12 * c, poses + (size_t)16 * c, 96);
+    const int cnt[4] = {ncam, npt, nobs, 0};
+    SlamBuf sb{}; StatsBuf d{}; double* dK;
+    ScratchLayout sc;
+    sc.take(&sb.m.cnt, 4); sc.take(&sb.m.cam_pose, (size_t)12 * ncam); sc.take(&sb.m.pt_xyz, (size_t)3 * npt);
+    sc.take(&sb.m.obs_cam, nobs); sc.take(&sb.m.obs_pt, nobs); sc.take(&sb.m.obs_xy, (size_t)2 * nobs); sc.take(&dK, 9);
+    slam_stats_take_scratch(sc, d, true, npt, nobs); slam_stats_take_rows(sc, d, true, 1, ncam);
+    int rc = sc.place(ctx); if (rc) return rc;
+    d.Kd = dK; d.high = high_threshold; d.cam_frame = nullptr;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(sb.m.cnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, s));
+    if (ncam) HIPCHK(hipMemcpyAsync(sb.m.cam_pose, rt.data(), (size_t)96 * ncam, hipMemcpyHostToDevice, s));
+    if (npt) HIPCHK(hipMemcpyAsync(sb.m.pt_xyz, points, (size_t)24 * npt, hipMemcpyHostToDevice, s));
+    if (nobs) {
+        HIPCHK(hipMemcpyAsync(sb.m.obs_cam, obs_cam, (size_t)4 * nobs, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sb.m.obs_pt, obs_pt, (size_t)4 * nobs, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sb.m.obs_xy, obs_xy, (size_t)16 * nobs, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d.bad, 0, sizeof(int), s));
+    { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats(s, 0, sb, d); }
+    HIPCHK(hipGetLastError());
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(total_sqerr, d.total_sqerr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(max_sqerr, d.max_sqerr, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_high, d.n_high, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(obs_hist, d.obs_hist, VO_STATS_HIST * 4, hipMemcpyDeviceToHost, s));
+    if (ncam) HIPCHK(hipMemcpyAsync(obs_matrix, d.obs_matrix, (size_t)4 * ncam * ncam, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&bad, d.bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    if (bad) FAIL(VO_ERR_INVALID, "an observation refers to a missing camera or point");
+    return VO_OK;
+}
+
 // ------------------------------------------------------------------ bundle adjustment: Map.optimize_map, src/map.py:104-186
 // The host's part is the bookkeeping g2o's graph does: reject what the kernel cannot hold, sort each problem's observations
 // by point (counting sort, stable in input order: a lane owns a point) and list, per block (c1 <= c2) of free cameras, the
@@ -2924,6 +3005,25 @@ static void forget_slam_maps(vo_ctx* ctx)
 {
     ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
     ctx->last.seq_map.clear(); ctx->last.snap_map = LastRun::Map(); ctx->last.snap_seq = -1;
+    ctx->last.stats = LastRun::Stats();
+}
+
+// the rows of a call that has come through (its stream has been waited for) -> the context's host copy
+static int slam_stats_download(vo_ctx* ctx, const StatsBuf& d, std::vector<int32_t> seq_off)
+{
+    LastRun::Stats& h = ctx->last.stats;
+    const size_t P = (size_t)seq_off.back(), C = (size_t)d.C;
+    h = LastRun::Stats();
+    h.total_sqerr.resize(P); h.max_sqerr.resize(P); h.n_high.resize(P); h.counts.resize(P * 3); h.obs_hist.resize(P * VO_STATS_HIST); h.obs_matrix.resize(P * C * C); h.cam_frame.resize(P * C);
+    HIPCHK(hipMemcpy(h.total_sqerr.data(), d.total_sqerr, P * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.max_sqerr.data(), d.max_sqerr, P * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.n_high.data(), d.n_high, P * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.counts.data(), d.counts, P * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.obs_hist.data(), d.obs_hist, P * VO_STATS_HIST * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.obs_matrix.data(), d.obs_matrix, P * C * C * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.cam_frame.data(), d.cam_frame, P * C * 4, hipMemcpyDeviceToHost));
+    h.C = d.C; h.seq_off = std::move(seq_off); h.valid = true;
+    return VO_OK;
 }
 
 // the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
@@ -2979,7 +3079,11 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
     sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
     double* dchi2; int *dit, *dtr;
     sc.take(&dchi2, (size_t)2 * B); sc.take(&dit, B); sc.take(&dtr, B);
+    const bool stats_on = ctx->slam_stats != 0;
+    StatsBuf stats{};
+    slam_stats_take_scratch(sc, stats, stats_on, np, no); slam_stats_take_rows(sc, stats, stats_on, B, cm);
     rc = sc.place(ctx); if (rc) return rc;
+    stats.Kd = dK;
     SlamMap snap{};
     slam_map_carve(map_mem, cm, np, no, &sb.m); slam_map_carve(snap_mem, cm, np, no, &snap);
     sb.cam_cap = (int)cm; sb.pt_cap = (int)np; sb.obs_cap = (int)no; sb.pair_cap = (int)npair;
@@ -3019,6 +3123,7 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
         snapshot(p, 3);
         { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit(s, p, o->max_cameras, cb, sb); }
         snapshot(p, 4);
+        if (stats_on) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats(s, p, sb, stats); }
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
@@ -3037,6 +3142,7 @@ extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_
     // the scratch buffer belongs to the next call: the two maps are kept as host copies
     rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
     if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, snap, cap, &ctx->last.map[1]); if (rc) return rc; }
+    if (stats_on) { rc = slam_stats_download(ctx, stats, {0, B}); if (rc) return rc; }
     return VO_OK;
 }
 
@@ -3111,7 +3217,10 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, bool restart, int F
     sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
     sc.take(&sb.pairs, npair); sc.take(&sb.blk_first, (size_t)nblk + 1);
     sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
+    st.stats = ctx->slam_stats != 0;
+    slam_stats_take_scratch(sc, st.sbuf, st.stats, np, no);
     const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
+    slam_stats_take_rows(sc, st.sbuf, st.stats, P, cm);
     sc.take(&cb.poses, (P + 1) * 12); sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P);
     sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P); sc.take(&sb.poses_last, (P + 1) * 12);
     sc.take(&st.dchi2, 2 * P); sc.take(&st.dit, P); sc.take(&st.dtr, P);
@@ -3120,6 +3229,7 @@ static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, bool restart, int F
     sc.take(&cb.rs.seg_poses, restart ? P * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? P * 12 : 0);
     HIPCHK(st.mem.alloc(&st.base, sc.bytes));
     sc.place_at(st.base);
+    st.sbuf.Kd = st.dK;
     if (!restart) cb.rs = RestartBuf{};
     st.restart = restart;
     st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
@@ -3166,6 +3276,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
             FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
         if (st.lost && !restart) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
         if (st.touched) FAIL(VO_ERR_INVALID, "%s: slot %d, the stream's last frame, was uploaded to or detected again", who, st.anchor);
+        if (st.stats != (ctx->slam_stats != 0)) FAIL(VO_ERR_INVALID, "%s: the stream was started with statistics %s (vo_set_slam_stats) and is continued only so", who, st.stats ? "on" : "off");
     }
     int F, cap;
     int rc = chain_check(ctx, B, who, &F, &cap); if (rc) return rc;
@@ -3249,6 +3360,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
             else launch_slam_limit_stream(s, p, o->max_cameras, cb, sb);
         }
         snapshot(p, 4);
+        if (st.stats) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats(s, p, sb, st.sbuf); }
     }
     HIPCHK(hipGetLastError());
     // the anchor camera of the next call: this call's last rows
@@ -3282,6 +3394,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     if (ctx->prof) prof_collect(ctx);
     rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
     if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, st.snap, cap, &ctx->last.map[1]); if (rc) return rc; }
+    if (st.stats) { rc = slam_stats_download(ctx, st.sbuf, {0, B}); if (rc) return rc; }
     // (a restart stream is lost when the device says so: a pair that fails and a pair that restarts can share a call)
     st.lost = restart && !alive;
     for (int p = 0; p < B && !restart; p++) if (status[p] != VO_OK) st.lost = true;
@@ -3408,7 +3521,11 @@ static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_
     sc.take(&dseq, S);
     sc.take(&cb.rs.st, restart ? (size_t)4 * S : 0); sc.take(&cb.rs.segment, restart ? B : 0); sc.take(&cb.rs.cause, restart ? B : 0);
     sc.take(&cb.rs.seg_poses, restart ? (size_t)B * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? (size_t)B * 12 : 0);
+    const bool stats_on = ctx->slam_stats != 0;
+    StatsBuf stats{};
+    slam_stats_take_scratch(sc, stats, stats_on, NP, NO); slam_stats_take_rows(sc, stats, stats_on, B, cm);
     rc = sc.place(ctx); if (rc) return rc;
+    stats.Kd = dK;
     if (!restart) cb.rs = RestartBuf{};
     if (snap_on) slam_map_carve(snap_mem, cm, snap_np, snap_no, &snap);
     D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
@@ -3485,6 +3602,7 @@ static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_
         snapshot(j, 3);
         { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_seqs(s, j, o->max_cameras, dseq, S); }
         snapshot(j, 4);
+        if (stats_on) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats_seqs(s, j, dseq, S, stats); }
     }
     HIPCHK(hipGetLastError());
     std::vector<double> hchi((size_t)2 * maxB * S); std::vector<int32_t> hit((size_t)maxB * S), htr((size_t)maxB * S);
@@ -3521,6 +3639,7 @@ static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_
     if (snap_on && ss == 0) ctx->last.map[1] = smap;
     ctx->last.seq_map = std::move(maps);
     if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
+    if (stats_on) { rc = slam_stats_download(ctx, stats, std::vector<int32_t>(seq_off, seq_off + S + 1)); if (rc) return rc; }
     return VO_OK;
 }
 
@@ -3585,7 +3704,10 @@ static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int 
     sc.take(&snap.pt_key, st.snap_np); sc.take(&snap.pt_xyz, st.snap_np * 3); sc.take(&snap.pt_feat, st.snap_np * 2);
     sc.take(&snap.obs_cam, st.snap_no); sc.take(&snap.obs_pt, st.snap_no); sc.take(&snap.obs_xy, st.snap_no * 2);
     sc.take(&st.dseq, S); sc.take(&st.dcar, S); sc.take(&st.drows, (size_t)S * (P + 1));
+    st.stats = ctx->slam_stats != 0;
+    slam_stats_take_scratch(sc, st.sbuf, st.stats, NP, NO);
     const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
+    slam_stats_take_rows(sc, st.sbuf, st.stats, P, cm);
     sc.take(&cb.poses, (P + S) * 12); sc.take(&sb.poses_last, (P + S) * 12);
     sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P); sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P);
     sc.take(&st.dchi2, 2 * P * S); sc.take(&st.dit, P * S); sc.take(&st.dtr, P * S);       // k_bundle_adjust writes problem s of step j at [j][s]
@@ -3593,6 +3715,7 @@ static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int 
     sc.take(&cb.rs.segment, P); sc.take(&cb.rs.cause, P); sc.take(&cb.rs.seg_poses, P * 12); sc.take(&cb.rs.seg_poses_last, P * 12);
     HIPCHK(st.mem.alloc(&st.base, sc.bytes));
     sc.place_at(st.base);
+    st.sbuf.Kd = st.dK;
     st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
     D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
     D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
@@ -3686,6 +3809,7 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
         if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
         if (!st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
         if (S != st.S) FAIL(VO_ERR_INVALID, "%s: the stream has %d sequences, the call names %d", who, st.S, S);
+        if (st.stats != (ctx->slam_stats != 0)) FAIL(VO_ERR_INVALID, "%s: the stream was started with statistics %s (vo_set_slam_stats) and is continued only so", who, st.stats ? "on" : "off");
     }
     int F, cap;
     int rc = streams_check(ctx, resume, S, seq_off, &F, &cap); if (rc) return rc;
@@ -3789,6 +3913,7 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
         snapshot(j, 3);
         { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_stream_restart_seqs(s, j, o->max_cameras, dseq, S); }
         snapshot(j, 4);
+        if (st.stats) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats_seqs(s, j, dseq, S, st.sbuf); }
     }
     HIPCHK(hipGetLastError());
     // the anchor camera of a sequence's next call: its last rows of this call (an idle sequence keeps the one it has)
@@ -3839,6 +3964,7 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
     if (snap_on && ss == 0) ctx->last.map[1] = smap;
     ctx->last.seq_map = std::move(maps);
     if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
+    if (st.stats) { rc = slam_stats_download(ctx, st.sbuf, std::vector<int32_t>(seq_off, seq_off + S + 1)); if (rc) return rc; }
     // the stream's state for the next call.  A sequence that advanced gives back every slot but its new anchor's; an idle one has
     // given back all it had at this call's carry.
     const int32_t* sl = ctx->last.slots.data();
@@ -3887,6 +4013,66 @@ extern "C" int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_
     const LastRun::Map* m = slam_chains_map_of(ctx, seq, which);
     if (!m) return VO_ERR_INVALID;
     return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
+}
+
+// the statistics rows of sequence seq of the most recent vo_slam_* call, nullptr (and the reason in ctx->err) if there are none
+static const LastRun::Stats* slam_stats_of(vo_ctx* ctx, int seq)
+{
+    const LastRun::Stats& h = ctx->last.stats;
+    const char* why = nullptr;
+    if (!h.valid) why = "no statistics: no vo_slam_* call has run with vo_set_slam_stats on since the last configure / vo_pairs_run / chain call";
+    else if (seq < 0 || seq + 1 >= (int)h.seq_off.size()) why = "no such sequence in the most recent vo_slam_* call";
+    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); return nullptr; }
+    return &h;
+}
+
+extern "C" int vo_slam_stats_size(vo_ctx* ctx, int seq, int32_t* B, int32_t* max_cameras)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!B || !max_cameras) FAIL(VO_ERR_INVALID, "bad arguments");
+    const LastRun::Stats* h = slam_stats_of(ctx, seq);
+    if (!h) return VO_ERR_INVALID;
+    *B = h->seq_off[(size_t)seq + 1] - h->seq_off[(size_t)seq]; *max_cameras = h->C - 1;
+    return VO_OK;
+}
+
+extern "C" int vo_slam_stats_counts(vo_ctx* ctx, int seq, int B, int32_t* n_cam, int32_t* n_pts, int32_t* n_obs)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const LastRun::Stats* h = slam_stats_of(ctx, seq);
+    if (!h) return VO_ERR_INVALID;
+    const int first = h->seq_off[(size_t)seq], n = h->seq_off[(size_t)seq + 1] - first;
+    if (B != n) FAIL(VO_ERR_INVALID, "sequence %d had %d pairs in the call, B = %d", seq, n, B);
+    if (B > 0 && (!n_cam || !n_pts || !n_obs)) FAIL(VO_ERR_INVALID, "bad arguments");
+    for (int p = 0; p < B; p++) {
+        const int32_t* c = h->counts.data() + 3 * ((size_t)first + p);
+        n_cam[p] = c[0]; n_pts[p] = c[1]; n_obs[p] = c[2];
+    }
+    return VO_OK;
+}
+
+extern "C" int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr, double* max_sqerr, int32_t* n_high, int32_t* obs_hist,
+                             int32_t* obs_matrix, int32_t* cam_frame)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const LastRun::Stats* h = slam_stats_of(ctx, seq);
+    if (!h) return VO_ERR_INVALID;
+    const int first = h->seq_off[(size_t)seq], n = h->seq_off[(size_t)seq + 1] - first, hc = h->C;
+    if (B != n) FAIL(VO_ERR_INVALID, "sequence %d had %d pairs in the call, B = %d", seq, n, B);
+    if (C < hc - 1) FAIL(VO_ERR_INVALID, "C = %d is less than the call's max_cameras = %d", C, hc - 1);
+    if (B > 0 && (!total_sqerr || !max_sqerr || !n_high || !obs_hist || !obs_matrix || !cam_frame)) FAIL(VO_ERR_INVALID, "bad arguments");
+    // (a row holds max_cameras + 1 cameras, the map after the limit at most max_cameras: the last row and column are empty)
+    const int k = std::min(C, hc);
+    for (int p = 0; p < B; p++) {
+        const size_t r = (size_t)first + p;
+        total_sqerr[p] = h->total_sqerr[r]; max_sqerr[p] = h->max_sqerr[r]; n_high[p] = h->n_high[r];
+        memcpy(obs_hist + (size_t)p * VO_STATS_HIST, h->obs_hist.data() + r * VO_STATS_HIST, VO_STATS_HIST * sizeof(int32_t));
+        for (int a = 0; a < C; a++) {
+            cam_frame[(size_t)p * C + a] = a < k ? h->cam_frame[r * hc + a] : -1;
+            for (int b = 0; b < C; b++) obs_matrix[((size_t)p * C + a) * C + b] = a < k && b < k ? h->obs_matrix[(r * hc + a) * hc + b] : 0;
+        }
+    }
+    return VO_OK;
 }
 
 extern "C" int vo_profile_enable(vo_ctx* ctx, int on)

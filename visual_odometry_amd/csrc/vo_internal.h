@@ -9,7 +9,7 @@ enum {
     ST_GRAY = 0, ST_RESIZE, ST_FAST, ST_SELECT_FAST, ST_HARRIS, ST_SELECT_HARRIS, ST_ANGLE,
     ST_BLUR, ST_BRIEF, ST_MATCH_NN, ST_MATCH_SELECT, ST_RANSAC, ST_POSE, ST_TRIANGULATE,
     ST_MISC, ST_RESERVED, ST_SIFT_SCALE, ST_SIFT_EXTREMA, ST_SIFT_ORIENT, ST_SIFT_SORT, ST_SIFT_DESC, ST_CV2_ORDER, ST_GATHER, ST_RESERVED2,
-    ST_SLAM_PREPARE, ST_SLAM_BA, ST_SLAM_FILTER, ST_SLAM_LIMIT
+    ST_SLAM_PREPARE, ST_SLAM_BA, ST_SLAM_FILTER, ST_SLAM_LIMIT, ST_SLAM_STATS
 };
 
 // ---- pyramid / work geometry, passed to kernels by value ------------------------------------
@@ -410,5 +410,23 @@ void launch_slam_restart_stream_seqs(hipStream_t s, PairBuf pb, int kp_cap, int 
 void launch_slam_add_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S);
 void launch_slam_filter_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);
 void launch_slam_limit_stream_restart_seqs(hipStream_t s, int j, int max_cameras, const SlamSeq* seqs, int S);
+// ---- show_map_statistics (src/map.py:234-297) of a resident map (slam_kernels.hip, k_slam_stats): one row of statistics per pair.
+// Passed to the two statistics kernels only; no other kernel sees it, and SlamBuf / SlamMap / ChainBuf / SlamSeq are as they were.
+struct StatsBuf {
+    double*  total_sqerr; double* max_sqerr;   // [rows] calculate_reprojection_error's sum in observation order; the largest term
+    int*     n_high;                    // [rows] observations with sqerr > high
+    int*     counts;                    // [rows][3] the three list lengths: cameras, points, observations
+    int*     obs_hist;                  // [rows][VO_STATS_HIST] points by number of observations, the last bin open-ended
+    int*     obs_matrix;                // [rows][C][C] points a pair of cameras sees together, upper triangle
+    int*     cam_frame;                 // [rows][C] the map's camera list, -1 past its end (nullptr: not wanted)
+    int      C;                         // cameras a row has room for (<= VO_BA_MAX_CAMERAS)
+    int*     pt_cur;                    // the kernel's own scratch: per point a count, then a cursor, then the end of its slots; a map
+    int*     slot;                      //   uses the range that starts at its pt0 / obs0.  slot: per observation, grouped by point, its camera
+    int*     bad;                       // [1] set when an observation names a missing camera or point (it is skipped)
+    const double* Kd;
+    double   high;                      // show_map_statistics' threshold of a "high reprojection error" (src/map.py:72: 10)
+};
+void launch_slam_stats(hipStream_t s, int p, SlamBuf sb, StatsBuf out);
+void launch_slam_stats_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S, StatsBuf out);
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

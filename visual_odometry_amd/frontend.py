@@ -402,6 +402,33 @@ class FrontEnd:
         m["cam_fixed"] = m["cam_fixed"].astype(bool)
         return m
 
+    def map_stats(self, on=True):
+        """Switch Map.show_map_statistics (src/map.py:234-297) for the resident map on or off (vo_set_slam_stats; off by default).
+        While on, every slam_chain / slam_chains / slam_stream / slam_stream_restart / slam_streams call runs one more kernel per
+        step and slam_stats() reports its rows; the calls' own results do not change.  A stream keeps the setting it started with."""
+        c = self.ctx
+        c.check(c.lib.vo_set_slam_stats(c.handle, int(bool(on))))
+
+    def slam_stats(self, seq=0):
+        """The statistics of sequence `seq` of the latest slam_* call, one row per pair of that sequence in the call, each for the
+        map as n_pts / n_obs / n_cam of that pair describe it: dict(total_sqerr [B] (calculate_reprojection_error: the sum in
+        observation order), mean_sqerr [B] (total / n_obs, 0 without observations), max_sqerr [B], n_high [B] (sqerr > 10),
+        obs_hist [B, 64] (points by number of observations, bin 63 = 63 or more, bin 0 = none), obs_matrix [B, C, C] (points two
+        cameras see together, upper triangle, by position in the camera list; C = max_cameras), cam_frame [B, C] (the camera
+        list, -1 past its end, counted as slam_map counts it)).  Raises VoError if the call ran with map_stats off."""
+        c = self.ctx
+        nb, nc = C.c_int32(0), C.c_int32(0)
+        c.check(c.lib.vo_slam_stats_size(c.handle, int(seq), C.addressof(nb), C.addressof(nc)))
+        B, cm = nb.value, nc.value
+        d = dict(total_sqerr=np.zeros(B), max_sqerr=np.zeros(B), n_high=np.zeros(B, np.int32), obs_hist=np.zeros((B, _lib.VO_STATS_HIST), np.int32),
+                 obs_matrix=np.zeros((B, cm, cm), np.int32), cam_frame=np.zeros((B, cm), np.int32))
+        c.check(c.lib.vo_slam_stats(c.handle, int(seq), B, cm, *[d[k].ctypes.data for k in ("total_sqerr", "max_sqerr", "n_high", "obs_hist",
+                                                                                            "obs_matrix", "cam_frame")]))
+        n = [np.zeros(B, np.int32) for _ in range(3)]
+        c.check(c.lib.vo_slam_stats_counts(c.handle, int(seq), B, *[v.ctypes.data for v in n]))
+        d["mean_sqerr"] = mean_sqerr(d["total_sqerr"], n[2])
+        return d
+
     def gather_records(self, B, world=1, wait=True):
         """All-gather the [R|t] + counts records (16 float64 per pair) of the first B pairs of the latest run_pairs
         over the context's RCCL communicator (ctx.comm_init; without one: the local records).  Returns a
@@ -556,6 +583,28 @@ def join_stream(outs):
     if restart:
         out["seg_poses"] = seg_poses
     return out
+
+
+STATS_KEYS = ("total_sqerr", "mean_sqerr", "max_sqerr", "n_high", "obs_hist", "obs_matrix", "cam_frame")
+
+
+def mean_sqerr(total_sqerr, n_obs):
+    """show_map_statistics' mean (src/map.py:240-241): total / n_obs where there are observations, 0.0 elsewhere."""
+    total, n = np.asarray(total_sqerr, np.float64), np.asarray(n_obs)
+    return np.divide(total, n, out=np.zeros(total.shape), where=n > 0)
+
+
+def join_stats(stats):
+    """The slam_stats() dicts of the calls of one stream, in order -> the whole flight's rows: every key concatenated along the pair
+    axis (a row is complete in itself; cam_frame already counts along the stream).  Calls in which the sequence was idle have no
+    rows and add nothing.  For slam_streams: join_stats([fe.slam_stats(s) after each call]) per sequence s.  Pure: no GPU, no library."""
+    stats = list(stats)
+    if not stats:
+        raise ValueError("join_stats takes at least one call")
+    widths = {np.asarray(d["cam_frame"]).shape[1] for d in stats}
+    if len(widths) != 1:
+        raise ValueError(f"the calls of one stream all have the same max_cameras, got row widths {sorted(widths)}")
+    return {k: np.concatenate([np.asarray(d[k]) for d in stats]) for k in STATS_KEYS}
 
 
 def stream_slice(out, s):

@@ -68,6 +68,39 @@ def calculate_reprojection_error(cameras, points, observations, camera_matrix, c
     return total
 
 
+def map_statistics(poses, points, obs_cam, obs_pt, obs_xy, camera_matrix, high_threshold=10.0, ctx=None):
+    """map.py:234-297 — Map.show_map_statistics as numbers, in one device call (vo_map_statistics); nothing is printed.  Arrays as
+    reprojection_sqerr takes them (poses [ncam, 4, 4]).  Returns dict(n_cam, n_pts, n_obs (the three list lengths), total_sqerr
+    (calculate_reprojection_error: the sum in observation order), mean_sqerr (total / n_obs, 0.0 without observations), max_sqerr,
+    n_high (observations with sqerr > high_threshold), obs_hist [64] (points by number of observations; bin 63 = 63 or more, bin 0 =
+    none), obs_matrix [ncam, ncam] (points two cameras see together, upper triangle, by position in the camera list)).
+    More than 64 cameras raise NotImplementedError, an observation of a missing camera or point VoError."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    oc = np.ascontiguousarray(obs_cam, np.int32).ravel(); op = np.ascontiguousarray(obs_pt, np.int32).ravel()
+    xy = np.ascontiguousarray(obs_xy, np.float64).reshape(-1, 2)
+    K = np.ascontiguousarray(camera_matrix, np.float64).reshape(3, 3)
+    n = len(oc)
+    if not (len(op) == n == len(xy)):
+        raise ValueError("observation arrays differ in length")
+    total, mx, nh = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int32(0)
+    hist = np.zeros(_lib.VO_STATS_HIST, np.int32); mat = np.zeros((len(poses), len(poses)), np.int32)
+    ctx = ctx or _lib.default_context()
+    rc = ctx.lib.vo_map_statistics(ctx.handle, _lib.ptr(poses), len(poses), _lib.ptr(points), len(points), _lib.ptr(oc), _lib.ptr(op), _lib.ptr(xy), n,
+                                   K.ctypes.data, float(high_threshold), ctypes.addressof(total), ctypes.addressof(mx), ctypes.addressof(nh),
+                                   hist.ctypes.data, _lib.ptr(mat))
+    if rc == _lib.VO_ERR_UNSUPPORTED:
+        raise NotImplementedError(ctx.last_error())
+    ctx.check(rc)
+    return dict(n_cam=len(poses), n_pts=len(points), n_obs=n, total_sqerr=total.value, mean_sqerr=total.value / n if n > 0 else 0.0,
+                max_sqerr=mx.value, n_high=nh.value, obs_hist=hist, obs_matrix=mat)
+
+
+def show_map_statistics(cameras, points, observations, camera_matrix, ctx=None):
+    """map.py:234-297 on the reference's record types (duck typed, as the functions above): the dict map_statistics returns."""
+    return map_statistics(*_arrays(cameras, points, observations), camera_matrix, 10.0, ctx)
+
+
 def feature_tracks(n_frames, cap, pair_frames, matches, ctx=None):
     """update_feature_mapper + track_feature_back_in_time (visual_slam.py:183-188, :94-99) for every feature at once.
 
