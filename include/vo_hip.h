@@ -706,8 +706,9 @@ int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, cons
  * How: vo_slam_chains_restart's host loop — every kernel once per step j = 0 .. max B_s - 1 with the sequence on a grid axis —
  * on the stream / restart kernel bodies (k_slam_*_stream_restart_seqs), with one k_slam_carry_restart_seqs launch in front.
  * [deviation] none in the results.
- * Out of scope: a multi-stream without restart, sequences that join or leave a live stream, sequences that share a slot, joining
- * segments or shards into one gauge, relocalisation, pruning, ratio matches. */
+ * Out of scope: a multi-stream without restart, changing S of a live stream (a flight that ends hands its seat to the next:
+ * vo_slam_streams_replace, below), sequences that share a slot, joining segments or shards into one gauge, relocalisation,
+ * pruning, ratio matches. */
 int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs /*[S]*/, const int32_t* seq_off /*[S+1]*/,
                     const double* K, const vo_slam_opts* opts, int snapshot_seq,
                     double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
@@ -715,6 +716,40 @@ int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs /
                     double* chi2 /*[B][2]*/, int32_t* ba_iterations_run, int32_t* ba_trials_run /*[B] each*/,
                     int32_t* segment /*[B]*/, int32_t* cause /*[B]*/, double* seg_poses_pnp /*[B][12]*/, double* seg_poses /*[B][12]*/,
                     int32_t* n_carried /*[S]*/, int32_t* carried_frame /*[S][max_cameras]*/, double* carried_poses /*[S][max_cameras][12]*/);
+
+/* ------------------------------------------------------------------ seats: a sequence takes a new flight when its own has ended
+ * With flights of unequal length a fixed set of S sequences leaves seats idle: a step costs nearly the same whether 1 or S
+ * sequences work in it.  A sequence index of a multi-stream is a SEAT; a seat is either held by a flight or VACANT.
+ * The contract is the family's one equality: for every flight, the calls from the one in which it took its seat to its last
+ * together compute the bytes a vo_slam_stream_restart stream computes for that flight alone with the same chunking — every
+ * output, vo_slam_chains_map after every call, vo_slam_stats — whichever seat it takes, whatever flight sat there before (longer,
+ * shorter, ended lost, carried many times), whatever the other seats do, whichever slots are used, and whether the stream began
+ * with vo_slam_streams(resume = 0) or vo_slam_streams_open.  A seat nobody replaces keeps the bytes it had without these entries.
+ *   vo_slam_streams_open: a multi-stream of S vacant seats.  What vo_slam_streams(resume = 0) does before its walk — drops the
+ *     stream there is, checks S, K and the options, allocates and clears — and no walk: it needs a batch configuration and no
+ *     vo_pairs_run.  total_pairs[s] >= 1 is the seat's CAPACITY: it sizes the seat's lists as resume = 0 sizes them.  The stream
+ *     keeps the statistics setting (vo_set_slam_stats) the context has at this call.  Every later call is vo_slam_streams(resume = 1).
+ *   vo_slam_streams_replace, between two calls of a live multi-stream: the flight of seat seq is over, the seat is vacant and its
+ *     anchor slot is free at once.  Host only, nothing is launched.  total_pairs is the bound of the next flight that takes the
+ *     seat, 1 .. the seat's capacity (what resume = 0 or open was given for it).  Replacing a vacant seat only sets the bound.
+ *     Refusals (VO_ERR_INVALID, the stream untouched and continuable): no live multi-stream; a stream of the single kinds; seq
+ *     out of range; total_pairs out of range.
+ *   A vacant seat in vo_slam_streams(resume = 1): it may be idle (B_s = 0) — it owns no anchor, so nothing of it appears in the
+ *     slot checks; it owns one pose row, all zero; n_carried[s] = 0 — or advance (B_s >= 1): a new flight takes the seat.  Its pair
+ *     0 may start at any slot no other sequence holds, and for it everything counts from zero: frame0, the pairs done, n_carried
+ *     = 0; segments are numbered from 0 with cause = 0 at its first pair; pose row 0 is the first camera, as at a stream's pair 0;
+ *     cam_frame and pt_feature[:, 0] of vo_slam_chains_map and vo_slam_stats count along the new flight.  After the first call
+ *     following a replace in which the seat stays vacant its map reports as empty.  "Every sequence idle" stays refused.
+ * How: the seat is reset on the device by the carry launch of the next resumed call, before k_chain_link — other sequences may
+ * already have frames in the slots it gave up.  A call of a stream with no vacant seat launches the kernels it launched before; a
+ * call with one launches k_slam_carry_restart_seats instead of k_slam_carry_restart_seqs: a seat whose flight goes on runs the
+ * same carry, a replaced one the reset (slam_kernels.hip), a vacant one that was reset already returns at once.
+ * [deviation] none in the results.
+ * Out of scope: changing S of a live stream, a flight with another K or other options than the stream's, a bound above the
+ * seat's capacity, seats for vo_slam_stream / vo_slam_stream_restart, sequences that share a slot, joining flights or segments
+ * into one gauge. */
+int vo_slam_streams_open(vo_ctx* ctx, int S, const int32_t* total_pairs /*[S]*/, const double* K, const vo_slam_opts* opts);
+int vo_slam_streams_replace(vo_ctx* ctx, int seq, int total_pairs);
 
 /* ------------------------------------------------------------------ Map.show_map_statistics (src/map.py:234-297) on the device
  * The second thing VisualSlam.run() does per frame (src/visual_slam.py:354), as numbers (nothing is printed).  For a map given as

@@ -103,6 +103,8 @@ _SIGS = {
     "vo_slam_chains": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_chains_restart": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_slam_streams": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vo_slam_streams_open": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "vo_slam_streams_replace": (C.c_int, [_P, C.c_int, C.c_int]),
     "vo_slam_chains_map_size": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vo_slam_chains_map": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_map_statistics": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P]),

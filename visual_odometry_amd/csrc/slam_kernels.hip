@@ -16,6 +16,7 @@
 // a lost frame: k_slam_restart_stream, and k_slam_*_stream_restart / k_slam_carry_restart — the stream kernels compiled with RS = true.
 // vo_slam_streams carries S such maps at once: k_slam_*_stream_restart_seqs, the same bodies with the sequence on the grid axis, and
 // k_slam_carry_restart_seqs, whose workgroups clear the rows their own sequence held and no others (SQ = true).
+// A seat of vo_slam_streams whose flight has ended takes another: k_slam_carry_restart_seats, the carry launch that also resets such a seat.
 // Every list order is fixed by the input: positions come from ordered prefix sums (ballots / wave scans combined in wave
 // order), integer atomics only count or hand out slots that are ordered afterwards, and there are no floating-point sums — but one:
 // k_slam_stats' total reprojection error, which one lane adds in observation order because that order is its contract.  That kernel
@@ -699,6 +700,55 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry_restart_seqs(const 
 void launch_slam_carry_restart_seqs(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, int S)
 {
     hipLaunchKernelGGL(k_slam_carry_restart_seqs, dim3(S), dim3(SLAM_THREADS), 0, s, seqs, car);
+}
+
+// vo_slam_streams with seats (vo_slam_streams_replace, vo_slam_streams_open): the carry launch of a call in which some seat is
+// vacant.  A seat whose flight goes on is carried by the body above.  A seat that was replaced since the last call is reset here,
+// before k_chain_link: other sequences may already have frames in the slots it gives up, and the flight that takes the seat — in
+// this call or a later one — must find what a stream's first call finds after its memset.  Integers and zeros only:
+//   the rows only this seat held — the slots of its last call's frames (car.rows), its old anchor row and BOTH its ghost rows
+//   (seat.rows) — are cleared in parent, in_map, pt_of, map_pt, and a frame slot's camera with them, as step C clears a row;
+//   the three list lengths, alive, map_count, the four segment state words and the seat's kept anchor camera become 0: the
+//   sequence is lost with nothing to report, so the next usable pair is an initial step that numbers its segment 0, cause 0.
+// The lists' tails, pt_feat, tmp and the bundle adjustment's buffers keep their old bytes: every kernel writes an entry of them
+// before it reads it (k_slam_restart_stream starts maps on such lists in every stream that loses a frame).
+// A seat that is vacant and was reset in an earlier call (or has been vacant since vo_slam_streams_open) returns at once.
+__device__ __forceinline__ void slam_seat_clear_row(int r, int F, int cap, ChainBuf cb, SlamBuf sb)
+{
+    const int tid = threadIdx.x;
+    const size_t at = chain_key(r, 0, cap);
+    for (int k = tid; k < cap; k += SLAM_THREADS) { cb.parent[at + k] = 0; cb.in_map[at + k] = 0; sb.pt_of[at + k] = 0; }
+    for (int k = tid; k < 3 * cap; k += SLAM_THREADS) cb.map_pt[3 * at + k] = 0.0;
+    if (r < F) {
+        if (tid < 12) cb.cam[(size_t)r * 12 + tid] = 0.0;
+        if (tid == 0) cb.cam_ok[r] = 0;
+    }
+}
+
+__device__ __forceinline__ void slam_seat_reset_wg(const SlamSeqCarry& c, const SlamSeat& t, ChainBuf cb, SlamBuf sb)
+{
+    const int tid = threadIdx.x, cap = c.c.kp_cap, F = c.c.F;
+    for (int n = 0; n < c.n_rows; n++) slam_seat_clear_row(c.rows[n], F, cap, cb, sb);
+    for (int n = 0; n < t.n_rows; n++) slam_seat_clear_row(t.rows[n], F, cap, cb, sb);
+    if (tid < 4) { sb.m.cnt[tid] = 0; cb.rs.st[tid] = 0; }
+    if (tid < 24) t.keep[tid] = 0.0;
+    if (tid == 0) { cb.alive[0] = 0; cb.map_count[0] = 0; }
+}
+
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_carry_restart_seats(const SlamSeq* __restrict__ seqs, const SlamSeqCarry* __restrict__ car,
+                                                                           const SlamSeat* __restrict__ seats)
+{
+    const SlamSeq& q = seqs[blockIdx.x];
+    const SlamSeqCarry& c = car[blockIdx.x];
+    const SlamSeat& t = seats[blockIdx.x];
+    if (t.mode == SEAT_VACANT) return;
+    if (t.mode == SEAT_RESET) { slam_seat_reset_wg(c, t, q.cb, q.sb); return; }
+    slam_carry_wg<true, true>(c.c, q.cb, q.sb, c.hops, c.rows, c.n_rows);
+}
+
+void launch_slam_carry_restart_seats(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, const SlamSeat* seats, int S)
+{
+    hipLaunchKernelGGL(k_slam_carry_restart_seats, dim3(S), dim3(SLAM_THREADS), 0, s, seqs, car, seats);
 }
 
 // show_map_statistics (src/map.py:234-297) of the map as it stands: calculate_reprojection_error's total (:72-97), the largest term

@@ -129,12 +129,19 @@ struct SlamStream {
         int n_rows = 0;                   // slots its last call's frames had, the anchor excepted: rows[s * (max_pairs + 1) ..]
         SlamSeq at{};                     // its descriptor before a call's offsets: the ranges of the lists that are its own
         size_t np = 0, no = 0;            // points and observations its lists hold
+        // seats (vo_slam_streams_replace / vo_slam_streams_open): a vacant seat has no flight and no anchor (anchor = -1, done = 0,
+        // total = the bound of the flight that takes it); until the carry launch of the next call has reset it (clean), old_anchor
+        // names the row its last flight's anchor had
+        int capacity = 0;                 // total_pairs of the call that sized its lists: the most a flight in this seat may reach
+        bool vacant = false, clean = false;
+        int old_anchor = -1;
     };
     bool multi = false;                   // begun by vo_slam_streams
     int S = 0;
     std::vector<Seq> seq;
     std::vector<int32_t> rows;
     SlamSeq* dseq = nullptr; SlamSeqCarry* dcar = nullptr; int* drows = nullptr;
+    SlamSeat* dseat = nullptr;            // what the carry launch does for every seat, when one of them is vacant
     size_t snap_np = 0, snap_no = 0;
     bool stats = false;                   // started with vo_set_slam_stats on: the rows and the kernel's scratch are part of the allocation
     StatsBuf sbuf{};
@@ -3026,11 +3033,9 @@ static int slam_stats_download(vo_ctx* ctx, const StatsBuf& d, std::vector<int32
     return VO_OK;
 }
 
-// the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
-static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, int B_snap, const char* who)
+// the option checks that ask nothing of a vo_pairs_run (vo_slam_streams_open has none)
+static int slam_opts_check_values(vo_ctx* ctx, const vo_slam_opts* o, const double* K)
 {
-    if (ctx->last.match_mode == 1 || ctx->last.match_mode == 3)
-        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio or nearest-neighbour matches two inliers can share a track root", who);
     if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
     if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
     if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);
@@ -3039,6 +3044,15 @@ static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, 
         FAIL(VO_ERR_UNSUPPORTED, "the map holds max_cameras + 1 cameras before the limit is applied, bundle adjustment at most %d", VO_BA_MAX_CAMERAS);
     if (!(o->huber_delta == o->huber_delta) || !(o->filter_threshold == o->filter_threshold) || !(K[0] == K[0]) || !(K[2] == K[2]) || !(K[5] == K[5]))
         FAIL(VO_ERR_INVALID, "camera parameters and thresholds must be numbers");
+    return VO_OK;
+}
+
+// the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
+static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, int B_snap, const char* who)
+{
+    if (ctx->last.match_mode == 1 || ctx->last.match_mode == 3)
+        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio or nearest-neighbour matches two inliers can share a track root", who);
+    const int rc = slam_opts_check_values(ctx, o, K); if (rc) return rc;
     if ((o->snapshot_pair >= 0) != (o->snapshot_stage >= 1) || o->snapshot_pair >= B_snap || o->snapshot_stage > 4)
         FAIL(VO_ERR_INVALID, "snapshot_pair must be -1 or a pair of the chain, snapshot_stage 1 .. 4 with it");
     return VO_OK;
@@ -3675,7 +3689,7 @@ static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int 
     st.snap_np = 0; st.snap_no = 0;
     for (int q = 0; q < S; q++) {
         SlamStream::Seq& e = st.seq[(size_t)q];
-        e.total = total[q];
+        e.total = total[q]; e.capacity = total[q];
         e.np = ((size_t)total[q] + 1) * cap; e.no = (size_t)2 * cap * std::min(cm, (size_t)total[q]);
         pt0[q + 1] = pt0[q] + e.np; ob0[q + 1] = ob0[q] + e.no; pr0[q + 1] = pr0[q] + e.no * (o->free_cameras + 1) / 2;
         st.snap_np = std::max(st.snap_np, e.np); st.snap_no = std::max(st.snap_no, e.no);
@@ -3703,7 +3717,7 @@ static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int 
     sc.take(&snap.cnt, 4); sc.take(&snap.cam_frame, cm); sc.take(&snap.cam_pose, cm * 12); sc.take(&snap.cam_fixed, cm);
     sc.take(&snap.pt_key, st.snap_np); sc.take(&snap.pt_xyz, st.snap_np * 3); sc.take(&snap.pt_feat, st.snap_np * 2);
     sc.take(&snap.obs_cam, st.snap_no); sc.take(&snap.obs_pt, st.snap_no); sc.take(&snap.obs_xy, st.snap_no * 2);
-    sc.take(&st.dseq, S); sc.take(&st.dcar, S); sc.take(&st.drows, (size_t)S * (P + 1));
+    sc.take(&st.dseq, S); sc.take(&st.dcar, S); sc.take(&st.drows, (size_t)S * (P + 1)); sc.take(&st.dseat, S);
     st.stats = ctx->slam_stats != 0;
     slam_stats_take_scratch(sc, st.sbuf, st.stats, NP, NO);
     const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
@@ -3766,16 +3780,16 @@ static int streams_check(vo_ctx* ctx, int resume, int S, const int32_t* seq_off,
     for (int i = 0; i < 2 * B; i++)
         if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
     std::vector<int> owner((size_t)F, -1);                  // the sequence a slot's frame belongs to: first of all the anchors
-    if (resume) for (int s = 0; s < S; s++) owner[(size_t)st.seq[(size_t)s].anchor] = s;
+    if (resume) for (int s = 0; s < S; s++) if (!st.seq[(size_t)s].vacant) owner[(size_t)st.seq[(size_t)s].anchor] = s;   // (a vacant seat has none)
     for (int s = 0; s < S; s++)
         for (int p = seq_off[s]; p < seq_off[s + 1]; p++) {
             const bool head = p == seq_off[s];
             const int a = sl[2 * p], c = sl[2 * p + 1];
-            if (head && resume) {
+            if (head && resume && !st.seq[(size_t)s].vacant) {
                 const SlamStream::Seq& e = st.seq[(size_t)s];
                 if (a != e.anchor) FAIL(VO_ERR_INVALID, "vo_slam_streams: pair 0 of sequence %d starts at slot %d, the sequence's last frame is in slot %d", s, a, e.anchor);
                 if (e.touched) FAIL(VO_ERR_INVALID, "vo_slam_streams: slot %d, the last frame of sequence %d, was uploaded to or detected again", e.anchor, s);
-            } else if (head) {
+            } else if (head) {                                  // a stream's pair 0, or a new flight's in a vacant seat: any slot nobody holds
                 if (owner[(size_t)a] >= 0)
                     FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", owner[(size_t)a], s, p, a, c);
                 owner[(size_t)a] = s;
@@ -3844,6 +3858,8 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
     const int R = F + 2 * S, gpar = st.carries & 1;
     // the descriptors of this call: a sequence's ranges of the lists, and its rows of the call's outputs
     std::vector<SlamSeq> seq((size_t)S); std::vector<SlamSeqCarry> car((size_t)S); std::vector<int32_t> hrows(st.rows);
+    std::vector<SlamSeat> seat((size_t)S);
+    bool seats = false;                                               // some seat is vacant: the carry launch is the seats form
     for (int q = 0; q < S; q++) {
         const SlamStream::Seq& h = st.seq[(size_t)q];
         const int first = seq_off[q];
@@ -3862,6 +3878,17 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
         k.c = SlamCarry{cap, F, h.anchor, gn, go, st.keep + (size_t)24 * q};
         k.hops = R; k.rows = st.drows + (size_t)q * row_cap;
         hrows[(size_t)q * row_cap + h.n_rows] = go; k.n_rows = h.n_rows + 1;
+        // seats: a vacant seat is not carried.  One replaced since the last call is reset — it gives up the slots of its last call's
+        // frames (k.rows without the ghost row above), its old anchor row and both ghost rows; one already reset is left alone.
+        SlamSeat& t = seat[(size_t)q];
+        t = SlamSeat{SEAT_CARRY, 0, {0, 0, 0}, st.keep + (size_t)24 * q};
+        if (resume && h.vacant) {
+            seats = true;
+            t.mode = h.clean ? SEAT_VACANT : SEAT_RESET;
+            k.n_rows = h.n_rows;
+            if (h.old_anchor >= 0) t.rows[t.n_rows++] = h.old_anchor;
+            t.rows[t.n_rows++] = gn; t.rows[t.n_rows++] = go;
+        }
     }
     HIPCHK(hipMemcpyAsync(st.dseq, seq.data(), (size_t)S * sizeof(SlamSeq), hipMemcpyHostToDevice, s));
     const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
@@ -3880,8 +3907,10 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
     if (resume) {
         HIPCHK(hipMemcpyAsync(st.dcar, car.data(), (size_t)S * sizeof(SlamSeqCarry), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(st.drows, hrows.data(), hrows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (seats) HIPCHK(hipMemcpyAsync(st.dseat, seat.data(), (size_t)S * sizeof(SlamSeat), hipMemcpyHostToDevice, s));
         StageTimer t(ctx, ST_MISC);
-        launch_slam_carry_restart_seqs(s, dseq, st.dcar, S);
+        if (seats) launch_slam_carry_restart_seats(s, dseq, st.dcar, st.dseat, S);
+        else launch_slam_carry_restart_seqs(s, dseq, st.dcar, S);
     }
     launch_chain_link(s, ctx->pb, cap, B, cb);
     for (int j = 0; j < maxB; j++) {
@@ -3972,7 +4001,9 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
         SlamStream::Seq& h = st.seq[(size_t)q];
         const int first = seq_off[q], Bq = seq[(size_t)q].count;
         h.n_rows = 0;
+        if (resume && h.vacant) { h.clean = true; h.old_anchor = -1; }    // (reset at this call's carry, if it had not been)
         if (Bq == 0) continue;
+        h.vacant = false;                                             // a flight has taken the seat
         int32_t* rows = st.rows.data() + (size_t)q * row_cap;
         rows[h.n_rows++] = sl[2 * first];
         for (int j = 0; j + 1 < Bq; j++) rows[h.n_rows++] = sl[2 * (first + j) + 1];
@@ -3981,6 +4012,61 @@ extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* to
     }
     st.carries = resume ? st.carries + 1 : 0;
     st.live = true;
+    return VO_OK;
+}
+
+// A multi-stream of S vacant seats: what vo_slam_streams(resume = 0) does before its walk, and no walk.  Every seat is as the memset
+// leaves it — the state a stream's first call starts from — so no seat needs a reset; the flights arrive in resumed calls.
+extern "C" int vo_slam_streams_open(vo_ctx* ctx, int S, const int32_t* total_pairs, const double* K, const vo_slam_opts* o)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const char* who = "vo_slam_streams_open";
+    drop_slam_stream(ctx);
+    forget_slam_maps(ctx);
+    if (!total_pairs || !K || !o) FAIL(VO_ERR_INVALID, "bad arguments");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (S < 1) FAIL(VO_ERR_INVALID, "%s takes at least one seat, got %d", who, S);
+    for (int q = 0; q < S; q++)
+        if (total_pairs[q] < 1) FAIL(VO_ERR_INVALID, "%s: total_pairs[%d] = %d: a seat holds flights of at least one pair", who, q, total_pairs[q]);
+    if (b.kp_cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many keypoints for the packed track table");
+    int rc = slam_opts_check_values(ctx, o, K); if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    SlamStream& st = ctx->stream_map;
+    rc = slam_streams_allocate(ctx, st, S, b.max_frames, b.kp_cap, b.max_pairs, total_pairs, o, K);
+    if (rc) { drop_slam_stream(ctx); return rc; }
+    rc = [&]() -> int {
+        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));
+        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return VO_OK;
+    }();
+    if (rc) { drop_slam_stream(ctx); return rc; }
+    for (SlamStream::Seq& h : st.seq) { h.vacant = true; h.clean = true; h.lost = true; }
+    st.carries = 0;
+    st.live = true;
+    return VO_OK;
+}
+
+// The flight of seat `seq` is over.  Host only: the seat gives its anchor slot back at once and is reset on the device by the carry
+// launch of the next call (k_slam_carry_restart_seats), whether a new flight takes it in that call or later.
+extern "C" int vo_slam_streams_replace(vo_ctx* ctx, int seq, int total_pairs)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const char* who = "vo_slam_streams_replace";
+    SlamStream& st = ctx->stream_map;
+    if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream (none was started, or a configure or vo_slam_chain* call dropped it)", who);
+    if (!st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by %s, which has no seats", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
+    if (seq < 0 || seq >= st.S) FAIL(VO_ERR_INVALID, "%s: the stream has seats 0 .. %d, got %d", who, st.S - 1, seq);
+    SlamStream::Seq& h = st.seq[(size_t)seq];
+    if (total_pairs < 1 || total_pairs > h.capacity)
+        FAIL(VO_ERR_INVALID, "%s: seat %d holds flights of 1 .. %d pairs (what its lists were sized for), got %d", who, seq, h.capacity, total_pairs);
+    h.total = total_pairs;
+    if (h.vacant) return VO_OK;                                       // (only the bound of the flight to come)
+    h.vacant = true; h.clean = false;
+    h.old_anchor = h.anchor; h.anchor = -1;
+    h.done = 0; h.last_ncam = 0; h.lost = true; h.touched = false;
     return VO_OK;
 }
 

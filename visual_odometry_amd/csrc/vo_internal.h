@@ -406,6 +406,17 @@ struct SlamSeqCarry {
     const int* rows; int n_rows;        // the rows only this sequence holds and does not keep: the slots of its last call's frames, its old ghost row
 };
 void launch_slam_carry_restart_seqs(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, int S);
+// ... with seats (vo_slam_streams_replace / vo_slam_streams_open): what the carry launch does for a sequence, in an array of its own
+// beside SlamSeqCarry.  A seat that is reset gives up car.rows (the slots of its last call's frames) and rows[] here.
+enum { SEAT_CARRY = 0,      // its flight goes on: the carry
+       SEAT_RESET = 1,      // replaced since the last call: cleared to what a stream's first call starts from
+       SEAT_VACANT = 2 };   // vacant and already reset: nothing
+struct SlamSeat {
+    int mode;
+    int n_rows; int rows[3];            // SEAT_RESET: the old anchor row (if it had one) and both ghost rows
+    double* keep;                       // [24] the seat's kept anchor camera
+};
+void launch_slam_carry_restart_seats(hipStream_t s, const SlamSeq* seqs, const SlamSeqCarry* car, const SlamSeat* seats, int S);
 void launch_slam_restart_stream_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const SlamSeq* seqs, int S);
 void launch_slam_add_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, int F, double max_norm, int free_cameras, const SlamSeq* seqs, int S);
 void launch_slam_filter_stream_restart_seqs(hipStream_t s, PairBuf pb, int kp_cap, int j, const double* Kd, double threshold, const SlamSeq* seqs, int S);

@@ -371,6 +371,30 @@ class FrontEnd:
         return dict(seq_off=off, n_carried=nc, carried_frame=[cf[s, :nc[s]].copy() for s in range(S)],
                     carried_poses=[cp[s, :nc[s]].reshape(-1, 3, 4).copy() for s in range(S)], **flat)
 
+    def slam_streams_open(self, n_seats, total_pairs, K, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED,
+                          max_point_norm=50.0, ba_iterations=40, huber_delta=1.0, free_cameras=2, filter_threshold=1.0, max_cameras=18, snapshot=None):
+        """A slam_streams stream of n_seats vacant seats (vo_slam_streams_open): nothing is walked and no run_pairs is needed.
+        total_pairs (a list of n_seats, or one number for all) is every seat's capacity — the longest flight it may hold.  Every
+        later call is slam_streams(..., resume=True) with this K and these options: a vacant seat may stay idle or take a flight,
+        whose pair 0 starts at any slot no other sequence holds and for which everything counts from zero (slam_streams_replace).
+        snapshot is accepted for symmetry with slam_streams and ignored: there is no pair to take one of."""
+        S = int(n_seats)
+        total = np.ascontiguousarray(np.broadcast_to(np.asarray(total_pairs, dtype=np.int32), (max(S, 0),)), dtype=np.int32)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        opts = _lib.SlamOpts(int(iterations), float(reproj_err), float(confidence), int(seed), float(max_point_norm), int(ba_iterations),
+                             float(huber_delta), int(free_cameras), float(filter_threshold), int(max_cameras), -1, 0)
+        c = self.ctx
+        c.check(c.lib.vo_slam_streams_open(c.handle, S, total.ctypes.data, K.ctypes.data, C.addressof(opts)))
+
+    def slam_streams_replace(self, seq, total_pairs):
+        """Between two calls of a live slam_streams stream: the flight of seat `seq` is over (vo_slam_streams_replace).  The seat is
+        vacant, its last frame's slot is free at once, and the next flight that takes it — in any later call, from any slot no
+        other sequence holds — starts from zero and may reach total_pairs pairs (at most the seat's capacity: what the stream's
+        first call or slam_streams_open was given for it).  That flight's calls together compute what slam_stream_restart computes
+        for it alone, byte for byte (split_flights).  Host only; replacing a vacant seat only sets the bound."""
+        c = self.ctx
+        c.check(c.lib.vo_slam_streams_replace(c.handle, int(seq), int(total_pairs)))
+
     def slam_map(self, which=0, seq=0):
         """The map of the latest slam_chain, or of sequence `seq` of the latest slam_chains or slam_streams call: which=0 at the end of the
         chain, 1 the snapshot.  dict(cam_frame [ncam] index of the camera's frame in the chain, cam_pose [ncam, 3, 4], cam_fixed [ncam] bool,
@@ -638,6 +662,33 @@ def join_streams(outs):
         own = [stream_slice(o, s) for o in outs]
         joined.append(join_stream([d for d in own if len(d["status"]) > 0]))
     return joined
+
+
+def split_flights(outs, took_seat):
+    """The dicts the calls of one slam_streams stream with seats returned, in order, and per seat s the call indices took_seat[s]
+    (increasing) at which a new flight took it -> per seat a list of flights, each the list of that flight's per-call
+    stream_slice dicts, ready for join_stream.  A flight owns the calls from the one in which it took the seat up to the next
+    flight's; calls in which the seat was idle — between two flights too — add nothing.  Pure: no GPU, no library."""
+    outs = list(outs)
+    if not outs:
+        raise ValueError("split_flights takes at least one call")
+    S = len(np.asarray(outs[0]["seq_off"]).ravel()) - 1
+    if any(len(np.asarray(o["seq_off"]).ravel()) - 1 != S for o in outs):
+        raise ValueError("the calls of one stream all have the same number of sequences")
+    if len(took_seat) != S:
+        raise ValueError(f"took_seat names {len(took_seat)} seats, the calls {S}")
+    flights = []
+    for s in range(S):
+        starts = [int(c) for c in took_seat[s]]
+        if any(b <= a for a, b in zip(starts, starts[1:])) or any(c < 0 or c >= len(outs) for c in starts):
+            raise ValueError(f"seat {s}: the calls at which flights took it must be increasing call indices, got {starts}")
+        own = [stream_slice(o, s) for o in outs]
+        if any(len(own[c]["status"]) == 0 for c in starts):
+            raise ValueError(f"seat {s}: a flight takes a seat in a call in which it advances, got {starts}")
+        if any(len(d["status"]) > 0 for d in own[:starts[0] if starts else len(outs)]):
+            raise ValueError(f"seat {s} advances before its first flight took it")
+        flights.append([[d for d in own[a:b] if len(d["status"]) > 0] for a, b in zip(starts, starts[1:] + [len(outs)])])
+    return flights
 
 
 def chain_poses(R, t):
