@@ -22,20 +22,31 @@ def _inv_pose(R, t):
     return np.array([[R[0, r], R[1, r], R[2, r], -(R[0, r] * t[0] + R[1, r] * t[1] + R[2, r] * t[2])] for r in range(3)])
 
 
-def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None, pnp=None):
+def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None, pnp=None, match_mode=2, failed_pairs=False):
     """The reference's loop over a sequence, on the oracle's stage outputs.  feats[f] = dict(xy, desc).
     follow = the device's poses [n, 3, 4]: every solvePnPRansac result is reported as computed, but the chain then continues from
     the DEVICE's camera, so that every step is compared on identical inputs (a RANSAC over points near its 8-pixel threshold turns
     a 1e-9 difference of the previous pose into a different winner: the free-running chains agree only while the geometry is good).
-    pnp = solvePnPRansac's options (iterations, reproj_err, confidence, seed) where they are not the defaults."""
+    pnp = solvePnPRansac's options (iterations, reproj_err, confidence, seed) where they are not the defaults.
+    match_mode = oracle.match_hamming's cross_check: 2 the strict cross-check, 0 every query's nearest row (matches are then not
+    one-to-one: the later match of a train row overwrites the feature_mapper entry of the earlier one, as the dict does).
+    failed_pairs = True: a pair without an essential matrix does not fail an assertion; it reports findEssentialMat's status, links
+    nothing and ends the chain, as a pair does that failed in vo_pairs_run."""
     feature_mapper, mappoints, cameras = {}, {}, {}
     out = dict(poses=[], n_corr=[], n_inl=[], status=[], n_map=[], E_inl=[], corr=[None])
     alive = True
     for p, (a, b) in enumerate(pairs):
-        qi, ti, _ = O.match_hamming(feats[a]["desc"], feats[b]["desc"], 2)
+        qi, ti, _ = O.match_hamming(feats[a]["desc"], feats[b]["desc"], match_mode)
         p1 = feats[a]["xy"][qi].astype(np.float64); p2 = feats[b]["xy"][ti].astype(np.float64)
         rc, E, mask, _ = O.find_essential_ransac(p1, p2, K)
-        assert rc == 0
+        assert rc == 0 or failed_pairs
+        if rc != 0:
+            n_map = len(mappoints)
+            out["E_inl"].append(0); out["corr"].append(None)
+            out["poses"] += [np.zeros((3, 4))] * (2 if p == 0 else 1)
+            out["n_corr"].append(0); out["n_inl"].append(0); out["status"].append(rc if alive else None); out["n_map"].append(n_map)
+            alive = False
+            continue
         inl = mask > 0
         _, R, t, _ = O.recover_pose(E[0], p1[inl], p2[inl], K)
         m3d = [((a, int(q)), (b, int(tt)), kp2) for q, tt, kp2 in zip(qi[inl], ti[inl], p2[inl])]     # matches_with_3d_information
@@ -63,7 +74,7 @@ def reference_chain(O, feats, pairs, K, max_norm=50.0, follow=None, pnp=None):
             if feature_id in mappoints:
                 obj.append(mappoints[feature_id]); img.append(kp2)
         out["n_corr"].append(len(obj)); out["corr"].append((np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2)))
-        rc, rvec, tvec, pmask, ninl = O.solve_pnp_ransac(np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2), K, **(pnp or {})) if len(obj) >= 4 else (-1, None, None, None, 0)
+        rc, rvec, tvec, pmask, ninl = O.solve_pnp_ransac(np.array(obj).reshape(-1, 3), np.array(img).reshape(-1, 2), K, **(pnp or {})) if len(obj) >= 4 else (-3, None, None, None, 0)     # VO_ERR_TOO_FEW, as tests/slam_reference.py reports it
         out["n_inl"].append(int(ninl))
         if rc != 0:                                                    # cv2 raises / retval False: no camera is added (:253-261)
             alive = False

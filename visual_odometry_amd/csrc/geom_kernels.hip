@@ -1549,25 +1549,35 @@ void launch_chain_triangulate(hipStream_t s, PairBuf pb, int kp_cap, int p, Chai
 }
 
 // the loop of :174-178 with add_point_observation_to_map (:138-151): skip points farther than max_norm; a match whose track root
-// already owns a map point only adds an observation (nothing to store without BA); otherwise a new point under featureid1
-__global__ __launch_bounds__(256) void k_chain_insert(PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb)
+// already owns a map point only adds an observation (nothing to store without BA); otherwise a new point under featureid1.
+// Pass 1 takes every decision against the map as it was before the loop (self.mappointdict is built at :154-156, before it) and
+// stores it in dec[match index]; pass 2 writes, after a barrier — as slam_add_wg does.  With nearest or ratio matches two queries
+// q < q' may share a train row whose track root is the unmapped (f1, q'): both get a point, whichever wave runs first.
+__global__ __launch_bounds__(256) void k_chain_insert(PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb, uint8_t* dec)
 {
     __shared__ int s_w[4];
     __shared__ int s_added;
     if (!cb.alive[0]) { if (threadIdx.x == 0) cb.n_map[p] = cb.map_count[0]; return; }
     const int f1 = pb.slots[2 * p], f2 = pb.slots[2 * p + 1];
     if (threadIdx.x == 0) s_added = 0;
-    int added = 0;
     chain_for_each_inlier(pb, kp_cap, p, s_w, [&](bool f, int i, int pos) {
         if (!f) return;
         const double x = cb.Xw[4 * (size_t)pos], y = cb.Xw[4 * (size_t)pos + 1], z = cb.Xw[4 * (size_t)pos + 2];
-        if (!(sqrt(x * x + y * y + z * z) <= max_norm)) return;                  // np.linalg.norm(match.point) > 50: continue (NaN: kept out)
-        int rf = f2, ri = pb.m_t[(size_t)p * kp_cap + i];
-        chain_root(cb.parent, kp_cap, F, rf, ri);
-        if (cb.in_map[chain_key(rf, ri, kp_cap)]) return;                        // add_new_observation_of_existing_point
+        bool add = sqrt(x * x + y * y + z * z) <= max_norm;                      // np.linalg.norm(match.point) > 50: continue (NaN: kept out)
+        if (add) {
+            int rf = f2, ri = pb.m_t[(size_t)p * kp_cap + i];
+            chain_root(cb.parent, kp_cap, F, rf, ri);
+            add = !cb.in_map[chain_key(rf, ri, kp_cap)];                         // mapped: add_new_observation_of_existing_point
+        }
+        dec[i] = add;
+    });
+    __syncthreads();
+    int added = 0;
+    chain_for_each_inlier(pb, kp_cap, p, s_w, [&](bool f, int i, int pos) {
+        if (!f || !dec[i]) return;
         const size_t k = chain_key(f1, pb.m_q[(size_t)p * kp_cap + i], kp_cap);  // add_new_match_to_map: keyed by featureid1
         cb.in_map[k] = 1;
-        cb.map_pt[3 * k] = x; cb.map_pt[3 * k + 1] = y; cb.map_pt[3 * k + 2] = z;
+        for (int d = 0; d < 3; d++) cb.map_pt[3 * k + d] = cb.Xw[4 * (size_t)pos + d];
         added++;
     });
     __syncthreads();
@@ -1576,7 +1586,7 @@ __global__ __launch_bounds__(256) void k_chain_insert(PairBuf pb, int kp_cap, in
     if (threadIdx.x == 0) { cb.map_count[0] += s_added; cb.n_map[p] = cb.map_count[0]; }
 }
 
-void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb)
+void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb, uint8_t* dec)
 {
-    hipLaunchKernelGGL(k_chain_insert, dim3(1), dim3(256), 0, s, pb, kp_cap, p, F, max_norm, cb);
+    hipLaunchKernelGGL(k_chain_insert, dim3(1), dim3(256), 0, s, pb, kp_cap, p, F, max_norm, cb, dec);
 }

@@ -2916,11 +2916,11 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
     rc = ensure_rng(ctx, seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
     const size_t fc = (size_t)F * cap;
-    ChainBuf cb{}; double* dK;
+    ChainBuf cb{}; double* dK; uint8_t* dec;
     ScratchLayout sc;
     sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
     sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4); sc.take(&cb.poses, (size_t)(B + 1) * 12);
-    sc.take(&dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
+    sc.take(&dK, 9); sc.take(&cb.in_map, fc); sc.take(&dec, cap); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
     sc.take(&cb.alive, 1); sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&cb.map_count, 1);
     rc = sc.place(ctx); if (rc) return rc;
     HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty map, no cameras
@@ -2935,7 +2935,7 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
                               cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
             launch_chain_pose(s, ctx->pb, p, dK, cb);
             launch_chain_triangulate(s, ctx->pb, cap, p, cb);
-            launch_chain_insert(s, ctx->pb, cap, p, F, max_point_norm, cb);
+            launch_chain_insert(s, ctx->pb, cap, p, F, max_point_norm, cb, dec);
         }
     }
     HIPCHK(hipGetLastError());

@@ -304,7 +304,7 @@ void launch_chain_init(hipStream_t s, PairBuf pb, int kp_cap, ChainBuf cb);
 void launch_chain_gather(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, ChainBuf cb);
 void launch_chain_pose(hipStream_t s, PairBuf pb, int p, const double* Kd, ChainBuf cb);
 void launch_chain_triangulate(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb);
-void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb);
+void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, ChainBuf cb, uint8_t* dec);   // dec: [cap] scratch
 // ---- bundle adjustment (ba_kernels.hip): Map.optimize_map, src/map.py:104-186.  One workgroup per problem.
 struct BaProblem {
     int cam0, pt0, obs0, pair0, blk0;   // where the problem's cameras / points / observations / pair list / block offsets start
