@@ -382,6 +382,41 @@ def sift_detect_and_compute(img, n_layers=3, contrast_threshold=0.04, edge_thres
     return dict(xy=xy[:k], size=size[:k], angle=ang[:k], response=resp[:k], octave=octv[:k], desc=desc[:k], n_found=n.value)
 
 
+# voo_sift_census_t (voo.h), field for field: (name, length); every element is an int32
+_SIFT_CENSUS_FIELDS = (("n_keypoints", 1), ("n_octaves", 1), ("n_taps", 1), ("taps", 12),
+                       ("cand", 2), ("cand_strip_first", 2), ("cand_strip_last", 2), ("cand_col_first", 2), ("cand_col_last", 2),
+                       ("cand_seg_first", 2), ("cand_seg_last", 2), ("cand_row_first", 2), ("cand_row_last", 2),
+                       ("ref_kept_steps", 5), ("ref_drop_layer", 1), ("ref_drop_border", 1), ("ref_drop_steps", 1), ("ref_drop_huge", 1),
+                       ("ref_drop_contrast", 1), ("ref_drop_det", 1), ("ref_drop_edge", 1), ("ref_singular", 1),
+                       ("ori_peaks", 5), ("ori_cut", 1), ("ori_cut_side", 4), ("ori_side_gt64", 1), ("ori_max_side", 1), ("ori_sample_wrap", 1),
+                       ("ori_bin_neg", 1), ("ori_bin_ge_n", 1), ("ori_snapped", 1),
+                       ("sort_dups", 1), ("sort_x_clamped", 1), ("sort_x_clamped_cols", 1),
+                       ("kp_layer", 9), ("desc_r64", 1), ("desc_max_radius", 1), ("desc_clipped", 1), ("desc_clipped_small", 1),
+                       ("desc_side_gt128", 1), ("desc_max_side", 1),                        ("desc_cut", 1), ("desc_cut_side", 4), ("desc_max_samples", 1))
+
+
+def sift_census(img, n_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6, nfeatures=0):
+    """Which branches of sift_detect_and_compute(img, same parameters) the image takes (voo_sift_census): a dict of ints and
+    lists of ints, named as voo_sift_census_t's fields; `taps` holds the n_taps Gaussian tap counts.  Pairs [a, b] of the
+    extrema counters are [all octaves, octave 0 alone]."""
+    a = _u8(img)
+    h, w = a.shape[:2]
+    cn = 1 if a.ndim == 2 else a.shape[2]
+    f = lib().voo_sift_census
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    raw = np.zeros(sum(n for _, n in _SIFT_CENSUS_FIELDS) + 16, np.int32)
+    assert lib().voo_sift_census_size() == 4 * (len(raw) - 16)
+    raw[-16:] = -12345                                                    # (a struct that outgrew this table would write here)
+    rc = f(a.ctypes.data, h, w, cn, a.strides[0], nfeatures, n_layers, contrast_threshold, edge_threshold, sigma, raw.ctypes.data)
+    assert rc == 0 and (raw[-16:] == -12345).all()
+    out, at = {}, 0
+    for name, n in _SIFT_CENSUS_FIELDS:
+        out[name] = int(raw[at]) if n == 1 else raw[at:at + n].tolist()
+        at += n
+    out["taps"] = out["taps"][:out["n_taps"]]
+    return out
+
+
 JPEG_ERRORS = {-1: "corrupt", -2: "unsupported", -3: "output too small"}
 
 

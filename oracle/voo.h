@@ -132,6 +132,53 @@ int voo_sift_detect_and_compute(const uint8_t* img, int h, int w, int channels, 
                                 double edgeThreshold, double sigma, float* kp_xy, float* kp_size, float* kp_angle, float* kp_response,
                                 int32_t* kp_octave, float* desc /*cap x 128*/, int cap, int32_t* n_out);
 
+/* The path census of one detectAndCompute (voo_sift_census): which branches of the code above an input takes, counted inside
+ * that code behind a pointer that is NULL in every other call.  tests/sift_cases.py chooses scenes by it, so that a device test
+ * named for a branch provably reaches it.  The three geometry constants are the device kernels' (sift_batch.hip: EX_COLS,
+ * EX_SEG, RK_NB); the oracle's own result does not depend on them.  Every field is an int32 (oracle.py mirrors the order). */
+#define VOO_SIFT_STRIP 62        /* columns a wavefront of k_sb_extrema owns; strips start at column 5 */
+#define VOO_SIFT_SEGMENT 256     /* rows it sweeps; segments start at row 5 */
+#define VOO_SIFT_XBUCKETS 4096   /* k_sb_bucket's integer buckets of x (doubled-image coordinates); the last one is clamped */
+typedef struct {
+    int32_t n_keypoints, n_octaves;
+    int32_t n_taps, taps[12];                /* createInitialImage's blur, then the nOctaveLayers + 2 incremental ones */
+    /* extrema before refinement; [0] all octaves, [1] octave 0 alone.  Columns / rows are the octave's own. */
+    int32_t cand[2];
+    int32_t cand_strip_first[2];             /* column 5 + 62 k, k >= 1 */
+    int32_t cand_strip_last[2];              /* column 5 + 62 k + 61 */
+    int32_t cand_col_first[2], cand_col_last[2];   /* columns 5 and w - 6 */
+    int32_t cand_seg_first[2];               /* row 5 + 256 k, k >= 1 */
+    int32_t cand_seg_last[2];                /* row 5 + 256 k + 255 */
+    int32_t cand_row_first[2], cand_row_last[2];   /* rows 5 and h - 6 */
+    /* adjustLocalExtrema: every candidate ends in exactly one of these */
+    int32_t ref_kept_steps[5];               /* kept after 0..4 moves */
+    int32_t ref_drop_layer, ref_drop_border; /* a move left the layer range / the 5-pixel border */
+    int32_t ref_drop_steps;                  /* no convergence in 5 steps */
+    int32_t ref_drop_huge;                   /* offset beyond INT_MAX / 3 (a near-singular Hessian) */
+    int32_t ref_drop_contrast, ref_drop_det, ref_drop_edge;
+    int32_t ref_singular;                    /* solves with d == 0 (offset 0: converges at once); not an exit */
+    /* calcOrientationHist and the peaks, per refined extremum */
+    int32_t ori_peaks[5];                    /* extrema with 0, 1, 2, 3, >= 4 peaks */
+    int32_t ori_cut, ori_cut_side[4];        /* windows that reach past rows 1 .. h - 2 / columns 1 .. w - 2: any; top, bottom, left, right */
+    int32_t ori_side_gt64, ori_max_side;     /* window side 2 radius + 1 */
+    int32_t ori_sample_wrap;                 /* samples whose bin rounded to 36 */
+    int32_t ori_bin_neg, ori_bin_ge_n;       /* peaks whose interpolated bin was < 0 / >= 36 before the wrap */
+    int32_t ori_snapped;                     /* angles within FLT_EPSILON of 360 set to 0 */
+    /* removeDuplicatedSorted, on the records before the duplicates leave */
+    int32_t sort_dups;
+    int32_t sort_x_clamped, sort_x_clamped_cols;   /* records with x >= 4095 (doubled coordinates) and how many integer columns they span */
+    /* calcSIFTDescriptor, per final keypoint */
+    int32_t kp_layer[9];                     /* final keypoints by layer 1..8 */
+    int32_t desc_r64, desc_max_radius;       /* radius >= 64 as cvRound gives it, before the clip; the largest */
+    int32_t desc_clipped, desc_clipped_small;/* radius clipped to the level's diagonal; of those, radii below 64 */
+    int32_t desc_side_gt128, desc_max_side;  /* window side 2 radius + 1 after the clip: more than 128 rows */
+    int32_t desc_cut, desc_cut_side[4];      /* windows with a sample inside the 4 x 4 cells but outside rows 1 .. h - 2 / columns 1 .. w - 2 */
+    int32_t desc_max_samples;                /* most valid samples of one keypoint */
+} voo_sift_census_t;
+int voo_sift_census_size(void);
+int voo_sift_census(const uint8_t* img, int h, int w, int channels, int row_stride, int nfeatures, int nLayers, double contrastThreshold,
+                    double edgeThreshold, double sigma, voo_sift_census_t* census);
+
 /* the JPEG decode of cv2.imread(filename), visual_slam.py:346 (voo_jpeg.c; pinned against Pillow's libjpeg-turbo) */
 #define VOO_OK 0
 #define VOO_JPEG_CORRUPT (-1)

@@ -30,6 +30,11 @@
 #define SIFT_DESCR_WIDTH 4
 #define SIFT_DESCR_HIST_BINS 8
 
+/* The path census (voo_sift_census): NULL in every normal call; when set, the functions below count which of their branches
+ * the input takes.  The counters sit beside the code they count and change nothing it computes. */
+static voo_sift_census_t* g_cen;
+#define CEN(...) do { if (g_cen) { __VA_ARGS__; } } while (0)
+
 static inline int rnd_f(float v) { return (int)lrintf(v); }
 static inline int rnd_d(double v) { return (int)lrint(v); }
 
@@ -184,6 +189,8 @@ static fimg* build_pyramids(const uint8_t* gray, int h, int w, int nLayers, doub
     const double k = pow(2., 1. / nLayers);
     for (int i = 1; i < per; i++) { const double sp = pow(k, (double)(i - 1)) * sigma, st = sp * k; sig[i] = sqrt(st * st - sp * sp); }
     const float sd = sqrtf(fmaxf((float)(sigma * sigma - 0.5 * 0.5 * 4), 0.01f));
+    CEN(g_cen->n_octaves = nOct; g_cen->n_taps = per; g_cen->taps[0] = voo_sift_gauss_kernel((double)sd, NULL);
+        for (int i = 1; i < per; i++) g_cen->taps[i] = voo_sift_gauss_kernel(sig[i], NULL));
     for (int o = 0; o < nOct; o++)
         for (int i = 0; i < per; i++) {
             fimg* dst = &g[o * per + i];
@@ -221,6 +228,9 @@ static float ori_hist(const fimg* img, int px, int py, int radius, float sigma, 
     float *X = buf, *Y = X + len, *W = Y + len, *temphist = W + len + 2;
     int k = 0;
     for (int i = 0; i < n; i++) temphist[i] = 0.f;
+    CEN(const int t = py - radius <= 0, b = py + radius >= img->h - 1, l = px - radius <= 0, r = px + radius >= img->w - 1;
+        g_cen->ori_cut += t | b | l | r; g_cen->ori_cut_side[0] += t; g_cen->ori_cut_side[1] += b; g_cen->ori_cut_side[2] += l; g_cen->ori_cut_side[3] += r;
+        g_cen->ori_side_gt64 += 2 * radius + 1 > 64; if (2 * radius + 1 > g_cen->ori_max_side) g_cen->ori_max_side = 2 * radius + 1);
     for (int i = -radius; i <= radius; i++) {
         const int y = py + i;
         if (y <= 0 || y >= img->h - 1) continue;
@@ -236,6 +246,7 @@ static float ori_hist(const fimg* img, int px, int py, int radius, float sigma, 
     for (int q = 0; q < k; q++) {
         const float w = cv_expf(W[q]), ori = fast_atan2_deg(Y[q], X[q]), mag = sqrtf(X[q] * X[q] + Y[q] * Y[q]);
         int bin = rnd_f((n / 360.f) * ori);
+        CEN(g_cen->ori_sample_wrap += bin >= n);
         if (bin >= n) bin -= n;
         if (bin < 0) bin += n;
         temphist[bin] += w * mag;
@@ -273,6 +284,7 @@ static void refine_and_orient(const fimg* dog, const fimg* gauss, int o, int lay
         const float a00 = dxx, a01 = dxy, a02 = dxs, a10 = dxy, a11 = dyy, a12 = dys, a20 = dxs, a21 = dys, a22 = dss;
         float d = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
         float X0 = 0, X1 = 0, X2 = 0;
+        CEN(g_cen->ref_singular += !(d != 0));
         if (d != 0) {
             d = 1 / d;
             X0 = d * (dD0 * (a11 * a22 - a12 * a21) - a01 * (dD1 * a22 - a12 * dD2) + a02 * (dD1 * a21 - a11 * dD2));
@@ -281,24 +293,27 @@ static void refine_and_orient(const fimg* dog, const fimg* gauss, int o, int lay
         }
         xi = -X2; xr = -X1; xc = -X0;
         if (fabsf(xi) < 0.5f && fabsf(xr) < 0.5f && fabsf(xc) < 0.5f) break;
-        if (fabsf(xi) > (float)(INT_MAX / 3) || fabsf(xr) > (float)(INT_MAX / 3) || fabsf(xc) > (float)(INT_MAX / 3)) return;
+        if (fabsf(xi) > (float)(INT_MAX / 3) || fabsf(xr) > (float)(INT_MAX / 3) || fabsf(xc) > (float)(INT_MAX / 3)) { CEN(g_cen->ref_drop_huge++); return; }
         c += rnd_f(xc); r += rnd_f(xr); layer += rnd_f(xi);
-        if (layer < 1 || layer > nLayers || c < SIFT_IMG_BORDER || c >= img->w - SIFT_IMG_BORDER || r < SIFT_IMG_BORDER || r >= img->h - SIFT_IMG_BORDER) return;
+        if (layer < 1 || layer > nLayers) { CEN(g_cen->ref_drop_layer++); return; }
+        if (c < SIFT_IMG_BORDER || c >= img->w - SIFT_IMG_BORDER || r < SIFT_IMG_BORDER || r >= img->h - SIFT_IMG_BORDER) { CEN(g_cen->ref_drop_border++); return; }
     }
-    if (i >= SIFT_MAX_INTERP_STEPS) return;
+    if (i >= SIFT_MAX_INTERP_STEPS) { CEN(g_cen->ref_drop_steps++); return; }
     {
         const fimg *img = &dog[o * (nLayers + 2) + layer], *prev = img - 1, *next = img + 1;
         const float dD0 = (DOG(img, r, c + 1) - DOG(img, r, c - 1)) * deriv_scale, dD1 = (DOG(img, r + 1, c) - DOG(img, r - 1, c)) * deriv_scale,
                     dD2 = (DOG(next, r, c) - DOG(prev, r, c)) * deriv_scale;
         const float t = dD0 * xc + dD1 * xr + dD2 * xi;
         contr = DOG(img, r, c) * img_scale + t * 0.5f;
-        if (fabsf(contr) * nLayers < contrastThr) return;
+        if (fabsf(contr) * nLayers < contrastThr) { CEN(g_cen->ref_drop_contrast++); return; }
         const float v2 = DOG(img, r, c) * 2.f;
         const float dxx = (DOG(img, r, c + 1) + DOG(img, r, c - 1) - v2) * second_deriv_scale, dyy = (DOG(img, r + 1, c) + DOG(img, r - 1, c) - v2) * second_deriv_scale;
         const float dxy = (DOG(img, r + 1, c + 1) - DOG(img, r + 1, c - 1) - DOG(img, r - 1, c + 1) + DOG(img, r - 1, c - 1)) * cross_deriv_scale;
         const float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
-        if (det <= 0 || tr * tr * edgeThr >= (edgeThr + 1) * (edgeThr + 1) * det) return;
+        if (det <= 0) { CEN(g_cen->ref_drop_det++); return; }
+        if (tr * tr * edgeThr >= (edgeThr + 1) * (edgeThr + 1) * det) { CEN(g_cen->ref_drop_edge++); return; }
     }
+    CEN(g_cen->ref_kept_steps[i]++);
     kpt_t kp;
     kp.x = (c + xc) * (1 << o); kp.y = (r + xr) * (1 << o);
     kp.octave = o + (layer << 8) + (rnd_d(((double)xi + 0.5) * 255) << 16);
@@ -310,16 +325,21 @@ static void refine_and_orient(const fimg* dog, const fimg* gauss, int o, int lay
     const int n = SIFT_ORI_HIST_BINS;
     const float omax = ori_hist(&gauss[o * (nLayers + 3) + layer], c, r, rnd_f(3 * 1.5f * scl_octv), 1.5f * scl_octv, hist, n);
     const float mag_thr = omax * 0.8f;
+    int npeaks = 0;
     for (int j = 0; j < n; j++) {
         const int l = j > 0 ? j - 1 : n - 1, r2 = j < n - 1 ? j + 1 : 0;
         if (hist[j] > hist[l] && hist[j] > hist[r2] && hist[j] >= mag_thr) {
             float bin = j + 0.5f * (hist[l] - hist[r2]) / (hist[l] - 2 * hist[j] + hist[r2]);
+            CEN(g_cen->ori_bin_neg += bin < 0; g_cen->ori_bin_ge_n += bin >= n);
             bin = bin < 0 ? n + bin : bin >= n ? bin - n : bin;
             kp.angle = 360.f - (float)((360.f / n) * bin);
+            CEN(g_cen->ori_snapped += fabsf(kp.angle - 360.f) < FLT_EPSILON);
             if (fabsf(kp.angle - 360.f) < FLT_EPSILON) kp.angle = 0.f;
             kpush(out, kp);
+            npeaks++;
         }
     }
+    CEN(g_cen->ori_peaks[npeaks < 4 ? npeaks : 4]++);
 }
 
 /* KeyPoint_LessThan (keypoint.cpp): the order removeDuplicatedSorted leaves the list in */
@@ -346,7 +366,11 @@ static void sift_descriptor(const fimg* img, float ptx, float pty, float ori, fl
     const float bins_per_rad = n / 360.f, exp_scale = -1.f / (d * d * 0.5f), hist_width = 3.f * scl;
     int radius = rnd_f(hist_width * 1.4142135623730951f * (d + 1) * 0.5f);
     const int rmax = (int)sqrt((double)img->w * img->w + (double)img->h * img->h);
+    CEN(g_cen->desc_r64 += radius >= 64; if (radius > g_cen->desc_max_radius) g_cen->desc_max_radius = radius;
+        g_cen->desc_clipped += radius > rmax; g_cen->desc_clipped_small += radius > rmax && radius < 64);
     if (radius > rmax) radius = rmax;
+    CEN(g_cen->desc_side_gt128 += 2 * radius + 1 > 128; if (2 * radius + 1 > g_cen->desc_max_side) g_cen->desc_max_side = 2 * radius + 1);
+    int cut[4] = {0, 0, 0, 0};
     cos_t /= hist_width; sin_t /= hist_width;
     const int len = (radius * 2 + 1) * (radius * 2 + 1), histlen = (d + 2) * (d + 2) * (n + 2);
     float* buf = (float*)malloc(sizeof(float) * ((size_t)len * 5 + histlen));
@@ -358,6 +382,7 @@ static void sift_descriptor(const fimg* img, float ptx, float pty, float ori, fl
             const float c_rot = j * cos_t - i * sin_t, r_rot = j * sin_t + i * cos_t;
             const float rbin = r_rot + d / 2 - 0.5f, cbin = c_rot + d / 2 - 0.5f;
             const int r = py + i, c = px + j;
+            CEN(if (rbin > -1 && rbin < d && cbin > -1 && cbin < d) { cut[0] |= r <= 0; cut[1] |= r >= img->h - 1; cut[2] |= c <= 0; cut[3] |= c >= img->w - 1; });
             if (rbin > -1 && rbin < d && cbin > -1 && cbin < d && r > 0 && r < img->h - 1 && c > 0 && c < img->w - 1) {
                 X[k] = img->p[(size_t)r * img->w + c + 1] - img->p[(size_t)r * img->w + c - 1];
                 Y[k] = img->p[(size_t)(r - 1) * img->w + c] - img->p[(size_t)(r + 1) * img->w + c];
@@ -366,6 +391,8 @@ static void sift_descriptor(const fimg* img, float ptx, float pty, float ori, fl
                 k++;
             }
         }
+    CEN(g_cen->desc_cut += cut[0] | cut[1] | cut[2] | cut[3]; for (int q = 0; q < 4; q++) g_cen->desc_cut_side[q] += cut[q];
+        if (k > g_cen->desc_max_samples) g_cen->desc_max_samples = k);
     for (int q = 0; q < k; q++) {
         const float Ori = fast_atan2_deg(Y[q], X[q]), Mag = sqrtf(X[q] * X[q] + Y[q] * Y[q]), Wq = cv_expf(W[q]);
         float rbin = RBin[q], cbin = CBin[q], obin = (Ori - ori) * bins_per_rad;
@@ -451,6 +478,16 @@ int voo_sift_detect_and_compute(const uint8_t* img, int h, int w, int channels, 
                                 if (val > 0 ? !(val >= nb) : !(val <= nb)) { ext = 0; break; }
                             }
                     }
+                    CEN(if (ext) for (int q = 0; q < (o == 0 ? 2 : 1); q++) {         /* [0] every octave, [1] octave 0 alone */
+                        const int dc = c - SIFT_IMG_BORDER, dr = r - SIFT_IMG_BORDER;
+                        g_cen->cand[q]++;
+                        g_cen->cand_strip_first[q] += dc >= VOO_SIFT_STRIP && dc % VOO_SIFT_STRIP == 0;
+                        g_cen->cand_strip_last[q] += dc % VOO_SIFT_STRIP == VOO_SIFT_STRIP - 1;
+                        g_cen->cand_col_first[q] += dc == 0; g_cen->cand_col_last[q] += c == cols - SIFT_IMG_BORDER - 1;
+                        g_cen->cand_seg_first[q] += dr >= VOO_SIFT_SEGMENT && dr % VOO_SIFT_SEGMENT == 0;
+                        g_cen->cand_seg_last[q] += dr % VOO_SIFT_SEGMENT == VOO_SIFT_SEGMENT - 1;
+                        g_cen->cand_row_first[q] += dr == 0; g_cen->cand_row_last[q] += r == rows - SIFT_IMG_BORDER - 1;
+                    });
                     if (ext) refine_and_orient(dog, g, o, i, r, c, nLayers, (float)contrastThreshold, (float)edgeThreshold, (float)sigma, &kps);
                 }
         }
@@ -460,11 +497,14 @@ int voo_sift_detect_and_compute(const uint8_t* img, int h, int w, int channels, 
     g_sort_base = kps.v;
     qsort(idx, (size_t)kps.n, sizeof(int), kp_less);
     int m = 0;
+    CEN(int last = -1;                                                         /* (sorted by x: equal columns are neighbours) */
+        for (int i = 0; i < kps.n; i++) { const float x = kps.v[idx[i]].x;
+            if (x >= (float)(VOO_SIFT_XBUCKETS - 1)) { g_cen->sort_x_clamped++; if ((int)x != last) { g_cen->sort_x_clamped_cols++; last = (int)x; } } });
     for (int i = 0; i < kps.n; i++) {
         const kpt_t* a = &kps.v[idx[i]];
         if (m > 0) {
             const kpt_t* b = &kps.v[idx[m - 1]];
-            if (a->x == b->x && a->y == b->y && a->size == b->size && a->angle == b->angle) continue;
+            if (a->x == b->x && a->y == b->y && a->size == b->size && a->angle == b->angle) { CEN(g_cen->sort_dups++); continue; }
         }
         idx[m++] = idx[i];
     }
@@ -485,6 +525,7 @@ int voo_sift_detect_and_compute(const uint8_t* img, int h, int w, int channels, 
         /* firstOctave = -1: back to the coordinates of the input image */
         kp.octave = (kp.octave & ~255) | ((kp.octave - 1) & 255);
         kp.x *= 0.5f; kp.y *= 0.5f; kp.size *= 0.5f;
+        CEN(g_cen->kp_layer[(kp.octave >> 8) & 255]++);
         if (i < cap) {
             if (kp_xy) { kp_xy[2 * i] = kp.x; kp_xy[2 * i + 1] = kp.y; }
             if (kp_size) kp_size[i] = kp.size;
@@ -503,7 +544,30 @@ int voo_sift_detect_and_compute(const uint8_t* img, int h, int w, int channels, 
         }
     }
     if (n_out) *n_out = m;
+    CEN(g_cen->n_keypoints = m);
     free(idx); free(kps.v);
     free_imgs(g, nOct * per); free_imgs(dog, nOct * (nLayers + 2));
     return 0;
+}
+
+int voo_sift_census_size(void) { return (int)sizeof(voo_sift_census_t); }
+
+/* The path census of one detectAndCompute: the call above, run once for the count and once more, with every descriptor
+ * computed, while the counters are live. */
+int voo_sift_census(const uint8_t* img, int h, int w, int channels, int row_stride, int nfeatures, int nLayers, double contrastThreshold,
+                    double edgeThreshold, double sigma, voo_sift_census_t* census)
+{
+    if (!census) return -1;
+    memset(census, 0, sizeof(*census));
+    int32_t n = 0;
+    int rc = voo_sift_detect_and_compute(img, h, w, channels, row_stride, nfeatures, nLayers, contrastThreshold, edgeThreshold, sigma,
+                                         NULL, NULL, NULL, NULL, NULL, NULL, 0, &n);
+    if (rc) return rc;
+    float* desc = (float*)malloc(sizeof(float) * 128 * (size_t)(n + 1));
+    g_cen = census;
+    rc = voo_sift_detect_and_compute(img, h, w, channels, row_stride, nfeatures, nLayers, contrastThreshold, edgeThreshold, sigma,
+                                     NULL, NULL, NULL, NULL, NULL, desc, n, &n);
+    g_cen = NULL;
+    free(desc);
+    return rc;
 }
