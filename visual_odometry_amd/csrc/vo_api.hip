@@ -1,215 +1,7 @@
 // vo_api.hip — context, device buffers and the C ABI of libvo_hip.so (see include/vo_hip.h).
 // Host-side plumbing only: every arithmetic stage is a HIP kernel in orb_/match_/geom_kernels.hip.
-#include "vo_internal.h"
-#include <float.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
-#include <type_traits>
-#include <algorithm>
-
-#define MAX_EVENTS 384                        // vo_slam_chain brackets five kernel groups per pair, six with vo_set_slam_stats on
-
-// The device (and pinned host) allocations of one lifetime: each one its own hipMalloc, all freed together by release() or
-// the destructor.  n == 0 allocates one element.
-struct DevList {
-    struct Entry { void* p; bool pinned; };
-    std::vector<Entry> ptrs;
-    DevList() = default;
-    DevList(const DevList&) = delete;
-    DevList& operator=(DevList&& o) noexcept { if (this != &o) { release(); ptrs.swap(o.ptrs); } return *this; }
-    ~DevList() { release(); }
-    template <typename T> hipError_t alloc(T** p, size_t n) { return keep(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)), (void**)p, false); }
-    template <typename T> hipError_t alloc_pinned(T** p, size_t n)
-    {
-        return keep(hipHostMalloc((void**)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault), (void**)p, true);
-    }
-    void release()
-    {
-        for (const Entry& e : ptrs) (void)(e.pinned ? hipHostFree(e.p) : hipFree(e.p));
-        ptrs.clear();
-    }
-private:
-    hipError_t keep(hipError_t e, void** p, bool pinned) { if (e == hipSuccess) ptrs.push_back({*p, pinned}); return e; }
-};
-
-// A device scratch buffer that only grows (capacity in elements): grow() is defined below vo_ctx
-template <typename T> struct Growable {
-    T* p = nullptr;
-    size_t cap = 0;
-    Growable() = default;
-    Growable(const Growable&) = delete;
-    ~Growable() { if (p) (void)hipFree(p); }
-    int grow(struct vo_ctx* ctx, size_t need, size_t n);
-    int grow(struct vo_ctx* ctx, size_t need) { return grow(ctx, need, need); }
-};
-
-// One SIFT configuration: per-slot results for max_frames slots + the scale-space scratch of one sub-batch of fb frames
-struct SiftState {
-    DevList mem;
-    bool configured = false, with_operands = false;
-    vo_sift_params prm{};
-    int h = 0, w = 0, fstride = 0, max_frames = 0, kp_cap = 0, cap_x = 0, raw_cap = 0, cand_cap = 0, surv_cap = 0, fb = 0;
-    SiftGeom P{};
-    float taps[16][SIFT_MAX_TAPS]; int ntaps[16];
-    SiftExpTab E{};
-    uint8_t* frames = nullptr;                                    // [slot][h][fstride] gray
-    float *kp_xy = nullptr, *kp_size = nullptr, *kp_angle = nullptr, *kp_resp = nullptr; int *kp_oct = nullptr, *kp_count = nullptr, *flags = nullptr;
-    uint8_t *desc = nullptr, *desc_x = nullptr; int* norms = nullptr;   // [slot][kp_cap][128] u8; int8 operand image + |v - 128|^2 for the matrix-core matcher
-    float *G = nullptr, *up = nullptr;                            // sub-batch scratch: the Gaussian pyramids (the DoG planes are never stored)
-    SiftCand* cand = nullptr; SiftSurv* surv = nullptr; SiftKp *kraw = nullptr, *ksorted = nullptr, *kfin = nullptr;
-    int *rank = nullptr, *counts = nullptr, *fin_count = nullptr, *fin_flags = nullptr;
-};
-
-// The process's ONE RCCL communicator.  Every context of the GPU holds a reference and issues its collectives on its own
-// stream, but each collective first waits (event) for the one submitted before it, whichever context that was: collectives
-// run one after the other in the order the host submitted them (the same on every rank), never two at once.
-// (A dedicated communicator stream was tried first: with 3 context streams it shares a hardware queue with one of them and
-//  cost 9 % of the single-GPU rate — 76.4 k vs 83.7 k pairs/s — through false serialisation.)
-struct CommShared {
-    void* comm = nullptr;
-    int rank = 0, world = 1, refs = 0;
-    hipEvent_t last = nullptr;            // end of the most recently submitted collective
-    bool last_set = false;
-};
-
-// What the most recent vo_pairs_run[_async] left in the pair buffers: cleared whenever those buffers may have changed
-struct LastRun {
-    int pairs = 0;
-    std::vector<int32_t> slots;           // its pair slots (host copy)
-    int points = 0;                       // ... and whether it triangulated (want_points)
-    int match_mode = 0;                   // ... and its vo_pair_opts.match_mode (vo_slam_chain needs one-to-one matches)
-    // host copies of the maps of the most recent vo_slam_chain: [0] at the end of the chain, [1] the snapshot
-    struct Map {
-        bool valid = false;
-        std::vector<int32_t> cam_frame, pt_feature, obs_cam, obs_pt;
-        std::vector<uint8_t> cam_fixed;
-        std::vector<double> cam_pose, points, obs_xy;
-    } map[2];
-    // ... of the most recent vo_slam_chains: every sequence's map at its end, and the snapshot of sequence snap_seq (-1: none)
-    std::vector<Map> seq_map;
-    Map snap_map;
-    int snap_seq = -1;
-    // ... and, if it ran with vo_set_slam_stats on, its statistics rows: sequence s owns rows seq_off[s] .. seq_off[s + 1] - 1
-    struct Stats {
-        bool valid = false;
-        int C = 0;                        // cameras a row holds: the call's max_cameras + 1
-        std::vector<int32_t> seq_off, n_high, counts, obs_hist, obs_matrix, cam_frame;
-        std::vector<double> total_sqerr, max_sqerr;
-    } stats;
-};
-
-// vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one
-// allocation that lives from the call that starts the stream (resume = 0) until the stream is dropped.
-struct SlamStream {
-    DevList mem;
-    bool live = false;                    // a resume = 0 call has run and nothing has dropped the stream since
-    bool lost = false;                    // its last call ended with a pair that was not localised
-    bool restart = false;                 // begun by vo_slam_stream_restart: a lost stream is continued and starts a new map
-    bool touched = false;                 // the anchor slot was uploaded to or detected again: the stream's last frame is gone
-    int anchor = -1;                      // slot of the stream's last frame
-    int done = 0, total = 0;              // pairs so far, pairs the stream may reach (what the lists were sized for)
-    int carries = 0, last_ncam = 0;       // resumed calls so far; cameras the map held at the end of the last call
-    int F = 0, cap = 0, max_pairs = 0;    // the configuration it was sized for
-    vo_slam_opts opts{};
-    double K[9] = {0};
-    uint8_t* base = nullptr; size_t bytes = 0;
-    uint8_t* call_mem = nullptr; size_t call_bytes = 0;     // the per-pair outputs: cleared at the start of every call
-    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; SlamMap snap{};
-    double *dK = nullptr, *dchi2 = nullptr, *keep = nullptr; int *dit = nullptr, *dtr = nullptr;
-    uint8_t *map_mem = nullptr, *snap_mem = nullptr; size_t map_bytes = 0;
-    // vo_slam_streams: S sequences in the one allocation.  The scalars above that describe the one sequence of vo_slam_stream*
-    // (anchor, done, total, last_ncam, lost, touched) are per sequence here; `carries` counts the resumed calls — every sequence is
-    // carried in each — and cb / sb / D / snap name the whole arrays, of which a sequence's descriptor owns its ranges.
-    struct Seq {
-        int anchor = -1, done = 0, total = 0, last_ncam = 0;
-        bool lost = false, touched = false;
-        int n_rows = 0;                   // slots its last call's frames had, the anchor excepted: rows[s * (max_pairs + 1) ..]
-        SlamSeq at{};                     // its descriptor before a call's offsets: the ranges of the lists that are its own
-        size_t np = 0, no = 0;            // points and observations its lists hold
-        // seats (vo_slam_streams_replace / vo_slam_streams_open): a vacant seat has no flight and no anchor (anchor = -1, done = 0,
-        // total = the bound of the flight that takes it); until the carry launch of the next call has reset it (clean), old_anchor
-        // names the row its last flight's anchor had
-        int capacity = 0;                 // total_pairs of the call that sized its lists: the most a flight in this seat may reach
-        bool vacant = false, clean = false;
-        int old_anchor = -1;
-    };
-    bool multi = false;                   // begun by vo_slam_streams
-    int S = 0;
-    std::vector<Seq> seq;
-    std::vector<int32_t> rows;
-    SlamSeq* dseq = nullptr; SlamSeqCarry* dcar = nullptr; int* drows = nullptr;
-    SlamSeat* dseat = nullptr;            // what the carry launch does for every seat, when one of them is vacant
-    size_t snap_np = 0, snap_no = 0;
-    bool stats = false;                   // started with vo_set_slam_stats on: the rows and the kernel's scratch are part of the allocation
-    StatsBuf sbuf{};
-};
-
-struct vo_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;         // non-blocking: no implicit ordering with the NULL stream (PyTorch / RCCL use it)
-    hipStream_t stream_jpg = nullptr;     // the JPEG decoder's coefficient buffer is cleared here, beside the upload of the files and k_jpeg_unstuff
-    hipEvent_t ev_jpg[2] = {nullptr, nullptr};
-    char err[512] = {0};
-    DevList mem;                          // context lifetime: dK, rng_tab, rng_host
-
-    bool configured = false;
-    DevList orb_mem;                      // the ORB configuration: tables, pyramid, blur, scores, ff.*, desc_x, selection state, cv2.*
-    int h = 0, w = 0, max_frames = 0, max_pairs = 0;
-    vo_orb_params params{};
-    PyrGeom g{};
-    ResizeTab tabs[VO_MAX_LEVELS]{};
-    uint8_t *pyr = nullptr, *blur = nullptr, *score = nullptr;
-    uint8_t* desc_x = nullptr;            // descriptors expanded to +1 / -1 bytes for the MFMA matcher
-    Growable<uint8_t> staging;                                       // host frames on their way into the slots
-    Growable<uint8_t> ingest_out;                                    // resized frames (frame ingest)
-    SiftState sift, sift1;                                           // SIFT: the batched detector's state; the single-image call's
-    Growable<uint8_t> sift_img;                                      // the single-image call's input on the device
-    int detector = 0;                                                // detector of the batched path: 0 = ORB (vo_batch_configure), 1 = SIFT (vo_batch_configure_sift)
-    int sift_pairs = 0;
-    // JPEG decode: the batch's files, clean streams, restart lists, coefficients, component planes, B G R output, descriptors
-    Growable<uint8_t> jpg_blob, jpg_clean, jpg_rst, jpg_coef, jpg_planes, jpg_out, jpg_img, jpg_tab;
-    Growable<int> ingest_tab;                                        // resize tables
-    int *sel_thr = nullptr, *sel_chunk_count = nullptr, *har_kept = nullptr;
-    float* har_thr = nullptr;
-    FrameFeat ff{};
-    DevList pb_mem;                       // the pair buffers, shared by ORB and SIFT
-    PairBuf pb{};
-    int pb_pairs = 0, pb_cap = 0;
-    double* dK = nullptr;
-    LastRun last;
-    SlamStream stream_map;                // vo_slam_stream's resident map (its own lifetime: see drop_slam_stream)
-
-    // scratch for the single-call operators
-    DevList raw_mem;                      // the single-call matcher: raw_desc, raw_desc_x, raw_xy, raw_count, raw_pb.*
-    int raw_cap = 0;
-    uint8_t* raw_desc = nullptr; float* raw_xy = nullptr; int* raw_count = nullptr; uint8_t* raw_desc_x = nullptr;
-    PairBuf raw_pb{};
-    Growable<uint8_t> scratch;                       // one call's device memory, laid out by ScratchLayout
-    uint32_t* rng_tab = nullptr; uint32_t* rng_host = nullptr; uint64_t rng_seed = 0; bool rng_valid = false;   // OpenCV RNG stream for the RANSAC seed
-
-    bool prof = false;
-    float prof_ms[VO_STAGE_COUNT] = {0};
-    int prof_n[VO_STAGE_COUNT] = {0};
-    hipEvent_t ev[MAX_EVENTS][2];
-    int ev_stage[MAX_EVENTS];
-    int n_ev = 0;
-    bool ev_ready = false;
-    hipEvent_t ev_det = nullptr;          // end of the most recent vo_frames_detect_async (vo_detect_after waits on it)
-    bool ev_det_set = false;
-    int descx_fp4 = -1;                   // operand image EVERY resident slot's desc_x holds: 1 FP4, 0 int8, -1 none written yet (descx_begin_write)
-    int matcher_kernel = 2;               // 2: block-scaled FP4 MFMA (default), 0: int8 MFMA on +127/-127 bytes, 1: XOR + popcount
-    CommShared* cs = nullptr;             // RCCL communicator of the trajectory gather: ONE per process, shared by its contexts (vo_comm_share)
-    Growable<double> rec_send, rec_recv;  // the gather's packed records: this rank's and every rank's
-    int kp_order = 1;                     // 1 (default): cv2's retainBest order — keypoint / match indices as cv2 numbers them; 0: canonical (octave, y, x)
-    Cv2Buf cv2{};
-    bool cv2_ready = false;
-    int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
-    int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
-    int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it
-};
+// The vo_slam_* entry points are slam_api.hip; vo_host.h has the context and the helpers the two files share.
+#include "vo_host.h"
 
 static const char* k_stage_names[VO_STAGE_COUNT] = {
     "gray", "pyramid_resize", "fast_score_nms", "select_fast", "harris", "select_harris", "ic_angle",
@@ -218,37 +10,7 @@ static const char* k_stage_names[VO_STAGE_COUNT] = {
     "sift_descriptor", "cv2_keypoint_order", "trajectory_gather", "reserved2", "slam_ba_prepare", "slam_bundle_adjust", "slam_filter",
     "slam_camera_limit", "slam_map_statistics"};
 
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            snprintf(ctx->err, sizeof(ctx->err), "%s:%d: %s -> %s", __FILE__, __LINE__, #expr,    \
-                     hipGetErrorString(e_));                                                      \
-            return VO_ERR_HIP;                                                                    \
-        }                                                                                         \
-    } while (0)
-
-#define FAIL(code, ...)                                                                           \
-    do { snprintf(ctx->err, sizeof(ctx->err), __VA_ARGS__); return (code); } while (0)
-
-// Room for `need` elements.  Without it: wait for the context's stream (queued work may still use the buffer), free, and
-// allocate n >= need elements.
-template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
-{
-    if (need <= cap) return VO_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    HIPCHK(hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)));
-    cap = n;
-    return VO_OK;
-}
-
 static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
-
-// The end of a stream: vo_destroy (the context's destructor), a configure call, a vo_slam_stream[_restart] or vo_slam_streams that
-// starts a new one and every vo_slam_chain* call come here.  (Every call that uses the allocation has waited for the context's stream before it returned.)
-static void drop_slam_stream(vo_ctx* ctx) { ctx->stream_map = SlamStream(); }
 
 // An upload, ingest or detection into slots first .. first + n - 1: if the stream's last frame is among them, no call can continue it
 // (vo_slam_streams: the sequence whose last frame it is cannot advance any more; the others can).
@@ -260,57 +22,7 @@ static void slam_stream_slots_written(vo_ctx* ctx, int first, int n)
         if (st.live && q.anchor >= first && q.anchor < first + n) q.touched = true;
 }
 
-// The device memory of one call: typed sub-buffers of ctx->scratch, each on a 256-byte boundary.  take() names a pointer
-// and its element count; place() grows the buffer to what was taken and sets the pointers, so size and offsets agree.
-struct ScratchLayout {
-    size_t bytes = 0;                     // all sub-buffers: they start at ctx->scratch.p
-    template <typename T> void take(T** p, size_t n)
-    {
-        slots.push_back({p, bytes, [](void* dst, uint8_t* at) { *static_cast<T**>(dst) = reinterpret_cast<T*>(at); }});
-        bytes += (n * sizeof(T) + 255) & ~(size_t)255;
-    }
-    void place_at(uint8_t* base) { for (const Slot& s : slots) s.set(s.dst, base + s.off); }   // (an allocation of the caller's, `bytes` long)
-    int place(vo_ctx* ctx)
-    {
-        int rc = ctx->scratch.grow(ctx, bytes, bytes + bytes / 4 + 64); if (rc) return rc;
-        for (const Slot& s : slots) s.set(s.dst, ctx->scratch.p + s.off);
-        return VO_OK;
-    }
-    struct Slot { void* dst; size_t off; void (*set)(void*, uint8_t*); };
-    std::vector<Slot> slots;
-};
-
-// vo_set_slam_stats: the statistics rows of P pairs with room for cm cameras, and k_slam_stats' scratch for np points and no
-// observations, as sub-buffers of a call's layout.  Off: nothing is taken, the layout is byte for byte what it was.
-static void slam_stats_take_scratch(ScratchLayout& sc, StatsBuf& d, bool on, size_t np, size_t no)
-{
-    if (!on) return;
-    sc.take(&d.pt_cur, np); sc.take(&d.slot, no); sc.take(&d.bad, 1);
-}
-
-static void slam_stats_take_rows(ScratchLayout& sc, StatsBuf& d, bool on, size_t P, size_t cm)
-{
-    if (!on) return;
-    sc.take(&d.total_sqerr, P); sc.take(&d.max_sqerr, P); sc.take(&d.n_high, P); sc.take(&d.counts, P * 3); sc.take(&d.obs_hist, P * VO_STATS_HIST);
-    sc.take(&d.obs_matrix, P * cm * cm); sc.take(&d.cam_frame, P * cm);
-    d.C = (int)cm; d.high = 10.0;
-}
-
-// ------------------------------------------------------------------ profiling brackets
-struct StageTimer {
-    vo_ctx* c; int idx;
-    StageTimer(vo_ctx* ctx, int stage) : c(ctx), idx(-1)
-    {
-        if (c->prof && c->n_ev < MAX_EVENTS) {
-            idx = c->n_ev++;
-            c->ev_stage[idx] = stage;
-            (void)hipEventRecord(c->ev[idx][0], c->stream);
-        }
-    }
-    ~StageTimer() { if (idx >= 0) (void)hipEventRecord(c->ev[idx][1], c->stream); }
-};
-
-static void prof_collect(vo_ctx* c)
+void prof_collect(vo_ctx* c)
 {
     for (int i = 0; i < c->n_ev; i++) {
         float ms = 0;
@@ -695,19 +407,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
     return VO_OK;
 }
 
-// ---- the batched path, whichever detector is configured: ORB (vo_batch_configure) or SIFT (vo_batch_configure_sift)
-struct Batch {
-    bool sift, ready;
-    int w, h, max_frames, max_pairs, kp_cap;
-    // the slots' resident results, as the pair stage reads them
-    const uint8_t *desc, *desc_x; const float* kp_xy; const int *kp_count, *flags, *norms;
-    int fp4;                              // operand image in desc_x (ORB: the one written at detection; SIFT: int8 rows + L2 norms)
-    // slot k's gray image at gray + k * gray_frame, rows of gray_stride bytes: level 0 of the ORB pyramid, or the SIFT slots' frames
-    uint8_t* gray; int gray_stride; size_t gray_frame;
-    uint8_t* gray_slot(int k) const { return gray + (size_t)k * gray_frame; }
-};
-
-static Batch batch(const vo_ctx* ctx)
+Batch batch(const vo_ctx* ctx)
 {
     if (ctx->detector == 1) {
         const SiftState& S = ctx->sift;
@@ -1143,10 +843,7 @@ extern "C" int vo_stage_blur(vo_ctx* ctx, const uint8_t* img, int h, int w, int 
 }
 
 // ------------------------------------------------------------------ pairs
-// cv::RNG (multiply-with-carry, core/operations.hpp RNG::next) output stream for `seed`; it depends on
-// nothing but the seed, so it is tabulated once and shared by every pair of every batch.
-#define RNG_TAB_N 8192
-static int ensure_rng(vo_ctx* ctx, uint64_t seed)
+int ensure_rng(vo_ctx* ctx, uint64_t seed)
 {
     if (ctx->rng_valid && ctx->rng_seed == seed) return VO_OK;
     if (!ctx->rng_tab) HIPCHK(ctx->mem.alloc(&ctx->rng_tab, RNG_TAB_N));
@@ -1863,7 +1560,7 @@ extern "C" int vo_map_statistics(vo_ctx* ctx, const double* poses, int ncam, con
     ScratchLayout sc;
     sc.take(&sb.m.cnt, 4); sc.take(&sb.m.cam_pose, (size_t)12 * ncam); sc.take(&sb.m.pt_xyz, (size_t)3 * npt);
     sc.take(&sb.m.obs_cam, nobs); sc.take(&sb.m.obs_pt, nobs); sc.take(&sb.m.obs_xy, (size_t)2 * nobs); sc.take(&dK, 9);
-    slam_stats_take_scratch(sc, d, true, npt, nobs); slam_stats_take_rows(sc, d, true, 1, ncam);
+    slam_stats_take_scratch(sc, d, npt, nobs); slam_stats_take_rows(sc, d, 1, ncam);
     int rc = sc.place(ctx); if (rc) return rc;
     d.Kd = dK; d.high = high_threshold; d.cam_frame = nullptr;
     hipStream_t s = ctx->stream;
@@ -2877,7 +2574,7 @@ extern "C" int vo_feature_tracks(vo_ctx* ctx, int F, int cap, const int32_t* pai
 
 // What vo_tracks_pnp_batch and vo_slam_chain ask of the most recent vo_pairs_run: all its B pairs, triangulated, every slot
 // inside the configuration, the pairs a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference walks a sequence in
-static int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out)
+int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out)
 {
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
@@ -2946,1218 +2643,6 @@ extern "C" int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iter
     HIPCHK(hipMemcpyAsync(n_map, cb.n_map, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
-    return VO_OK;
-}
-
-// ------------------------------------------------------------------ the reference's complete per-frame map step, on resident data
-// vo_tracks_pnp_batch's walk with what ends every frame of VisualSlam.estimate_current_camera_position (src/visual_slam.py:190-266)
-// joined to it: the Observations of add_information_to_map, freeze_nonlast_cameras, Map.optimize_map, the threshold filter and
-// limit_number_of_camera_in_map — on a map that stays in HBM (slam_kernels.hip), pair after pair with no host round trip.
-// The map's three lists, carved from one block so that a snapshot is one device-to-device copy; base == nullptr: the size only
-static size_t slam_map_carve(uint8_t* base, size_t ncam, size_t npt, size_t nobs, SlamMap* m)
-{
-    size_t o = 0;
-    auto put = [&](auto** p, size_t n) {
-        using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
-        if (base) *p = reinterpret_cast<T*>(base + o);
-        o += (n * sizeof(T) + 255) & ~(size_t)255;
-    };
-    put(&m->cnt, 4); put(&m->cam_frame, ncam); put(&m->cam_pose, ncam * 12); put(&m->cam_fixed, ncam); put(&m->pt_key, npt); put(&m->pt_xyz, npt * 3);
-    put(&m->obs_cam, nobs); put(&m->obs_pt, nobs); put(&m->obs_xy, nobs * 2);
-    return o;
-}
-
-// first, count: the pairs of the run that are the map's chain (pt_feature names a frame by its index along that chain)
-static int slam_map_download(vo_ctx* ctx, const SlamMap& m, int cap, LastRun::Map* out, int first = 0, int count = -1)
-{
-    int cnt[4];
-    HIPCHK(hipMemcpy(cnt, m.cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-    const size_t nc = cnt[0], np = cnt[1], no = cnt[2];
-    std::vector<int32_t> key(np);
-    out->cam_frame.resize(nc); out->cam_pose.resize(nc * 12); out->cam_fixed.resize(nc); out->points.resize(np * 3);
-    out->obs_cam.resize(no); out->obs_pt.resize(no); out->obs_xy.resize(no * 2); out->pt_feature.resize(np * 2);
-    if (nc) {
-        HIPCHK(hipMemcpy(out->cam_frame.data(), m.cam_frame, nc * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->cam_pose.data(), m.cam_pose, nc * 96, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->cam_fixed.data(), m.cam_fixed, nc, hipMemcpyDeviceToHost));
-    }
-    if (np) {
-        HIPCHK(hipMemcpy(key.data(), m.pt_key, np * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->points.data(), m.pt_xyz, np * 24, hipMemcpyDeviceToHost));
-    }
-    if (no) {
-        HIPCHK(hipMemcpy(out->obs_cam.data(), m.obs_cam, no * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->obs_pt.data(), m.obs_pt, no * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(out->obs_xy.data(), m.obs_xy, no * 16, hipMemcpyDeviceToHost));
-    }
-    if (m.pt_feat) {                                                  // vo_slam_stream keeps the feature ids as (frame, keypoint) on the device
-        if (np) HIPCHK(hipMemcpy(out->pt_feature.data(), m.pt_feat, np * 8, hipMemcpyDeviceToHost));
-        out->valid = true;
-        return VO_OK;
-    }
-    // feature id (slot, keypoint) -> (index of the frame in the chain, keypoint)
-    const int32_t* sl = ctx->last.slots.data() + 2 * (size_t)first;
-    const size_t npairs = count < 0 ? ctx->last.slots.size() / 2 : (size_t)count;
-    for (size_t i = 0; i < np; i++) {
-        const int slot = key[i] / cap;
-        int frame = sl[0] == slot ? 0 : -1;
-        for (size_t p = 0; frame < 0 && p < npairs; p++) if (sl[2 * p + 1] == slot) frame = (int)p + 1;
-        out->pt_feature[2 * i] = frame; out->pt_feature[2 * i + 1] = key[i] % cap;
-    }
-    out->valid = true;
-    return VO_OK;
-}
-
-static void forget_slam_maps(vo_ctx* ctx)
-{
-    ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
-    ctx->last.seq_map.clear(); ctx->last.snap_map = LastRun::Map(); ctx->last.snap_seq = -1;
-    ctx->last.stats = LastRun::Stats();
-}
-
-// the rows of a call that has come through (its stream has been waited for) -> the context's host copy
-static int slam_stats_download(vo_ctx* ctx, const StatsBuf& d, std::vector<int32_t> seq_off)
-{
-    LastRun::Stats& h = ctx->last.stats;
-    const size_t P = (size_t)seq_off.back(), C = (size_t)d.C;
-    h = LastRun::Stats();
-    h.total_sqerr.resize(P); h.max_sqerr.resize(P); h.n_high.resize(P); h.counts.resize(P * 3); h.obs_hist.resize(P * VO_STATS_HIST); h.obs_matrix.resize(P * C * C); h.cam_frame.resize(P * C);
-    HIPCHK(hipMemcpy(h.total_sqerr.data(), d.total_sqerr, P * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.max_sqerr.data(), d.max_sqerr, P * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.n_high.data(), d.n_high, P * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.counts.data(), d.counts, P * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.obs_hist.data(), d.obs_hist, P * VO_STATS_HIST * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.obs_matrix.data(), d.obs_matrix, P * C * C * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.cam_frame.data(), d.cam_frame, P * C * 4, hipMemcpyDeviceToHost));
-    h.C = d.C; h.seq_off = std::move(seq_off); h.valid = true;
-    return VO_OK;
-}
-
-// the option checks that ask nothing of a vo_pairs_run (vo_slam_streams_open has none)
-static int slam_opts_check_values(vo_ctx* ctx, const vo_slam_opts* o, const double* K)
-{
-    if (o->ba_iterations < 0 || o->ba_iterations > 1000) FAIL(VO_ERR_INVALID, "ba_iterations must be 0 .. 1000, got %d", o->ba_iterations);
-    if (o->free_cameras < 1) FAIL(VO_ERR_INVALID, "free_cameras must be at least 1, got %d", o->free_cameras);
-    if (o->free_cameras > VO_BA_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "bundle adjustment frees at most %d cameras, got %d", VO_BA_MAX_FREE, o->free_cameras);
-    if (o->max_cameras < 2) FAIL(VO_ERR_INVALID, "max_cameras must be at least 2, got %d", o->max_cameras);
-    if ((int64_t)o->max_cameras + 1 > VO_BA_MAX_CAMERAS)
-        FAIL(VO_ERR_UNSUPPORTED, "the map holds max_cameras + 1 cameras before the limit is applied, bundle adjustment at most %d", VO_BA_MAX_CAMERAS);
-    if (!(o->huber_delta == o->huber_delta) || !(o->filter_threshold == o->filter_threshold) || !(K[0] == K[0]) || !(K[2] == K[2]) || !(K[5] == K[5]))
-        FAIL(VO_ERR_INVALID, "camera parameters and thresholds must be numbers");
-    return VO_OK;
-}
-
-// the option checks of vo_slam_chain and vo_slam_chains; B_snap: pairs of the chain snapshot_pair counts along
-static int slam_opts_check(vo_ctx* ctx, const vo_slam_opts* o, const double* K, int B_snap, const char* who)
-{
-    if (ctx->last.match_mode == 1 || ctx->last.match_mode == 3)
-        FAIL(VO_ERR_UNSUPPORTED, "%s needs one-to-one matches (cross-check): with ratio or nearest-neighbour matches two inliers can share a track root", who);
-    const int rc = slam_opts_check_values(ctx, o, K); if (rc) return rc;
-    if ((o->snapshot_pair >= 0) != (o->snapshot_stage >= 1) || o->snapshot_pair >= B_snap || o->snapshot_stage > 4)
-        FAIL(VO_ERR_INVALID, "snapshot_pair must be -1 or a pair of the chain, snapshot_stage 1 .. 4 with it");
-    return VO_OK;
-}
-
-extern "C" int vo_slam_chain(vo_ctx* ctx, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
-                             int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
-                             double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
-        FAIL(VO_ERR_INVALID, "bad arguments");
-    int F, cap;
-    drop_slam_stream(ctx);
-    int rc = chain_check(ctx, B, "vo_slam_chain", &F, &cap); if (rc) return rc;
-    forget_slam_maps(ctx);
-    rc = slam_opts_check(ctx, o, K, B, "vo_slam_chain"); if (rc) return rc;
-    const size_t fc = (size_t)F * cap;
-    HIPCHK(hipSetDevice(ctx->device));
-    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    // capacities from the configuration: a pair adds at most one point and two observations per match
-    const size_t cm = (size_t)o->max_cameras + 1, np = fc, no = (size_t)2 * B * cap, npair = no * (o->free_cameras + 1) / 2;
-    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
-    if (np >= ((size_t)1 << 31) || npair >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the map's lists would not fit 32-bit indices");
-    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; double* dK; uint8_t *map_mem, *snap_mem;
-    const size_t map_bytes = slam_map_carve(nullptr, cm, np, no, &sb.m);
-    ScratchLayout sc;
-    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
-    sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4); sc.take(&cb.poses, (size_t)(B + 1) * 12);
-    sc.take(&dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
-    sc.take(&cb.alive, 1); sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&cb.map_count, 1);
-    sc.take(&map_mem, map_bytes); sc.take(&snap_mem, map_bytes);
-    sc.take(&sb.pt_of, fc); sc.take(&sb.dec, cap); sc.take(&sb.tmp, np); sc.take(&sb.idx, no); sc.take(&sb.n_pts, B); sc.take(&sb.n_obs, B); sc.take(&sb.n_cam, B);
-    sc.take(&sb.poses_last, (size_t)(B + 1) * 12);
-    sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
-    sc.take(&sb.pairs, npair); sc.take(&sb.blk_first, (size_t)nblk + 1);
-    sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
-    double* dchi2; int *dit, *dtr;
-    sc.take(&dchi2, (size_t)2 * B); sc.take(&dit, B); sc.take(&dtr, B);
-    const bool stats_on = ctx->slam_stats != 0;
-    StatsBuf stats{};
-    slam_stats_take_scratch(sc, stats, stats_on, np, no); slam_stats_take_rows(sc, stats, stats_on, B, cm);
-    rc = sc.place(ctx); if (rc) return rc;
-    stats.Kd = dK;
-    SlamMap snap{};
-    slam_map_carve(map_mem, cm, np, no, &sb.m); slam_map_carve(snap_mem, cm, np, no, &snap);
-    sb.cam_cap = (int)cm; sb.pt_cap = (int)np; sb.obs_cap = (int)no; sb.pair_cap = (int)npair;
-    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
-    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
-    HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty map, no cameras, zero results
-    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
-    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
-    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
-    auto snapshot = [&](int p, int stage) {
-        if (p == o->snapshot_pair && stage == o->snapshot_stage) (void)hipMemcpyAsync(snap_mem, map_mem, map_bytes, hipMemcpyDeviceToDevice, s);
-    };
-    launch_chain_link(s, ctx->pb, cap, B, cb);
-    for (int p = 0; p < B; p++) {
-        {
-            StageTimer t(ctx, ST_MISC);
-            if (p == 0) launch_chain_init(s, ctx->pb, cap, cb);
-            else {
-                launch_chain_gather(s, ctx->pb, cap, p, F, cb);
-                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
-                launch_chain_pose(s, ctx->pb, p, dK, cb);
-                launch_chain_triangulate(s, ctx->pb, cap, p, cb);
-            }
-            launch_slam_add(s, ctx->pb, cap, p, F, o->max_point_norm, o->free_cameras, cb, sb);
-        }
-        snapshot(p, 1);
-        if (ba) {
-            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare(s, cb, sb); }
-            BaBuf Dp = D;
-            Dp.chi2 = dchi2 + 2 * p; Dp.iterations_run = dit + p; Dp.trials_run = dtr + p;
-            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dp, prm, 1, o->free_cameras); }
-        }
-        snapshot(p, 2);
-        // pair 0 ends with optimize_map (:90); what it wrote back still has to reach the tables the next pair reads
-        if (ba || (filt && p > 0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter(s, ctx->pb, dK, p > 0 ? o->filter_threshold : 0.0, cb, sb); }
-        snapshot(p, 3);
-        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit(s, p, o->max_cameras, cb, sb); }
-        snapshot(p, 4);
-        if (stats_on) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats(s, p, sb, stats); }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(chi2, dchi2, (size_t)B * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ba_iterations_run, dit, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ba_trials_run, dtr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (ctx->prof) prof_collect(ctx);
-    // the scratch buffer belongs to the next call: the two maps are kept as host copies
-    rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
-    if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, snap, cap, &ctx->last.map[1]); if (rc) return rc; }
-    if (stats_on) { rc = slam_stats_download(ctx, stats, {0, B}); if (rc) return rc; }
-    return VO_OK;
-}
-
-static int slam_map_copy_out(vo_ctx* ctx, const LastRun::Map* m, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature, double* points,
-                             int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
-{
-    if ((!m->cam_frame.empty() && (!cam_frame || !cam_pose || !cam_fixed)) || (!m->points.empty() && (!pt_feature || !points)) ||
-        (!m->obs_cam.empty() && (!obs_cam || !obs_pt || !obs_xy))) FAIL(VO_ERR_INVALID, "bad arguments");
-    auto copy = [](auto* dst, const auto& v) { if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-    copy(cam_frame, m->cam_frame); copy(cam_pose, m->cam_pose); copy(cam_fixed, m->cam_fixed); copy(pt_feature, m->pt_feature); copy(points, m->points);
-    copy(obs_cam, m->obs_cam); copy(obs_pt, m->obs_pt); copy(obs_xy, m->obs_xy);
-    return VO_OK;
-}
-
-static const LastRun::Map* slam_map_of(vo_ctx* ctx, int which)
-{
-    if (which < 0 || which > 1 || !ctx->last.map[which].valid) {
-        snprintf(ctx->err, sizeof(ctx->err), which < 0 || which > 1 ? "which must be 0 (the map at the end of the chain) or 1 (the snapshot)"
-                                                                   : "no such map: vo_slam_chain has not run (or not with a snapshot) since the last configure / vo_pairs_run");
-        return nullptr;
-    }
-    return &ctx->last.map[which];
-}
-
-extern "C" int vo_slam_map_size(vo_ctx* ctx, int which, int32_t* ncam, int32_t* npt, int32_t* nobs)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    if (!ncam || !npt || !nobs) FAIL(VO_ERR_INVALID, "bad arguments");
-    const LastRun::Map* m = slam_map_of(ctx, which);
-    if (!m) return VO_ERR_INVALID;
-    *ncam = (int32_t)m->cam_frame.size(); *npt = (int32_t)(m->points.size() / 3); *nobs = (int32_t)m->obs_cam.size();
-    return VO_OK;
-}
-
-extern "C" int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature, double* points,
-                           int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const LastRun::Map* m = slam_map_of(ctx, which);
-    if (!m) return VO_ERR_INVALID;
-    return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
-}
-
-// ------------------------------------------------------------------ the map step, one call after another on one resident map
-// vo_slam_chain's walk on buffers of their own lifetime (SlamStream): the first call of a stream clears them as vo_slam_chain
-// clears the scratch buffer and runs vo_slam_chain's steps; a call that continues it clears the per-pair outputs only, lets
-// k_slam_carry restate the keys (slam_kernels.hip) and runs a p >= 1 step for every pair.  The work buffers keep what the last
-// step left in them, as they do between two steps of one call.
-static int slam_stream_allocate(vo_ctx* ctx, SlamStream& st, bool restart, int F, int cap, int max_pairs, int total, const vo_slam_opts* o, const double* K)
-{
-    // the slot-keyed tables have two ghost rows behind the F slots.  Lists: a pair adds at most one point per match; a camera takes
-    // at most kp_cap observations as a pair's second frame and kp_cap as the next pair's first (one-to-one matches), and the map
-    // holds at most max_cameras + 1 cameras — or every pair's two observations per match, if the stream is shorter than that.
-    const size_t fc = (size_t)(F + 2) * cap, cm = (size_t)o->max_cameras + 1, np = ((size_t)total + 1) * cap;
-    const size_t no = (size_t)2 * cap * std::min(cm, (size_t)total), npair = no * (o->free_cameras + 1) / 2;
-    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
-    const size_t P = (size_t)max_pairs;
-    if (F + 2 >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames for the packed track table");
-    if (np >= ((size_t)1 << 31) || npair >= ((size_t)1 << 31) || fc >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the map's lists would not fit 32-bit indices");
-    ChainBuf& cb = st.cb; SlamBuf& sb = st.sb; BaBuf& D = st.D;
-    size_t o_feat = 0;
-    st.map_bytes = slam_map_carve(nullptr, cm, np, no, &sb.m);
-    o_feat = st.map_bytes; st.map_bytes += (np * 2 * sizeof(int) + 255) & ~(size_t)255;       // pt_feat rides behind the lists: a snapshot takes it along
-    ScratchLayout sc;
-    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.obj, (size_t)cap * 3); sc.take(&cb.img, (size_t)cap * 2);
-    sc.take(&cb.rvec, 3); sc.take(&cb.tvec, 3); sc.take(&cb.P1, 12); sc.take(&cb.P2, 12); sc.take(&cb.Xw, (size_t)cap * 4);
-    sc.take(&st.dK, 9); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&cb.off, 2); sc.take(&cb.pmask, cap); sc.take(&cb.pninl, 1); sc.take(&cb.pstatus, 1);
-    sc.take(&cb.alive, 1); sc.take(&cb.map_count, 1); sc.take(&st.keep, 24);
-    sc.take(&cb.rs.st, restart ? 4 : 0);                              // (the segment state outlives the call, as the alive flag does)
-    sc.take(&st.map_mem, st.map_bytes); sc.take(&st.snap_mem, st.map_bytes);
-    sc.take(&sb.pt_of, fc); sc.take(&sb.dec, cap); sc.take(&sb.tmp, np); sc.take(&sb.idx, no);
-    sc.take(&sb.prob, 1); sc.take(&sb.cam_col, cm); sc.take(&sb.pt_first, np + 1); sc.take(&sb.s_cam, no); sc.take(&sb.s_pt, no); sc.take(&sb.s_xy, no * 2);
-    sc.take(&sb.pairs, npair); sc.take(&sb.blk_first, (size_t)nblk + 1);
-    sc.take(&D.X2, np * 3); sc.take(&D.W, no * 18); sc.take(&D.Hpp, np * 6); sc.take(&D.bp, np * 3); sc.take(&D.Hpi, np * 6);
-    st.stats = ctx->slam_stats != 0;
-    slam_stats_take_scratch(sc, st.sbuf, st.stats, np, no);
-    const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
-    slam_stats_take_rows(sc, st.sbuf, st.stats, P, cm);
-    sc.take(&cb.poses, (P + 1) * 12); sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P);
-    sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P); sc.take(&sb.poses_last, (P + 1) * 12);
-    sc.take(&st.dchi2, 2 * P); sc.take(&st.dit, P); sc.take(&st.dtr, P);
-    sc.take(&sb.st.carried_frame, cm); sc.take(&sb.st.carried_poses, cm * 12);
-    sc.take(&cb.rs.segment, restart ? P : 0); sc.take(&cb.rs.cause, restart ? P : 0);
-    sc.take(&cb.rs.seg_poses, restart ? P * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? P * 12 : 0);
-    HIPCHK(st.mem.alloc(&st.base, sc.bytes));
-    sc.place_at(st.base);
-    st.sbuf.Kd = st.dK;
-    if (!restart) cb.rs = RestartBuf{};
-    st.restart = restart;
-    st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
-    slam_map_carve(st.map_mem, cm, np, no, &sb.m); slam_map_carve(st.snap_mem, cm, np, no, &st.snap);
-    sb.m.pt_feat = reinterpret_cast<int*>(st.map_mem + o_feat); st.snap.pt_feat = reinterpret_cast<int*>(st.snap_mem + o_feat);
-    sb.cam_cap = (int)cm; sb.pt_cap = (int)np; sb.obs_cap = (int)no; sb.pair_cap = (int)npair;
-    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
-    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
-    st.F = F; st.cap = cap; st.max_pairs = max_pairs; st.total = total; st.opts = *o; memcpy(st.K, K, sizeof(st.K));
-    return VO_OK;
-}
-
-// K and every option but the snapshot's are those the stream was started with
-static bool slam_stream_same_setup(const SlamStream& st, const double* K, const vo_slam_opts* o)
-{
-    const vo_slam_opts& a = st.opts;
-    return memcmp(K, st.K, sizeof(st.K)) == 0 && o->pnp_iterations == a.pnp_iterations && o->reproj_err == a.reproj_err && o->confidence == a.confidence &&
-           o->seed == a.seed && o->max_point_norm == a.max_point_norm && o->ba_iterations == a.ba_iterations && o->huber_delta == a.huber_delta &&
-           o->free_cameras == a.free_cameras && o->filter_threshold == a.filter_threshold && o->max_cameras == a.max_cameras;
-}
-
-// The walk of vo_slam_stream and vo_slam_stream_restart.  restart: vo_slam_chains_restart's step for the one chain of the stream —
-// k_chain_gather / k_chain_pose decide (cb.rs is set), k_slam_restart_stream joins every step, step 0 of the stream is an initial
-// step like any other — and the alive flag and the segment state words stay on the device between the calls.  Without it the
-// stream carries vo_slam_stream's launches and nothing else.
-static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
-                           int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
-                           double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                           int32_t* n_carried, int32_t* carried_frame, double* carried_poses,
-                           int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const char* who = restart ? "vo_slam_stream_restart" : "vo_slam_stream";
-    if (!resume) drop_slam_stream(ctx);
-    forget_slam_maps(ctx);
-    if (!K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run ||
-        !n_carried || !carried_frame || !carried_poses) FAIL(VO_ERR_INVALID, "bad arguments");
-    if (restart && (!segment || !cause || !seg_poses_pnp || !seg_poses)) FAIL(VO_ERR_INVALID, "bad arguments");
-    SlamStream& st = ctx->stream_map;
-    if (resume) {
-        if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
-        if (st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by vo_slam_streams and is continued only by it", who);
-        if (st.restart != restart)
-            FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
-        if (st.lost && !restart) FAIL(VO_ERR_INVALID, "vo_slam_stream: the stream's last call ended with a pair that was not localised; it cannot be continued");
-        if (st.touched) FAIL(VO_ERR_INVALID, "%s: slot %d, the stream's last frame, was uploaded to or detected again", who, st.anchor);
-        if (st.stats != (ctx->slam_stats != 0)) FAIL(VO_ERR_INVALID, "%s: the stream was started with statistics %s (vo_set_slam_stats) and is continued only so", who, st.stats ? "on" : "off");
-    }
-    int F, cap;
-    int rc = chain_check(ctx, B, who, &F, &cap); if (rc) return rc;
-    rc = slam_opts_check(ctx, o, K, B, who); if (rc) return rc;
-    const int32_t* sl = ctx->last.slots.data();
-    if (resume) {
-        if (sl[0] != st.anchor) FAIL(VO_ERR_INVALID, "%s: pair 0 starts at slot %d, the stream's last frame is in slot %d", who, sl[0], st.anchor);
-        if (!slam_stream_same_setup(st, K, o)) FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
-        if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "%s: %d + %d pairs pass the stream's total_pairs = %d", who, st.done, B, st.total);
-    } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "%s: total_pairs = %d is less than the call's %d pairs", who, total_pairs, B);
-    HIPCHK(hipSetDevice(ctx->device));
-    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    if (!resume) {
-        rc = slam_stream_allocate(ctx, st, restart, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
-        if (rc) { drop_slam_stream(ctx); return rc; }
-        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));              // empty feature_mapper, empty map, no cameras, zero results
-        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
-    } else HIPCHK(hipMemsetAsync(st.call_mem, 0, st.call_bytes, s));
-    ChainBuf cb = st.cb; SlamBuf sb = st.sb;
-    sb.st.frame0 = resume ? st.done : 0;
-    // (after a call that ended lost the anchor frame is not in the map: every camera of the map is a carried one)
-    sb.st.n_carried = !resume ? 0 : restart && st.lost ? st.last_ncam : st.last_ncam - 1;
-    double* dK = st.dK;
-    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
-    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
-    auto snapshot = [&](int p, int stage) {
-        if (p == o->snapshot_pair && stage == o->snapshot_stage) (void)hipMemcpyAsync(st.snap_mem, st.map_mem, st.map_bytes, hipMemcpyDeviceToDevice, s);
-    };
-    st.live = false;                                                  // (until the call has come through)
-    if (resume) {
-        StageTimer t(ctx, ST_MISC);
-        const int gn = F + (st.carries & 1);
-        const SlamCarry carry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.keep};
-        if (restart) launch_slam_carry_restart(s, carry, cb, sb);
-        else launch_slam_carry(s, carry, cb, sb);
-    }
-    launch_chain_link(s, ctx->pb, cap, B, cb);
-    for (int p = 0; p < B; p++) {
-        {
-            StageTimer t(ctx, ST_MISC);
-            if (restart) {
-                launch_chain_gather(s, ctx->pb, cap, p, F + 2, cb);
-                if (p > 0 || resume) {
-                    launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                      ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
-                    launch_chain_pose(s, ctx->pb, p, dK, cb);
-                }
-                launch_slam_restart_stream(s, ctx->pb, cap, p, cb, sb);
-                if (p > 0 || resume) launch_chain_triangulate(s, ctx->pb, cap, p, cb);
-            }
-            else if (p == 0 && !resume) launch_chain_init(s, ctx->pb, cap, cb);
-            else {
-                launch_chain_gather(s, ctx->pb, cap, p, F + 2, cb);   // (a track may end in a ghost row: two more hops at most)
-                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, 1, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus);
-                launch_chain_pose(s, ctx->pb, p, dK, cb);
-                launch_chain_triangulate(s, ctx->pb, cap, p, cb);
-            }
-            if (restart) launch_slam_add_stream_restart(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
-            else launch_slam_add_stream(s, ctx->pb, cap, p, F + 2, o->max_point_norm, o->free_cameras, cb, sb);
-        }
-        snapshot(p, 1);
-        if (ba) {
-            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare(s, cb, sb); }
-            BaBuf Dp = st.D;
-            Dp.chi2 = st.dchi2 + 2 * p; Dp.iterations_run = st.dit + p; Dp.trials_run = st.dtr + p;
-            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dp, prm, 1, o->free_cameras); }
-        }
-        snapshot(p, 2);
-        const bool step0 = p == 0 && !resume;
-        if (ba || (filt && !step0)) {
-            StageTimer t(ctx, ST_SLAM_FILTER);
-            if (restart) launch_slam_filter_stream_restart(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb);
-            else launch_slam_filter_stream(s, ctx->pb, dK, step0 ? 0.0 : o->filter_threshold, cb, sb);
-        }
-        snapshot(p, 3);
-        {
-            StageTimer t(ctx, ST_SLAM_LIMIT);
-            if (restart) launch_slam_limit_stream_restart(s, p, o->max_cameras, cb, sb);
-            else launch_slam_limit_stream(s, p, o->max_cameras, cb, sb);
-        }
-        snapshot(p, 4);
-        if (st.stats) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats(s, p, sb, st.sbuf); }
-    }
-    HIPCHK(hipGetLastError());
-    // the anchor camera of the next call: this call's last rows
-    HIPCHK(hipMemcpyAsync(st.keep, cb.poses + (size_t)B * 12, 96, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(st.keep + 12, sb.poses_last + (size_t)B * 12, 96, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + 1) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(chi2, st.dchi2, (size_t)B * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ba_iterations_run, st.dit, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(ba_trials_run, st.dtr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    *n_carried = sb.st.n_carried;
-    if (sb.st.n_carried > 0) {
-        HIPCHK(hipMemcpyAsync(carried_frame, sb.st.carried_frame, (size_t)sb.st.n_carried * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(carried_poses, sb.st.carried_poses, (size_t)sb.st.n_carried * 96, hipMemcpyDeviceToHost, s));
-    }
-    int alive = 1;
-    if (restart) {
-        HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&alive, cb.alive, 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (ctx->prof) prof_collect(ctx);
-    rc = slam_map_download(ctx, sb.m, cap, &ctx->last.map[0]); if (rc) return rc;
-    if (o->snapshot_pair >= 0) { rc = slam_map_download(ctx, st.snap, cap, &ctx->last.map[1]); if (rc) return rc; }
-    if (st.stats) { rc = slam_stats_download(ctx, st.sbuf, {0, B}); if (rc) return rc; }
-    // (a restart stream is lost when the device says so: a pair that fails and a pair that restarts can share a call)
-    st.lost = restart && !alive;
-    for (int p = 0; p < B && !restart; p++) if (status[p] != VO_OK) st.lost = true;
-    st.anchor = sl[2 * B - 1]; st.done = (resume ? st.done : 0) + B; st.carries = resume ? st.carries + 1 : 0;
-    st.last_ncam = n_cam[B - 1]; st.touched = false; st.live = true;
-    return VO_OK;
-}
-
-extern "C" int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
-                              int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
-                              double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                              int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
-{
-    return slam_stream_run(ctx, false, resume, total_pairs, B, K, o, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run,
-                           ba_trials_run, n_carried, carried_frame, carried_poses, nullptr, nullptr, nullptr, nullptr);
-}
-
-extern "C" int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
-                                      int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
-                                      double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                                      int32_t* n_carried, int32_t* carried_frame, double* carried_poses,
-                                      int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
-{
-    return slam_stream_run(ctx, true, resume, total_pairs, B, K, o, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run,
-                           ba_trials_run, n_carried, carried_frame, carried_poses, segment, cause, seg_poses_pnp, seg_poses);
-}
-
-// ------------------------------------------------------------------ the map step for S independent sequences in one call
-// vo_slam_chain's walk, every kernel of a step launched once with the sequence on a grid axis (k_*_seqs): the host loop runs over
-// the step j = 0 .. max B_s - 1, a workgroup does step j of its own sequence on pair seq_off[s] + j.  The slot-keyed tables are
-// shared (the sequences' slots are disjoint: checked here); every list is carved once for all sequences and a sequence owns the
-// range its capacities give it — cameras max_cameras + 1, points (B_s + 1) kp_cap, observations 2 B_s kp_cap — so k_bundle_adjust
-// runs the S problems through BaProblem's offsets unchanged and the scratch grows with B, not with S * B.
-static int chains_check(vo_ctx* ctx, int S, const int32_t* seq_off, int* F_out, int* cap_out)
-{
-    const Batch b = batch(ctx);
-    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (S < 1) FAIL(VO_ERR_INVALID, "vo_slam_chains takes at least one sequence, got %d", S);
-    if (seq_off[0] != 0) FAIL(VO_ERR_INVALID, "seq_off[0] must be 0, got %d", seq_off[0]);
-    for (int s = 0; s < S; s++)
-        if (seq_off[s + 1] <= seq_off[s]) FAIL(VO_ERR_INVALID, "seq_off must be strictly increasing: sequence %d has %d pairs", s, seq_off[s + 1] - seq_off[s]);
-    if (ctx->last.pairs < 1 || seq_off[S] != ctx->last.pairs)
-        FAIL(VO_ERR_INVALID, "vo_slam_chains takes all %d pairs of the most recent vo_pairs_run, seq_off ends at %d", ctx->last.pairs, seq_off[S]);
-    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
-    const int F = b.max_frames, cap = b.kp_cap, B = seq_off[S];
-    const int32_t* sl = ctx->last.slots.data();
-    for (int i = 0; i < 2 * B; i++)
-        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
-    std::vector<int> owner((size_t)F, -1);                  // the sequence a slot's frame belongs to
-    for (int s = 0; s < S; s++)
-        for (int p = seq_off[s]; p < seq_off[s + 1]; p++) {
-            const bool head = p == seq_off[s];
-            const int a = sl[2 * p], c = sl[2 * p + 1];
-            const int other = head && owner[(size_t)a] >= 0 ? owner[(size_t)a] : owner[(size_t)c];
-            if (other >= 0 && other != s)
-                FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", other, s, p, a, c);
-            if ((!head && a != sl[2 * p - 1]) || (head && a == c) || owner[(size_t)c] == s)
-                FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue sequence %d as a chain of distinct frames", p, a, c, s);
-            owner[(size_t)a] = s; owner[(size_t)c] = s;
-        }
-    if (F >= (1 << 20) || cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many frames or keypoints for the packed track table");
-    *F_out = F; *cap_out = cap;
-    return VO_OK;
-}
-
-// The walk of vo_slam_chains and vo_slam_chains_restart.  restart: a sequence that loses tracking starts a new map from the next
-// usable pair, decided on the device (k_chain_gather, k_chain_pose) and done by k_slam_restart_seqs, which joins every step;
-// step 0 is then an initial step like any other (k_chain_gather meets a sequence that has no map yet).  Without it the stream
-// carries vo_slam_chains' launches and nothing else.
-static int slam_chains_run(vo_ctx* ctx, bool restart, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
-                           double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
-                           int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                           int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    drop_slam_stream(ctx);
-    forget_slam_maps(ctx);
-    if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run)
-        FAIL(VO_ERR_INVALID, "bad arguments");
-    if (restart && (!segment || !cause || !seg_poses_pnp || !seg_poses)) FAIL(VO_ERR_INVALID, "bad arguments");
-    int F, cap;
-    int rc = chains_check(ctx, S, seq_off, &F, &cap); if (rc) return rc;
-    const bool snap_on = o->snapshot_pair >= 0;        // (snapshot_seq is ignored otherwise)
-    if (snap_on && (snapshot_seq < 0 || snapshot_seq >= S)) FAIL(VO_ERR_INVALID, "snapshot_seq must be a sequence of the call (0 .. %d), got %d", S - 1, snapshot_seq);
-    const int ss = snap_on ? snapshot_seq : 0;
-    const int B = seq_off[S], Bss = seq_off[ss + 1] - seq_off[ss];
-    rc = slam_opts_check(ctx, o, K, Bss, "vo_slam_chains"); if (rc) return rc;
-    int maxB = 0;
-    for (int q = 0; q < S; q++) maxB = std::max(maxB, seq_off[q + 1] - seq_off[q]);
-    const size_t fc = (size_t)F * cap;
-    HIPCHK(hipSetDevice(ctx->device));
-    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    // capacities from the configuration: a pair adds at most one point and two observations per match
-    const size_t cm = (size_t)o->max_cameras + 1, NC = cm * S, NP = (size_t)(B + S) * cap, NO = (size_t)2 * B * cap;
-    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
-    std::vector<size_t> pair0((size_t)S + 1, 0);
-    for (int q = 0; q < S; q++) pair0[q + 1] = pair0[q] + (size_t)2 * (seq_off[q + 1] - seq_off[q]) * cap * (o->free_cameras + 1) / 2;
-    const size_t NPAIR = pair0[S];
-    if (NP >= ((size_t)1 << 31) || NPAIR >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the maps' lists would not fit 32-bit indices");
-    ChainBuf cb{}; SlamBuf sb{}; BaBuf D{}; SlamMap snap{}; double* dK; uint8_t* snap_mem; SlamSeq* dseq;
-    const size_t snap_np = (size_t)(Bss + 1) * cap, snap_no = (size_t)2 * Bss * cap;
-    ScratchLayout sc;
-    // shared, keyed by slot
-    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&sb.pt_of, fc);
-    sc.take(&dK, 9);
-    // per sequence: the current problem and the step's state
-    sc.take(&cb.obj, (size_t)S * cap * 3); sc.take(&cb.img, (size_t)S * cap * 2); sc.take(&cb.Xw, (size_t)S * cap * 4); sc.take(&cb.pmask, (size_t)S * cap);
-    sc.take(&sb.dec, (size_t)S * cap); sc.take(&cb.off, (size_t)2 * S); sc.take(&cb.rvec, (size_t)3 * S); sc.take(&cb.tvec, (size_t)3 * S);
-    sc.take(&cb.pninl, S); sc.take(&cb.pstatus, S); sc.take(&cb.P1, (size_t)12 * S); sc.take(&cb.P2, (size_t)12 * S); sc.take(&cb.alive, S); sc.take(&cb.map_count, S);
-    // per pair, in the run's order; sequence s owns the pose rows seq_off[s] + s .. seq_off[s + 1] + s
-    sc.take(&cb.poses, (size_t)(B + S) * 12); sc.take(&sb.poses_last, (size_t)(B + S) * 12);
-    sc.take(&cb.n_corr, B); sc.take(&cb.n_inl, B); sc.take(&cb.status, B); sc.take(&cb.n_map, B); sc.take(&sb.n_pts, B); sc.take(&sb.n_obs, B); sc.take(&sb.n_cam, B);
-    // the maps' lists and the bundle adjustment's, each carved once: a sequence's range starts at its BaProblem offsets
-    sc.take(&sb.m.cnt, (size_t)4 * S); sc.take(&sb.m.cam_frame, NC); sc.take(&sb.m.cam_pose, NC * 12); sc.take(&sb.m.cam_fixed, NC);
-    sc.take(&sb.m.pt_key, NP); sc.take(&sb.m.pt_xyz, NP * 3); sc.take(&sb.m.obs_cam, NO); sc.take(&sb.m.obs_pt, NO); sc.take(&sb.m.obs_xy, NO * 2);
-    sc.take(&sb.tmp, NP); sc.take(&sb.idx, NO); sc.take(&sb.prob, S); sc.take(&sb.cam_col, NC); sc.take(&sb.pt_first, NP + S);
-    sc.take(&sb.s_cam, NO); sc.take(&sb.s_pt, NO); sc.take(&sb.s_xy, NO * 2); sc.take(&sb.pairs, NPAIR); sc.take(&sb.blk_first, (size_t)S * (nblk + 1));
-    sc.take(&D.X2, NP * 3); sc.take(&D.W, NO * 18); sc.take(&D.Hpp, NP * 6); sc.take(&D.bp, NP * 3); sc.take(&D.Hpi, NP * 6);
-    // k_bundle_adjust writes problem s of step j at [j][s]
-    double* dchi2; int *dit, *dtr;
-    sc.take(&dchi2, (size_t)2 * maxB * S); sc.take(&dit, (size_t)maxB * S); sc.take(&dtr, (size_t)maxB * S);
-    sc.take(&snap_mem, snap_on ? slam_map_carve(nullptr, cm, snap_np, snap_no, &snap) : 0);
-    sc.take(&dseq, S);
-    sc.take(&cb.rs.st, restart ? (size_t)4 * S : 0); sc.take(&cb.rs.segment, restart ? B : 0); sc.take(&cb.rs.cause, restart ? B : 0);
-    sc.take(&cb.rs.seg_poses, restart ? (size_t)B * 12 : 0); sc.take(&cb.rs.seg_poses_last, restart ? (size_t)B * 12 : 0);
-    const bool stats_on = ctx->slam_stats != 0;
-    StatsBuf stats{};
-    slam_stats_take_scratch(sc, stats, stats_on, NP, NO); slam_stats_take_rows(sc, stats, stats_on, B, cm);
-    rc = sc.place(ctx); if (rc) return rc;
-    stats.Kd = dK;
-    if (!restart) cb.rs = RestartBuf{};
-    if (snap_on) slam_map_carve(snap_mem, cm, snap_np, snap_no, &snap);
-    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
-    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
-    std::vector<SlamSeq> seq((size_t)S);
-    for (int q = 0; q < S; q++) {
-        const int first = seq_off[q], Bq = seq_off[q + 1] - first;
-        SlamSeq& e = seq[(size_t)q];
-        e.first = first; e.count = Bq;
-        BaProblem at{};
-        at.cam0 = (int)(cm * q); at.pt0 = (int)((size_t)(first + q) * cap); at.obs0 = (int)((size_t)2 * first * cap); at.pair0 = (int)pair0[q]; at.blk0 = q * (nblk + 1);
-        ChainBuf& c = e.cb; c = cb;
-        c.obj0 = q * cap;                                    // k_pnp_ransac indexes the whole arrays by the sequence's {first, end}
-        c.off += 2 * q; c.rvec += 3 * q; c.tvec += 3 * q; c.pmask += (size_t)q * cap; c.pninl += q; c.pstatus += q; c.P1 += 12 * q; c.P2 += 12 * q;
-        c.obj += (size_t)q * cap * 3; c.img += (size_t)q * cap * 2; c.Xw += (size_t)q * cap * 4; c.alive += q; c.map_count += q;
-        c.n_corr += first; c.n_inl += first; c.status += first; c.n_map += first; c.poses += (size_t)(first + q) * 12;
-        if (restart) { c.rs.st += 4 * q; c.rs.segment += first; c.rs.cause += first; c.rs.seg_poses += (size_t)first * 12; c.rs.seg_poses_last += (size_t)first * 12; }
-        SlamBuf& m = e.sb; m = sb;
-        m.base = at;
-        m.cam_cap = (int)cm; m.pt_cap = (Bq + 1) * cap; m.obs_cap = 2 * Bq * cap; m.pair_cap = (int)(pair0[q + 1] - pair0[q]);
-        m.m.cnt += 4 * q; m.m.cam_frame += at.cam0; m.m.cam_pose += (size_t)at.cam0 * 12; m.m.cam_fixed += at.cam0;
-        m.m.pt_key += at.pt0; m.m.pt_xyz += (size_t)at.pt0 * 3; m.m.obs_cam += at.obs0; m.m.obs_pt += at.obs0; m.m.obs_xy += (size_t)at.obs0 * 2;
-        m.dec += (size_t)q * cap; m.tmp += at.pt0; m.idx += at.obs0; m.n_pts += first; m.n_obs += first; m.n_cam += first; m.poses_last += (size_t)(first + q) * 12;
-        m.prob += q; m.cam_col += at.cam0; m.pt_first += at.pt0 + q; m.s_cam += at.obs0; m.s_pt += at.obs0; m.s_xy += (size_t)at.obs0 * 2;
-        m.pairs += at.pair0; m.blk_first += at.blk0;
-    }
-    HIPCHK(hipMemsetAsync(ctx->scratch.p, 0, sc.bytes, s));          // empty feature_mapper, empty maps, no cameras, zero results
-    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dseq, seq.data(), (size_t)S * sizeof(SlamSeq), hipMemcpyHostToDevice, s));
-    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
-    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
-    const SlamMap live = seq[(size_t)ss].sb.m;
-    auto snapshot = [&](int j, int stage) {                          // the sequence's ranges of the lists: a few device-to-device copies
-        if (!snap_on || j != o->snapshot_pair || stage != o->snapshot_stage) return;
-        auto cp = [&](auto* dst, const auto* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * sizeof(*src), hipMemcpyDeviceToDevice, s); };
-        cp(snap.cnt, live.cnt, 4); cp(snap.cam_frame, live.cam_frame, cm); cp(snap.cam_pose, live.cam_pose, cm * 12); cp(snap.cam_fixed, live.cam_fixed, cm);
-        cp(snap.pt_key, live.pt_key, snap_np); cp(snap.pt_xyz, live.pt_xyz, snap_np * 3);
-        cp(snap.obs_cam, live.obs_cam, snap_no); cp(snap.obs_pt, live.obs_pt, snap_no); cp(snap.obs_xy, live.obs_xy, snap_no * 2);
-    };
-    launch_chain_link(s, ctx->pb, cap, B, cb);
-    for (int j = 0; j < maxB; j++) {
-        {
-            StageTimer t(ctx, ST_MISC);
-            if (restart) {
-                launch_chain_gather_seqs(s, ctx->pb, cap, j, F, dseq, S);
-                if (j > 0) {
-                    launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                      ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
-                    launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
-                }
-                launch_slam_restart_seqs(s, ctx->pb, cap, j, dseq, S);
-                if (j > 0) launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
-            }
-            else if (j == 0) launch_chain_init_seqs(s, ctx->pb, cap, dseq, S);
-            else {
-                launch_chain_gather_seqs(s, ctx->pb, cap, j, F, dseq, S);
-                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
-                launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
-                launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
-            }
-            launch_slam_add_seqs(s, ctx->pb, cap, j, F, o->max_point_norm, o->free_cameras, dseq, S);
-        }
-        snapshot(j, 1);
-        if (ba) {
-            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare_seqs(s, j, dseq, S); }
-            BaBuf Dj = D;
-            Dj.chi2 = dchi2 + (size_t)2 * j * S; Dj.iterations_run = dit + (size_t)j * S; Dj.trials_run = dtr + (size_t)j * S;
-            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dj, prm, S, o->free_cameras); }
-        }
-        snapshot(j, 2);
-        // step 0 ends with optimize_map (:90); what it wrote back still has to reach the tables the next pair reads
-        if (ba || (filt && j > 0)) { StageTimer t(ctx, ST_SLAM_FILTER); launch_slam_filter_seqs(s, ctx->pb, cap, j, dK, j > 0 ? o->filter_threshold : 0.0, dseq, S); }
-        snapshot(j, 3);
-        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_seqs(s, j, o->max_cameras, dseq, S); }
-        snapshot(j, 4);
-        if (stats_on) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats_seqs(s, j, dseq, S, stats); }
-    }
-    HIPCHK(hipGetLastError());
-    std::vector<double> hchi((size_t)2 * maxB * S); std::vector<int32_t> hit((size_t)maxB * S), htr((size_t)maxB * S);
-    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hchi.data(), dchi2, hchi.size() * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hit.data(), dit, hit.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(htr.data(), dtr, htr.size() * 4, hipMemcpyDeviceToHost, s));
-    if (restart) {
-        HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (ctx->prof) prof_collect(ctx);
-    for (int q = 0; q < S; q++)                                       // [step][sequence] -> the pair's position in the run
-        for (int j = 0; j < seq_off[q + 1] - seq_off[q]; j++) {
-            const size_t at = (size_t)j * S + q, p = (size_t)seq_off[q] + j;
-            chi2[2 * p] = hchi[2 * at]; chi2[2 * p + 1] = hchi[2 * at + 1]; ba_iterations_run[p] = hit[at]; ba_trials_run[p] = htr[at];
-        }
-    // the scratch buffer belongs to the next call: the maps are kept as host copies
-    std::vector<LastRun::Map> maps((size_t)S);
-    for (int q = 0; q < S; q++) { rc = slam_map_download(ctx, seq[(size_t)q].sb.m, cap, &maps[(size_t)q], seq_off[q], seq_off[q + 1] - seq_off[q]); if (rc) return rc; }
-    LastRun::Map smap;
-    if (snap_on) { rc = slam_map_download(ctx, snap, cap, &smap, seq_off[ss], Bss); if (rc) return rc; }
-    ctx->last.map[0] = maps[0];                                       // what vo_slam_map reports: sequence 0, and its snapshot if it has one
-    if (snap_on && ss == 0) ctx->last.map[1] = smap;
-    ctx->last.seq_map = std::move(maps);
-    if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
-    if (stats_on) { rc = slam_stats_download(ctx, stats, std::vector<int32_t>(seq_off, seq_off + S + 1)); if (rc) return rc; }
-    return VO_OK;
-}
-
-extern "C" int vo_slam_chains(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
-                              double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
-                              int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run)
-{
-    return slam_chains_run(ctx, false, S, seq_off, K, o, snapshot_seq, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2,
-                           ba_iterations_run, ba_trials_run, nullptr, nullptr, nullptr, nullptr);
-}
-
-extern "C" int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off, const double* K, const vo_slam_opts* o, int snapshot_seq,
-                                      double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs,
-                                      int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                                      int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses)
-{
-    return slam_chains_run(ctx, true, S, seq_off, K, o, snapshot_seq, poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2,
-                           ba_iterations_run, ba_trials_run, segment, cause, seg_poses_pnp, seg_poses);
-}
-
-// ------------------------------------------------------------------ S restart streams in one call, carried from call to call
-// vo_slam_stream_restart's walk with vo_slam_chains_restart's layout: the slot-keyed tables are shared (disjoint slots, and two ghost
-// rows per sequence behind them), every list is carved once for all sequences — a sequence owns the range total_pairs[s] gives it —
-// and the per-pair outputs are laid out per call by seq_off.  One allocation with the stream's lifetime (SlamStream).
-static int slam_streams_allocate(vo_ctx* ctx, SlamStream& st, int S, int F, int cap, int max_pairs, const int32_t* total, const vo_slam_opts* o, const double* K)
-{
-    const size_t R = (size_t)F + 2 * (size_t)S, fc = R * cap, cm = (size_t)o->max_cameras + 1, NC = cm * S, P = (size_t)max_pairs;
-    const int nblk = o->free_cameras * (o->free_cameras + 1) / 2;
-    if (R >= ((size_t)1 << 20)) FAIL(VO_ERR_INVALID, "vo_slam_streams: max_frames + 2 S = %zu rows are too many for the packed track table", R);
-    std::vector<size_t> pt0((size_t)S + 1, 0), ob0((size_t)S + 1, 0), pr0((size_t)S + 1, 0);
-    st.seq.assign((size_t)S, SlamStream::Seq());
-    st.rows.assign((size_t)S * (P + 1), 0);
-    st.snap_np = 0; st.snap_no = 0;
-    for (int q = 0; q < S; q++) {
-        SlamStream::Seq& e = st.seq[(size_t)q];
-        e.total = total[q]; e.capacity = total[q];
-        e.np = ((size_t)total[q] + 1) * cap; e.no = (size_t)2 * cap * std::min(cm, (size_t)total[q]);
-        pt0[q + 1] = pt0[q] + e.np; ob0[q + 1] = ob0[q] + e.no; pr0[q + 1] = pr0[q] + e.no * (o->free_cameras + 1) / 2;
-        st.snap_np = std::max(st.snap_np, e.np); st.snap_no = std::max(st.snap_no, e.no);
-    }
-    const size_t NP = pt0[S], NO = ob0[S], NPAIR = pr0[S];
-    if (NP >= ((size_t)1 << 31) || NPAIR >= ((size_t)1 << 31) || fc >= ((size_t)1 << 31)) FAIL(VO_ERR_INVALID, "the maps' lists would not fit 32-bit indices");
-    ChainBuf& cb = st.cb; SlamBuf& sb = st.sb; BaBuf& D = st.D; SlamMap& snap = st.snap;
-    ScratchLayout sc;
-    // shared, keyed by slot (and ghost row)
-    sc.take(&cb.parent, fc); sc.take(&cb.map_pt, fc * 3); sc.take(&cb.cam, (size_t)F * 12); sc.take(&cb.in_map, fc); sc.take(&cb.cam_ok, F); sc.take(&sb.pt_of, fc);
-    sc.take(&st.dK, 9);
-    // per sequence: the current problem, the step's state, and what outlives a call — alive, the segment state words, the anchor camera
-    sc.take(&cb.obj, (size_t)S * cap * 3); sc.take(&cb.img, (size_t)S * cap * 2); sc.take(&cb.Xw, (size_t)S * cap * 4); sc.take(&cb.pmask, (size_t)S * cap);
-    sc.take(&sb.dec, (size_t)S * cap); sc.take(&cb.off, (size_t)2 * S); sc.take(&cb.rvec, (size_t)3 * S); sc.take(&cb.tvec, (size_t)3 * S);
-    sc.take(&cb.pninl, S); sc.take(&cb.pstatus, S); sc.take(&cb.P1, (size_t)12 * S); sc.take(&cb.P2, (size_t)12 * S); sc.take(&cb.alive, S); sc.take(&cb.map_count, S);
-    sc.take(&cb.rs.st, (size_t)4 * S); sc.take(&st.keep, (size_t)24 * S);
-    // the maps' lists and the bundle adjustment's, each carved once: a sequence's range starts at its BaProblem offsets
-    sc.take(&sb.m.cnt, (size_t)4 * S); sc.take(&sb.m.cam_frame, NC); sc.take(&sb.m.cam_pose, NC * 12); sc.take(&sb.m.cam_fixed, NC);
-    sc.take(&sb.m.pt_key, NP); sc.take(&sb.m.pt_xyz, NP * 3); sc.take(&sb.m.pt_feat, NP * 2);
-    sc.take(&sb.m.obs_cam, NO); sc.take(&sb.m.obs_pt, NO); sc.take(&sb.m.obs_xy, NO * 2);
-    sc.take(&sb.tmp, NP); sc.take(&sb.idx, NO); sc.take(&sb.prob, S); sc.take(&sb.cam_col, NC); sc.take(&sb.pt_first, NP + S);
-    sc.take(&sb.s_cam, NO); sc.take(&sb.s_pt, NO); sc.take(&sb.s_xy, NO * 2); sc.take(&sb.pairs, NPAIR); sc.take(&sb.blk_first, (size_t)S * (nblk + 1));
-    sc.take(&D.X2, NP * 3); sc.take(&D.W, NO * 18); sc.take(&D.Hpp, NP * 6); sc.take(&D.bp, NP * 3); sc.take(&D.Hpi, NP * 6);
-    // the snapshot: room for the largest sequence
-    sc.take(&snap.cnt, 4); sc.take(&snap.cam_frame, cm); sc.take(&snap.cam_pose, cm * 12); sc.take(&snap.cam_fixed, cm);
-    sc.take(&snap.pt_key, st.snap_np); sc.take(&snap.pt_xyz, st.snap_np * 3); sc.take(&snap.pt_feat, st.snap_np * 2);
-    sc.take(&snap.obs_cam, st.snap_no); sc.take(&snap.obs_pt, st.snap_no); sc.take(&snap.obs_xy, st.snap_no * 2);
-    sc.take(&st.dseq, S); sc.take(&st.dcar, S); sc.take(&st.drows, (size_t)S * (P + 1)); sc.take(&st.dseat, S);
-    st.stats = ctx->slam_stats != 0;
-    slam_stats_take_scratch(sc, st.sbuf, st.stats, NP, NO);
-    const size_t call0 = sc.bytes;                                    // from here on: what a call reports, sized for max_pairs pairs
-    slam_stats_take_rows(sc, st.sbuf, st.stats, P, cm);
-    sc.take(&cb.poses, (P + S) * 12); sc.take(&sb.poses_last, (P + S) * 12);
-    sc.take(&cb.n_corr, P); sc.take(&cb.n_inl, P); sc.take(&cb.status, P); sc.take(&cb.n_map, P); sc.take(&sb.n_pts, P); sc.take(&sb.n_obs, P); sc.take(&sb.n_cam, P);
-    sc.take(&st.dchi2, 2 * P * S); sc.take(&st.dit, P * S); sc.take(&st.dtr, P * S);       // k_bundle_adjust writes problem s of step j at [j][s]
-    sc.take(&sb.st.carried_frame, NC); sc.take(&sb.st.carried_poses, NC * 12);
-    sc.take(&cb.rs.segment, P); sc.take(&cb.rs.cause, P); sc.take(&cb.rs.seg_poses, P * 12); sc.take(&cb.rs.seg_poses_last, P * 12);
-    HIPCHK(st.mem.alloc(&st.base, sc.bytes));
-    sc.place_at(st.base);
-    st.sbuf.Kd = st.dK;
-    st.bytes = sc.bytes; st.call_mem = st.base + call0; st.call_bytes = sc.bytes - call0;
-    D.prob = sb.prob; D.poses = sb.m.cam_pose; D.cam_col = sb.cam_col; D.X = sb.m.pt_xyz; D.pt_first = sb.pt_first;
-    D.obs_cam = sb.s_cam; D.obs_pt = sb.s_pt; D.obs_xy = sb.s_xy; D.pairs = sb.pairs; D.blk_first = sb.blk_first;
-    for (int q = 0; q < S; q++) {
-        SlamStream::Seq& e = st.seq[(size_t)q];
-        BaProblem at{};
-        at.cam0 = (int)(cm * q); at.pt0 = (int)pt0[q]; at.obs0 = (int)ob0[q]; at.pair0 = (int)pr0[q]; at.blk0 = q * (nblk + 1);
-        ChainBuf& c = e.at.cb; c = cb;
-        c.obj0 = q * cap;                                    // k_pnp_ransac indexes the whole arrays by the sequence's {first, end}
-        c.off += 2 * q; c.rvec += 3 * q; c.tvec += 3 * q; c.pmask += (size_t)q * cap; c.pninl += q; c.pstatus += q; c.P1 += 12 * q; c.P2 += 12 * q;
-        c.obj += (size_t)q * cap * 3; c.img += (size_t)q * cap * 2; c.Xw += (size_t)q * cap * 4; c.alive += q; c.map_count += q; c.rs.st += 4 * q;
-        SlamBuf& m = e.at.sb; m = sb;
-        m.base = at;
-        m.cam_cap = (int)cm; m.pt_cap = (int)e.np; m.obs_cap = (int)e.no; m.pair_cap = (int)(pr0[q + 1] - pr0[q]);
-        m.m.cnt += 4 * q; m.m.cam_frame += at.cam0; m.m.cam_pose += (size_t)at.cam0 * 12; m.m.cam_fixed += at.cam0;
-        m.m.pt_key += at.pt0; m.m.pt_xyz += (size_t)at.pt0 * 3; m.m.pt_feat += (size_t)at.pt0 * 2;
-        m.m.obs_cam += at.obs0; m.m.obs_pt += at.obs0; m.m.obs_xy += (size_t)at.obs0 * 2;
-        m.dec += (size_t)q * cap; m.tmp += at.pt0; m.idx += at.obs0;
-        m.prob += q; m.cam_col += at.cam0; m.pt_first += at.pt0 + q; m.s_cam += at.obs0; m.s_pt += at.obs0; m.s_xy += (size_t)at.obs0 * 2;
-        m.pairs += at.pair0; m.blk_first += at.blk0;
-        m.st.carried_frame += at.cam0; m.st.carried_poses += (size_t)at.cam0 * 12;
-    }
-    st.restart = true; st.multi = true; st.S = S;
-    st.F = F; st.cap = cap; st.max_pairs = max_pairs; st.opts = *o; memcpy(st.K, K, sizeof(st.K));
-    return VO_OK;
-}
-
-// What vo_slam_streams asks of the most recent vo_pairs_run: vo_slam_chains' checks, and in a resumed call the stream's — a
-// sequence may be idle, one that advances starts at its anchor slot, and no anchor slot is among another sequence's pairs.
-static int streams_check(vo_ctx* ctx, int resume, int S, const int32_t* seq_off, int* F_out, int* cap_out)
-{
-    const SlamStream& st = ctx->stream_map;
-    const Batch b = batch(ctx);
-    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (S < 1) FAIL(VO_ERR_INVALID, "vo_slam_streams takes at least one sequence, got %d", S);
-    if (seq_off[0] != 0) FAIL(VO_ERR_INVALID, "seq_off[0] must be 0, got %d", seq_off[0]);
-    for (int s = 0; s < S; s++) {
-        const int n = seq_off[s + 1] - seq_off[s];
-        if (n < 0 || (n == 0 && !resume))
-            FAIL(VO_ERR_INVALID, "vo_slam_streams: sequence %d has %d pairs (a sequence may be idle, with none, only in a resumed call)", s, n);
-    }
-    if (seq_off[S] < 1) FAIL(VO_ERR_INVALID, "vo_slam_streams: every sequence is idle; at least one must advance");
-    if (seq_off[S] != ctx->last.pairs)
-        FAIL(VO_ERR_INVALID, "vo_slam_streams takes all %d pairs of the most recent vo_pairs_run, seq_off ends at %d", ctx->last.pairs, seq_off[S]);
-    if (!ctx->last.points) FAIL(VO_ERR_INVALID, "the most recent vo_pairs_run did not triangulate (want_points)");
-    const int F = b.max_frames, cap = b.kp_cap, B = seq_off[S];
-    const int32_t* sl = ctx->last.slots.data();
-    for (int i = 0; i < 2 * B; i++)
-        if (sl[i] < 0 || sl[i] >= F) FAIL(VO_ERR_INVALID, "pair slot %d of the most recent vo_pairs_run is out of range", sl[i]);
-    std::vector<int> owner((size_t)F, -1);                  // the sequence a slot's frame belongs to: first of all the anchors
-    if (resume) for (int s = 0; s < S; s++) if (!st.seq[(size_t)s].vacant) owner[(size_t)st.seq[(size_t)s].anchor] = s;   // (a vacant seat has none)
-    for (int s = 0; s < S; s++)
-        for (int p = seq_off[s]; p < seq_off[s + 1]; p++) {
-            const bool head = p == seq_off[s];
-            const int a = sl[2 * p], c = sl[2 * p + 1];
-            if (head && resume && !st.seq[(size_t)s].vacant) {
-                const SlamStream::Seq& e = st.seq[(size_t)s];
-                if (a != e.anchor) FAIL(VO_ERR_INVALID, "vo_slam_streams: pair 0 of sequence %d starts at slot %d, the sequence's last frame is in slot %d", s, a, e.anchor);
-                if (e.touched) FAIL(VO_ERR_INVALID, "vo_slam_streams: slot %d, the last frame of sequence %d, was uploaded to or detected again", e.anchor, s);
-            } else if (head) {                                  // a stream's pair 0, or a new flight's in a vacant seat: any slot nobody holds
-                if (owner[(size_t)a] >= 0)
-                    FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", owner[(size_t)a], s, p, a, c);
-                owner[(size_t)a] = s;
-            }
-            if ((!head && a != sl[2 * p - 1]) || owner[(size_t)c] == s)
-                FAIL(VO_ERR_INVALID, "pair %d (%d, %d) does not continue sequence %d as a chain of distinct frames", p, a, c, s);
-            if (owner[(size_t)c] >= 0)
-                FAIL(VO_ERR_INVALID, "sequences %d and %d share a frame slot (pair %d (%d, %d)): a frame two sequences share is uploaded into two slots", owner[(size_t)c], s, p, a, c);
-            owner[(size_t)c] = s;
-        }
-    if (cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many keypoints for the packed track table");
-    *F_out = F; *cap_out = cap;
-    return VO_OK;
-}
-
-extern "C" int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs, const int32_t* seq_off, const double* K, const vo_slam_opts* o,
-                               int snapshot_seq, double* poses_pnp, double* poses, int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts,
-                               int32_t* n_obs, int32_t* n_cam, double* chi2, int32_t* ba_iterations_run, int32_t* ba_trials_run,
-                               int32_t* segment, int32_t* cause, double* seg_poses_pnp, double* seg_poses,
-                               int32_t* n_carried, int32_t* carried_frame, double* carried_poses)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const char* who = "vo_slam_streams";
-    if (!resume) drop_slam_stream(ctx);
-    forget_slam_maps(ctx);
-    if (!seq_off || !K || !o || !poses_pnp || !poses || !n_corr || !n_inl || !status || !n_pts || !n_obs || !n_cam || !chi2 || !ba_iterations_run || !ba_trials_run ||
-        !segment || !cause || !seg_poses_pnp || !seg_poses || !n_carried || !carried_frame || !carried_poses || (!resume && !total_pairs))
-        FAIL(VO_ERR_INVALID, "bad arguments");
-    SlamStream& st = ctx->stream_map;
-    if (resume) {
-        if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream to continue (none was started, or a configure or vo_slam_chain* call dropped it)", who);
-        if (!st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by %s and is continued only by it", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
-        if (S != st.S) FAIL(VO_ERR_INVALID, "%s: the stream has %d sequences, the call names %d", who, st.S, S);
-        if (st.stats != (ctx->slam_stats != 0)) FAIL(VO_ERR_INVALID, "%s: the stream was started with statistics %s (vo_set_slam_stats) and is continued only so", who, st.stats ? "on" : "off");
-    }
-    int F, cap;
-    int rc = streams_check(ctx, resume, S, seq_off, &F, &cap); if (rc) return rc;
-    const bool snap_on = o->snapshot_pair >= 0;        // (snapshot_seq is ignored otherwise)
-    if (snap_on && (snapshot_seq < 0 || snapshot_seq >= S)) FAIL(VO_ERR_INVALID, "snapshot_seq must be a sequence of the call (0 .. %d), got %d", S - 1, snapshot_seq);
-    const int ss = snap_on ? snapshot_seq : 0;
-    const int B = seq_off[S];
-    rc = slam_opts_check(ctx, o, K, snap_on ? seq_off[ss + 1] - seq_off[ss] : 1, who); if (rc) return rc;
-    int maxB = 0;
-    for (int q = 0; q < S; q++) {
-        const int Bq = seq_off[q + 1] - seq_off[q];
-        maxB = std::max(maxB, Bq);
-        if (resume) {
-            const SlamStream::Seq& e = st.seq[(size_t)q];
-            if ((int64_t)e.done + Bq > e.total) FAIL(VO_ERR_INVALID, "%s: sequence %d: %d + %d pairs pass its total_pairs = %d", who, q, e.done, Bq, e.total);
-        } else if (total_pairs[q] < Bq) FAIL(VO_ERR_INVALID, "%s: total_pairs[%d] = %d is less than the sequence's %d pairs in this call", who, q, total_pairs[q], Bq);
-    }
-    if (resume && !slam_stream_same_setup(st, K, o))
-        FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
-    HIPCHK(hipSetDevice(ctx->device));
-    rc = ensure_rng(ctx, o->seed); if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    const int max_pairs = batch(ctx).max_pairs;
-    if (!resume) {
-        rc = slam_streams_allocate(ctx, st, S, F, cap, max_pairs, total_pairs, o, K);
-        if (rc) { drop_slam_stream(ctx); return rc; }
-        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));              // empty feature_mapper, empty maps, no cameras, zero results
-        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
-    } else HIPCHK(hipMemsetAsync(st.call_mem, 0, st.call_bytes, s));
-    const ChainBuf& cb = st.cb; const SlamBuf& sb = st.sb;
-    const size_t cm = (size_t)o->max_cameras + 1, row_cap = (size_t)max_pairs + 1;
-    const int R = F + 2 * S, gpar = st.carries & 1;
-    // the descriptors of this call: a sequence's ranges of the lists, and its rows of the call's outputs
-    std::vector<SlamSeq> seq((size_t)S); std::vector<SlamSeqCarry> car((size_t)S); std::vector<int32_t> hrows(st.rows);
-    std::vector<SlamSeat> seat((size_t)S);
-    bool seats = false;                                               // some seat is vacant: the carry launch is the seats form
-    for (int q = 0; q < S; q++) {
-        const SlamStream::Seq& h = st.seq[(size_t)q];
-        const int first = seq_off[q];
-        SlamSeq& e = seq[(size_t)q]; e = h.at;
-        e.first = first; e.count = seq_off[q + 1] - first;
-        ChainBuf& c = e.cb;
-        c.n_corr += first; c.n_inl += first; c.status += first; c.n_map += first; c.poses += (size_t)(first + q) * 12;
-        c.rs.segment += first; c.rs.cause += first; c.rs.seg_poses += (size_t)first * 12; c.rs.seg_poses_last += (size_t)first * 12;
-        SlamBuf& m = e.sb;
-        m.n_pts += first; m.n_obs += first; m.n_cam += first; m.poses_last += (size_t)(first + q) * 12;
-        m.st.frame0 = resume ? h.done : 0;
-        // (after a call that ended lost the anchor frame is not in the map: every camera of the map is a carried one)
-        m.st.n_carried = !resume ? 0 : h.lost ? h.last_ncam : h.last_ncam - 1;
-        SlamSeqCarry& k = car[(size_t)q];
-        const int gn = F + 2 * q + gpar, go = F + 2 * q + 1 - gpar;
-        k.c = SlamCarry{cap, F, h.anchor, gn, go, st.keep + (size_t)24 * q};
-        k.hops = R; k.rows = st.drows + (size_t)q * row_cap;
-        hrows[(size_t)q * row_cap + h.n_rows] = go; k.n_rows = h.n_rows + 1;
-        // seats: a vacant seat is not carried.  One replaced since the last call is reset — it gives up the slots of its last call's
-        // frames (k.rows without the ghost row above), its old anchor row and both ghost rows; one already reset is left alone.
-        SlamSeat& t = seat[(size_t)q];
-        t = SlamSeat{SEAT_CARRY, 0, {0, 0, 0}, st.keep + (size_t)24 * q};
-        if (resume && h.vacant) {
-            seats = true;
-            t.mode = h.clean ? SEAT_VACANT : SEAT_RESET;
-            k.n_rows = h.n_rows;
-            if (h.old_anchor >= 0) t.rows[t.n_rows++] = h.old_anchor;
-            t.rows[t.n_rows++] = gn; t.rows[t.n_rows++] = go;
-        }
-    }
-    HIPCHK(hipMemcpyAsync(st.dseq, seq.data(), (size_t)S * sizeof(SlamSeq), hipMemcpyHostToDevice, s));
-    const BaParams prm{K[0], K[2], K[5], o->huber_delta, o->ba_iterations};
-    const bool ba = o->ba_iterations > 0, filt = o->filter_threshold > 0;
-    const SlamMap live = seq[(size_t)ss].sb.m, snap = st.snap;
-    const size_t snap_np = st.seq[(size_t)ss].np, snap_no = st.seq[(size_t)ss].no;
-    auto snapshot = [&](int j, int stage) {                          // the sequence's ranges of the lists: a few device-to-device copies
-        if (!snap_on || j != o->snapshot_pair || stage != o->snapshot_stage) return;
-        auto cp = [&](auto* dst, const auto* src, size_t n) { (void)hipMemcpyAsync(dst, src, n * sizeof(*src), hipMemcpyDeviceToDevice, s); };
-        cp(snap.cnt, live.cnt, 4); cp(snap.cam_frame, live.cam_frame, cm); cp(snap.cam_pose, live.cam_pose, cm * 12); cp(snap.cam_fixed, live.cam_fixed, cm);
-        cp(snap.pt_key, live.pt_key, snap_np); cp(snap.pt_xyz, live.pt_xyz, snap_np * 3); cp(snap.pt_feat, live.pt_feat, snap_np * 2);
-        cp(snap.obs_cam, live.obs_cam, snap_no); cp(snap.obs_pt, live.obs_pt, snap_no); cp(snap.obs_xy, live.obs_xy, snap_no * 2);
-    };
-    st.live = false;                                                  // (until the call has come through)
-    SlamSeq* dseq = st.dseq; double* dK = st.dK;
-    if (resume) {
-        HIPCHK(hipMemcpyAsync(st.dcar, car.data(), (size_t)S * sizeof(SlamSeqCarry), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(st.drows, hrows.data(), hrows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (seats) HIPCHK(hipMemcpyAsync(st.dseat, seat.data(), (size_t)S * sizeof(SlamSeat), hipMemcpyHostToDevice, s));
-        StageTimer t(ctx, ST_MISC);
-        if (seats) launch_slam_carry_restart_seats(s, dseq, st.dcar, st.dseat, S);
-        else launch_slam_carry_restart_seqs(s, dseq, st.dcar, S);
-    }
-    launch_chain_link(s, ctx->pb, cap, B, cb);
-    for (int j = 0; j < maxB; j++) {
-        const bool step0 = j == 0 && !resume;
-        {
-            StageTimer t(ctx, ST_MISC);
-            launch_chain_gather_seqs(s, ctx->pb, cap, j, R, dseq, S);  // (a track may end in a ghost row)
-            if (!step0) {
-                launch_pnp_ransac(s, cb.obj, cb.img, cb.off, S, dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
-                                  ctx->pnp_refine, cb.rvec, cb.tvec, cb.pmask, cb.pninl, cb.pstatus, 2);
-                launch_chain_pose_seqs(s, ctx->pb, j, dK, dseq, S);
-            }
-            launch_slam_restart_stream_seqs(s, ctx->pb, cap, j, dseq, S);
-            if (!step0) launch_chain_triangulate_seqs(s, ctx->pb, cap, j, dseq, S);
-            launch_slam_add_stream_restart_seqs(s, ctx->pb, cap, j, R, o->max_point_norm, o->free_cameras, dseq, S);
-        }
-        snapshot(j, 1);
-        if (ba) {
-            { StageTimer t(ctx, ST_SLAM_PREPARE); launch_slam_ba_prepare_seqs(s, j, dseq, S); }
-            BaBuf Dj = st.D;
-            Dj.chi2 = st.dchi2 + (size_t)2 * j * S; Dj.iterations_run = st.dit + (size_t)j * S; Dj.trials_run = st.dtr + (size_t)j * S;
-            { StageTimer t(ctx, ST_SLAM_BA); launch_bundle_adjust(s, Dj, prm, S, o->free_cameras); }
-        }
-        snapshot(j, 2);
-        if (ba || (filt && !step0)) {
-            StageTimer t(ctx, ST_SLAM_FILTER);
-            launch_slam_filter_stream_restart_seqs(s, ctx->pb, cap, j, dK, step0 ? 0.0 : o->filter_threshold, dseq, S);
-        }
-        snapshot(j, 3);
-        { StageTimer t(ctx, ST_SLAM_LIMIT); launch_slam_limit_stream_restart_seqs(s, j, o->max_cameras, dseq, S); }
-        snapshot(j, 4);
-        if (st.stats) { StageTimer t(ctx, ST_SLAM_STATS); launch_slam_stats_seqs(s, j, dseq, S, st.sbuf); }
-    }
-    HIPCHK(hipGetLastError());
-    // the anchor camera of a sequence's next call: its last rows of this call (an idle sequence keeps the one it has)
-    for (int q = 0; q < S; q++) {
-        const int Bq = seq[(size_t)q].count;
-        if (Bq == 0) continue;
-        HIPCHK(hipMemcpyAsync(st.keep + (size_t)24 * q, seq[(size_t)q].cb.poses + (size_t)Bq * 12, 96, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(st.keep + (size_t)24 * q + 12, seq[(size_t)q].sb.poses_last + (size_t)Bq * 12, 96, hipMemcpyDeviceToDevice, s));
-    }
-    std::vector<double> hchi((size_t)2 * maxB * S); std::vector<int32_t> hit((size_t)maxB * S), htr((size_t)maxB * S), alive((size_t)S, 1);
-    HIPCHK(hipMemcpyAsync(poses_pnp, cb.poses, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(poses, sb.poses_last, (size_t)(B + S) * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_corr, cb.n_corr, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_inl, cb.n_inl, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, cb.status, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_pts, sb.n_pts, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_obs, sb.n_obs, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(n_cam, sb.n_cam, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hchi.data(), st.dchi2, hchi.size() * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hit.data(), st.dit, hit.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(htr.data(), st.dtr, htr.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(segment, cb.rs.segment, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(cause, cb.rs.cause, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(seg_poses_pnp, cb.rs.seg_poses, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(seg_poses, cb.rs.seg_poses_last, (size_t)B * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(alive.data(), cb.alive, (size_t)S * 4, hipMemcpyDeviceToHost, s));
-    for (int q = 0; q < S; q++) {
-        const int n = seq[(size_t)q].count > 0 ? seq[(size_t)q].sb.st.n_carried : 0;
-        n_carried[q] = n;
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync(carried_frame + (size_t)q * o->max_cameras, seq[(size_t)q].sb.st.carried_frame, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(carried_poses + (size_t)q * o->max_cameras * 12, seq[(size_t)q].sb.st.carried_poses, (size_t)n * 96, hipMemcpyDeviceToHost, s));
-        }
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (ctx->prof) prof_collect(ctx);
-    for (int q = 0; q < S; q++)                                       // [step][sequence] -> the pair's position in the run
-        for (int j = 0; j < seq[(size_t)q].count; j++) {
-            const size_t at = (size_t)j * S + q, p = (size_t)seq_off[q] + j;
-            chi2[2 * p] = hchi[2 * at]; chi2[2 * p + 1] = hchi[2 * at + 1]; ba_iterations_run[p] = hit[at]; ba_trials_run[p] = htr[at];
-        }
-    // host copies of every sequence's map, an idle one's too: vo_pairs_run forgot the ones of the call before
-    std::vector<LastRun::Map> maps((size_t)S);
-    for (int q = 0; q < S; q++) { rc = slam_map_download(ctx, seq[(size_t)q].sb.m, cap, &maps[(size_t)q]); if (rc) return rc; }
-    LastRun::Map smap;
-    if (snap_on) { rc = slam_map_download(ctx, snap, cap, &smap); if (rc) return rc; }
-    ctx->last.map[0] = maps[0];                                       // what vo_slam_map reports: sequence 0, and its snapshot if it has one
-    if (snap_on && ss == 0) ctx->last.map[1] = smap;
-    ctx->last.seq_map = std::move(maps);
-    if (snap_on) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = ss; }
-    if (st.stats) { rc = slam_stats_download(ctx, st.sbuf, std::vector<int32_t>(seq_off, seq_off + S + 1)); if (rc) return rc; }
-    // the stream's state for the next call.  A sequence that advanced gives back every slot but its new anchor's; an idle one has
-    // given back all it had at this call's carry.
-    const int32_t* sl = ctx->last.slots.data();
-    for (int q = 0; q < S; q++) {
-        SlamStream::Seq& h = st.seq[(size_t)q];
-        const int first = seq_off[q], Bq = seq[(size_t)q].count;
-        h.n_rows = 0;
-        if (resume && h.vacant) { h.clean = true; h.old_anchor = -1; }    // (reset at this call's carry, if it had not been)
-        if (Bq == 0) continue;
-        h.vacant = false;                                             // a flight has taken the seat
-        int32_t* rows = st.rows.data() + (size_t)q * row_cap;
-        rows[h.n_rows++] = sl[2 * first];
-        for (int j = 0; j + 1 < Bq; j++) rows[h.n_rows++] = sl[2 * (first + j) + 1];
-        h.anchor = sl[2 * (first + Bq) - 1]; h.done = (resume ? h.done : 0) + Bq; h.last_ncam = n_cam[first + Bq - 1];
-        h.lost = !alive[(size_t)q]; h.touched = false;
-    }
-    st.carries = resume ? st.carries + 1 : 0;
-    st.live = true;
-    return VO_OK;
-}
-
-// A multi-stream of S vacant seats: what vo_slam_streams(resume = 0) does before its walk, and no walk.  Every seat is as the memset
-// leaves it — the state a stream's first call starts from — so no seat needs a reset; the flights arrive in resumed calls.
-extern "C" int vo_slam_streams_open(vo_ctx* ctx, int S, const int32_t* total_pairs, const double* K, const vo_slam_opts* o)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const char* who = "vo_slam_streams_open";
-    drop_slam_stream(ctx);
-    forget_slam_maps(ctx);
-    if (!total_pairs || !K || !o) FAIL(VO_ERR_INVALID, "bad arguments");
-    const Batch b = batch(ctx);
-    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
-    if (S < 1) FAIL(VO_ERR_INVALID, "%s takes at least one seat, got %d", who, S);
-    for (int q = 0; q < S; q++)
-        if (total_pairs[q] < 1) FAIL(VO_ERR_INVALID, "%s: total_pairs[%d] = %d: a seat holds flights of at least one pair", who, q, total_pairs[q]);
-    if (b.kp_cap >= (1 << 20)) FAIL(VO_ERR_INVALID, "too many keypoints for the packed track table");
-    int rc = slam_opts_check_values(ctx, o, K); if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    SlamStream& st = ctx->stream_map;
-    rc = slam_streams_allocate(ctx, st, S, b.max_frames, b.kp_cap, b.max_pairs, total_pairs, o, K);
-    if (rc) { drop_slam_stream(ctx); return rc; }
-    rc = [&]() -> int {
-        HIPCHK(hipMemsetAsync(st.base, 0, st.bytes, s));
-        HIPCHK(hipMemcpyAsync(st.dK, K, 72, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return VO_OK;
-    }();
-    if (rc) { drop_slam_stream(ctx); return rc; }
-    for (SlamStream::Seq& h : st.seq) { h.vacant = true; h.clean = true; h.lost = true; }
-    st.carries = 0;
-    st.live = true;
-    return VO_OK;
-}
-
-// The flight of seat `seq` is over.  Host only: the seat gives its anchor slot back at once and is reset on the device by the carry
-// launch of the next call (k_slam_carry_restart_seats), whether a new flight takes it in that call or later.
-extern "C" int vo_slam_streams_replace(vo_ctx* ctx, int seq, int total_pairs)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const char* who = "vo_slam_streams_replace";
-    SlamStream& st = ctx->stream_map;
-    if (!st.live) FAIL(VO_ERR_INVALID, "%s: there is no stream (none was started, or a configure or vo_slam_chain* call dropped it)", who);
-    if (!st.multi) FAIL(VO_ERR_INVALID, "%s: the stream was started by %s, which has no seats", who, st.restart ? "vo_slam_stream_restart" : "vo_slam_stream");
-    if (seq < 0 || seq >= st.S) FAIL(VO_ERR_INVALID, "%s: the stream has seats 0 .. %d, got %d", who, st.S - 1, seq);
-    SlamStream::Seq& h = st.seq[(size_t)seq];
-    if (total_pairs < 1 || total_pairs > h.capacity)
-        FAIL(VO_ERR_INVALID, "%s: seat %d holds flights of 1 .. %d pairs (what its lists were sized for), got %d", who, seq, h.capacity, total_pairs);
-    h.total = total_pairs;
-    if (h.vacant) return VO_OK;                                       // (only the bound of the flight to come)
-    h.vacant = true; h.clean = false;
-    h.old_anchor = h.anchor; h.anchor = -1;
-    h.done = 0; h.last_ncam = 0; h.lost = true; h.touched = false;
-    return VO_OK;
-}
-
-static const LastRun::Map* slam_chains_map_of(vo_ctx* ctx, int seq, int which)
-{
-    const LastRun& l = ctx->last;
-    const char* why = nullptr;
-    if (which < 0 || which > 1) why = "which must be 0 (the map at the end of the sequence) or 1 (the snapshot)";
-    else if (l.seq_map.empty()) why = "no such map: vo_slam_chains has not run since the last configure / vo_pairs_run / chain call";
-    else if (seq < 0 || seq >= (int)l.seq_map.size()) why = "no such sequence in the most recent vo_slam_chains";
-    else if (which == 1 && seq != l.snap_seq) why = "no such map: the most recent vo_slam_chains took no snapshot of this sequence";
-    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); return nullptr; }
-    return which == 1 ? &l.snap_map : &l.seq_map[(size_t)seq];
-}
-
-extern "C" int vo_slam_chains_map_size(vo_ctx* ctx, int seq, int which, int32_t* ncam, int32_t* npt, int32_t* nobs)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    if (!ncam || !npt || !nobs) FAIL(VO_ERR_INVALID, "bad arguments");
-    const LastRun::Map* m = slam_chains_map_of(ctx, seq, which);
-    if (!m) return VO_ERR_INVALID;
-    *ncam = (int32_t)m->cam_frame.size(); *npt = (int32_t)(m->points.size() / 3); *nobs = (int32_t)m->obs_cam.size();
-    return VO_OK;
-}
-
-extern "C" int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, double* cam_pose, uint8_t* cam_fixed, int32_t* pt_feature,
-                                  double* points, int32_t* obs_cam, int32_t* obs_pt, double* obs_xy)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const LastRun::Map* m = slam_chains_map_of(ctx, seq, which);
-    if (!m) return VO_ERR_INVALID;
-    return slam_map_copy_out(ctx, m, cam_frame, cam_pose, cam_fixed, pt_feature, points, obs_cam, obs_pt, obs_xy);
-}
-
-// the statistics rows of sequence seq of the most recent vo_slam_* call, nullptr (and the reason in ctx->err) if there are none
-static const LastRun::Stats* slam_stats_of(vo_ctx* ctx, int seq)
-{
-    const LastRun::Stats& h = ctx->last.stats;
-    const char* why = nullptr;
-    if (!h.valid) why = "no statistics: no vo_slam_* call has run with vo_set_slam_stats on since the last configure / vo_pairs_run / chain call";
-    else if (seq < 0 || seq + 1 >= (int)h.seq_off.size()) why = "no such sequence in the most recent vo_slam_* call";
-    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); return nullptr; }
-    return &h;
-}
-
-extern "C" int vo_slam_stats_size(vo_ctx* ctx, int seq, int32_t* B, int32_t* max_cameras)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    if (!B || !max_cameras) FAIL(VO_ERR_INVALID, "bad arguments");
-    const LastRun::Stats* h = slam_stats_of(ctx, seq);
-    if (!h) return VO_ERR_INVALID;
-    *B = h->seq_off[(size_t)seq + 1] - h->seq_off[(size_t)seq]; *max_cameras = h->C - 1;
-    return VO_OK;
-}
-
-extern "C" int vo_slam_stats_counts(vo_ctx* ctx, int seq, int B, int32_t* n_cam, int32_t* n_pts, int32_t* n_obs)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const LastRun::Stats* h = slam_stats_of(ctx, seq);
-    if (!h) return VO_ERR_INVALID;
-    const int first = h->seq_off[(size_t)seq], n = h->seq_off[(size_t)seq + 1] - first;
-    if (B != n) FAIL(VO_ERR_INVALID, "sequence %d had %d pairs in the call, B = %d", seq, n, B);
-    if (B > 0 && (!n_cam || !n_pts || !n_obs)) FAIL(VO_ERR_INVALID, "bad arguments");
-    for (int p = 0; p < B; p++) {
-        const int32_t* c = h->counts.data() + 3 * ((size_t)first + p);
-        n_cam[p] = c[0]; n_pts[p] = c[1]; n_obs[p] = c[2];
-    }
-    return VO_OK;
-}
-
-extern "C" int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr, double* max_sqerr, int32_t* n_high, int32_t* obs_hist,
-                             int32_t* obs_matrix, int32_t* cam_frame)
-{
-    if (!ctx) return VO_ERR_INVALID;
-    const LastRun::Stats* h = slam_stats_of(ctx, seq);
-    if (!h) return VO_ERR_INVALID;
-    const int first = h->seq_off[(size_t)seq], n = h->seq_off[(size_t)seq + 1] - first, hc = h->C;
-    if (B != n) FAIL(VO_ERR_INVALID, "sequence %d had %d pairs in the call, B = %d", seq, n, B);
-    if (C < hc - 1) FAIL(VO_ERR_INVALID, "C = %d is less than the call's max_cameras = %d", C, hc - 1);
-    if (B > 0 && (!total_sqerr || !max_sqerr || !n_high || !obs_hist || !obs_matrix || !cam_frame)) FAIL(VO_ERR_INVALID, "bad arguments");
-    // (a row holds max_cameras + 1 cameras, the map after the limit at most max_cameras: the last row and column are empty)
-    const int k = std::min(C, hc);
-    for (int p = 0; p < B; p++) {
-        const size_t r = (size_t)first + p;
-        total_sqerr[p] = h->total_sqerr[r]; max_sqerr[p] = h->max_sqerr[r]; n_high[p] = h->n_high[r];
-        memcpy(obs_hist + (size_t)p * VO_STATS_HIST, h->obs_hist.data() + r * VO_STATS_HIST, VO_STATS_HIST * sizeof(int32_t));
-        for (int a = 0; a < C; a++) {
-            cam_frame[(size_t)p * C + a] = a < k ? h->cam_frame[r * hc + a] : -1;
-            for (int b = 0; b < C; b++) obs_matrix[((size_t)p * C + a) * C + b] = a < k && b < k ? h->obs_matrix[(r * hc + a) * hc + b] : 0;
-        }
-    }
     return VO_OK;
 }
 

@@ -297,7 +297,7 @@ struct ChainBuf {
     int*     n_corr; int* n_inl; int* status; int* n_map;   // [P] per-pair outputs
     double*  poses;               // [P + 1][12]: camera of pair 0's first frame, then of every pair's second frame
     int*     map_count;           // [1]
-    RestartBuf rs;                // vo_slam_chains_restart only
+    RestartBuf rs;                // set with SlamDims::restart (slam_layout.h), all nullptr without it
 };
 void launch_chain_link(hipStream_t s, PairBuf pb, int kp_cap, int P, ChainBuf cb);
 void launch_chain_init(hipStream_t s, PairBuf pb, int kp_cap, ChainBuf cb);
@@ -337,9 +337,9 @@ struct SlamMap {
     double*  pt_xyz;                    // [points][3]
     int*     obs_cam; int* obs_pt;      // [observations] indices into the two lists above
     double*  obs_xy;                    // [observations][2]
-    int*     pt_feat;                   // vo_slam_stream only (nullptr elsewhere): [points][2] the owning feature id as (frame along the stream, keypoint)
+    int*     pt_feat;                   // set with SlamDims::stream (nullptr without it): [points][2] the owning feature id as (frame along the stream, keypoint)
 };
-// vo_slam_stream: what a call that continues a map needs beside the lists.  All zero / nullptr in every other entry.
+// A stream (SlamDims::stream): what a call that continues a map needs beside the lists.  All zero / nullptr without the switch.
 struct StreamBuf {
     int      frame0;                    // index along the stream of the call's first frame (0: the call that starts the stream)
     int      n_carried;                 // cameras the map held at the carry beside the anchor: they have no slot in this call
@@ -358,7 +358,7 @@ struct SlamBuf {
     // what k_slam_ba_prepare hands k_bundle_adjust (BaBuf's const members)
     BaProblem* prob; int* cam_col; int* pt_first; int* s_cam; int* s_pt; double* s_xy; int2* pairs; int* blk_first;
     BaProblem base;                     // where this map's lists start in the arrays BaBuf names: cam0 .. blk0 (all 0 for a single chain)
-    StreamBuf st;                       // vo_slam_stream only
+    StreamBuf st;                       // set with SlamDims::stream
 };
 void launch_slam_add(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, double max_norm, int free_cameras, ChainBuf cb, SlamBuf sb);
 void launch_slam_ba_prepare(hipStream_t s, ChainBuf cb, SlamBuf sb);
