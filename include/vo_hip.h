@@ -160,6 +160,35 @@ int vo_recover_pose(vo_ctx* ctx, const double* E, const double* p1, const double
 int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, const double* x1, const double* x2,
                    int M, double* X);
 
+/* cv2.computeCorrespondEpilines(points, whichImage, F) — src/feature_detection.py:118-125.  OpenCV 4.7's behaviour, restated
+ * from its source as remembered; parity with a cv2 build is unpinned, like the rest of this library.
+ * points: N x 2 of point_type 0 (f64), 1 (f32) or 2 (i32); F: 9 doubles, used as given for which_image 1 and transposed for 2.
+ * Per point, in f64, left to right, one rounding per operation: a = f0 x + f1 y + f2, b = f3 x + f4 y + f5,
+ * c = f6 x + f7 y + f8; nu = a a + b b; nu = nu ? 1 / sqrt(nu) : 1; line = (a nu, b nu, c nu).
+ * lines: N x 3 of depth max(input depth, f32): f64 for f64 points, f32 (each value cast once at the end) for f32 and i32
+ * points.  N = 0 is legal.  Three-column (homogeneous) points are not built. */
+int vo_correspond_epilines(vo_ctx* ctx, const void* points, int N, int point_type, int which_image, const double* F, void* lines);
+
+/* The symmetric epipolar distances of src/feature_detection.py:127-140 and their statistics for the B pairs the most recent
+ * vo_pairs_run left on the device (res[p].E and the pixel inliers), one workgroup per pair, no host round trip.
+ *   F = K^-T E K^-1, with K^-1 as the pair path normalises pixels: ifx = 1 / K[0], ify = 1 / K[4], bx = -K[2] ifx,
+ *   by = -K[5] ify; G = E K^-1 (G[r][2] = E[r][0] bx + E[r][1] by + E[r][2]); F = K^-T G (F[2][c] = bx G[0][c] + by G[1][c]
+ *   + G[2][c]).  K must be [fx 0 cx; 0 fy cy; 0 0 1] with finite entries and fx, fy != 0: skew, another last row or a zero
+ *   focal length is VO_ERR_UNSUPPORTED (the pair path reads only those four entries).
+ *   [deviation] The reference script passes its ESSENTIAL matrix together with PIXEL points to computeCorrespondEpilines,
+ *   which measures nothing; here the lines are those of the pixel fundamental matrix, so the distances are in pixels.
+ *   Per E inlier k, in match order: d_k = |l1_k . (x2_k, 1)| + |l2_k . (x1_k, 1)|, l1 = epiline of x1 in image 2
+ *   (which_image 1), l2 = epiline of x2 in image 1 (which_image 2), normalised as vo_correspond_epilines does, each dot
+ *   product as l0 x + l1 y + l2.
+ *   mean[p], std[p] (population, two passes, as np.std) and max[p] are SEQUENTIAL sums over k in match order starting from
+ *   0.0 (the rule of vo_slam_stats' total_sqerr), so the bytes are defined by the data; numpy's pairwise np.mean / np.std
+ *   can differ from them in the last bits.
+ * n[p]: the pair's inliers; a pair whose status is not VO_OK or that has no inliers gives n = 0 and zeros; one inlier
+ * gives std = 0.  dist: NULL, or B x kp_cap doubles (vo_batch_kp_capacity): row p holds d_0 .. d_{n[p]-1}, then zeros.
+ * Refused as vo_tracks_pnp_batch refuses: VO_ERR_NOT_CONFIGURED before vo_batch_configure, VO_ERR_INVALID when B is not
+ * the most recent run's pair count (a configure call in between clears it).  The run need not have triangulated. */
+int vo_pairs_epipolar(vo_ctx* ctx, int B, const double* K, int32_t* n, double* mean, double* std_dev, double* max_dist, double* dist);
+
 /* ------------------------------------------------------------------ stage outputs (parity tests) */
 /* size in bytes of the packed outputs below (sum over levels of w_l * h_l); < 0 for invalid parameters */
 int64_t vo_packed_pyramid_bytes(int h, int w, const vo_orb_params* params);

@@ -67,6 +67,8 @@ _SIGS = {
     "vo_find_essential_ransac": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_double, C.c_double, C.c_int, C.c_uint64, _P, _P, _P, _P]),
     "vo_recover_pose": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_double, _P, _P, _P, _P]),
     "vo_triangulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P]),
+    "vo_correspond_epilines": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "vo_pairs_epipolar": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_packed_pyramid_bytes": (C.c_int64, [C.c_int, C.c_int, _P]),
     "vo_stage_pyramid": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "vo_stage_fast_scores": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

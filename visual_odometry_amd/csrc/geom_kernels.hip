@@ -1590,3 +1590,119 @@ void launch_chain_insert(hipStream_t s, PairBuf pb, int kp_cap, int p, int F, do
 {
     hipLaunchKernelGGL(k_chain_insert, dim3(1), dim3(256), 0, s, pb, kp_cap, p, F, max_norm, cb, dec);
 }
+
+// ------------------------------------------------------------------ computeCorrespondEpilines and the epipolar distances
+// cv2.computeCorrespondEpilines(points, whichImage, F) (src/feature_detection.py:118-125), restated from OpenCV 4.7's
+// fundam.cpp; parity with a cv2 build is unpinned, like the rest of the project.  f[] is F for whichImage 1 and F^T for 2 (the
+// caller transposes).  All arithmetic is f64, left to right, one rounding per operation (-ffp-contract=off):
+//   a = f0 x + f1 y + f2, b = f3 x + f4 y + f5, c = f6 x + f7 y + f8;  nu = a a + b b;  nu = nu ? 1 / sqrt(nu) : 1;  (a, b, c) *= nu
+__device__ __forceinline__ void epiline_one(const double* f, double x, double y, double* l)
+{
+    const double a = f[0] * x + f[1] * y + f[2];
+    const double b = f[3] * x + f[4] * y + f[5];
+    const double c = f[6] * x + f[7] * y + f[8];
+    double nu = a * a + b * b;
+    nu = nu != 0.0 ? 1.0 / sqrt(nu) : 1.0;
+    l[0] = a * nu; l[1] = b * nu; l[2] = c * nu;
+}
+
+// One lane per point.  point_type 0: f64 points, f64 lines; 1: f32 points, 2: i32 points, both f32 lines (cv2's output depth is
+// max(input depth, f32)), every value cast once at the end.
+__global__ void k_epilines(const void* pts, int point_type, int N, const double* Fg, void* lines)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    double f[9], l[3], x, y;
+#pragma unroll
+    for (int k = 0; k < 9; k++) f[k] = Fg[k];
+    if (point_type == 0)      { x = ((const double*)pts)[2 * (size_t)i]; y = ((const double*)pts)[2 * (size_t)i + 1]; }
+    else if (point_type == 1) { x = (double)((const float*)pts)[2 * (size_t)i]; y = (double)((const float*)pts)[2 * (size_t)i + 1]; }
+    else                      { x = (double)((const int32_t*)pts)[2 * (size_t)i]; y = (double)((const int32_t*)pts)[2 * (size_t)i + 1]; }
+    epiline_one(f, x, y, l);
+    if (point_type == 0) {
+        double* o = (double*)lines + 3 * (size_t)i;
+        o[0] = l[0]; o[1] = l[1]; o[2] = l[2];
+    } else {
+        float* o = (float*)lines + 3 * (size_t)i;
+        o[0] = (float)l[0]; o[1] = (float)l[1]; o[2] = (float)l[2];
+    }
+}
+
+void launch_epilines(hipStream_t s, const void* pts, int point_type, int N, const double* F, void* lines)
+{
+    if (N <= 0) return;
+    hipLaunchKernelGGL(k_epilines, dim3((N + 63) / 64), dim3(64), 0, s, pts, point_type, N, F, lines);
+}
+
+// The symmetric epipolar distance of every E inlier of a resident pair and its statistics (src/feature_detection.py:127-140), one
+// workgroup per pair.  F = K^-T E K^-1 with K^-1 as the pair path normalises pixels (k_match_select, k_prepare_points):
+//   ifx = 1 / K[0], ify = 1 / K[4], bx = -K[2] ifx, by = -K[5] ify,  K^-1 = [ifx 0 bx; 0 ify by; 0 0 1]
+//   G = E K^-1:  G[r][0] = E[r][0] ifx, G[r][1] = E[r][1] ify, G[r][2] = E[r][0] bx + E[r][1] by + E[r][2]
+//   F = K^-T G:  F[0][c] = ifx G[0][c], F[1][c] = ify G[1][c], F[2][c] = bx G[0][c] + by G[1][c] + G[2][c]
+// d_k = |l1 . (x2, 1)| + |l2 . (x1, 1)|, l1 = epiline of x1 under F, l2 = epiline of x2 under F^T, each dot as l0 x + l1 y + l2.
+// mean, the population standard deviation (two passes, as np.std) and the maximum are SEQUENTIAL sums in match order from 0.0
+// (k_slam_stats' rule for total_sqerr), made by one lane: the bytes are defined by the data, not by a reduction tree.
+__device__ __forceinline__ void pixel_fundamental(const double* E, const double* K, double* F)
+{
+    const double ifx = 1. / K[0], ify = 1. / K[4];
+    const double bx = -K[2] * ifx, by = -K[5] * ify;
+    double G[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        G[3 * r] = E[3 * r] * ifx; G[3 * r + 1] = E[3 * r + 1] * ify;
+        G[3 * r + 2] = E[3 * r] * bx + E[3 * r + 1] * by + E[3 * r + 2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        F[c] = ifx * G[c]; F[3 + c] = ify * G[3 + c];
+        F[6 + c] = bx * G[c] + by * G[3 + c] + G[6 + c];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pairs_epipolar(PairBuf pb, int kp_cap, const double* Kd, double* dist, int* n_out, double* mean_out,
+                                                        double* std_out, double* max_out)
+{
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const vo_pair_result* res = pb.res + p;
+    int n = res->status == VO_OK ? res->n_inl : 0;
+    n = n < 0 ? 0 : (n > kp_cap ? kp_cap : n);
+    double* d = dist + (size_t)p * kp_cap;
+    if (n > 0) {
+        double K[9], E[9], F[9], Ft[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) { K[k] = Kd[k]; E[k] = res->E[k]; }
+        pixel_fundamental(E, K, F);
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) Ft[3 * r + c] = F[3 * c + r];
+        const double* a = pb.ipx1 + (size_t)p * kp_cap * 2;
+        const double* b = pb.ipx2 + (size_t)p * kp_cap * 2;
+        for (int k = tid; k < n; k += 256) {
+            const double x1 = a[2 * k], y1 = a[2 * k + 1], x2 = b[2 * k], y2 = b[2 * k + 1];
+            double l1[3], l2[3];
+            epiline_one(F, x1, y1, l1);
+            epiline_one(Ft, x2, y2, l2);
+            d[k] = fabs(l1[0] * x2 + l1[1] * y2 + l1[2]) + fabs(l2[0] * x1 + l2[1] * y1 + l2[2]);
+        }
+    }
+    for (int k = n + tid; k < kp_cap; k += 256) d[k] = 0.0;
+    __syncthreads();                    // the workgroup's own global writes, read back by its lane 0
+    if (tid != 0) return;
+    double mean = 0.0, sd = 0.0, mx = 0.0;
+    if (n > 0) {
+        double sum = 0.0;
+        for (int k = 0; k < n; k++) { const double v = d[k]; sum += v; mx = v > mx ? v : mx; }
+        mean = sum / (double)n;
+        double sq = 0.0;
+        for (int k = 0; k < n; k++) { const double e = d[k] - mean; sq += e * e; }
+        sd = sqrt(sq / (double)n);
+    }
+    n_out[p] = n; mean_out[p] = mean; std_out[p] = sd; max_out[p] = mx;
+}
+
+void launch_pairs_epipolar(hipStream_t s, PairBuf pb, int kp_cap, int P, const double* Kd, double* dist, int* n, double* mean, double* sd, double* mx)
+{
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_pairs_epipolar, dim3(P), dim3(256), 0, s, pb, kp_cap, Kd, dist, n, mean, sd, mx);
+}

@@ -1460,6 +1460,65 @@ extern "C" int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, c
     return VO_OK;
 }
 
+extern "C" int vo_correspond_epilines(vo_ctx* ctx, const void* points, int N, int point_type, int which_image, const double* F, void* lines)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!F || N < 0 || (N > 0 && (!points || !lines))) FAIL(VO_ERR_INVALID, "bad arguments");
+    if (point_type < 0 || point_type > 2) FAIL(VO_ERR_INVALID, "point_type must be 0 (f64), 1 (f32) or 2 (i32)");
+    if (which_image != 1 && which_image != 2) FAIL(VO_ERR_INVALID, "whichImage must be 1 or 2");
+    if (N == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t in_b = (size_t)2 * N * (point_type == 0 ? 8 : 4), out_b = (size_t)3 * N * (point_type == 0 ? 8 : 4);
+    double Fh[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Fh[3 * r + c] = which_image == 1 ? F[3 * r + c] : F[3 * c + r];
+    double *dF, *dpts, *dlines;                                   // doubles: both arrays start 8-byte aligned whatever the type
+    ScratchLayout sc;
+    sc.take(&dF, 9); sc.take(&dpts, (in_b + 7) / 8); sc.take(&dlines, (out_b + 7) / 8);
+    int rc = sc.place(ctx); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(dF, Fh, sizeof(Fh), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dpts, points, in_b, hipMemcpyHostToDevice, s));
+    { StageTimer t(ctx, ST_MISC); launch_epilines(s, dpts, point_type, N, dF, dlines); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(lines, dlines, out_b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                               // Fh is a stack array: the call ends synchronised
+    if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
+extern "C" int vo_pairs_epipolar(vo_ctx* ctx, int B, const double* K, int32_t* n, double* mean, double* std_dev, double* max_dist, double* dist)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!K || !n || !mean || !std_dev || !max_dist) FAIL(VO_ERR_INVALID, "bad arguments");
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (B < 1 || B != ctx->last.pairs) FAIL(VO_ERR_INVALID, "vo_pairs_epipolar takes all %d pairs of the most recent vo_pairs_run", ctx->last.pairs);
+    // K^-1 is restated as the pair path normalises pixels: it reads fx, fy, cx, cy only.  Any other shape would be read differently
+    // there and here, so it is refused: skew, a last row that is not (0, 0, 1), a zero or non-finite focal length
+    if (K[1] != 0 || K[3] != 0 || K[6] != 0 || K[7] != 0 || K[8] != 1 || !(K[0] != 0) || !(K[4] != 0) || !std::isfinite(K[0]) || !std::isfinite(K[4]) ||
+        !std::isfinite(K[2]) || !std::isfinite(K[5]))
+        FAIL(VO_ERR_UNSUPPORTED, "vo_pairs_epipolar takes K = [fx 0 cx; 0 fy cy; 0 0 1] with finite entries and fx, fy != 0");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int cap = b.kp_cap;
+    double *dK, *dmean, *dsd, *dmx, *ddist; int* dn;
+    ScratchLayout sc;
+    sc.take(&dK, 9); sc.take(&dmean, B); sc.take(&dsd, B); sc.take(&dmx, B); sc.take(&ddist, (size_t)B * cap); sc.take(&dn, B);
+    int rc = sc.place(ctx); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(dK, K, 72, hipMemcpyHostToDevice, s));
+    { StageTimer t(ctx, ST_MISC); launch_pairs_epipolar(s, ctx->pb, cap, B, dK, ddist, dn, dmean, dsd, dmx); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(n, dn, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(mean, dmean, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(std_dev, dsd, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(max_dist, dmx, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, ddist, (size_t)B * cap * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
 extern "C" int vo_stage_five_point(vo_ctx* ctx, const double* x1, const double* x2, double* E, int32_t* n_models)
 {
     if (!ctx) return VO_ERR_INVALID;

@@ -262,6 +262,10 @@ void launch_triangulate_pairs(hipStream_t s, PairBuf pb, int kp_cap, int P, Rans
 void launch_triangulate_raw(hipStream_t s, const double* P1, const double* P2, const double* x1, const double* x2,
                             int M, double* X);
 void launch_five_point_raw(hipStream_t s, const double* x1, const double* x2, double* E, int* nm, int dk_early);
+// cv2.computeCorrespondEpilines: F is already transposed for whichImage 2; point_type 0 f64 (f64 lines), 1 f32, 2 i32 (f32 lines)
+void launch_epilines(hipStream_t s, const void* pts, int point_type, int N, const double* F, void* lines);
+// per resident pair: dist [P][kp_cap] (zeros past the pair's inliers), n / mean / sd / mx [P]
+void launch_pairs_epipolar(hipStream_t s, PairBuf pb, int kp_cap, int P, const double* Kd, double* dist, int* n, double* mean, double* sd, double* mx);
 void launch_reprojection(hipStream_t s, const double* poses, int ncam, const double* points, int npt, const int* obs_cam,
                          const int* obs_pt, const double* obs_xy, int nobs, const double* Kd, double threshold,
                          double* sqerr, uint8_t* keep, int* bad);

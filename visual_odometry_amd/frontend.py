@@ -184,6 +184,7 @@ class FrontEnd:
         fn = c.lib.vo_pairs_run if wait else c.lib.vo_pairs_run_async
         self._keep = (ps, K, opts)                  # keep the argument buffers alive until the work has been consumed
         self._warn_capacity(c.check(fn(c.handle, ps.ctypes.data, B, K.ctypes.data, C.addressof(opts), res.ctypes.data, _lib.ptr(X), self.kp_cap)))
+        self._last_pairs = B
         return res, X
 
     def _warn_capacity(self, rc):
@@ -463,6 +464,25 @@ class FrontEnd:
         c = self.ctx
         c.check(c.lib.vo_pairs_gather(c.handle, int(B), out.ctypes.data, int(bool(wait))))
         return out.reshape(world, B, _lib.VO_RECORD_DOUBLES)
+
+    def epipolar_stats(self, K, want_dist=False, n_pairs=None):
+        """The symmetric epipolar distances of src/feature_detection.py:127-140 for every pair of the latest run_pairs, computed
+        on what it left on the device (vo_pairs_epipolar): per E inlier k in match order d_k = |l1 . (x2, 1)| + |l2 . (x1, 1)|
+        with the epilines of the PIXEL fundamental matrix K^-T E K^-1 [deviation: the script passes E with pixel points].
+        Returns dict(n [B] int32, mean, std, max [B] float64: sequential sums in match order, so np.mean / np.std of the same
+        distances can differ in the last bits; dist: with want_dist a list of B arrays [n[p]], else None).  A failed pair gives
+        n = 0 and zeros.  n_pairs defaults to the latest run's pair count; any other value is refused by the library."""
+        B = int(getattr(self, "_last_pairs", 0) if n_pairs is None else n_pairs)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        n = np.zeros(max(B, 1), np.int32); mean = np.zeros(max(B, 1)); sd = np.zeros(max(B, 1)); mx = np.zeros(max(B, 1))
+        dist = np.zeros((max(B, 1), self.kp_cap)) if want_dist else None
+        c = self.ctx
+        rc = c.lib.vo_pairs_epipolar(c.handle, B, K.ctypes.data, n.ctypes.data, mean.ctypes.data, sd.ctypes.data, mx.ctypes.data, _lib.ptr(dist))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return dict(n=n[:B], mean=mean[:B], std=sd[:B], max=mx[:B],
+                    dist=[dist[p, :n[p]].copy() for p in range(B)] if want_dist else None)
 
     def pair_matches(self, pair):
         cap = self.kp_cap

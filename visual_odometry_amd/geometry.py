@@ -77,6 +77,42 @@ def triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2, ctx=None):
     return X
 
 
+_EPILINE_TYPES = {np.dtype(np.float64): (0, np.float64), np.dtype(np.float32): (1, np.float32), np.dtype(np.int32): (2, np.float32)}
+
+
+def epiline_points(points):
+    """The N x 2 array computeCorrespondEpilines reads from `points` (N x 2, N x 1 x 2, 1 x N x 2 or a list of pairs) and its
+    vo_correspond_epilines point_type.  float64, float32 and int32 keep their depth; a list and any other dtype go to float64."""
+    p = np.asarray(points)
+    if p.dtype not in _EPILINE_TYPES:
+        p = p.astype(np.float64)
+    if p.ndim == 3 and 1 in p.shape[:2]:
+        p = p.reshape(-1, p.shape[2])
+    if p.size == 0:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] not in (2, 3):
+        raise ValueError("points must be an N x 2 array")
+    if p.shape[1] == 3:
+        raise NotImplementedError("homogeneous (three-column) points are not built (the reference passes keypoint.pt pairs)")
+    return np.ascontiguousarray(p), _EPILINE_TYPES[p.dtype]
+
+
+def computeCorrespondEpilines(points, whichImage, F, ctx=None):
+    """cv2.computeCorrespondEpilines(points, whichImage, F) (src/feature_detection.py:118-125) -> lines [N, 1, 3]: float64 for
+    float64 points, float32 for float32 and int32 points."""
+    p, (ptype, out_dtype) = epiline_points(points)
+    if whichImage not in (1, 2):
+        raise ValueError("whichImage must be 1 or 2")
+    Fm = np.ascontiguousarray(F, dtype=np.float64)
+    if Fm.shape != (3, 3):
+        raise ValueError("F must be 3x3")
+    N = len(p)
+    lines = np.zeros((max(N, 1), 3), out_dtype)
+    ctx = ctx or _lib.default_context()
+    ctx.check(ctx.lib.vo_correspond_epilines(ctx.handle, p.ctypes.data, N, ptype, int(whichImage), Fm.ctypes.data, lines.ctypes.data))
+    return lines[:N].reshape(N, 1, 3)
+
+
 def five_point(x1, x2, ctx=None):
     """All essential matrices through 5 normalised correspondences (stage test hook)."""
     x1 = np.ascontiguousarray(x1, dtype=np.float64).reshape(5, 2)

@@ -3,13 +3,13 @@
 Same constructor, methods and attributes that src/visual_slam.py reads (raw_matches, filtered_matches,
 essential_matrix, R, t (3x1), relative_pose, null_projection_matrix, projection_matrix,
 points3d_reconstr (4xM, w = 1), matches_with_3d_information); cv2.findEssentialMat / recoverPose /
-triangulatePoints are replaced by visual_odometry_amd.geometry.
+triangulatePoints are visual_odometry_amd.cv2_surface's: by default visual_odometry_amd.geometry.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from . import geometry
+from . import cv2_surface
 from .initials import Match, Match3D
 
 DISTANCE_GATE = 1130          # image_pair.py:258 (a SIFT-L2 gate; never binds for Hamming <= 256)
@@ -57,8 +57,8 @@ class ImagePair:
 
     def determine_essential_matrix(self, matches):
         p1, p2 = self.get_image_points(matches)
-        E, mask = geometry.findEssentialMat(p1, p2, self.camera_matrix, geometry.FM_RANSAC,
-                                            RANSAC_CONFIDENCE, RANSAC_THRESHOLD_PX)
+        E, mask = cv2_surface.findEssentialMat(p1, p2, self.camera_matrix, cv2_surface.FM_RANSAC,
+                                               RANSAC_CONFIDENCE, RANSAC_THRESHOLD_PX)
         if E is None:
             # cv2 returns None here and the reference then dies with AttributeError (image_pair.py:289)
             raise ValueError(f"essential matrix needs >= 5 usable matches, got {len(matches)}")
@@ -67,7 +67,7 @@ class ImagePair:
 
     def estimate_camera_movement(self, matches):
         p1, p2 = self.get_image_points(matches)
-        _, self.R, self.t, _ = geometry.recoverPose(self.essential_matrix, p1, p2, self.camera_matrix)
+        _, self.R, self.t, _ = cv2_surface.recoverPose(self.essential_matrix, p1, p2, self.camera_matrix)
         self.relative_pose = np.eye(4)
         self.relative_pose[:3, :3] = self.R
         self.relative_pose[:3, 3] = self.t.T[0]
@@ -84,7 +84,7 @@ class ImagePair:
         if second_projection_matrix is not None:
             self.projection_matrix = K @ second_projection_matrix
         p1, p2 = self.get_image_points(matches)
-        X = geometry.triangulatePoints(self.projection_matrix, self.null_projection_matrix, p1.T, p2.T)
+        X = cv2_surface.triangulatePoints(self.projection_matrix, self.null_projection_matrix, p1.T, p2.T)
         X /= X[3, :]
         self.points3d_reconstr = X
         self.matches_with_3d_information = [
@@ -97,17 +97,14 @@ class ImagePair:
             print(X.transpose())
 
     def visualize_matches(self, matches):
-        """Side-by-side image with one line per match (numpy rasteriser; the reference uses cv2.line)."""
+        """Side-by-side image with one line per match (cv2_surface.line, a numpy rasteriser; the reference uses cv2.line)."""
         h, w = self.frame1.image.shape[:2]
         a, b = self.frame1.image, self.frame2.image
         if a.ndim == 2:
             a, b = np.stack([a] * 3, axis=2), np.stack([b] * 3, axis=2)
         vis = np.concatenate((a, b), axis=1).copy()
         for m in matches:
-            x0, y0 = int(m.keypoint1[0]), int(m.keypoint1[1])
-            x1, y1 = int(m.keypoint2[0] + w), int(m.keypoint2[1])
-            n = max(abs(x1 - x0), abs(y1 - y0), 1)
-            xs = np.clip(np.rint(np.linspace(x0, x1, n + 1)).astype(int), 0, vis.shape[1] - 1)
-            ys = np.clip(np.rint(np.linspace(y0, y1, n + 1)).astype(int), 0, vis.shape[0] - 1)
-            vis[ys, xs] = np.clip(np.asarray(m.color) * 256, 0, 255).astype(vis.dtype)
+            start = (int(m.keypoint1[0]), int(m.keypoint1[1]))
+            end = (int(m.keypoint2[0] + w), int(m.keypoint2[1]))
+            vis = cv2_surface.line(vis, start, end, list(np.asarray(m.color) * 256), 1)
         return vis
