@@ -6,7 +6,7 @@
     -> update_feature_mapper / estimate_current_camera_position (solvePnPRansac) / add_information_to_map   (:183-266, :153-180)
 
 Only the compressed file bytes cross PCIe; every stage after that reads what the previous one left in HBM.
-    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart] [--stream N]
+    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart] [--stream N] [--dist k1,k2,p1,p2[,k3]]
 --restart: afterwards the complete map step (bundle adjustment, filter, camera limit) on the same resident pairs with restart=True — a lost frame
 starts a new map instead of ending the chain — and one track per segment, each in its own gauge.
 --stream N: the same files once more in chunks of N pairs through slam_stream on a front end with only N + 1 frame slots — the map stays on the
@@ -14,7 +14,10 @@ device between the chunks, every chunk's files are decoded into the slots the ch
 slam_chain call on all the files.
 --stream N --restart together: the chunks go through slam_stream_restart instead — a lost frame starts a new map in whichever chunk it falls,
 and a chunk that ends lost is continued — and one track per segment is printed from the joined calls (join_stream, split_segments); they are the
-segments of slam_chain(restart=True) on all the files."""
+segments of slam_chain(restart=True) on all the files.
+--dist k1,k2,p1,p2[,k3]: a camera with a real lens — after each detection the keypoints are undistorted on the device (FrontEnd.undistort,
+cv2.undistortPoints' arithmetic) and everything after runs on ideal pixels.  (The synthetic frames here come from a pinhole, so the option shows
+the call in place, not a better track.)  Without it the output is what it was."""
 import argparse
 import io
 import os
@@ -37,7 +40,11 @@ def main():
     ap.add_argument("--step", type=float, default=4.0, help="flight distance per frame (the camera is 30 units above the ground)")
     ap.add_argument("--restart", action="store_true", help="also run slam_chain(restart=True) and print one track per segment")
     ap.add_argument("--stream", type=int, default=0, metavar="N", help="also walk the files in chunks of N pairs through slam_stream (N + 1 frame slots)")
+    ap.add_argument("--dist", type=lambda s: [float(v) for v in s.split(",")], default=None, metavar="k1,k2,p1,p2[,k3]",
+                    help="lens distortion coefficients: undistort the keypoints on the device after each detection (FrontEnd.undistort)")
     a = ap.parse_args()
+    if a.dist is not None and len(a.dist) not in (4, 5):
+        ap.error("--dist takes 4 or 5 comma-separated coefficients")
     from PIL import Image
     n = a.frames
     dw, dh = int(a.width * a.scale), int(a.height * a.scale)
@@ -55,6 +62,8 @@ def main():
     t0 = time.perf_counter()
     fe.ingest_jpeg(packed)                                      # decode + resize + gray on the device
     fe.detect(0, n)
+    if a.dist is not None:
+        fe.undistort(0, n, K, a.dist)                           # K is the matrix of the resized frames; the coefficients survive a resize
     res, _ = fe.run_pairs(pairs, K, want_points=True)
     out = fe.localize_chain(n - 1, K)                           # tracks -> solvePnPRansac -> cameras -> new map points
     dt = time.perf_counter() - t0
@@ -81,6 +90,8 @@ def main():
             new = slots[:b + 1] if c == 0 else slots[1:b + 1]
             for slot, f in zip(new, range(first + (c > 0), first + b + 1)):
                 st.ingest_jpeg([files[f]], first_slot=slot); st.detect(slot, 1)
+                if a.dist is not None:
+                    st.undistort(slot, 1, K, a.dist)            # the chunk's new frames only: the anchor slot was undistorted in its own chunk
             st.run_pairs([[slots[j], slots[j + 1]] for j in range(b)], K, want_points=True)
             out = call(b, K, resume=c > 0, total_pairs=n - 1)
             outs.append(out)

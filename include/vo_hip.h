@@ -189,6 +189,45 @@ int vo_correspond_epilines(vo_ctx* ctx, const void* points, int N, int point_typ
  * the most recent run's pair count (a configure call in between clears it).  The run need not have triangulated. */
 int vo_pairs_epipolar(vo_ctx* ctx, int B, const double* K, int32_t* n, double* mean, double* std_dev, double* max_dist, double* dist);
 
+/* cv2.undistortPoints(src, K, dist, R, P) with its default termination — the lens model the reference names and never wires
+ * up: src/image_and_keypoints.py:21-25 stores the drone camera's five coefficients (k1, k2, p1, p2, k3) in self.distCoeffs and
+ * nothing reads them.  OpenCV 4.7's undistort.dispatch.cpp, restated from its source as remembered.
+ * [deviations] five fixed-point iterations, always (cv2's default criteria; no epsilon-terminated form); no thin-prism and no
+ *   tilt terms (ndist 12 and 14: VO_ERR_UNSUPPORTED); parity with a cv2 build is unpinned, like the rest of this library — the
+ *   checker is the numpy restatement tests/undistort_reference.py, and the contract is byte equality with it.
+ * dist: ndist doubles in cv2's order k1 k2 p1 p2 [k3 [k4 k5 k6]]; ndist 4, 5 or 8 (absent coefficients are zero and go through
+ * the same expressions); any other count, 0 included, and dist == NULL: VO_ERR_INVALID (no distortion = four zeros).  K: 3x3 row-major, read as fx = K[0], cx = K[2],
+ * fy = K[4], cy = K[5]; fx == 0 or fy == 0: VO_ERR_INVALID.  R, P: 9 doubles each (3x3 row-major; of a 3x4 P its left 3x3)
+ * or NULL = identity.  RR = P R is formed on the host, RR[i][j] = P[i][0] R[0][j] + P[i][1] R[1][j] + P[i][2] R[2][j].
+ * Per point (u, v), in f64, left to right, one rounding per operation:
+ *   ifx = 1 / fx, ify = 1 / fy;  x = (u - cx) ifx, y = (v - cy) ify;  x0 = x, y0 = y
+ *   five times:  r2 = x x + y y
+ *                icdist = (1 + ((k6 r2 + k5) r2 + k4) r2) / (1 + ((k3 r2 + k2) r2 + k1) r2)
+ *                if (icdist < 0) { x = x0, y = y0; stop }            (cv2's fallback outside the model's valid range)
+ *                dx = ((2 p1) x) y + p2 (r2 + (2 x) x),  dy = p1 (r2 + (2 y) y) + ((2 p2) x) y
+ *                x = (x0 - dx) icdist,  y = (y0 - dy) icdist
+ *   xx = RR0 x + RR1 y + RR2, yy = RR3 x + RR4 y + RR5, ww = 1 / (RR6 x + RR7 y + RR8);  out = (xx ww, yy ww)
+ * All-zero coefficients give the bytes of plain normalisation; NaN / Inf input propagates through its own row only.
+ * points: N x 2 of point_type 0 (f64) or 1 (f32), as vo_correspond_epilines names them; out: N x 2 of the same type, an f32 value
+ * being the f64 result rounded once.  N = 0 returns VO_OK and touches nothing. */
+int vo_undistort_points(vo_ctx* ctx, const void* points, int N, int point_type, const double K[9], const double* dist, int ndist,
+                        const double* R /*9 or NULL*/, const double* P /*9 or NULL*/, void* out);
+/* The resident form: the same arithmetic with R = I and P = K on the keypoint positions of slots [first_slot, first_slot + F) of the
+ * live batch configuration (ORB or SIFT), in place: kp_xy = float32(undistort(double(kp_xy))), for the slot's kp_count keypoints
+ * as the device holds the count — no host round trip.  Every kernel after detection takes pixel positions from that array only, so
+ * the pair path, the chain and the map step then run on ideal pixels, unchanged.
+ * K is the camera matrix of the frames AS THEY SIT IN THE SLOTS, i.e. after any resize (vo_frames_ingest[_jpeg] scale fx, fy, cx,
+ * cy with the image); the coefficients are dimensionless — they act on normalised coordinates — and survive a resize unchanged.
+ * Enqueued on the context's stream: behind vo_frames_detect_async, before the next vo_pairs_run; returns after the stream's work,
+ * as vo_frames_detect does.  Only kp_xy of those slots changes: descriptors, angles, sizes, responses, octaves, counts and flags
+ * keep their bytes, as does everything of every other slot.  The detected positions are not kept: read them before the call.
+ * The context marks an undistorted slot (host side): a call whose range holds a marked slot is refused (VO_ERR_INVALID, nothing
+ * changed) — also for the anchor slot of a live vo_slam_stream*, undistorted when it was a new frame.  Whatever gives a slot new
+ * keypoints clears its mark: vo_frames_detect[_async], vo_frames_upload*, vo_frames_ingest[_jpeg], vo_stage_orb_rows,
+ * vo_stage_sift_rows; a configure call clears all.  VO_ERR_NOT_CONFIGURED before a batch configuration; VO_ERR_INVALID for a
+ * slot range out of bounds; ndist, K as vo_undistort_points.  Profiling stage "undistort_points". */
+int vo_frames_undistort(vo_ctx* ctx, int first_slot, int F, const double K[9], const double* dist, int ndist);
+
 /* ------------------------------------------------------------------ stage outputs (parity tests) */
 /* size in bytes of the packed outputs below (sum over levels of w_l * h_l); < 0 for invalid parameters */
 int64_t vo_packed_pyramid_bytes(int h, int w, const vo_orb_params* params);
@@ -824,7 +863,7 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since
  * the last vo_profile_reset. */
-#define VO_STAGE_COUNT 29
+#define VO_STAGE_COUNT 30
 int vo_profile_enable(vo_ctx* ctx, int on);
 int vo_profile_reset(vo_ctx* ctx);
 int vo_profile_read(vo_ctx* ctx, float* ms /*VO_STAGE_COUNT*/, int32_t* launches /*VO_STAGE_COUNT*/);

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("VO_HIP_LIBRARY") or os.path.join(_HERE, "libvo_hip.so
 VO_OK, VO_WARN_CAPACITY = 0, 1
 VO_ERR_INVALID, VO_ERR_HIP, VO_ERR_TOO_FEW, VO_ERR_NO_MODEL, VO_ERR_NOT_CONFIGURED, VO_ERR_AMBIGUOUS = -1, -2, -3, -4, -5, -6
 VO_ERR_UNSUPPORTED = -7
-VO_STAGE_COUNT = 29
+VO_STAGE_COUNT = 30
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
 VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
 VO_STATS_HIST = 64
@@ -69,6 +69,8 @@ _SIGS = {
     "vo_triangulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P]),
     "vo_correspond_epilines": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "vo_pairs_epipolar": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "vo_undistort_points": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    "vo_frames_undistort": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int]),
     "vo_packed_pyramid_bytes": (C.c_int64, [C.c_int, C.c_int, _P]),
     "vo_stage_pyramid": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "vo_stage_fast_scores": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

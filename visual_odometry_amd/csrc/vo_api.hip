@@ -8,14 +8,16 @@ static const char* k_stage_names[VO_STAGE_COUNT] = {
     "gaussian_blur", "rbrief", "match_nn", "match_select", "essential_ransac", "recover_pose",
     "triangulate", "misc", "reserved", "sift_scale_space", "sift_extrema", "sift_refine_orient", "sift_sort_unique",
     "sift_descriptor", "cv2_keypoint_order", "trajectory_gather", "reserved2", "slam_ba_prepare", "slam_bundle_adjust", "slam_filter",
-    "slam_camera_limit", "slam_map_statistics"};
+    "slam_camera_limit", "slam_map_statistics", "undistort_points"};
 
 static void clear_last_run(vo_ctx* ctx) { ctx->last = LastRun(); }
 
 // An upload, ingest or detection into slots first .. first + n - 1: if the stream's last frame is among them, no call can continue it
 // (vo_slam_streams: the sequence whose last frame it is cannot advance any more; the others can).
+// ... and the slots' keypoints are no longer the ones vo_frames_undistort rewrote: their marks go.
 static void slam_stream_slots_written(vo_ctx* ctx, int first, int n)
 {
+    for (int k = first < 0 ? 0 : first; k < first + n && k < (int)ctx->undistorted.size(); k++) ctx->undistorted[(size_t)k] = 0;
     SlamStream& st = ctx->stream_map;
     if (st.live && st.anchor >= first && st.anchor < first + n) st.touched = true;
     for (SlamStream::Seq& q : st.seq)
@@ -189,6 +191,7 @@ static void free_config(vo_ctx* c)
     c->pb_pairs = c->pb_cap = 0;
     clear_last_run(c);
     drop_slam_stream(c);
+    c->undistorted.clear();
 }
 
 static void comm_release(vo_ctx* ctx);
@@ -328,6 +331,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
         ctx->detector = 0;
         clear_last_run(ctx);
         drop_slam_stream(ctx);
+        ctx->undistorted.clear();
         return VO_OK;
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1487,6 +1491,75 @@ extern "C" int vo_correspond_epilines(vo_ctx* ctx, const void* points, int N, in
     return VO_OK;
 }
 
+// cv2.undistortPoints' arguments as the kernels take them: the camera, the coefficients by name (absent ones zero), RR = P R
+static int undistort_params(vo_ctx* ctx, const double* K, const double* dist, int ndist, const double* R, const double* P, UndistortParams* up)
+{
+    if (!K) FAIL(VO_ERR_INVALID, "K is NULL");
+    if (ndist == 12 || ndist == 14) FAIL(VO_ERR_UNSUPPORTED, "thin-prism and tilt coefficients (%d distortion coefficients) are not built", ndist);
+    if (ndist != 4 && ndist != 5 && ndist != 8) FAIL(VO_ERR_INVALID, "4, 5 or 8 distortion coefficients are needed, not %d", ndist);
+    if (!dist) FAIL(VO_ERR_INVALID, "dist is NULL");
+    if (K[0] == 0 || K[4] == 0) FAIL(VO_ERR_INVALID, "fx and fy must not be 0");
+    double k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < ndist; i++) k[i] = dist[i];
+    up->fx = K[0]; up->fy = K[4]; up->cx = K[2]; up->cy = K[5];
+    up->k1 = k[0]; up->k2 = k[1]; up->p1 = k[2]; up->p2 = k[3]; up->k3 = k[4]; up->k4 = k[5]; up->k5 = k[6]; up->k6 = k[7];
+    static const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double* Rm = R ? R : I3;
+    const double* Pm = P ? P : I3;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) up->RR[3 * i + j] = Pm[3 * i] * Rm[j] + Pm[3 * i + 1] * Rm[3 + j] + Pm[3 * i + 2] * Rm[6 + j];
+    return VO_OK;
+}
+
+extern "C" int vo_undistort_points(vo_ctx* ctx, const void* points, int N, int point_type, const double K[9], const double* dist, int ndist,
+                                   const double* R, const double* P, void* out)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (N < 0 || (N > 0 && (!points || !out))) FAIL(VO_ERR_INVALID, "bad arguments");
+    if (point_type != 0 && point_type != 1) FAIL(VO_ERR_INVALID, "point_type must be 0 (f64) or 1 (f32)");
+    UndistortParams up;
+    int rc = undistort_params(ctx, K, dist, ndist, R, P, &up); if (rc) return rc;
+    if (N == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)2 * N * (point_type == 0 ? 8 : 4);
+    double *dpts, *dout;                                          // doubles: both arrays start 8-byte aligned whatever the type
+    ScratchLayout sc;
+    sc.take(&dpts, (bytes + 7) / 8); sc.take(&dout, (bytes + 7) / 8);
+    rc = sc.place(ctx); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(dpts, points, bytes, hipMemcpyHostToDevice, s));
+    { StageTimer t(ctx, ST_UNDISTORT); launch_undistort_points(s, dpts, point_type, N, up, dout); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
+extern "C" int vo_frames_undistort(vo_ctx* ctx, int first_slot, int F, const double K[9], const double* dist, int ndist)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_batch_configure has not been called");
+    if (F < 0 || first_slot < 0 || first_slot + F > b.max_frames) FAIL(VO_ERR_INVALID, "slot range out of bounds");
+    UndistortParams up;
+    int rc = undistort_params(ctx, K, dist, ndist, nullptr, K, &up); if (rc) return rc;
+    for (int k = first_slot; k < first_slot + F && k < (int)ctx->undistorted.size(); k++)
+        if (ctx->undistorted[(size_t)k]) FAIL(VO_ERR_INVALID, "slot %d has been undistorted already", k);
+    if (F == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    {
+        StageTimer t(ctx, ST_UNDISTORT);
+        launch_undistort_frames(ctx->stream, const_cast<float*>(b.kp_xy) + (size_t)first_slot * b.kp_cap * 2, b.kp_count + first_slot, b.kp_cap, F, up);
+    }
+    HIPCHK(hipGetLastError());
+    if (ctx->undistorted.size() < (size_t)b.max_frames) ctx->undistorted.resize((size_t)b.max_frames, 0);
+    for (int k = first_slot; k < first_slot + F; k++) ctx->undistorted[(size_t)k] = 1;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) prof_collect(ctx);
+    return VO_OK;
+}
+
 extern "C" int vo_pairs_epipolar(vo_ctx* ctx, int B, const double* K, int32_t* n, double* mean, double* std_dev, double* max_dist, double* dist)
 {
     if (!ctx) return VO_ERR_INVALID;
@@ -2282,6 +2355,7 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     HIPCHK(hipStreamSynchronize(ctx->stream));
     clear_last_run(ctx);                                        // the pair buffers may be replaced below
     drop_slam_stream(ctx);
+    ctx->undistorted.clear();
     // frames per launch chain: the small octaves' launches are latency-bound (a dependent chain of ~50 launches per sub-batch)
     // and the wave-per-keypoint kernels like long grids, so the more frames share a chain the better (1280 x 720, pairs/s with
     // 64 / 96 / 128 / 192 / 256 frames: 4.59 / 4.68 / 4.79 / 4.94 / 4.94 k): up to 192 frames, within 48 GB of scale-space scratch
@@ -2753,6 +2827,7 @@ extern "C" double vo_stage_bytes(vo_ctx* ctx, int stage, int F)
         if (stage == ST_SIFT_SCALE) b = (double)S.w * S.h + 4.0 * p0 * 3 + 4.0 * px * ((L + 2) + (L + 2)) + 4.0 * (px - p0) * 1.25;
         else if (stage == ST_SIFT_EXTREMA) b = 4.0 * px * (L + 3);
         else if (stage == ST_MATCH_NN) b = 2.0 * S.kp_cap * 128;
+        else if (stage == ST_UNDISTORT) b = 16.0 * S.kp_cap;                       // a full slot: 8 B read and 8 B written per keypoint
         return b * F;
     }
     if (!ctx || !ctx->configured) return 0.0;
@@ -2773,6 +2848,7 @@ extern "C" double vo_stage_bytes(vo_ctx* ctx, int stage, int F)
     case ST_MATCH_SELECT: b = 16 * N; break;
     case ST_RANSAC: b = 33 * N; break;                                             // SURVEY 8(d) geometry 65 N: 4 f64 coords + mask per match ...
     case ST_POSE: b = 32 * N; break;                                               // ... + the inliers' coordinates again
+    case ST_UNDISTORT: b = 16 * N; break;                                          // kp_xy: 8 B read and 8 B written per keypoint
     default: b = 0;
     }
     return b * F;

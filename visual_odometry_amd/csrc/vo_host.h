@@ -201,6 +201,7 @@ struct vo_ctx {
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
     int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it
+    std::vector<uint8_t> undistorted;     // per slot: vo_frames_undistort has rewritten its kp_xy (empty: no slot); cleared by whatever gives the slot new keypoints
 };
 
 #define HIPCHK(expr)                                                                              \

@@ -9,7 +9,7 @@ enum {
     ST_GRAY = 0, ST_RESIZE, ST_FAST, ST_SELECT_FAST, ST_HARRIS, ST_SELECT_HARRIS, ST_ANGLE,
     ST_BLUR, ST_BRIEF, ST_MATCH_NN, ST_MATCH_SELECT, ST_RANSAC, ST_POSE, ST_TRIANGULATE,
     ST_MISC, ST_RESERVED, ST_SIFT_SCALE, ST_SIFT_EXTREMA, ST_SIFT_ORIENT, ST_SIFT_SORT, ST_SIFT_DESC, ST_CV2_ORDER, ST_GATHER, ST_RESERVED2,
-    ST_SLAM_PREPARE, ST_SLAM_BA, ST_SLAM_FILTER, ST_SLAM_LIMIT, ST_SLAM_STATS
+    ST_SLAM_PREPARE, ST_SLAM_BA, ST_SLAM_FILTER, ST_SLAM_LIMIT, ST_SLAM_STATS, ST_UNDISTORT
 };
 
 // ---- pyramid / work geometry, passed to kernels by value ------------------------------------
@@ -264,6 +264,17 @@ void launch_triangulate_raw(hipStream_t s, const double* P1, const double* P2, c
 void launch_five_point_raw(hipStream_t s, const double* x1, const double* x2, double* E, int* nm, int dk_early);
 // cv2.computeCorrespondEpilines: F is already transposed for whichImage 2; point_type 0 f64 (f64 lines), 1 f32, 2 i32 (f32 lines)
 void launch_epilines(hipStream_t s, const void* pts, int point_type, int N, const double* F, void* lines);
+// cv2.undistortPoints (undistort_kernels.hip): the camera, the eight rational-model coefficients (absent ones zero) and RR = P R,
+// passed to the kernels by value
+struct UndistortParams {
+    double fx, fy, cx, cy;
+    double k1, k2, p1, p2, k3, k4, k5, k6;
+    double RR[9];
+};
+// point_type 0: f64 points in and out, 1: f32 in and out (the f64 result rounded once)
+void launch_undistort_points(hipStream_t s, const void* pts, int point_type, int N, UndistortParams up, void* out);
+// the keypoints of F slots in place: kp_xy [F][kp_cap][2], kp_count [F] (both already offset to the first slot)
+void launch_undistort_frames(hipStream_t s, float* kp_xy, const int* kp_count, int kp_cap, int F, UndistortParams up);
 // per resident pair: dist [P][kp_cap] (zeros past the pair's inliers), n / mean / sd / mx [P]
 void launch_pairs_epipolar(hipStream_t s, PairBuf pb, int kp_cap, int P, const double* Kd, double* dist, int* n, double* mean, double* sd, double* mx);
 void launch_reprojection(hipStream_t s, const double* poses, int ncam, const double* points, int npt, const int* obs_cam,

@@ -6,6 +6,7 @@ Carried names (reference call sites: src/visual_slam.py:16-19, :231-243, :303-37
 src/frame_generator.py:25; src/image_and_keypoints.py:8-9, :42; src/feature_detection.py:118-125):
   constructors / constants  SIFT_create ORB_create BFMatcher NORM_L2 NORM_HAMMING FM_RANSAC RANSAC INTER_LINEAR INTER_AREA
   arithmetic                findEssentialMat recoverPose triangulatePoints solvePnPRansac Rodrigues computeCorrespondEpilines
+                            undistortPoints (the lens model of src/image_and_keypoints.py:21-25, which the reference never applies)
                             resize imread imdecode line
   headless display          imshow waitKey destroyAllWindows
 Any other attribute raises AttributeError naming this surface.  Arguments are positional in cv2's order.
@@ -26,7 +27,7 @@ INTER_LINEAR, INTER_AREA = 1, 3
 IMREAD_COLOR = 1
 
 ARITHMETIC = ("findEssentialMat", "recoverPose", "triangulatePoints", "solvePnPRansac", "Rodrigues", "computeCorrespondEpilines",
-              "resize", "imread", "imdecode")
+              "undistortPoints", "resize", "imread", "imdecode")
 
 
 class HipBackend:
@@ -67,6 +68,10 @@ class HipBackend:
     def computeCorrespondEpilines(self, points, whichImage, F):
         from . import geometry
         return geometry.computeCorrespondEpilines(points, whichImage, F)
+
+    def undistortPoints(self, src, cameraMatrix, distCoeffs, R, P):
+        from . import geometry
+        return geometry.undistortPoints(src, cameraMatrix, distCoeffs, R, P)
 
     def resize(self, src, dsize, interpolation):
         from . import ingest
@@ -135,6 +140,11 @@ def Rodrigues(src):
 def computeCorrespondEpilines(points, whichImage, F):
     _touch()
     return backend.computeCorrespondEpilines(points, whichImage, F)
+
+
+def undistortPoints(src, cameraMatrix, distCoeffs, R=None, P=None):
+    _touch()
+    return backend.undistortPoints(src, cameraMatrix, distCoeffs, R, P)
 
 
 def resize(src, dsize, interpolation=INTER_LINEAR):

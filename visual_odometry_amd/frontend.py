@@ -113,9 +113,27 @@ class FrontEnd:
         fn = c.lib.vo_frames_detect if wait else c.lib.vo_frames_detect_async
         self._warn_capacity(c.check(fn(c.handle, int(first_slot), int(count))))
 
+    def undistort(self, first_slot, count, K, dist):
+        """A camera with a real lens (vo_frames_undistort): rewrites the keypoint positions of `count` detected slots in place with
+        cv2.undistortPoints(xy, K, dist, None, K) — five iterations, float64 arithmetic, one rounding back to float32 — on the
+        device, ordered behind detect(wait=False) and before the next run_pairs.  Everything downstream (run_pairs, localize_chain,
+        the slam_* calls) reads positions from there only and so runs on ideal pixels; features(slot)["xy"] returns them too.
+        The detected positions are not kept: a caller who wants them reads features(slot)["xy"] BEFORE this call.
+        K: the camera matrix of the frames as they sit in the slots (after ingest's resize); dist: 4, 5 or 8 coefficients
+        (k1 k2 p1 p2 [k3 [k4 k5 k6]]), which a resize leaves unchanged.  A slot can be undistorted once per detection: a second
+        call on it raises VoError (VO_ERR_INVALID) until the slot is uploaded to, detected or staged again."""
+        from .geometry import dist_coeffs
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        d = dist_coeffs(dist)
+        c = self.ctx
+        rc = c.lib.vo_frames_undistort(c.handle, int(first_slot), int(count), K.ctypes.data, d.ctypes.data, len(d))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+
     def features(self, slot):
         """Keypoints and descriptors of a detected slot.  ORB: desc [n, 32] uint8; SIFT: desc [n, 128] float32 (the integer bin
-        values 0..255 cv2 returns as floats)."""
+        values 0..255 cv2 returns as floats).  After undistort() on the slot, xy holds the ideal (undistorted) pixels."""
         sift = self.detector == "sift"
         kp = _lib.KeypointBuffers(self.kp_cap, 128 if sift else 32)
         c = self.ctx

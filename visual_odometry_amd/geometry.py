@@ -113,6 +113,48 @@ def computeCorrespondEpilines(points, whichImage, F, ctx=None):
     return lines[:N].reshape(N, 1, 3)
 
 
+def dist_coeffs(distCoeffs):
+    """cv2's distCoeffs argument as the C ABI takes it: a flat float64 array; None or an empty array is four zeros."""
+    d = np.zeros(4) if distCoeffs is None else np.ascontiguousarray(distCoeffs, dtype=np.float64).ravel()
+    return np.zeros(4) if d.size == 0 else d
+
+
+def undistortPoints(src, cameraMatrix, distCoeffs, R=None, P=None, ctx=None):
+    """cv2.undistortPoints(src, cameraMatrix, distCoeffs, R, P) with its default termination (five iterations) -> [N, 1, 2] of
+    src's float type.  src: [N, 2], [N, 1, 2] or [1, N, 2], float32 or float64 (anything else is read as float64); distCoeffs:
+    4, 5 or 8 values (k1 k2 p1 p2 [k3 [k4 k5 k6]]), None or empty = zeros; 12 and 14 (thin prism, tilt) raise
+    NotImplementedError.  R: 3x3 or None; P: 3x3 or 3x4 (its left 3x3 is used, as cv2 does) or None: normalised coordinates come
+    back.  The lens model the reference carries in src/image_and_keypoints.py:21-25 and never applies."""
+    p = np.asarray(src)
+    if p.dtype not in (np.float32, np.float64):
+        p = p.astype(np.float64)
+    if p.ndim == 3 and 1 in p.shape[:2]:
+        p = p.reshape(-1, p.shape[2])
+    if p.size == 0:
+        p = p.reshape(0, 2)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("src must be an N x 2, N x 1 x 2 or 1 x N x 2 array")
+    p = np.ascontiguousarray(p)
+    K = np.ascontiguousarray(cameraMatrix, dtype=np.float64).reshape(3, 3)
+    d = dist_coeffs(distCoeffs)
+    Rm = None if R is None else np.ascontiguousarray(np.asarray(R, np.float64).reshape(3, 3))
+    Pm = None
+    if P is not None:
+        Pm = np.asarray(P, np.float64)
+        if Pm.shape not in ((3, 3), (3, 4)):
+            raise ValueError("P must be 3x3 or 3x4")
+        Pm = np.ascontiguousarray(Pm[:, :3])
+    N = len(p)
+    out = np.zeros((max(N, 1), 2), p.dtype)
+    ctx = ctx or _lib.default_context()
+    rc = ctx.lib.vo_undistort_points(ctx.handle, p.ctypes.data, N, 0 if p.dtype == np.float64 else 1, K.ctypes.data, d.ctypes.data, len(d),
+                                     _lib.ptr(Rm), _lib.ptr(Pm), out.ctypes.data)
+    if rc == _lib.VO_ERR_UNSUPPORTED:
+        raise NotImplementedError(ctx.last_error())
+    ctx.check(rc)
+    return out[:N].reshape(N, 1, 2)
+
+
 def five_point(x1, x2, ctx=None):
     """All essential matrices through 5 normalised correspondences (stage test hook)."""
     x1 = np.ascontiguousarray(x1, dtype=np.float64).reshape(5, 2)
@@ -130,7 +172,10 @@ def solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs=None, use
                    reprojectionError=8.0, confidence=0.99, flags=SOLVEPNP_ITERATIVE, seed=OPENCV_RNG_SEED, ctx=None):
     """cv2.solvePnPRansac as the reference calls it (src/visual_slam.py:231-235: positional objectPoints, imagePoints,
     cameraMatrix, zeros(4)) -> (retval, rvec 3x1, tvec 3x1, inliers n_inl x 1 int32 indices or None).
-    Only the reference's configuration is built: zero distortion, no extrinsic guess, SOLVEPNP_ITERATIVE."""
+    Only the reference's configuration is built: zero distortion, no extrinsic guess, SOLVEPNP_ITERATIVE.
+    A camera with a real lens: undistort the image points first (undistortPoints with P = cameraMatrix, or FrontEnd.undistort on
+    resident keypoints) and pass zeros here.  That is not what cv2 computes with non-zero distCoeffs — cv2 measures the RANSAC
+    error in distorted pixels — so non-zero coefficients stay refused instead of being rerouted."""
     if distCoeffs is not None and np.any(np.asarray(distCoeffs, np.float64) != 0):
         raise NotImplementedError("only zero distortion coefficients are built (the reference passes np.zeros(4))")
     if useExtrinsicGuess or flags != SOLVEPNP_ITERATIVE:
