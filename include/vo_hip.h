@@ -620,8 +620,8 @@ int vo_slam_map(vo_ctx* ctx, int which, int32_t* cam_frame, double* cam_pose /*[
  * can reach any more keeps its place in the lists and in the bundle adjustment, as in the reference, but has no key.
  * [deviation] none in the results; the per-call cost is one k_slam_carry launch and the download of the map for vo_slam_map.
  * Several sequences per stream call: vo_slam_streams, below.  Out of scope: pruning points that have lost every
- * observation (the reference keeps them: the lists and k_bundle_adjust's cost grow with the flight), relocalisation against an
- * earlier map, and any change to the entries above. */
+ * observation (the reference keeps them: the lists and k_bundle_adjust's cost grow with the flight), relocalisation inside the
+ * walk (vo_map_localize, below, is the operator; nothing here calls it), and any change to the entries above. */
 int vo_slam_stream(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
                    double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
                    int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam,
@@ -685,8 +685,8 @@ int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, doub
  * always; row p belongs to the previous segment's gauge (or is zero) — except row 0 of a sequence whose first pair starts
  * segment 0, which holds that first camera as it does in vo_slam_chains.  A sequence that never loses a frame gets
  * vo_slam_chains' bytes in every output and map, segment = 0, cause = 0.
- * Out of scope: joining segments into one gauge (tracking was lost: there is nothing to join them with), relocalisation
- * against the old map, a restart form of vo_tracks_pnp_batch, ratio matches (VO_ERR_UNSUPPORTED as before). */
+ * Out of scope: joining segments into one gauge (tracking was lost: there is nothing to join them with), using vo_map_localize
+ * (below) against the old map from inside the walk, a restart form of vo_tracks_pnp_batch, ratio matches (VO_ERR_UNSUPPORTED as before). */
 int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/, const double* K, const vo_slam_opts* opts, int snapshot_seq,
                            double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
                            int32_t* n_corr, int32_t* n_inl, int32_t* status, int32_t* n_pts, int32_t* n_obs, int32_t* n_cam /*[B] each*/,
@@ -728,7 +728,7 @@ int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/,
  * restart; a key in a ghost row is cleared like any other.  The ghost rows keep alternating across segments.
  * [deviation] none in the results; the cost is one more launch per step, and four small downloads and the alive word per call.
  * Several sequences per stream call: vo_slam_streams, below.  Out of scope: joining segments into one gauge, relocalisation
- * against an old map, pruning points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change
+ * against an old map from inside the walk (vo_map_localize is the operator), pruning points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change
  * to the entries above. */
 int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
                            double* poses_pnp /*(B+1)x12*/, double* poses /*(B+1)x12*/,
@@ -775,7 +775,7 @@ int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, cons
  * on the stream / restart kernel bodies (k_slam_*_stream_restart_seqs), with one k_slam_carry_restart_seqs launch in front.
  * [deviation] none in the results.
  * Out of scope: a multi-stream without restart, changing S of a live stream (a flight that ends hands its seat to the next:
- * vo_slam_streams_replace, below), sequences that share a slot, joining segments or shards into one gauge, relocalisation,
+ * vo_slam_streams_replace, below), sequences that share a slot, joining segments or shards into one gauge, relocalisation from inside the walk,
  * pruning, ratio matches. */
 int vo_slam_streams(vo_ctx* ctx, int resume, int S, const int32_t* total_pairs /*[S]*/, const int32_t* seq_off /*[S+1]*/,
                     const double* K, const vo_slam_opts* opts, int snapshot_seq,
@@ -858,6 +858,64 @@ int vo_slam_stats_size(vo_ctx* ctx, int seq, int32_t* B, int32_t* max_cameras);
 int vo_slam_stats_counts(vo_ctx* ctx, int seq, int B, int32_t* n_cam /*[B]*/, int32_t* n_pts /*[B]*/, int32_t* n_obs /*[B]*/);
 int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*/, double* max_sqerr /*[B]*/, int32_t* n_high /*[B]*/,
                   int32_t* obs_hist /*[B][VO_STATS_HIST]*/, int32_t* obs_matrix /*[B][C][C]*/, int32_t* cam_frame /*[B][C]*/);
+
+/* ------------------------------------------------------------------ relocalisation: a resident frame placed in a map by its descriptors
+ * What the reference carries and never uses: TrackedPoint keeps match.descriptor1 for every map point (src/visual_slam.py:72-76,
+ * :102-106) and MatchWithMap has descriptor1 (image), descriptor2 (map) and a distance that is always `0  # TODO: Set to the proper
+ * feature distance` (:211-217).  Localisation there, and in vo_tracks_pnp_batch / vo_slam_*, goes through feature tracks from the
+ * previous frame only; a frame without a track into the map — after a loss, a loop frame, another camera's frame — cannot be placed.
+ * These entries place it: for a staged map of npt points (xyz float64, one descriptor row each) and Q detected slots,
+ *   1 matches = bf.match(frame descriptors, map descriptors) of cv2.BFMatcher(NORM_L2 for SIFT rows / NORM_HAMMING for ORB rows,
+ *     crossCheck=True): query = frame, train = map (MatchWithMap's orientation); strict mutual nearest neighbours, the lowest index
+ *     winning ties in both directions (vo_pair_opts.match_mode 0); ascending keypoint order; distance as cv2 reports it, float32:
+ *     sqrtf((float)d^2) for SIFT rows, the integer as float for ORB rows — the value the reference's TODO asks for.  Then
+ *     `m.distance < max_distance`, strict, the float32 value against the double (visual_odometry_template_02/visual_slam.py:205-208);
+ *     max_distance <= 0: no filter.
+ *   2 correspondences in match order: obj[k] = the map point of trainIdx, img[k] = float64(kp_xy[queryIdx]).
+ *   3 cv2.solvePnPRansac(obj, img, K, zeros(4)) with pnp_iterations, reproj_err, confidence, seed (cv2: 100, 8.0, 0.99, 2^64 - 1) and
+ *     the context's vo_set_pnp_refine mode: exactly vo_solve_pnp_ransac_batch on those arrays (k_pnp_ransac, unchanged).
+ *     poses[q] = [Rodrigues(rvec) | tvec], world -> camera IN THE MAP'S OWN GAUGE.  status[q]: VO_OK; VO_ERR_TOO_FEW (fewer than 4
+ *     correspondences: cv2 raises) or VO_ERR_NO_MODEL (retval False), pose zeros; a model with fewer than min_inliers inliers becomes
+ *     VO_ERR_NO_MODEL, pose zeros, its n_inl still reported.  A failed query does not touch the others.
+ * Nothing returns to the host between the three steps.  Two calls on the same input return the same bytes.
+ *
+ * vo_map_stage: the map from host arrays — rows [npt][D], D = 32 under an ORB batch configuration and 128 (values 0..255) under a
+ *   SIFT one; points [npt][3].  The parity seam, and how a caller brings back a map saved earlier (vo_map_rows).  npt 0 .. 65536;
+ *   more: VO_ERR_UNSUPPORTED.  VO_ERR_NOT_CONFIGURED before a batch configuration.  VO_ERR_INVALID for a SIFT row with |row|^2 > 2^20,
+ *   the bound the integer matcher's order rests on (vo_stage_sift_rows' rule); no map is staged then.
+ * vo_map_from_slam: the map of the latest vo_slam_chain (seq = 0) or of sequence seq of the latest vo_slam_chains[_restart]; which as
+ *   in vo_slam_map.  Copied ON THE DEVICE, no host round trip: the coordinates as the map's list holds them, and per point the
+ *   descriptor row of its owning feature, gathered from the slot it was detected in (pt_feature -> chain frame -> slot of the latest
+ *   vo_pairs_run, keypoint): TrackedPoint.descriptor = match.descriptor1.  The slots must still hold those frames.  VO_ERR_INVALID
+ *   where vo_slam_map / vo_slam_chains_map would refuse, and when another call has laid out the context's scratch buffer since the
+ *   chain ran (the single-call operators, vo_tracks_pnp_batch, another chain): call it right after the chain.  VO_ERR_UNSUPPORTED for
+ *   a stream's map (vo_slam_stream*, vo_slam_streams): its older frames have left their slots and their descriptor rows are gone —
+ *   a stream keeps no descriptor store of its own; save each chunk's map with vo_slam_chains + vo_map_rows instead.
+ * vo_map_rows: the staged map back (up to cap points; *npt = its size): what a caller saves before the frames leave their slots.
+ * vo_map_localize: Q <= max_pairs detected slots against the staged map in one call.  No staged map: VO_ERR_INVALID.  A slot flagged
+ *   for its descriptor norm (SIFT): VO_ERR_INVALID AFTER the run, as vo_pairs_run reports it.  Profiling stages: match_nn (k_nn_map),
+ *   match_select (k_map_select), misc (k_pnp_ransac and the poses).
+ * vo_map_matches: query q's match list of the latest vo_map_localize — map point, keypoint, distance — and solvePnPRansac's inlier
+ *   mask (0 / 1) over it.
+ * Lifetime: the staged map and vo_map_localize's work buffers are an allocation of their own, released by vo_destroy and by a
+ *   configure call.  vo_pairs_run, the vo_slam_* calls and detections leave it alone; vo_map_localize leaves the pair results, the
+ *   chain's maps and a live stream alone.  A new vo_map_stage / vo_map_from_slam replaces the map (also when it fails).
+ * Out of scope: automatic use inside the restart walks, a stream's own descriptor store, ratio matching against the map, the
+ * similarity that joins two segments' gauges, maps of more than 65536 points. */
+typedef struct {
+    double   max_distance;      /* 0: no filter */
+    int32_t  pnp_iterations;    /* 100 */
+    double   reproj_err;        /* 8.0 */
+    double   confidence;        /* 0.99 */
+    uint64_t seed;              /* 0xFFFFFFFFFFFFFFFF */
+    int32_t  min_inliers;       /* 0 */
+} vo_reloc_opts;
+int vo_map_stage(vo_ctx* ctx, const uint8_t* rows /*[npt][D]*/, const double* points /*[npt][3]*/, int npt);
+int vo_map_from_slam(vo_ctx* ctx, int seq, int which);
+int vo_map_rows(vo_ctx* ctx, uint8_t* rows /*[cap][D]*/, double* points /*[cap][3]*/, int cap, int32_t* npt);
+int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* opts,
+                    double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
+int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
 
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the

@@ -50,6 +50,11 @@ class SlamOpts(C.Structure):
                 ("snapshot_pair", C.c_int32), ("snapshot_stage", C.c_int32)]
 
 
+class RelocOpts(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("pnp_iterations", C.c_int32), ("reproj_err", C.c_double), ("confidence", C.c_double),
+                ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
+
+
 PAIR_RESULT_DTYPE = np.dtype([("n_kp1", "<i4"), ("n_kp2", "<i4"), ("n_match", "<i4"), ("n_inl", "<i4"),
                               ("n_good", "<i4"), ("status", "<i4"), ("ransac_iters", "<i4"), ("reserved", "<i4"),
                               ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,))], align=True)
@@ -116,6 +121,11 @@ _SIGS = {
     "vo_slam_stats_size": (C.c_int, [_P, C.c_int, _P, _P]),
     "vo_slam_stats_counts": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "vo_slam_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "vo_map_stage": (C.c_int, [_P, _P, _P, C.c_int]),
+    "vo_map_from_slam": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vo_map_rows": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "vo_map_localize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "vo_comm_unique_id": (C.c_int, [_P]),
     "vo_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "vo_comm_destroy": (C.c_int, [_P]),

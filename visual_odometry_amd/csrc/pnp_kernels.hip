@@ -1851,6 +1851,27 @@ void launch_rodrigues(hipStream_t s, const double* in, int in_is_matrix, double*
     hipLaunchKernelGGL(k_rodrigues, dim3(1), dim3(64), 0, s, in, in_is_matrix, out);
 }
 
+// The poses of B problems k_pnp_ransac has solved (vo_map_localize): [Rodrigues(rvec) | tvec] row-major 3 x 4, k_rodrigues'
+// arithmetic; zeros for a problem without a model.  A model with fewer than min_inliers inliers is turned into VO_ERR_NO_MODEL here.
+__global__ void k_pnp_poses(const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int st = status[b];
+    if (st == VO_OK && ninl[b] < min_inliers) { st = VO_ERR_NO_MODEL; status[b] = st; }
+    double* P = poses + (size_t)b * 12;
+    if (st != VO_OK) { for (int k = 0; k < 12; k++) P[k] = 0.0; return; }
+    double R[9], r[3] = {rvec[3 * b], rvec[3 * b + 1], rvec[3 * b + 2]};
+    dp_rodrigues_to_mat(r, R);
+    for (int rr = 0; rr < 3; rr++) { for (int c = 0; c < 3; c++) P[rr * 4 + c] = R[rr * 3 + c]; P[rr * 4 + 3] = tvec[3 * b + rr]; }
+}
+
+void launch_pnp_poses(hipStream_t s, const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses)
+{
+    if (B <= 0) return;
+    hipLaunchKernelGGL(k_pnp_poses, dim3((B + 63) / 64), dim3(64), 0, s, rvec, tvec, ninl, status, B, min_inliers, poses);
+}
+
 
 // ------------------------------------------------------------------ the localisation chain: the camera of a localised frame
 // src/visual_slam.py:237-251: retval -> R, _ = cv2.Rodrigues(rvec); TrackedCamera(R, tvec, ...).  Also the two projection

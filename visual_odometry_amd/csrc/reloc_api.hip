@@ -1,0 +1,162 @@
+// reloc_api.hip — the vo_map_* entry points of libvo_hip.so: a frame placed in a map by its descriptors (include/vo_hip.h,
+// "relocalisation").  Host code only; the kernels are reloc_kernels.hip and, unchanged, k_pnp_ransac (pnp_kernels.hip).
+// vo_map_from_slam is in slam_api.hip, beside the maps it reads; it stages through map_stage_device like vo_map_stage.
+#include "vo_host.h"
+
+#define VO_MAP_MAX_POINTS 65536
+
+// Room for npt rows and for the work of max_pairs queries of kp_cap keypoints.  The allocation is kept while it fits (rows past npt
+// then keep what a larger map left); otherwise it is released as a whole and made again.
+static int map_reserve(vo_ctx* ctx, const Batch& b, int npt)
+{
+    MapState& M = ctx->map;
+    const int D = b.sift ? 128 : 32, rows = std::max(256, (npt + 255) & ~255);
+    if (M.m.rows && M.m.D == D && M.m.cap_rows >= rows && M.Q_cap >= b.max_pairs && M.kp_cap == b.kp_cap) return VO_OK;
+    if ((size_t)b.max_pairs * b.kp_cap >= ((size_t)1 << 31) || (size_t)b.max_pairs * rows >= ((size_t)1 << 31))
+        FAIL(VO_ERR_INVALID, "max_pairs x kp_cap and max_pairs x map rows must fit 32-bit indices");
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    drop_map(ctx);
+    const size_t R = (size_t)rows, Q = (size_t)b.max_pairs, C = (size_t)b.kp_cap;
+    DevList& mem = M.mem; MapBuf& m = M.m; RelocBuf& r = M.r;
+    HIPCHK(mem.alloc(&m.rows, R * D)); HIPCHK(mem.alloc(&m.xyz, R * 3)); HIPCHK(mem.alloc(&m.flag, 1));
+    if (b.sift) {
+        HIPCHK(mem.alloc(&m.img, R * 128)); HIPCHK(mem.alloc(&m.norms, R));
+        HIPCHK(hipMemsetAsync(m.img, 0, R * 128, ctx->stream)); HIPCHK(hipMemsetAsync(m.norms, 0, R * sizeof(int), ctx->stream));
+    }
+    HIPCHK(hipMemsetAsync(m.rows, 0, R * D, ctx->stream));
+    HIPCHK(mem.alloc(&r.slots, Q)); HIPCHK(mem.alloc(&r.nn_idx, Q * C)); HIPCHK(mem.alloc(&r.nn_dist, Q * C)); HIPCHK(mem.alloc(&r.rn_idx, Q * R));
+    HIPCHK(mem.alloc(&r.m_q, Q * C)); HIPCHK(mem.alloc(&r.m_t, Q * C)); HIPCHK(mem.alloc(&r.m_d, Q * C)); HIPCHK(mem.alloc(&r.m_count, Q));
+    HIPCHK(mem.alloc(&r.obj, Q * C * 3)); HIPCHK(mem.alloc(&r.img, Q * C * 2)); HIPCHK(mem.alloc(&r.off, 2 * Q));
+    HIPCHK(mem.alloc(&r.rvec, 3 * Q)); HIPCHK(mem.alloc(&r.tvec, 3 * Q)); HIPCHK(mem.alloc(&r.mask, Q * C));
+    HIPCHK(mem.alloc(&r.ninl, Q)); HIPCHK(mem.alloc(&r.status, Q)); HIPCHK(mem.alloc(&r.poses, 12 * Q)); HIPCHK(mem.alloc(&M.dK, 9));
+    m.D = D; m.cap_rows = rows; m.npt = 0;
+    M.Q_cap = b.max_pairs; M.kp_cap = b.kp_cap;
+    return VO_OK;
+}
+
+int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int npt, const char* who)
+{
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "%s: vo_batch_configure[_sift] has not been called", who);
+    if (npt < 0) FAIL(VO_ERR_INVALID, "%s: npt must not be negative", who);
+    if (npt > VO_MAP_MAX_POINTS) FAIL(VO_ERR_UNSUPPORTED, "%s: a staged map holds at most %d points, got %d", who, VO_MAP_MAX_POINTS, npt);
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc = map_reserve(ctx, b, npt); if (rc) return rc;
+    MapState& M = ctx->map;
+    hipStream_t s = ctx->stream;
+    M.staged = false; M.last_Q = 0;
+    M.m.npt = npt;
+    HIPCHK(hipMemsetAsync(M.m.flag, 0, sizeof(int), s));
+    launch_map_gather(s, M.m, src, key, n_keys, xyz);
+    HIPCHK(hipGetLastError());
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, M.m.flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flag & 2) FAIL(VO_ERR_INVALID, "%s: a SIFT descriptor row of the map broke the norm bound of the integer matcher (|row|^2 > 2^20)", who);
+    M.staged = true;
+    return VO_OK;
+}
+
+extern "C" int vo_map_stage(vo_ctx* ctx, const uint8_t* rows, const double* points, int npt)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_map_stage: vo_batch_configure[_sift] has not been called");
+    if (npt < 0 || (npt > 0 && (!rows || !points))) FAIL(VO_ERR_INVALID, "vo_map_stage: npt >= 0 rows and points are needed");
+    if (npt > VO_MAP_MAX_POINTS) FAIL(VO_ERR_UNSUPPORTED, "vo_map_stage: a staged map holds at most %d points, got %d", VO_MAP_MAX_POINTS, npt);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));                        // the staging buffer may be in use
+    const size_t D = b.sift ? 128 : 32, row_bytes = ((size_t)npt * D + 255) & ~(size_t)255, need = row_bytes + (size_t)npt * 24;
+    uint8_t* drows = nullptr; double* dxyz = nullptr;
+    if (npt > 0) {
+        int rc = ctx->staging.grow(ctx, need); if (rc) return rc;
+        drows = ctx->staging.p; dxyz = (double*)(ctx->staging.p + row_bytes);
+        HIPCHK(hipMemcpyAsync(drows, rows, (size_t)npt * D, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dxyz, points, (size_t)npt * 24, hipMemcpyHostToDevice, s));
+    }
+    return map_stage_device(ctx, drows, nullptr, 0, dxyz, npt, "vo_map_stage");
+}
+
+extern "C" int vo_map_rows(vo_ctx* ctx, uint8_t* rows, double* points, int cap, int32_t* npt)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const MapState& M = ctx->map;
+    if (!M.staged) FAIL(VO_ERR_INVALID, "vo_map_rows: no map is staged");
+    if (!npt || cap < 0) FAIL(VO_ERR_INVALID, "bad arguments");
+    *npt = M.m.npt;
+    const size_t n = (size_t)std::min(cap, M.m.npt);
+    if (n == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (rows) HIPCHK(hipMemcpy(rows, M.m.rows, n * M.m.D, hipMemcpyDeviceToHost));
+    if (points) HIPCHK(hipMemcpy(points, M.m.xyz, n * 24, hipMemcpyDeviceToHost));
+    return VO_OK;
+}
+
+extern "C" int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* o, double* poses,
+                               int32_t* n_match, int32_t* n_inl, int32_t* status)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_map_localize: vo_batch_configure[_sift] has not been called");
+    MapState& M = ctx->map;
+    if (!M.staged) FAIL(VO_ERR_INVALID, "vo_map_localize: no map is staged (vo_map_stage, vo_map_from_slam)");
+    if (Q < 0 || Q > b.max_pairs || Q > M.Q_cap) FAIL(VO_ERR_INVALID, "vo_map_localize: 0 <= Q <= max_pairs queries, got %d", Q);
+    if (!K || !o || (Q > 0 && (!slots || !poses || !n_match || !n_inl || !status))) FAIL(VO_ERR_INVALID, "bad arguments");
+    for (int q = 0; q < Q; q++) if (slots[q] < 0 || slots[q] >= b.max_frames) FAIL(VO_ERR_INVALID, "vo_map_localize: slot %d out of range", slots[q]);
+    M.last_Q = 0;
+    if (Q == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const RelocBuf& r = M.r;
+    const int cap = b.kp_cap;
+    HIPCHK(hipMemcpyAsync(r.slots, slots, (size_t)Q * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(M.dK, K, 72, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(r.rvec, 0, (size_t)Q * 24, s)); HIPCHK(hipMemsetAsync(r.tvec, 0, (size_t)Q * 24, s));
+    { StageTimer t(ctx, ST_MATCH_NN); launch_nn_map(s, M.m, r, Q, b.desc, b.desc_x, b.norms, b.kp_count, cap, desc_x_rows(cap)); }
+    { StageTimer t(ctx, ST_MATCH_SELECT); launch_map_select(s, M.m, r, Q, b.kp_xy, b.kp_count, cap, o->max_distance); }
+    {
+        StageTimer t(ctx, ST_MISC);
+        launch_pnp_ransac(s, r.obj, r.img, r.off, Q, M.dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                          ctx->pnp_refine, r.rvec, r.tvec, r.mask, r.ninl, r.status, 2);
+        launch_pnp_poses(s, r.rvec, r.tvec, r.ninl, r.status, Q, o->min_inliers, r.poses);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(poses, r.poses, (size_t)Q * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_match, r.m_count, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, r.ninl, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, r.status, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (ctx->prof) prof_collect(ctx);
+    M.last_Q = Q;
+    if (b.sift) {                                           // a flagged slot, reported after the run as vo_pairs_run reports it
+        std::vector<int> fl((size_t)b.max_frames);
+        HIPCHK(hipMemcpy(fl.data(), b.flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int q = 0; q < Q; q++)
+            if (fl[(size_t)slots[q]] & 2) FAIL(VO_ERR_INVALID, "a SIFT descriptor row broke the norm bound of the integer matcher (slot %d)", (int)slots[q]);
+    }
+    return VO_OK;
+}
+
+extern "C" int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const MapState& M = ctx->map;
+    if (!M.staged || q < 0 || q >= M.last_Q || !n_out || cap < 0) FAIL(VO_ERR_INVALID, "vo_map_matches: no such query in the most recent vo_map_localize");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, M.r.m_count + q, sizeof(int), hipMemcpyDeviceToHost));
+    if (n > cap) n = cap;
+    *n_out = n;
+    const size_t o = (size_t)q * M.kp_cap;
+    if (n > 0) {
+        if (pt_idx) HIPCHK(hipMemcpy(pt_idx, M.r.m_t + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (kp_idx) HIPCHK(hipMemcpy(kp_idx, M.r.m_q + o, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        if (dist) HIPCHK(hipMemcpy(dist, M.r.m_d + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+        if (inlier_mask) HIPCHK(hipMemcpy(inlier_mask, M.r.mask + o, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return VO_OK;
+}

@@ -115,6 +115,7 @@ static int slam_place_scratch(vo_ctx* ctx, const SlamDims& d, SlamBufs& b)
 {
     const size_t bytes = slam_layout(d, nullptr, b);
     int rc = ctx->scratch.grow(ctx, bytes, bytes + bytes / 4 + 64); if (rc) return rc;
+    ctx->scratch_epoch++;
     slam_layout(d, ctx->scratch.p, b);
     return VO_OK;
 }
@@ -333,6 +334,12 @@ static int slam_download(vo_ctx* ctx, bool multi, int steps, int snap_seq, const
         ctx->last.seq_map = std::move(maps);
         if (snap_seq >= 0) { ctx->last.snap_map = std::move(smap); ctx->last.snap_seq = snap_seq; }
     }
+    // ... and where the lists themselves still lie, for vo_map_from_slam
+    LastRun::DevMaps& dv = ctx->last.dev;
+    dv = LastRun::DevMaps();
+    for (size_t q = 0; q < S; q++) dv.seq.push_back({seq[q].sb.m.pt_key, seq[q].sb.m.pt_xyz});
+    if (snap_seq >= 0) dv.snap = {b.snap.pt_key, b.snap.pt_xyz};
+    dv.stream = d.stream; dv.n_keys = (int)((size_t)d.F * d.cap); dv.epoch = ctx->scratch_epoch;
     if (d.stats) { int rc = slam_stats_download(ctx, b.stats, std::move(seq_off)); if (rc) return rc; }
     return VO_OK;
 }
@@ -878,6 +885,28 @@ static const LastRun::Map* slam_chains_map_of(vo_ctx* ctx, int seq, int which)
     else if (which == 1 && seq != l.snap_seq) why = "no such map: the most recent vo_slam_chains took no snapshot of this sequence";
     if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s", why); return nullptr; }
     return which == 1 ? &l.snap_map : &l.seq_map[(size_t)seq];
+}
+
+// The relocaliser's map from a chain that has just run: the coordinates as the map's list holds them and, per point, the
+// descriptor row of its owning feature (TrackedPoint.descriptor = match.descriptor1, src/visual_slam.py:72-76) gathered from the
+// slots by k_map_gather — pt_key is slot * kp_cap + keypoint already, the device form of pt_feature -> chain frame -> slot.  Device
+// to device: the host contributes the point count it already holds.
+extern "C" int vo_map_from_slam(vo_ctx* ctx, int seq, int which)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const LastRun& l = ctx->last;
+    const bool multi = !l.seq_map.empty();
+    if (!multi && seq != 0) FAIL(VO_ERR_INVALID, "the most recent vo_slam_* call had one sequence: seq must be 0, got %d", seq);
+    const LastRun::Map* m = multi ? slam_chains_map_of(ctx, seq, which) : slam_map_of(ctx, which);
+    if (!m) return VO_ERR_INVALID;
+    const LastRun::DevMaps& dv = l.dev;
+    if (dv.stream)
+        FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_slam: a stream's map names frames that have left their slots, and their descriptor rows with them");
+    if (dv.epoch != ctx->scratch_epoch || (size_t)seq >= dv.seq.size())
+        FAIL(VO_ERR_INVALID, "vo_map_from_slam: another call has used the scratch buffer the chain's map lay in; call it right after the chain");
+    const LastRun::DevMaps::Lists& L = which == 1 ? dv.snap : dv.seq[(size_t)seq];
+    const Batch b = batch(ctx);
+    return map_stage_device(ctx, b.desc, L.pt_key, dv.n_keys, L.pt_xyz, (int)(m->points.size() / 3), "vo_map_from_slam");
 }
 
 extern "C" int vo_slam_chains_map_size(vo_ctx* ctx, int seq, int which, int32_t* ncam, int32_t* npt, int32_t* nobs)

@@ -191,6 +191,7 @@ static void free_config(vo_ctx* c)
     c->pb_pairs = c->pb_cap = 0;
     clear_last_run(c);
     drop_slam_stream(c);
+    drop_map(c);
     c->undistorted.clear();
 }
 
@@ -198,7 +199,7 @@ static void comm_release(vo_ctx* ctx);
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F);
 
-extern "C" int vo_version(void) { return 120; }
+extern "C" int vo_version(void) { return 121; }
 
 extern "C" int vo_create(int device_id, vo_ctx** out)
 {
@@ -331,6 +332,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
         ctx->detector = 0;
         clear_last_run(ctx);
         drop_slam_stream(ctx);
+        drop_map(ctx);
         ctx->undistorted.clear();
         return VO_OK;
     }
@@ -2355,6 +2357,7 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     HIPCHK(hipStreamSynchronize(ctx->stream));
     clear_last_run(ctx);                                        // the pair buffers may be replaced below
     drop_slam_stream(ctx);
+    drop_map(ctx);
     ctx->undistorted.clear();
     // frames per launch chain: the small octaves' launches are latency-bound (a dependent chain of ~50 launches per sub-batch)
     // and the wave-per-keypoint kernels like long grids, so the more frames share a chain the better (1280 x 720, pairs/s with

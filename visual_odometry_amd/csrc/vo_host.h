@@ -100,6 +100,30 @@ struct LastRun {
         std::vector<int32_t> seq_off, n_high, counts, obs_hist, obs_matrix, cam_frame;
         std::vector<double> total_sqerr, max_sqerr;
     } stats;
+    // ... and where those maps still lie on the device, for vo_map_from_slam: the lists of a chain call live in the scratch buffer,
+    // which belongs to the next call that lays it out (scratch_epoch then moves on); a stream's map has lost its older frames' rows
+    struct DevMaps {
+        struct Lists { const int* pt_key = nullptr; const double* pt_xyz = nullptr; };
+        std::vector<Lists> seq;           // per sequence: the map at its end
+        Lists snap;                       // the snapshot's lists (of sequence snap_seq, or of the one chain)
+        bool stream = false;              // the call was a stream's: keys name ghost rows and frames that have left their slots
+        int n_keys = 0;                   // rows the slots' descriptor array holds: max_frames * kp_cap
+        uint64_t epoch = 0;               // scratch_epoch when the call laid the buffer out
+    } dev;
+};
+
+// The staged map of the relocaliser (vo_map_stage / vo_map_from_slam) and the work buffers of vo_map_localize: an allocation of its
+// own lifetime, released by vo_destroy and by a configure call; vo_pairs_run, the vo_slam_* calls and detections leave it alone.
+// It is sized when a map is staged — for that map's rows rounded up to 256 and the configuration's max_pairs x kp_cap — and kept
+// while the next map fits: rows past npt then hold what the larger map left, and k_nn_map has to bound its reads by npt alone.
+struct MapState {
+    DevList mem;
+    bool staged = false;
+    MapBuf m{};
+    RelocBuf r{};
+    double* dK = nullptr;
+    int Q_cap = 0, kp_cap = 0;            // what the work buffers were sized for
+    int last_Q = 0;                       // queries of the most recent vo_map_localize (vo_map_matches); 0: none since the map was staged
 };
 
 // vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one
@@ -173,6 +197,8 @@ struct vo_ctx {
     double* dK = nullptr;
     LastRun last;
     SlamStream stream_map;                // vo_slam_stream's resident map (its own lifetime: see drop_slam_stream)
+    MapState map;                         // the relocaliser's staged map (its own lifetime: see drop_map)
+    uint64_t scratch_epoch = 0;           // counts the layouts placed in `scratch`: what an earlier call left there is gone when it has moved
 
     // scratch for the single-call operators
     DevList raw_mem;                      // the single-call matcher: raw_desc, raw_desc_x, raw_xy, raw_count, raw_pb.*
@@ -233,6 +259,7 @@ template <typename T> int Growable<T>::grow(vo_ctx* ctx, size_t need, size_t n)
 inline int ScratchLayout::place(vo_ctx* ctx)
 {
     int rc = ctx->scratch.grow(ctx, bytes, bytes + bytes / 4 + 64); if (rc) return rc;
+    ctx->scratch_epoch++;
     place_at(ctx->scratch.p);
     return VO_OK;
 }
@@ -241,8 +268,12 @@ inline int ScratchLayout::place(vo_ctx* ctx)
 // starts a new one and every vo_slam_chain* call come here.  (Every call that uses the allocation has waited for the context's stream before it returned.)
 static inline void drop_slam_stream(vo_ctx* ctx) { ctx->stream_map = SlamStream(); }
 
+// The end of the staged map: vo_destroy (the context's destructor) and the configure calls.  (vo_map_localize waits for the stream.)
+static inline void drop_map(vo_ctx* ctx) { ctx->map = MapState(); }
+
 static inline void forget_slam_maps(vo_ctx* ctx)
 {
+    ctx->last.dev = LastRun::DevMaps();
     ctx->last.map[0] = LastRun::Map(); ctx->last.map[1] = LastRun::Map();
     ctx->last.seq_map.clear(); ctx->last.snap_map = LastRun::Map(); ctx->last.snap_seq = -1;
     ctx->last.stats = LastRun::Stats();
@@ -286,3 +317,8 @@ int ensure_rng(vo_ctx* ctx, uint64_t seed);
 // What vo_tracks_pnp_batch and vo_slam_chain ask of the most recent vo_pairs_run: all its B pairs, triangulated, every slot
 // inside the configuration, the pairs a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference walks a sequence in
 int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out);
+
+// The one way a map is staged (reloc_api.hip): npt rows through k_map_gather — row i of `src` (device, [npt][D]) with key ==
+// nullptr, else row key[i] of the slots' descriptors — and its coordinates xyz (device, [npt][3]).  vo_map_stage uploads and
+// comes here; vo_map_from_slam (slam_api.hip) comes here with the map's own lists.  Synchronous.
+int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int npt, const char* who);

@@ -454,5 +454,38 @@ struct StatsBuf {
 };
 void launch_slam_stats(hipStream_t s, int p, SlamBuf sb, StatsBuf out);
 void launch_slam_stats_seqs(hipStream_t s, int j, const SlamSeq* seqs, int S, StatsBuf out);
+// ---- relocalisation of resident frames against a staged map by descriptors (reloc_kernels.hip): vo_map_stage / _from_slam / _localize
+struct MapBuf {
+    int      D;                         // bytes of a descriptor row: 32 under an ORB configuration, 128 under a SIFT one
+    int      cap_rows;                  // rows the arrays have room for (a multiple of 256); rows past npt keep what a larger map left
+    int      npt;
+    uint8_t* rows;                      // [cap_rows][D] the rows as staged: what vo_map_rows returns, and the operand of the popcount kernel
+    uint8_t* img;                       // SIFT: the int8 operand image k_nn_l2i8 reads, one "slot" of cap_rows rows (sift_rows.h)
+    int*     norms;                     // SIFT: [cap_rows] |v - 128|^2
+    double*  xyz;                       // [cap_rows][3]
+    int*     flag;                      // [1] bit 1: a SIFT row broke the norm bound
+};
+struct RelocBuf {
+    int*     slots;                     // [Q] the queries' frame slots
+    int*     nn_idx; int* nn_dist;      // [Q][kp_cap] nearest map row of every keypoint and its distance (SIFT: integer d^2; ORB: Hamming)
+    int*     rn_idx;                    // [Q][cap_rows] nearest keypoint of query q for every map row
+    int*     m_q; int* m_t; float* m_d; // [Q][kp_cap] the match list: keypoint, map point, cv2's float32 distance
+    int*     m_count;                   // [Q]
+    double*  obj; double* img;          // [Q][kp_cap][3], [Q][kp_cap][2]: query q's problem starts at row q kp_cap
+    int*     off;                       // [Q][2] {first, end}: k_pnp_ransac's offsets with off_stride 2
+    double*  rvec; double* tvec;        // [Q][3]
+    uint8_t* mask;                      // [Q][kp_cap]
+    int*     ninl; int* status;         // [Q]
+    double*  poses;                     // [Q][12]
+};
+// rows of a map from the slots' descriptors (src [slot][kp_cap][D], key = slot kp_cap + keypoint, n_keys = rows src holds) or, with
+// key == nullptr, from src [npt][D] as it stands: both through the one store
+void launch_map_gather(hipStream_t s, MapBuf m, const uint8_t* src, const int* key, int n_keys, const double* xyz);
+void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
+                   int kp_cap, int cap_x);
+void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance);
+// [Rodrigues(rvec) | tvec] of B solved problems, zeros for the others; a model with fewer than min_inliers inliers becomes VO_ERR_NO_MODEL
+void launch_pnp_poses(hipStream_t s, const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses);
+
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

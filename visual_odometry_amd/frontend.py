@@ -512,6 +512,80 @@ class FrontEnd:
         k = n.value
         return qi[:k].copy(), ti[:k].copy(), d[:k].copy(), m[:k].copy()
 
+    # ---- relocalisation: a resident frame placed in a map by its descriptors (vo_map_*) -------
+    def _map_row_width(self):
+        return 128 if self.detector == "sift" else 32
+
+    def stage_map(self, rows, points):
+        """Stage a map the caller holds (vo_map_stage): rows [npt, 32] uint8 under ORB, [npt, 128] under SIFT (uint8, or the
+        integer-valued float32 rows features() hands out); points [npt, 3] float64 in the map's own gauge.  Replaces the map
+        staged before; up to 65536 points (NotImplementedError beyond)."""
+        D = self._map_row_width()
+        r = np.asarray(rows)
+        if r.ndim != 2 or r.shape[1] != D:
+            raise ValueError(f"rows must be [npt, {D}]")
+        if r.dtype != np.uint8:
+            u = r.astype(np.uint8)
+            if not np.array_equal(u.astype(r.dtype), r):
+                raise ValueError("descriptor rows must hold integer values 0..255")
+            r = u
+        r = np.ascontiguousarray(r)
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        if len(p) != len(r):
+            raise ValueError("points must be [npt, 3]")
+        c = self.ctx
+        rc = c.lib.vo_map_stage(c.handle, r.ctypes.data, p.ctypes.data, len(r))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+
+    def map_from_slam(self, which=0, seq=0):
+        """Stage the map of the latest slam_chain (seq=0) or of sequence `seq` of the latest slam_chains (vo_map_from_slam; which
+        as in slam_map), on the device: the map's coordinates, and per point the descriptor row of its owning feature
+        (TrackedPoint.descriptor = match.descriptor1) gathered from the slot it was detected in.  Call it right after the chain,
+        while the slots still hold its frames.  A stream's map: NotImplementedError (its older frames have left their slots)."""
+        c = self.ctx
+        rc = c.lib.vo_map_from_slam(c.handle, int(seq), int(which))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+
+    def map_rows(self):
+        """The staged map back (vo_map_rows): (rows [npt, D] uint8, points [npt, 3] float64) — what to save before a segment's
+        frames leave their slots, and what stage_map takes later."""
+        c = self.ctx
+        n = C.c_int32(0)
+        c.check(c.lib.vo_map_rows(c.handle, None, None, 0, C.addressof(n)))
+        rows = np.zeros((n.value, self._map_row_width()), np.uint8); pts = np.zeros((n.value, 3))
+        c.check(c.lib.vo_map_rows(c.handle, rows.ctypes.data, pts.ctypes.data, n.value, C.addressof(n)))
+        return rows, pts
+
+    def relocalize(self, slots, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0):
+        """Place detected slots in the staged map by their descriptors (vo_map_localize), all in one call on the device:
+        bf.match(frame, map) with crossCheck=True -> `distance < max_distance` (0: no filter) -> cv2.solvePnPRansac on the 3D-2D
+        matches.  Returns dict(poses [Q, 3, 4] world -> camera in the map's gauge, zeros where status != 0; n_match, n_inl,
+        status [Q]: 0, VO_ERR_TOO_FEW (fewer than 4 matches) or VO_ERR_NO_MODEL (no model, or fewer than min_inliers inliers))."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        Q = len(sl)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        opts = _lib.RelocOpts(float(max_distance), int(iterations), float(reproj_err), float(confidence), int(seed), int(min_inliers))
+        poses = np.zeros((Q, 12)); nm = np.zeros(Q, np.int32); ni = np.zeros(Q, np.int32); st = np.zeros(Q, np.int32)
+        c = self.ctx
+        c.check(c.lib.vo_map_localize(c.handle, sl.ctypes.data, Q, K.ctypes.data, C.addressof(opts), poses.ctypes.data, nm.ctypes.data,
+                                      ni.ctypes.data, st.ctypes.data))
+        return dict(poses=poses.reshape(Q, 3, 4), n_match=nm, n_inl=ni, status=st)
+
+    def map_matches(self, q):
+        """Query q's matches of the latest relocalize(): (map point [n], keypoint [n], distance [n] float32 as cv2 reports it —
+        the value of the reference's `distance = 0  # TODO` — and solvePnPRansac's inlier mask [n] uint8), in keypoint order."""
+        cap = self.kp_cap
+        pi = np.empty(cap, np.int32); ki = np.empty(cap, np.int32); d = np.empty(cap, np.float32)
+        m = np.empty(cap, np.uint8); n = C.c_int32(0)
+        c = self.ctx
+        c.check(c.lib.vo_map_matches(c.handle, int(q), pi.ctypes.data, ki.ctypes.data, d.ctypes.data, m.ctypes.data, cap, C.addressof(n)))
+        k = n.value
+        return pi[:k].copy(), ki[:k].copy(), d[:k].copy(), m[:k].copy()
+
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on=True):
         c = self.ctx

@@ -230,3 +230,38 @@ def Rodrigues(src, ctx=None):
     else:
         raise ValueError("Rodrigues takes a 3-vector or a 3x3 matrix")
     return out, None
+
+
+def relocalize(map_points, map_descriptors, keypoints_xy, descriptors, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99,
+               seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None):
+    """Place one frame in a map by its descriptors, from host arrays (FrontEnd.stage_map + set_*_rows + relocalize in one call):
+    map_points [npt, 3] float64, map_descriptors [npt, D], keypoints_xy [n, 2], descriptors [n, D]; D = 32 (ORB rows, uint8:
+    Hamming) or 128 (SIFT rows, integer values 0..255: L2).  What the reference's MatchWithMap is for and never does
+    (src/visual_slam.py:211-217): bf.match(descriptors, map_descriptors) with crossCheck=True, `distance < max_distance` (0: no
+    filter), cv2.solvePnPRansac on the matches.  Returns dict(status, pose [3, 4] world -> camera in the map's gauge (zeros when
+    status != 0), n_match, n_inl, matches = (map point, keypoint, distance float32, inlier mask)).
+    The context is configured for this call (a small batch configuration sized to the frame); a caller with resident frames uses
+    FrontEnd.relocalize instead."""
+    from .frontend import FrontEnd
+    d = np.asarray(descriptors)
+    if d.ndim != 2 or d.shape[1] not in (32, 128):
+        raise ValueError("descriptors must be [n, 32] (ORB) or [n, 128] (SIFT)")
+    if d.dtype != np.uint8:
+        u = d.astype(np.uint8)
+        if not np.array_equal(u.astype(d.dtype), d):
+            raise ValueError("descriptor rows must hold integer values 0..255")
+        d = u
+    xy = np.ascontiguousarray(keypoints_xy, dtype=np.float32).reshape(-1, 2)
+    if len(xy) != len(d):
+        raise ValueError("keypoints_xy must be [n, 2]")
+    ctx = ctx or _lib.default_context()
+    if d.shape[1] == 128:
+        fe = FrontEnd(32, 32, max_frames=1, max_pairs=1, detector="sift", kp_cap=max(len(d), 1), ctx=ctx)
+        fe.set_sift_rows(0, d, xy)
+    else:
+        fe = FrontEnd(64, 64, max_frames=1, max_pairs=1, nfeatures=max(len(d), 1), nlevels=1, ctx=ctx)
+        fe.set_orb_rows(0, d, xy)
+    fe.stage_map(map_descriptors, map_points)
+    out = fe.relocalize([0], K, max_distance, iterations, reproj_err, confidence, seed, min_inliers)
+    return dict(status=int(out["status"][0]), pose=out["poses"][0], n_match=int(out["n_match"][0]), n_inl=int(out["n_inl"][0]),
+                matches=fe.map_matches(0))
