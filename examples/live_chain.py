@@ -6,7 +6,7 @@
     -> update_feature_mapper / estimate_current_camera_position (solvePnPRansac) / add_information_to_map   (:183-266, :153-180)
 
 Only the compressed file bytes cross PCIe; every stage after that reads what the previous one left in HBM.
-    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart] [--stream N] [--dist k1,k2,p1,p2[,k3]]
+    python examples/live_chain.py [--frames 8] [--width 3840 --height 2160 --scale 0.3] [--detector sift|orb] [--step 4.0] [--restart] [--stream N] [--dist k1,k2,p1,p2[,k3]] [--join MAX_ERROR [--blank F]]
 --restart: afterwards the complete map step (bundle adjustment, filter, camera limit) on the same resident pairs with restart=True — a lost frame
 starts a new map instead of ending the chain — and one track per segment, each in its own gauge.
 --stream N: the same files once more in chunks of N pairs through slam_stream on a front end with only N + 1 frame slots — the map stays on the
@@ -17,7 +17,12 @@ and a chunk that ends lost is continued — and one track per segment is printed
 segments of slam_chain(restart=True) on all the files.
 --dist k1,k2,p1,p2[,k3]: a camera with a real lens — after each detection the keypoints are undistorted on the device (FrontEnd.undistort,
 cv2.undistortPoints' arithmetic) and everything after runs on ideal pixels.  (The synthetic frames here come from a pinhole, so the option shows
-the call in place, not a better track.)  Without it the output is what it was."""
+the call in place, not a better track.)  Without it the output is what it was.
+--join MAX_ERROR [--blank F]: the segments of slam_chain(restart=True) in ONE gauge.  While the frames are resident every segment's pairs run
+once more as a sequence of slam_chains and its map is saved (map_from_slam + map_rows: points and their descriptor rows); every later map is
+aligned to the one before it by those rows (stage_map + align_maps: the similarity between the two gauges, MAX_ERROR in the earlier map's
+units, its first pair's baseline); join_segments composes the similarities and one track is printed.  --blank F replaces file F by a gray
+frame, so that there is a loss to join across."""
 import argparse
 import io
 import os
@@ -28,7 +33,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visual_odometry_amd import ingest, synth  # noqa: E402
-from visual_odometry_amd.frontend import FrontEnd, join_stream, split_segments  # noqa: E402
+from visual_odometry_amd.frontend import FrontEnd, join_segments, join_stream, split_segments  # noqa: E402
 
 
 def main():
@@ -42,6 +47,8 @@ def main():
     ap.add_argument("--stream", type=int, default=0, metavar="N", help="also walk the files in chunks of N pairs through slam_stream (N + 1 frame slots)")
     ap.add_argument("--dist", type=lambda s: [float(v) for v in s.split(",")], default=None, metavar="k1,k2,p1,p2[,k3]",
                     help="lens distortion coefficients: undistort the keypoints on the device after each detection (FrontEnd.undistort)")
+    ap.add_argument("--join", type=float, default=0.0, metavar="MAX_ERROR", help="join the restart segments into one gauge by their maps' descriptors (align_maps)")
+    ap.add_argument("--blank", type=int, default=-1, metavar="F", help="replace file F by a gray frame: a lost frame")
     a = ap.parse_args()
     if a.dist is not None and len(a.dist) not in (4, 5):
         ap.error("--dist takes 4 or 5 comma-separated coefficients")
@@ -51,7 +58,9 @@ def main():
     # a seeded synthetic flight rendered at the working size, blown up to "camera" files (there is no footage in the repository)
     seq = synth.sequence(n, dw, dh, step=a.step)
     files = []
-    for g in seq["frames"]:
+    for f, g in enumerate(seq["frames"]):
+        if f == a.blank:
+            g = np.full_like(g, 127)
         b = io.BytesIO()
         Image.fromarray(np.stack([g, g, g], -1)).resize((a.width, a.height), Image.BICUBIC).save(b, "JPEG", quality=92)
         files.append(b.getvalue())
@@ -78,6 +87,29 @@ def main():
         for i, sg in enumerate(out["segments"]):
             track = np.array([-P[:, :3].T @ P[:, 3] for P in sg["poses"]])
             print(f"segment {i}: frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']}, camera centres in its own gauge:")
+            print(np.round(track, 2))
+    if a.join > 0:
+        segs = fe.slam_chain(n - 1, K, restart=True)["segments"]
+        seg_pairs = [[[sg["first_pair"] + j, sg["first_pair"] + j + 1] for j in range(sg["n_pairs"])] for sg in segs]
+        fe.run_pairs([p for sp in seg_pairs for p in sp], K, want_points=True)
+        chains = fe.slam_chains([len(sp) for sp in seg_pairs], K)  # every segment as a sequence of its own: its track and its map
+        maps = []
+        for k in range(len(segs)):
+            fe.map_from_slam(seq=k)                             # on the device, while the segment's frames are in their slots
+            maps.append(fe.map_rows())                          # (rows, points): what survives the frames
+        sims = []
+        for k in range(1, len(segs)):
+            fe.stage_map(*maps[k - 1])
+            r = fe.align_maps(*maps[k], max_error=a.join)       # segment k's gauge -> segment k - 1's
+            print(f"segments {k - 1} <- {k}: maps of {len(maps[k - 1][0])} and {len(maps[k][0])} points, {r['n_match'][0]} matches, {r['n_inl'][0]} inliers, "
+                  f"status {r['status'][0]}, scale {r['scale'][0]:.4f}")
+            sims.append(None if r["status"][0] else (r["scale"][0], r["R"][0], r["t"][0]))
+        tracks = [dict(first_pair=sg["first_pair"], n_pairs=sg["n_pairs"], poses_pnp=c["poses_pnp"], poses=c["poses"]) for sg, c in zip(segs, chains)]
+        joined, loose = join_segments(tracks, sims)
+        print(f"one track in segment 0's gauge ({len(joined)} of {len(segs)} segments joined; not connected: {loose}):")
+        for sg in joined:
+            track = np.array([-P[:, :3].T @ P[:, 3] for P in sg["poses"]])
+            print(f"frames {sg['first_pair']}..{sg['first_pair'] + sg['n_pairs']} (scale {sg['sim'][0]:.4f}):")
             print(np.round(track, 2))
     if a.stream > 0:
         whole = fe.slam_chain(n - 1, K, restart=a.restart)      # the yardstick: one call, every frame resident

@@ -685,7 +685,7 @@ int vo_slam_chains_map(vo_ctx* ctx, int seq, int which, int32_t* cam_frame, doub
  * always; row p belongs to the previous segment's gauge (or is zero) — except row 0 of a sequence whose first pair starts
  * segment 0, which holds that first camera as it does in vo_slam_chains.  A sequence that never loses a frame gets
  * vo_slam_chains' bytes in every output and map, segment = 0, cause = 0.
- * Out of scope: joining segments into one gauge (tracking was lost: there is nothing to join them with), using vo_map_localize
+ * Out of scope: joining segments into one gauge inside the walk (vo_map_align, below, joins two saved maps afterwards), using vo_map_localize
  * (below) against the old map from inside the walk, a restart form of vo_tracks_pnp_batch, ratio matches (VO_ERR_UNSUPPORTED as before). */
 int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/, const double* K, const vo_slam_opts* opts, int snapshot_seq,
                            double* poses_pnp /*(B+S)x12*/, double* poses /*(B+S)x12*/,
@@ -727,7 +727,7 @@ int vo_slam_chains_restart(vo_ctx* ctx, int S, const int32_t* seq_off /*[S+1]*/,
  * and k_slam_carry have a restart form (slam_kernels.hip).  A point whose key the carry marked none has nothing to clear at a
  * restart; a key in a ghost row is cleared like any other.  The ghost rows keep alternating across segments.
  * [deviation] none in the results; the cost is one more launch per step, and four small downloads and the alive word per call.
- * Several sequences per stream call: vo_slam_streams, below.  Out of scope: joining segments into one gauge, relocalisation
+ * Several sequences per stream call: vo_slam_streams, below.  Out of scope: joining segments into one gauge inside the walk (vo_map_align), relocalisation
  * against an old map from inside the walk (vo_map_localize is the operator), pruning points without observations, ratio matches, a restart form of vo_tracks_pnp_batch, any change
  * to the entries above. */
 int vo_slam_stream_restart(vo_ctx* ctx, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* opts,
@@ -900,8 +900,8 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  * Lifetime: the staged map and vo_map_localize's work buffers are an allocation of their own, released by vo_destroy and by a
  *   configure call.  vo_pairs_run, the vo_slam_* calls and detections leave it alone; vo_map_localize leaves the pair results, the
  *   chain's maps and a live stream alone.  A new vo_map_stage / vo_map_from_slam replaces the map (also when it fails).
- * Out of scope: automatic use inside the restart walks, a stream's own descriptor store, ratio matching against the map, the
- * similarity that joins two segments' gauges, maps of more than 65536 points. */
+ * Out of scope: automatic use inside the restart walks, a stream's own descriptor store, ratio matching against the map, maps of
+ * more than 65536 points.  (The similarity that joins two segments' gauges: map alignment, below.) */
 typedef struct {
     double   max_distance;      /* 0: no filter */
     int32_t  pnp_iterations;    /* 100 */
@@ -916,6 +916,64 @@ int vo_map_rows(vo_ctx* ctx, uint8_t* rows /*[cap][D]*/, double* points /*[cap][
 int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* opts,
                     double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
 int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
+
+/* ------------------------------------------------------------------ map alignment: the similarity that joins two maps, by descriptors
+ * After a lost frame the restart walks start a new map, and every segment is a trajectory in a gauge of its own: its origin is its
+ * first camera, its unit its first pair's baseline.  A frame's pose in the other map (vo_map_localize) fixes rotation and translation
+ * and says nothing about the ratio of the units; two MAPS that see the same ground fix all seven degrees of freedom.  The reference
+ * has no counterpart (it re-initialises with self.map.clean() and forgets the old map), so the rules are this library's own, in the
+ * spirit of cv::RANSACPointSetRegistrator as k_ransac and k_pnp_ransac follow it.  For one problem of n correspondences (b_i, a_i),
+ * X_a = s R X_b + t, float64 throughout:
+ *   Fit of m >= 3 points (Umeyama / Horn): centroids ac, bc; var_b = sum |b_i - bc|^2 / m; H = sum (a_i - ac)(b_i - bc)^T / m;
+ *     H = U D V^T by the one-sided Jacobi SVD (rotations and threshold of the library's jacobi_svd, sigma descending);
+ *     S = diag(1, 1, sign(det U det V)); R = U S V^T; s = tr(D S) / var_b; t = ac - s R bc.  The third column of U is taken as
+ *     u1 x u2, so det U = +1, sign(det V) decides S and tr(D S) = sigma_1 + sigma_2 + sign(det V) u3 . (H v3): what any orthonormal
+ *     completion gives, and well defined for the rank-2 H of a three-point sample, where the S branch is taken on about half of all
+ *     samples.  No model when var_b == 0, when s, R or t is not finite, or when s <= 0.
+ *   Subset check: a sample is rejected when, on either side (a or b), the difference vectors d1, d2 from its point 0 have
+ *     |d1 . d2| > 0.996 sqrt(|d1|^2 |d2|^2), or one of them is zero — exactly that comparison, no division.  0.996 is this library's
+ *     constant.  A rejected sample is an iteration that produced no model: it has consumed its random numbers and counts towards niters.
+ *   Sampling: OpenCV's MWC stream from `seed` (the context's table, as k_pnp_ransac reads it); three indices next() % n, a repeat is
+ *     redrawn immediately.
+ *   Scoring: e_i = |s R b_i + t - a_i|^2 in float64, cast to float32; point i is an inlier iff e_i <= (float)(max_error^2).  max_error
+ *     is in the units of map A.
+ *   Update and stop: hypotheses are consumed in order; update iff good > max(best, 2), strictly; then niters =
+ *     RANSACUpdateNumIters(confidence, (n - good) / n, 3, niters).  iterations < 1 counts as 1.
+ *   n < 3: VO_ERR_TOO_FEW.  n == 3: one fit (the subset check applies), every point an inlier; rejected or no model: VO_ERR_NO_MODEL.
+ *   Result: mask = the best RANSAC model's inlier mask, n_inl its count; the reported (s, R, t) is the same fit over the inliers (the
+ *     arrangement of solvePnPRansac).  Fewer than min_inliers inliers, or a refit without a model: VO_ERR_NO_MODEL, the model zeroed,
+ *     n_inl and the mask still reported.  A failed problem does not touch the others.  Two calls on the same input return the same bytes.
+ *
+ * vo_sim3_ransac_batch: the parity seam — B problems of given correspondences, problem b = rows offsets[b] .. offsets[b + 1] - 1 of
+ *   src (b) and dst (a), [n][3] each; sim [B][13] = s, R row-major, t; mask over all rows.  max_distance is not read.  VO_ERR_INVALID:
+ *   max_error <= 0, confidence outside (0, 1), decreasing offsets, missing arrays.
+ * vo_map_align: Q query maps (rows [off[Q]][D] as vo_map_stage takes them, points [off[Q]][3], off [Q + 1] with off[0] == 0) against the
+ *   staged map, in one call on the device: every query map is stored the way the staged one is (the same row store, the same norm
+ *   bound: a flagged SIFT row is VO_ERR_INVALID for the call); matches = the cross-check match of query rows (cv2's query) against the
+ *   staged rows (train) under vo_map_localize's rules — strict mutual nearest neighbours, lowest index winning ties in both
+ *   directions, float32 `distance < max_distance` (<= 0: no filter), ascending query-row order; b = the query's point, a = the staged
+ *   point; then exactly vo_sim3_ransac_batch on those lists.  sim[q] takes query map q's gauge to the staged map's.  An empty query map
+ *   is VO_ERR_TOO_FEW for that query alone.  VO_ERR_UNSUPPORTED: Q > 64, off[Q] > 65536.  VO_ERR_INVALID: no staged map, max_error <= 0,
+ *   confidence outside (0, 1), off[0] != 0 or decreasing offsets.  Profiling stages: match_nn, match_select, misc.
+ * vo_map_align_matches: query q's match list of the latest vo_map_align — staged row, query row, distance — and the inlier mask.
+ * Lifetime: the query maps and work buffers are an allocation of their own, made by the first vo_map_align and ended with the staged
+ *   map's; a newly staged map forgets the queries.  The pair results, the chains' maps, a live stream and vo_map_localize's results
+ *   are left alone.
+ * Out of scope: a stream's own descriptor store, automatic joining inside the restart walks, pose-graph or bundle refinement after
+ * the join, ratio matching. */
+typedef struct {
+    double   max_distance;      /* descriptor filter as in vo_reloc_opts; 0: none */
+    double   max_error;         /* inlier bound in map A's units; > 0 */
+    int32_t  iterations;        /* 1000 */
+    double   confidence;        /* 0.99 */
+    uint64_t seed;              /* 0xFFFFFFFFFFFFFFFF */
+    int32_t  min_inliers;       /* 0 */
+} vo_align_opts;
+int vo_sim3_ransac_batch(vo_ctx* ctx, const double* src /*b*/, const double* dst /*a*/, const int32_t* offsets /*[B + 1]*/, int B,
+                         const vo_align_opts* opts, double* sim /*[B][13]*/, uint8_t* mask, int32_t* n_inl, int32_t* status);
+int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* points, const int32_t* off /*[Q + 1]*/, int Q, const vo_align_opts* opts,
+                 double* sim /*[Q][13]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
+int vo_map_align_matches(vo_ctx* ctx, int q, int32_t* a_idx, int32_t* b_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
 
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the

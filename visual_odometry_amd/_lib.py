@@ -55,6 +55,11 @@ class RelocOpts(C.Structure):
                 ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
 
 
+class AlignOpts(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("max_error", C.c_double), ("iterations", C.c_int32), ("confidence", C.c_double),
+                ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
+
+
 PAIR_RESULT_DTYPE = np.dtype([("n_kp1", "<i4"), ("n_kp2", "<i4"), ("n_match", "<i4"), ("n_inl", "<i4"),
                               ("n_good", "<i4"), ("status", "<i4"), ("ransac_iters", "<i4"), ("reserved", "<i4"),
                               ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,))], align=True)
@@ -126,6 +131,9 @@ _SIGS = {
     "vo_map_rows": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "vo_map_localize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
+    "vo_sim3_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "vo_map_align": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "vo_map_align_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "vo_comm_unique_id": (C.c_int, [_P]),
     "vo_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "vo_comm_destroy": (C.c_int, [_P]),

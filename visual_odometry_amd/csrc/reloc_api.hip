@@ -44,7 +44,7 @@ int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys
     int rc = map_reserve(ctx, b, npt); if (rc) return rc;
     MapState& M = ctx->map;
     hipStream_t s = ctx->stream;
-    M.staged = false; M.last_Q = 0;
+    M.staged = false; M.last_Q = 0; M.al.last_Q = 0;
     M.m.npt = npt;
     HIPCHK(hipMemsetAsync(M.m.flag, 0, sizeof(int), s));
     launch_map_gather(s, M.m, src, key, n_keys, xyz);

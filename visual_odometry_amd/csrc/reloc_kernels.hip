@@ -9,9 +9,12 @@
 //   k_map_select   bf.match(frame, map) with crossCheck=True, the distance filter, and the 3D-2D correspondences in the layout
 //                  k_pnp_ransac takes (pnp_kernels.hip, launched unchanged)
 // Semantics follow OpenCV's batchDistance: ascending scan, strict `<`, so the lowest index wins ties, in both directions.
+// Further down: map alignment (vo_map_align, vo_sim3_ransac_batch) — k_align_gather, k_nn_align[_orb], k_align_select over the same stores
+// and bodies, and k_sim3_ransac.
 #include "vo_internal.h"
 #include "sift_rows.h"
 #include <limits.h>
+#include <float.h>
 
 // ------------------------------------------------------------------ the map store
 // Row `id` of the map from `src_row` (D bytes).  SIFT (D = 128): called by a whole wavefront, lane l moves bytes 2 l, 2 l + 1 —
@@ -317,4 +320,525 @@ void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* 
 {
     if (Q <= 0) return;
     hipLaunchKernelGGL(k_map_select, dim3(Q), dim3(256), 0, s, m, r, kp_xy, kp_count, kp_cap, max_distance);
+}
+
+// ================================================================== map-to-map alignment (vo_map_align, vo_sim3_ransac_batch)
+//   k_align_gather     Q query maps' rows into operands of their own, through the map's stores (map_store_row_sift / _orb)
+//   k_nn_align[_orb]   nearest neighbours in both directions between every query map and the staged one: the bodies above, both
+//                      operands given by pointer
+//   k_align_select     the cross-check match, the distance filter, and the 3D-3D lists (b = query point, a = staged point)
+//   k_sim3_ransac      X_a = s R X_b + t by RANSAC over Umeyama's closed form (include/vo_hip.h, "map alignment")
+
+// Query q's operand as a map of its own: its rows start at row pad[q] (a multiple of 256) of the padded arrays, so that the 64-row
+// fragments and the 128-row chunks of nn_map_l2_body stay inside what belongs to it.
+__device__ __forceinline__ MapBuf align_query_map(const AlignBuf& a, int q)
+{
+    const int p0 = a.pad[q];
+    MapBuf m;
+    m.D = a.D; m.cap_rows = a.pad[q + 1] - p0; m.npt = a.off[q + 1] - a.off[q];
+    m.rows = a.rows + (size_t)p0 * a.D; m.img = a.img ? a.img + (size_t)p0 * 128 : nullptr; m.norms = a.norms ? a.norms + p0 : nullptr;
+    m.xyz = a.xyz + (size_t)a.off[q] * 3; m.flag = a.flag;
+    return m;
+}
+
+// row g of the caller's concatenated rows -> row g - off[q] of query map q
+__global__ __launch_bounds__(256) void k_align_gather(AlignBuf a, const uint8_t* src)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int per = a.D == 128 ? 4 : 32, sub = a.D == 128 ? tid >> 6 : tid >> 3;
+    for (int g = blockIdx.x * per + sub; g < a.total; g += gridDim.x * per) {
+        int q = 0;
+        while (q + 1 < a.Q && a.off[q + 1] <= g) q++;
+        const MapBuf m = align_query_map(a, q);
+        if (a.D == 128) map_store_row_sift(m, g - a.off[q], src + (size_t)g * 128, lane);
+        else map_store_row_orb(m, g - a.off[q], src + (size_t)g * 32, tid & 7);
+    }
+}
+
+__global__ __launch_bounds__(NM_THREADS) void k_nn_align(MapBuf m, AlignBuf a, int fwd_blocks, int rev_blocks)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_b[2][NM_STAGE_ROWS * 128];
+    const int q = blockIdx.x / (fwd_blocks + rev_blocks), blk = blockIdx.x % (fwd_blocks + rev_blocks);
+    const MapBuf f = align_query_map(a, q);
+    if (blk < fwd_blocks) {
+        const int row0 = blk * NM_BLOCK_ROWS;
+        if (row0 >= f.npt) return;
+        nn_map_l2_body(s_b, f.img, f.norms, f.npt, m.img, m.norms, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q]);
+    } else {
+        const int row0 = (blk - fwd_blocks) * NM_BLOCK_ROWS;
+        if (row0 >= m.npt) return;
+        nn_map_l2_body(s_b, m.img, m.norms, m.npt, f.img, f.norms, f.npt, row0, a.rn_idx + (size_t)q * m.cap_rows, nullptr);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_nn_align_orb(MapBuf m, AlignBuf a, int fwd_blocks, int rev_blocks)
+{
+    __shared__ uint4 s_b[NO_TILE * 2];
+    const int q = blockIdx.x / (fwd_blocks + rev_blocks), blk = blockIdx.x % (fwd_blocks + rev_blocks);
+    const MapBuf f = align_query_map(a, q);
+    if (blk < fwd_blocks) {
+        const int row0 = blk * NO_BLOCK_ROWS;
+        if (row0 >= f.npt) return;
+        nn_map_hamming_body(s_b, f.rows, f.npt, m.rows, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q]);
+    } else {
+        const int row0 = (blk - fwd_blocks) * NO_BLOCK_ROWS;
+        if (row0 >= m.npt) return;
+        nn_map_hamming_body(s_b, m.rows, m.npt, f.rows, f.npt, row0, a.rn_idx + (size_t)q * m.cap_rows, nullptr);
+    }
+}
+
+// k_map_select's rules with a map's rows in the place of a frame's; the lists of query q start at off[q]: b_idx (query row),
+// a_idx (staged row), cv2's float32 distance, src[k] = the query's point, dst[k] = the staged map's point.
+__global__ __launch_bounds__(256) void k_align_select(MapBuf m, AlignBuf a, double max_distance)
+{
+    __shared__ int s_w[4];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int o = a.off[q], nq = a.off[q + 1] - o;
+    const int* fidx = a.nn_idx + a.pad[q]; const int* fdist = a.nn_dist + a.pad[q];
+    const int* ridx = a.rn_idx + (size_t)q * m.cap_rows;
+    const bool l2 = m.D == 128;
+    int out_base = 0;
+    for (int base = 0; base < nq; base += 256) {
+        const int i = base + tid;
+        int t = -1; float fd = 0.f;
+        if (i < nq && m.npt > 0) {
+            t = fidx[i];
+            if (t >= 0 && ridx[t] != i) t = -1;
+            if (t >= 0) {
+                const int d = fdist[i];
+                fd = l2 ? sqrtf((float)d) : (float)d;
+                if (max_distance > 0 && !((double)fd < max_distance)) t = -1;
+            }
+        }
+        int tot;
+        const int pos = o + out_base + ms_excl_scan_256(t >= 0 ? 1 : 0, s_w, &tot);
+        if (t >= 0) {
+            a.m_b[pos] = i; a.m_a[pos] = t; a.m_d[pos] = fd;
+            for (int k = 0; k < 3; k++) { a.src[(size_t)pos * 3 + k] = a.xyz[(size_t)(o + i) * 3 + k]; a.dst[(size_t)pos * 3 + k] = m.xyz[(size_t)t * 3 + k]; }
+        }
+        out_base += tot;
+    }
+    if (tid == 0) { a.m_count[q] = out_base; a.poff[2 * q] = o; a.poff[2 * q + 1] = o + out_base; }
+}
+
+void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows)
+{
+    if (a.Q <= 0) return;
+    if (a.total > 0) {
+        const int per = a.D == 128 ? 4 : 32, g = (a.total + per - 1) / per;
+        hipLaunchKernelGGL(k_align_gather, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, a, src_rows);
+    }
+    const int fwd = (max_rows + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
+    if (fwd + rev > 0) {
+        if (m.D == 128) hipLaunchKernelGGL(k_nn_align, dim3((unsigned)a.Q * (fwd + rev)), dim3(NM_THREADS), 0, s, m, a, fwd, rev);
+        else hipLaunchKernelGGL(k_nn_align_orb, dim3((unsigned)a.Q * (fwd + rev)), dim3(256), 0, s, m, a, fwd, rev);
+    }
+}
+
+void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance)
+{
+    if (a.Q <= 0) return;
+    hipLaunchKernelGGL(k_align_select, dim3(a.Q), dim3(256), 0, s, m, a, max_distance);
+}
+
+// ------------------------------------------------------------------ k_sim3_ransac: X_a = s R X_b + t from 3D-3D correspondences
+// The operator is stated in include/vo_hip.h ("map alignment"); the skeleton is k_pnp_ransac's (pnp_kernels.hip): one workgroup per
+// problem, rounds of 64 hypotheses — wave 0 draws the 64 subsets from the tabulated MWC stream and fits one model per lane, the four
+// waves score four hypotheses at a time, and every lane carries the same copy of niters / best, so hypotheses are consumed in order
+// and the stop rule is the sequential one.  A fit is closed form: the moments of the sample, a 3 x 3 one-sided Jacobi SVD held in
+// registers (dp_jacobi_svd's rotations and threshold, unrolled over constant indices: no scratch), and U completed by u3 = u1 x u2.
+// A three-point H has rank 2, so sigma_3 u_3 is rounding noise; with u3 = u1 x u2, det U = +1 and S = diag(1, 1, sign(det V)),
+// tr(D S) = sigma_1 + sigma_2 + sign(det V) u3 . (H v3): the same R and s as any orthonormal completion gives, and continuous in H.
+// The correspondences of a problem of up to SIM3_LDS_PTS points are staged in LDS, one array per coordinate (consecutive lanes,
+// consecutive banks); a larger problem reads global memory.
+#define SIM3_LDS_PTS 3072                  // 6 doubles each: 144 KB of the 160 KB a workgroup can have
+#define SIM3_STREAM 448
+#define SIM3_COS 0.996                     // the subset check's cosine (include/vo_hip.h)
+struct Sim3Shared {
+    double   pts[6][SIM3_LDS_PTS];          // b.x b.y b.z a.x a.y a.z
+    double   model[64][13];                 // s, R row-major, t
+    double   red[4][10];
+    uint32_t stream[SIM3_STREAM];
+    int      sub[64][3];
+    int      ok[64];
+    int      cnt[2][4];
+    int      used;
+};
+
+// cv::RNG::next and cv::RANSACUpdateNumIters as pnp_kernels.hip states them (static there)
+__device__ static inline uint32_t sim3_rng_next(uint64_t* state)
+{
+    *state = (uint64_t)(uint32_t)*state * 4164903690U + (uint32_t)(*state >> 32);
+    return (uint32_t)*state;
+}
+
+__device__ static int sim3_update_num_iters(double p, double ep, int model_points, int max_iters)
+{
+    p = p < 0 ? 0 : p; p = p > 1 ? 1 : p;
+    ep = ep < 0 ? 0 : ep; ep = ep > 1 ? 1 : ep;
+    double num = 1. - p > DBL_MIN ? 1. - p : DBL_MIN;
+    double denom = 1. - pow(1. - ep, model_points);
+    if (denom < DBL_MIN) return 0;
+    num = log(num);
+    denom = log(denom);
+    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)lrint(num / denom);
+}
+
+template <bool ST>
+__device__ __forceinline__ void sim3_point(const Sim3Shared& sh, const double* src, const double* dst, int i, double* b, double* a)
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        b[k] = ST ? sh.pts[k][i] : src[(size_t)i * 3 + k];
+        a[k] = ST ? sh.pts[3 + k][i] : dst[(size_t)i * 3 + k];
+    }
+}
+
+__device__ __forceinline__ double sim3_dot(const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
+
+// one side of the subset check: the two difference vectors from point 0 are neither zero nor nearly collinear
+__device__ __forceinline__ bool sim3_side_ok(const double* p0, const double* p1, const double* p2)
+{
+    const double d1[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]}, d2[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+    const double n1 = sim3_dot(d1, d1), n2 = sim3_dot(d2, d2), dt = sim3_dot(d1, d2);
+    return n1 != 0 && n2 != 0 && !(fabs(dt) > SIM3_COS * sqrt(n1 * n2));
+}
+
+// The model M = {s, R row-major, t} from the centroids ac, bc, var_b = sum |b - bc|^2 / m and H = sum (a - ac)(b - bc)^T / m
+// (row-major).  false: no model (M is then not to be used).
+__device__ __forceinline__ bool sim3_from_moments(const double* ac, const double* bc, double var_b, const double* H, double* M)
+{
+    const double eps = DBL_EPSILON * 10;
+    double c[3][3], v[3][3], w[3];          // c[i] = column i of H, then sigma_i u_i; v[i] = right singular vector i
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { c[i][k] = H[3 * k + i]; v[i][k] = i == k ? 1. : 0.; }
+        w[i] = sim3_dot(c[i], c[i]);
+    }
+    for (int iter = 0; iter < 30; iter++) {
+        bool changed = false;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int j = i + 1; j < 3; j++) {
+                double a = w[i], p = sim3_dot(c[i], c[j]), b = w[j];
+                if (fabs(p) <= eps * sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b;
+                double gamma, cs, sn;
+                {
+                    double x = fabs(p), y = fabs(beta);
+                    if (x < y) { const double t = x; x = y; y = t; }
+                    const double r = y / x;          // x > 0: |p| > 0 here
+                    gamma = x * sqrt(1 + r * r);
+                }
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    sn = sqrt(delta / gamma);
+                    cs = p / (gamma * sn * 2);
+                } else {
+                    cs = sqrt((gamma + beta) / (gamma * 2));
+                    sn = p / (gamma * cs * 2);
+                }
+                a = b = 0;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const double t0 = cs * c[i][k] + sn * c[j][k], t1 = -sn * c[i][k] + cs * c[j][k];
+                    c[i][k] = t0; c[j][k] = t1;
+                    a += t0 * t0; b += t1 * t1;
+                    const double s0 = cs * v[i][k] + sn * v[j][k], s1 = -sn * v[i][k] + cs * v[j][k];
+                    v[i][k] = s0; v[j][k] = s1;
+                }
+                w[i] = a; w[j] = b;
+                changed = true;
+            }
+        if (!changed) break;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) w[i] = sqrt(sim3_dot(c[i], c[i]));
+    // descending sigma: a three-element network of compare-and-swaps, constant indices
+#define SIM3_CSWAP(i, j)                                                                                           \
+    {                                                                                                              \
+        const bool sw = w[i] < w[j];                                                                               \
+        const double tw = w[i]; w[i] = sw ? w[j] : w[i]; w[j] = sw ? tw : w[j];                                    \
+        _Pragma("unroll") for (int k = 0; k < 3; k++) {                                                            \
+            const double tc = c[i][k], tv = v[i][k];                                                               \
+            c[i][k] = sw ? c[j][k] : tc; c[j][k] = sw ? tc : c[j][k];                                              \
+            v[i][k] = sw ? v[j][k] : tv; v[j][k] = sw ? tv : v[j][k];                                              \
+        }                                                                                                          \
+    }
+    SIM3_CSWAP(0, 1) SIM3_CSWAP(0, 2) SIM3_CSWAP(1, 2)
+#undef SIM3_CSWAP
+    double u1[3], u2[3], u3[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { u1[k] = c[0][k] / w[0]; u2[k] = c[1][k] / w[1]; }
+    u3[0] = u1[1] * u2[2] - u1[2] * u2[1]; u3[1] = u1[2] * u2[0] - u1[0] * u2[2]; u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+    const double detv = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[0][1] * (v[1][0] * v[2][2] - v[1][2] * v[2][0]) +
+                        v[0][2] * (v[1][0] * v[2][1] - v[1][1] * v[2][0]);
+    const double sg = detv < 0 ? -1. : 1.;
+    const double s = (w[0] + w[1] + sg * sim3_dot(u3, c[2])) / var_b;
+    M[0] = s;
+    bool fin = isfinite(s);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) { M[1 + 3 * r + k] = u1[r] * v[0][k] + u2[r] * v[1][k] + sg * u3[r] * v[2][k]; fin = fin && isfinite(M[1 + 3 * r + k]); }
+#pragma unroll
+    for (int r = 0; r < 3; r++) { M[10 + r] = ac[r] - s * sim3_dot(M + 1 + 3 * r, bc); fin = fin && isfinite(M[10 + r]); }
+    return var_b > 0 && fin && s > 0;
+}
+
+// the subset check and the fit of three correspondences
+__device__ __forceinline__ bool sim3_minimal(const double (*b)[3], const double (*a)[3], double* M)
+{
+    if (!sim3_side_ok(a[0], a[1], a[2]) || !sim3_side_ok(b[0], b[1], b[2])) return false;
+    double ac[3], bc[3], H[9], var_b = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { ac[k] = (a[0][k] + a[1][k] + a[2][k]) / 3; bc[k] = (b[0][k] + b[1][k] + b[2][k]) / 3; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) H[k] = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double da[3] = {a[i][0] - ac[0], a[i][1] - ac[1], a[i][2] - ac[2]}, db[3] = {b[i][0] - bc[0], b[i][1] - bc[1], b[i][2] - bc[2]};
+        var_b += sim3_dot(db, db);
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) H[3 * r + k] += da[r] * db[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) H[k] /= 3;
+    return sim3_from_moments(ac, bc, var_b / 3, H, M);
+}
+
+// e_i = |s R b_i + t - a_i|^2 in float64, compared as float32
+template <bool ST>
+__device__ __forceinline__ bool sim3_inlier(const Sim3Shared& sh, const double* src, const double* dst, int i, const double* M, float thr)
+{
+    double b[3], a[3], e = 0;
+    sim3_point<ST>(sh, src, dst, i, b, a);
+#pragma unroll
+    for (int r = 0; r < 3; r++) { const double d = M[0] * sim3_dot(M + 1 + 3 * r, b) + M[10 + r] - a[r]; e += d * d; }
+    return (float)e <= thr;
+}
+
+// K sums over the workgroup in a fixed order: the butterfly of a wavefront, then the four wavefronts in turn; every thread gets them
+template <int K>
+__device__ __forceinline__ void sim3_reduce(Sim3Shared& sh, double* acc)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; k++)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc[k] += __shfl_xor(acc[k], d, 64);
+    __syncthreads();                                        // the previous sums have been read
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; k++) sh.red[wave][k] = acc[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) acc[k] = ((sh.red[0][k] + sh.red[1][k]) + sh.red[2][k]) + sh.red[3][k];
+}
+
+template <bool ST>
+__device__ __forceinline__ void sim3_problem(Sim3Shared& sh, const double* src, const double* dst, int n, int iterations, float thr, double confidence,
+                                             uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask,
+                                             int* ninl, int* status)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (ST) {
+        for (int i = tid; i < n; i += 256)
+#pragma unroll
+            for (int k = 0; k < 3; k++) { sh.pts[k][i] = src[(size_t)i * 3 + k]; sh.pts[3 + k][i] = dst[(size_t)i * 3 + k]; }
+        __syncthreads();
+    }
+    auto fail = [&](int good) {                             // no model: zeros, the count of the mask as it stands
+        if (tid == 0) {
+            for (int k = 0; k < 13; k++) sim[k] = 0;
+            *status = VO_ERR_NO_MODEL; *ninl = good;
+        }
+    };
+    // every thread carries the same copy of the sequential state
+    int niters = iterations > 1 ? iterations : 1, max_good = 0, pos = 0;
+    double best[13];
+#pragma unroll
+    for (int k = 0; k < 13; k++) best[k] = 0;
+    if (n == 3) {                                           // model_points == npoints: one fit, every point an inlier
+        double b[3][3], a[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) sim3_point<ST>(sh, src, dst, i, b[i], a[i]);
+        if (sim3_minimal(b, a, best)) max_good = 3;
+        if (tid < 3) mask[tid] = max_good > 0 ? 1 : 0;
+    } else {
+        for (int r0 = 0; r0 < niters; r0 += 64) {
+            const int nh = min(64, niters - r0);
+            for (int i = tid; i < SIM3_STREAM; i += 256) sh.stream[i] = pos + i < rng_n ? rng_tab[pos + i] % (uint32_t)n : 0u;
+            __syncthreads();
+            // subset h starts where subset h - 1 stopped in the RNG stream; a repeated index costs extra numbers, so the 64 lanes of
+            // wave 0 draw in parallel from assumed starts (3 numbers per earlier subset), a prefix sum of the numbers actually used
+            // gives the true starts, and the lanes repeat until the starts stop moving
+            if (wave == 0) {
+                int start = 3 * lane, used = 3;
+                for (;;) {
+                    int idx[3];
+                    used = 0;
+                    if (lane < nh) {
+#pragma unroll
+                        for (int i = 0; i < 3; i++) {
+                            int v; bool dup;
+                            do {
+                                const int at = start + used;
+                                if (at < SIM3_STREAM && pos + at < rng_n) v = (int)sh.stream[at];
+                                else {                      // beyond the staged window / table: recompute directly
+                                    uint64_t st = seed ? seed : 0xffffffffULL;
+                                    uint32_t x = 0;
+                                    if (pos + at < rng_n) x = rng_tab[pos + at];
+                                    else { for (int q = 0; q <= pos + at; q++) x = sim3_rng_next(&st); }
+                                    v = (int)(x % (uint32_t)n);
+                                }
+                                used++;
+                                dup = false;
+#pragma unroll
+                                for (int k = 0; k < 3; k++) dup |= k < i && idx[k] == v;
+                            } while (dup);
+                            idx[i] = v;
+                        }
+#pragma unroll
+                        for (int i = 0; i < 3; i++) sh.sub[lane][i] = idx[i];
+                    }
+                    int inc = used;                          // inclusive prefix of the numbers used
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+                    const int true_start = inc - used;
+                    const bool moved = lane < nh && true_start != start;
+                    start = true_start;
+                    if (lane == 63) sh.used = inc;
+                    if (!__any(moved)) break;
+                }
+            }
+            __syncthreads();
+            pos += sh.used;
+            if (wave == 0 && lane < nh) {                   // one closed-form fit per lane
+                double b[3][3], a[3][3], M[13];
+#pragma unroll
+                for (int i = 0; i < 3; i++) sim3_point<ST>(sh, src, dst, sh.sub[lane][i], b[i], a[i]);
+                const bool ok = sim3_minimal(b, a, M);
+#pragma unroll
+                for (int k = 0; k < 13; k++) sh.model[lane][k] = M[k];
+                sh.ok[lane] = ok ? 1 : 0;
+            }
+            __syncthreads();
+            bool done = false;
+            for (int bt = 0; bt * 4 < nh && !done; bt++) {  // four hypotheses at a time, consumed in order
+                const int h = bt * 4 + wave;
+                if (h < nh) {
+                    int good = 0;
+                    if (sh.ok[h]) {                         // a rejected sample is an iteration without a model
+                        double M[13];
+#pragma unroll
+                        for (int k = 0; k < 13; k++) M[k] = sh.model[h][k];
+                        for (int base = 0; base < n; base += 64) {
+                            const int i = base + lane;
+                            const bool in = i < n && sim3_inlier<ST>(sh, src, dst, i, M, thr);
+                            good += __popcll(__ballot(in));
+                        }
+                    }
+                    if (lane == 0) sh.cnt[bt & 1][wave] = good;
+                }
+                __syncthreads();
+                for (int w = 0; w < 4; w++) {
+                    const int h2 = bt * 4 + w;
+                    if (h2 >= nh) break;
+                    if (r0 + h2 >= niters) { done = true; break; }
+                    const int good = sh.cnt[bt & 1][w];
+                    if (good > max(max_good, 2)) {
+#pragma unroll
+                        for (int k = 0; k < 13; k++) best[k] = sh.model[h2][k];
+                        max_good = good;
+                        niters = sim3_update_num_iters(confidence, (double)(n - good) / n, 3, niters);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // the mask of the best RANSAC model; thread t writes, and later reads, points t, t + 256, ...
+        for (int i = tid; i < n; i += 256) mask[i] = max_good > 0 && sim3_inlier<ST>(sh, src, dst, i, best, thr) ? 1 : 0;
+    }
+    if (max_good <= 0 || max_good < min_inliers) { fail(max_good); return; }
+    // the same fit over the inliers: centroids first, then the centred moments
+    const double m = (double)max_good;
+    double acc[10];
+#pragma unroll
+    for (int k = 0; k < 10; k++) acc[k] = 0;
+    for (int i = tid; i < n; i += 256)
+        if (mask[i]) {
+            double b[3], a[3];
+            sim3_point<ST>(sh, src, dst, i, b, a);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { acc[k] += a[k]; acc[3 + k] += b[k]; }
+        }
+    sim3_reduce<6>(sh, acc);
+    const double ac[3] = {acc[0] / m, acc[1] / m, acc[2] / m}, bc[3] = {acc[3] / m, acc[4] / m, acc[5] / m};
+#pragma unroll
+    for (int k = 0; k < 10; k++) acc[k] = 0;
+    for (int i = tid; i < n; i += 256)
+        if (mask[i]) {
+            double b[3], a[3];
+            sim3_point<ST>(sh, src, dst, i, b, a);
+            const double da[3] = {a[0] - ac[0], a[1] - ac[1], a[2] - ac[2]}, db[3] = {b[0] - bc[0], b[1] - bc[1], b[2] - bc[2]};
+            acc[9] += sim3_dot(db, db);
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc[3 * r + k] += da[r] * db[k];
+        }
+    sim3_reduce<10>(sh, acc);
+#pragma unroll
+    for (int k = 0; k < 10; k++) acc[k] /= m;
+    double M[13];
+    const bool ok = sim3_from_moments(ac, bc, acc[9], acc, M);
+    if (!ok) { fail(max_good); return; }
+    if (tid == 0) {
+        for (int k = 0; k < 13; k++) sim[k] = M[k];
+        *status = VO_OK; *ninl = max_good;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sim3_ransac(const double* src_all, const double* dst_all, const int* offsets, int off_stride, int iterations,
+                                                     double max_error, double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n,
+                                                     int min_inliers, double* sim_out, uint8_t* mask_all, int* ninl_out, int* status_out)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn_sim3[];   // more than the static limit
+    Sim3Shared& sh = *(Sim3Shared*)s_dyn_sim3;
+    const int pb = blockIdx.x, tid = threadIdx.x;
+    const int o0 = offsets[pb * off_stride], n = offsets[pb * off_stride + 1] - o0;
+    const double* src = src_all + (size_t)o0 * 3; const double* dst = dst_all + (size_t)o0 * 3;
+    uint8_t* mask = mask_all + o0;
+    double* sim = sim_out + (size_t)pb * 13;
+    if (n < 3) {
+        if (tid == 0) {
+            for (int k = 0; k < 13; k++) sim[k] = 0;
+            status_out[pb] = VO_ERR_TOO_FEW; ninl_out[pb] = 0;
+        }
+        for (int i = tid; i < n; i += 256) mask[i] = 0;
+        return;
+    }
+    const float thr = (float)(max_error * max_error);
+    if (n <= SIM3_LDS_PTS)
+        sim3_problem<true>(sh, src, dst, n, iterations, thr, confidence, seed, rng_tab, rng_n, min_inliers, sim, mask, ninl_out + pb, status_out + pb);
+    else
+        sim3_problem<false>(sh, src, dst, n, iterations, thr, confidence, seed, rng_tab, rng_n, min_inliers, sim, mask, ninl_out + pb, status_out + pb);
+}
+
+void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, const int* offsets, int off_stride, int B, int iterations, double max_error,
+                        double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask, int* ninl,
+                        int* status)
+{
+    if (B <= 0) return;
+    static_assert(sizeof(Sim3Shared) <= 160 * 1024, "one workgroup's LDS");
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)k_sim3_ransac, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sim3Shared)); attr = true; }
+    hipLaunchKernelGGL(k_sim3_ransac, dim3(B), dim3(256), sizeof(Sim3Shared), s, src, dst, offsets, off_stride, iterations, max_error, confidence, seed,
+                       rng_tab, rng_n, min_inliers, sim, mask, ninl, status);
 }

@@ -124,6 +124,15 @@ struct MapState {
     double* dK = nullptr;
     int Q_cap = 0, kp_cap = 0;            // what the work buffers were sized for
     int last_Q = 0;                       // queries of the most recent vo_map_localize (vo_map_matches); 0: none since the map was staged
+    // vo_map_align's query maps and work buffers: a second allocation, made by the first call that needs it and kept while the next
+    // one fits; it ends with the staged map (drop_map), and a newly staged map forgets its queries
+    struct Align {
+        DevList mem;
+        AlignBuf a{};
+        int Q_cap = 0, pad_cap = 0, total_cap = 0, map_rows = 0;   // what it was sized for
+        int last_Q = 0;                   // queries of the most recent vo_map_align (vo_map_align_matches)
+        std::vector<int32_t> off, pad;    // host copies of that call's offsets
+    } al;
 };
 
 // vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one

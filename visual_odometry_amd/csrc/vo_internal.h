@@ -486,6 +486,32 @@ void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* de
 void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance);
 // [Rodrigues(rvec) | tvec] of B solved problems, zeros for the others; a model with fewer than min_inliers inliers becomes VO_ERR_NO_MODEL
 void launch_pnp_poses(hipStream_t s, const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses);
+// ---- map alignment: Q query maps against the staged one (reloc_kernels.hip): vo_map_align, vo_sim3_ransac_batch
+struct AlignBuf {
+    int      Q, D, total;               // query maps, bytes of a row, rows of all of them
+    int*     off;                       // [Q + 1] query q's rows and points in the caller's arrays: off[q] .. off[q + 1] - 1
+    int*     pad;                       // [Q + 1] where its operand starts in the padded arrays: every map on a multiple of 256 rows
+    uint8_t* rows;                      // [pad[Q]][D] the rows as MapBuf::rows holds a map's
+    uint8_t* img; int* norms;           // SIFT: the int8 operand image and |v - 128|^2, a "slot" per query map
+    double*  xyz;                       // [total][3] the queries' points as uploaded
+    int*     flag;                      // [1] bit 1: a SIFT row broke the norm bound
+    int*     nn_idx; int* nn_dist;      // [pad[Q]] nearest staged row of every query row and its distance
+    int*     rn_idx;                    // [Q][cap_rows of the staged map] nearest row of query q for every staged row
+    int*     m_b; int* m_a; float* m_d; // [total] the match lists, query q's at off[q]: query row, staged row, cv2's float32 distance
+    int*     m_count;                   // [Q]
+    double*  src; double* dst;          // [total][3] the correspondences: b = the query's point, a = the staged map's
+    int*     poff;                      // [Q][2] {first, end}: k_sim3_ransac's offsets with off_stride 2
+    double*  sim;                       // [Q][13] s, R row-major, t
+    uint8_t* mask;                      // [total]
+    int*     ninl; int* status;         // [Q]
+};
+// the queries' rows (device, [total][D]) into their operands, then both directions' nearest neighbours; max_rows = the largest query map
+void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows);
+void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance);
+// B problems src -> dst ([n][3] each); problem b is rows offsets[b off_stride] .. offsets[b off_stride + 1] - 1; sim [B][13]
+void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, const int* offsets, int off_stride, int B, int iterations, double max_error,
+                        double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask, int* ninl,
+                        int* status);
 
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

@@ -516,10 +516,8 @@ class FrontEnd:
     def _map_row_width(self):
         return 128 if self.detector == "sift" else 32
 
-    def stage_map(self, rows, points):
-        """Stage a map the caller holds (vo_map_stage): rows [npt, 32] uint8 under ORB, [npt, 128] under SIFT (uint8, or the
-        integer-valued float32 rows features() hands out); points [npt, 3] float64 in the map's own gauge.  Replaces the map
-        staged before; up to 65536 points (NotImplementedError beyond)."""
+    def _map_rows_u8(self, rows):
+        """a map's descriptor rows as the library takes them: [npt, D] uint8, contiguous"""
         D = self._map_row_width()
         r = np.asarray(rows)
         if r.ndim != 2 or r.shape[1] != D:
@@ -529,7 +527,13 @@ class FrontEnd:
             if not np.array_equal(u.astype(r.dtype), r):
                 raise ValueError("descriptor rows must hold integer values 0..255")
             r = u
-        r = np.ascontiguousarray(r)
+        return np.ascontiguousarray(r)
+
+    def stage_map(self, rows, points):
+        """Stage a map the caller holds (vo_map_stage): rows [npt, 32] uint8 under ORB, [npt, 128] under SIFT (uint8, or the
+        integer-valued float32 rows features() hands out); points [npt, 3] float64 in the map's own gauge.  Replaces the map
+        staged before; up to 65536 points (NotImplementedError beyond)."""
+        r = self._map_rows_u8(rows)
         p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         if len(p) != len(r):
             raise ValueError("points must be [npt, 3]")
@@ -585,6 +589,47 @@ class FrontEnd:
         c.check(c.lib.vo_map_matches(c.handle, int(q), pi.ctypes.data, ki.ctypes.data, d.ctypes.data, m.ctypes.data, cap, C.addressof(n)))
         k = n.value
         return pi[:k].copy(), ki[:k].copy(), d[:k].copy(), m[:k].copy()
+
+    # ---- map alignment: the similarity that joins two maps, by their descriptors (vo_map_align) ------
+    def align_maps(self, rows, points, max_error, offsets=None, max_distance=0.0, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED,
+                   min_inliers=0):
+        """Align Q query maps to the staged map by their descriptors (vo_map_align), all in one call on the device: the cross-check
+        match of every query map's rows against the staged rows -> `distance < max_distance` (0: no filter) -> RANSAC over the
+        3D-3D matches for X_staged = scale R X_query + t.  rows [total, D] and points [total, 3] hold the query maps one after
+        the other, map q being rows offsets[q]:offsets[q + 1] (offsets None: one map); what map_rows() returned for them.
+        max_error is the inlier bound in the STAGED map's units and has no default.  Returns dict(scale [Q], R [Q, 3, 3], t [Q, 3]
+        (zeros where status != 0), n_match, n_inl, status [Q]: 0, VO_ERR_TOO_FEW (fewer than 3 matches) or VO_ERR_NO_MODEL).
+        Up to 64 maps and 65536 rows in one call (NotImplementedError beyond)."""
+        r = self._map_rows_u8(rows)
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        if len(p) != len(r):
+            raise ValueError("points must be [total, 3]")
+        off = np.ascontiguousarray([0, len(r)] if offsets is None else offsets, dtype=np.int32).ravel()
+        Q = len(off) - 1
+        if Q < 0 or int(off[-1]) != len(r):
+            raise ValueError("offsets must be [Q + 1] and end at the number of rows")
+        opts = _lib.AlignOpts(float(max_distance), float(max_error), int(iterations), float(confidence), int(seed), int(min_inliers))
+        sim = np.zeros((Q, 13)); nm = np.zeros(Q, np.int32); ni = np.zeros(Q, np.int32); st = np.zeros(Q, np.int32)
+        c = self.ctx
+        rc = c.lib.vo_map_align(c.handle, r.ctypes.data, p.ctypes.data, off.ctypes.data, Q, C.addressof(opts), sim.ctypes.data, nm.ctypes.data,
+                                ni.ctypes.data, st.ctypes.data)
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        self._align_rows = np.diff(off)
+        return dict(scale=sim[:, 0].copy(), R=sim[:, 1:10].reshape(Q, 3, 3).copy(), t=sim[:, 10:].copy(), n_match=nm, n_inl=ni, status=st)
+
+    def map_align_matches(self, q):
+        """Query map q's matches of the latest align_maps(): (staged row [n], query row [n], distance [n] float32 as cv2 reports
+        it, the RANSAC inlier mask [n] uint8), in query-row order."""
+        c = self.ctx
+        n = C.c_int32(0)
+        rows = getattr(self, "_align_rows", ())
+        cap = max(int(rows[int(q)]), 1) if 0 <= int(q) < len(rows) else 1
+        ai = np.empty(cap, np.int32); bi = np.empty(cap, np.int32); d = np.empty(cap, np.float32); m = np.empty(cap, np.uint8)
+        c.check(c.lib.vo_map_align_matches(c.handle, int(q), ai.ctypes.data, bi.ctypes.data, d.ctypes.data, m.ctypes.data, cap, C.addressof(n)))
+        k = n.value
+        return ai[:k].copy(), bi[:k].copy(), d[:k].copy(), m[:k].copy()
 
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on=True):
@@ -658,6 +703,55 @@ def split_segments(segment, poses_pnp, poses, seg_poses_pnp, seg_poses):
                         poses=np.concatenate([sl[p:p + 1], pl[p + 1:p + n + 1]])))
         p += n
     return out
+
+
+def apply_similarity(poses, scale, R, t):
+    """World -> camera poses [..., 3, 4] of gauge B in gauge A, for the similarity X_a = scale R X_b + t (align_maps,
+    geometry.estimate_similarity): [R_c | t_c] -> [R_c R^T | scale t_c - R_c R^T t].  The rotation stays a proper rotation; the
+    camera frame's units become A's, so a point scale R X + t of gauge A has the camera coordinates scale (R_c X + t_c).  Pure."""
+    T = np.asarray(poses, np.float64)
+    if T.shape[-2:] != (3, 4):
+        raise ValueError("poses must be [..., 3, 4]")
+    R = np.asarray(R, np.float64).reshape(3, 3); t = np.asarray(t, np.float64).reshape(3)
+    Rc = T[..., :3] @ R.T
+    return np.concatenate([Rc, (float(scale) * T[..., 3] - Rc @ t)[..., None]], axis=-1)
+
+
+def compose_similarity(outer, inner):
+    """(scale, R, t) of X -> outer(inner(X)) for two similarities given as (scale, R, t)."""
+    s1, R1, t1 = float(outer[0]), np.asarray(outer[1], np.float64).reshape(3, 3), np.asarray(outer[2], np.float64).reshape(3)
+    s2, R2, t2 = float(inner[0]), np.asarray(inner[1], np.float64).reshape(3, 3), np.asarray(inner[2], np.float64).reshape(3)
+    return s1 * s2, R1 @ R2, s1 * (R1 @ t2) + t1
+
+
+def join_segments(segments, sims):
+    """split_segments' list in ONE gauge, segment 0's.  sims[k - 1], for every later segment k, is the similarity that takes
+    segment k's gauge to segment k - 1's — (scale, R, t) or a dict with those keys, as align_maps / estimate_similarity return for
+    segment k's map against segment k - 1's — or None where the two maps could not be aligned.  Returns (joined, unconnected):
+    joined = the segments connected to segment 0 through an unbroken run of similarities, as copies with poses_pnp and poses taken
+    through the composed similarity (apply_similarity) and two more keys, `index` (its place in `segments`) and `sim` (the composed
+    (scale, R, t) into segment 0's gauge); unconnected = the indices of the others, which stay in gauges of their own.  Pure."""
+    segments = list(segments); sims = list(sims)
+    if len(sims) != max(len(segments) - 1, 0):
+        raise ValueError(f"{len(segments)} segments take {max(len(segments) - 1, 0)} similarities, got {len(sims)}")
+    joined, unconnected = [], []
+    total = (1.0, np.eye(3), np.zeros(3))
+    for k, seg in enumerate(segments):
+        if k > 0 and total is not None:
+            s = sims[k - 1]
+            if isinstance(s, dict):
+                s = (s["scale"], s["R"], s["t"])
+            total = None if s is None else compose_similarity(total, s)
+        if total is None:
+            unconnected.append(k)
+            continue
+        d = {key: (v.copy() if isinstance(v, np.ndarray) else v) for key, v in seg.items()}
+        for key in ("poses_pnp", "poses"):
+            if key in d:
+                d[key] = apply_similarity(d[key], *total)
+        d["index"] = k; d["sim"] = total
+        joined.append(d)
+    return joined, unconnected
 
 
 STREAM_PAIR_KEYS = ("chi2", "n_corr", "n_inl", "status", "n_pts", "n_obs", "n_cam", "ba_iterations", "ba_trials")

@@ -265,3 +265,32 @@ def relocalize(map_points, map_descriptors, keypoints_xy, descriptors, K, max_di
     out = fe.relocalize([0], K, max_distance, iterations, reproj_err, confidence, seed, min_inliers)
     return dict(status=int(out["status"][0]), pose=out["poses"][0], n_match=int(out["n_match"][0]), n_inl=int(out["n_inl"][0]),
                 matches=fe.map_matches(0))
+
+
+def estimate_similarity_batch(src, dst, offsets, max_error, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None):
+    """B independent similarity problems in one launch (vo_sim3_ransac_batch); problem b owns rows offsets[b]:offsets[b+1] of src
+    and dst.  Returns dict(status [B], scale [B], R [B, 3, 3], t [B, 3], n_inl [B], mask [total] uint8)."""
+    b = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 3))
+    a = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 3))
+    if len(a) != len(b):
+        raise ValueError("src and dst must hold the same number of points")
+    off = np.ascontiguousarray(offsets, np.int32)
+    B = len(off) - 1
+    opts = _lib.AlignOpts(0.0, float(max_error), int(iterations), float(confidence), int(seed), int(min_inliers))
+    sim = np.zeros((B, 13)); mask = np.zeros(max(len(b), 1), np.uint8); ninl = np.zeros(B, np.int32); status = np.zeros(B, np.int32)
+    ctx = ctx or _lib.default_context()
+    ctx.check(ctx.lib.vo_sim3_ransac_batch(ctx.handle, b.ctypes.data, a.ctypes.data, off.ctypes.data, B, C.addressof(opts), sim.ctypes.data,
+                                           mask.ctypes.data, ninl.ctypes.data, status.ctypes.data))
+    return dict(status=status, scale=sim[:, 0].copy(), R=sim[:, 1:10].reshape(B, 3, 3).copy(), t=sim[:, 10:].copy(), n_inl=ninl,
+                mask=mask[:len(b)])
+
+
+def estimate_similarity(src, dst, max_error, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None):
+    """The similarity dst ~ scale R src + t from 3D-3D correspondences with outliers (vo_sim3_ransac_batch, one problem): RANSAC
+    over Umeyama's closed form on three points, then the same fit over the inliers.  src, dst [n, 3]; max_error is the inlier
+    bound in dst's units — it has no default: it is in the caller's units and nobody can choose it for them.  Returns dict(status:
+    0, VO_ERR_TOO_FEW (n < 3) or VO_ERR_NO_MODEL; scale, R [3, 3], t [3] (zeros when status != 0); n_inl; mask [n] uint8, the
+    best RANSAC model's inliers)."""
+    n = len(np.asarray(src, np.float64).reshape(-1, 3))
+    o = estimate_similarity_batch(src, dst, [0, n], max_error, iterations, confidence, seed, min_inliers, ctx)
+    return dict(status=int(o["status"][0]), scale=float(o["scale"][0]), R=o["R"][0], t=o["t"][0], n_inl=int(o["n_inl"][0]), mask=o["mask"])
