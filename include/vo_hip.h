@@ -959,8 +959,8 @@ int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* 
  * Lifetime: the query maps and work buffers are an allocation of their own, made by the first vo_map_align and ended with the staged
  *   map's; a newly staged map forgets the queries.  The pair results, the chains' maps, a live stream and vo_map_localize's results
  *   are left alone.
- * Out of scope: a stream's own descriptor store, automatic joining inside the restart walks, pose-graph or bundle refinement after
- * the join, ratio matching. */
+ * Out of scope: a stream's own descriptor store, automatic joining inside the restart walks, bundle refinement after the join (the
+ * pose-graph refinement is vo_pose_graph, below), ratio matching. */
 typedef struct {
     double   max_distance;      /* descriptor filter as in vo_reloc_opts; 0: none */
     double   max_error;         /* inlier bound in map A's units; > 0 */
@@ -974,6 +974,58 @@ int vo_sim3_ransac_batch(vo_ctx* ctx, const double* src /*b*/, const double* dst
 int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* points, const int32_t* off /*[Q + 1]*/, int Q, const vo_align_opts* opts,
                  double* sim /*[Q][13]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
 int vo_map_align_matches(vo_ctx* ctx, int q, int32_t* a_idx, int32_t* b_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
+
+/* ------------------------------------------------------------------ pose graph: Sim(3) pose-graph optimisation on the device
+ * The restart walks cut a flight into segments, vo_map_localize places a frame in an older map, vo_map_align measures the similarity
+ * between two maps: a loop closure arrives as seven numbers.  This section uses it: loop and join constraints are distributed over
+ * all poses of a flight, as ORB-SLAM's essential graph and g2o's types_sim3 do.  The reference has no counterpart and g2o is not
+ * installed anywhere this project runs, so the rules are this library's own; the checker is tests/pose_graph_reference.py.
+ *   Elements: S = (s, R, t) acts as x -> s R x + t; 13 doubles s, R row-major, t (vo_sim3_ransac_batch's `sim`).
+ *   Tangent: d = (w, u, sigma) in R^7: rotation, translation, log-scale.  hat(d) = [[ [w]x + sigma I, u ], [0, 0]] (4x4);
+ *     exp(d) = its matrix exponential: R = exp([w]x), s = e^sigma, t = V u, V = integral over [0, 1] of e^(tau sigma) exp(tau [w]x)
+ *     = C I + A [w]x + B [w]x^2.  With th = |w| and the moments m_k(sigma) = integral of tau^k e^(tau sigma):
+ *       th >= 1e-2: R from sin th / th and 2 sin^2(th / 2) / th^2; a = e^sigma sin th, 1 - b = 2 sin^2(th / 2) - expm1(sigma) cos th,
+ *         c = th^2 + sigma^2, C = m_0, A = (a sigma + (1 - b) th) / (th c), B = (C - (a th - (1 - b) sigma) / c) / th^2;
+ *       th <  1e-2: series to th^6 for R; A = m_1 - th^2 m_3 / 6 + th^4 m_5 / 120, B = m_2 / 2 - th^2 m_4 / 24 + th^4 m_6 / 720, C = m_0;
+ *       |sigma| >= 1e-2: m_0 = expm1(sigma) / sigma, m_k = (e^sigma - k m_(k-1)) / sigma;
+ *       |sigma| <  1e-2: m_k = sum over n = 0 .. 7 of sigma^n / (n! (n + k + 1)).
+ *     log is the inverse, the rotation angle in [0, pi): the unit quaternion of R (Eigen's conversion, w >= 0), n = |(x, y, z)|,
+ *     w = (2 atan2(n, q_w) / n) (x, y, z), below n = 1e-8 the factor is (2 / q_w)(1 - (n / q_w)^2 / 3); sigma = ln s; u = V^-1 t.
+ *   Adjoint: Ad(S) = [[R, 0, 0], [[t]x R, s R, -t], [0, 0, 1]] (blocks 3, 3, 1): S exp(d) S^-1 = exp(Ad(S) d).
+ *   Vertices: vertex i is S_i, world -> camera i (a pose [R | t] of this library has s = 1).  Update S_i <- exp(d_i) S_i, stored as
+ *     the product of the 13 numbers (no re-orthogonalisation).  A fixed vertex keeps its input bytes.
+ *   Edges: edge k = (i, j, C_k, w_k[7]), w_k > 0: E_k = C_k S_i S_j^-1, e_k = log(E_k), chi2_k = sum w_k e_k^2.  Huber as in the bundle
+ *     adjustment (rho = 2 delta sqrt(chi2_k) - delta^2 beyond delta, the weight is rho' only); huber_delta <= 0 turns it off.
+ *     Jacobians, first order (exact at E_k = I): d e_k / d d_i = Ad(C_k), d e_k / d d_j = -Ad(E_k).
+ *   Levenberg-Marquardt: exactly the bundle adjustment's rules (tau = 1e-5, lambda from the first linearisation, its nu and lambda
+ *     updates, at most 10 trials per iteration, a non-positive Cholesky pivot is a failed trial, no convergence test, `iterations`
+ *     fixed by the caller) with one change: rho = (chi2 - chi2_trial) / (d^T (lambda d + b)), without g2o's + 1e-3 (residuals here
+ *     are radians and map units; chi2 itself is of the order 1e-3: docs/kernels/k_pose_graph.md).  A trial is rejected if that
+ *     denominator is <= 0 or not finite, or if the trial chi2 is not finite.
+ *   Capacity: an edge with |i - j| == 1 is a chain edge, every other a loop edge.  Per graph at most VO_PGO_MAX_VERTICES vertices and
+ *     VO_PGO_MAX_LOOPS loop edges, any number of chain edges, duplicates included.  Beyond: VO_ERR_UNSUPPORTED in that graph's status,
+ *     its data unchanged, the rest of the batch runs.
+ *   Validity, each VO_ERR_INVALID for that graph alone, checked before capacity except the last: an index out of range, i == j, a
+ *     weight <= 0 or not finite; a vertex that is not connected to a fixed vertex.  The call itself returns VO_ERR_INVALID for
+ *     decreasing offsets, missing arrays or iterations outside 1 .. 1000.
+ *   Determinism: two calls on the same input return the same bytes; a graph alone returns the same bytes as anywhere in a batch.
+ * vo_pose_graph_batch: graph b = vertices vert_off[b] .. vert_off[b + 1] - 1 and edges edge_off[b] .. edge_off[b + 1] - 1; edge indices
+ *   are local to the graph.  chi2[b] = robust chi2 before and after; iterations_run, trials_run as vo_bundle_adjust_batch reports them.
+ *   Profiling stage: misc (k_pose_graph).  vo_pose_graph: one graph; a status other than VO_OK is its return value.
+ * Out of scope: automatic loop detection inside the streams, more than 32 loop edges or a multi-workgroup solver for one graph, full
+ * 7x7 information matrices, exact Jacobians (the left-Jacobian inverse of Sim(3)), bundle adjustment of the corrected map. */
+#define VO_PGO_MAX_VERTICES 8192
+#define VO_PGO_MAX_LOOPS    32
+typedef struct {
+    int32_t iterations;         /* 10 */
+    double  huber_delta;        /* 0: off */
+} vo_pgo_opts;
+int vo_pose_graph_batch(vo_ctx* ctx, int B, const int32_t* vert_off /*[B + 1]*/, const int32_t* edge_off /*[B + 1]*/,
+                        double* sims /*[V][13], in and out*/, const uint8_t* fixed /*[V]*/, const int32_t* edges /*[E][2], local indices*/,
+                        const double* meas /*[E][13]*/, const double* info /*[E][7]*/, const vo_pgo_opts* opts,
+                        double* chi2 /*[B][2]: initial, final*/, int32_t* iterations_run, int32_t* trials_run, int32_t* status);
+int vo_pose_graph(vo_ctx* ctx, double* sims /*[nv][13]*/, const uint8_t* fixed, int nv, const int32_t* edges /*[ne][2]*/, const double* meas,
+                  const double* info, int ne, const vo_pgo_opts* opts, double* chi2 /*[2]*/, int32_t* iterations_run, int32_t* trials_run);
 
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the

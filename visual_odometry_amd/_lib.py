@@ -19,6 +19,7 @@ VO_ERR_UNSUPPORTED = -7
 VO_STAGE_COUNT = 30
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
 VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
+VO_PGO_MAX_VERTICES, VO_PGO_MAX_LOOPS = 8192, 32
 VO_STATS_HIST = 64
 
 
@@ -41,6 +42,10 @@ class PairOpts(C.Structure):
 
 class BaOpts(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("huber_delta", C.c_double)]
+
+
+class PgoOpts(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("huber_delta", C.c_double)]
 
 
 class SlamOpts(C.Structure):
@@ -143,6 +148,8 @@ _SIGS = {
     "vo_comm_allgather_f64": (C.c_int, [_P, _P, C.c_int, _P]),
     "vo_pair_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "vo_reprojection_filter": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_double, _P, _P]),
+    "vo_pose_graph_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vo_pose_graph": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "vo_bundle_adjust_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     "vo_bundle_adjust": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P]),

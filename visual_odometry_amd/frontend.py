@@ -724,6 +724,137 @@ def compose_similarity(outer, inner):
     return s1 * s2, R1 @ R2, s1 * (R1 @ t2) + t1
 
 
+# ---- Sim(3) vertices of the pose graph (include/vo_hip.h, "pose graph"; map_filters.optimize_pose_graph).  A similarity is 13 doubles
+# s, R row-major, t and acts as x -> s R x + t; a tangent is (w, u, sigma): rotation, translation, log-scale.  Pure numpy.
+SIM3_TH_W, SIM3_TH_S, SIM3_TH_LOG = 1e-2, 1e-2, 1e-8
+
+
+def _sim3(S):
+    S = np.asarray(S, np.float64).reshape(13)
+    return float(S[0]), S[1:10].reshape(3, 3), S[10:13]
+
+
+def _sim3_pack(s, R, t):
+    return np.concatenate([[float(s)], np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)])
+
+
+def _hat3(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _sim3_v(w, sigma):
+    """V = C I + A [w]x + B [w]x^2, the header's closed forms and series"""
+    th = float(np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]))
+    m = np.empty(7)
+    if abs(sigma) < SIM3_TH_S:
+        fact = [1.0, 1.0, 2.0, 6.0, 24.0, 120.0, 720.0, 5040.0]
+        for k in range(7):
+            m[k] = sum(sigma ** n / (fact[n] * (n + k + 1)) for n in range(8))
+    else:
+        m[0] = np.expm1(sigma) / sigma
+        for k in range(1, 7):
+            m[k] = (np.exp(sigma) - k * m[k - 1]) / sigma
+    if th < SIM3_TH_W:
+        t2 = th * th
+        A = m[1] - t2 * m[3] / 6 + t2 * t2 * m[5] / 120
+        B = m[2] / 2 - t2 * m[4] / 24 + t2 * t2 * m[6] / 720
+    else:
+        em, h = np.expm1(sigma), np.sin(0.5 * th)
+        a, omb, c = (em + 1) * np.sin(th), 2 * h * h - em * np.cos(th), th * th + sigma * sigma
+        A = (a * sigma + omb * th) / (th * c)
+        B = (m[0] - (a * th - omb * sigma) / c) / (th * th)
+    W = _hat3(w)
+    return m[0] * np.eye(3) + A * W + B * (W @ W)
+
+
+def sim3_exp(d):
+    """The similarity exp(hat(d)) of a tangent d = (w, u, sigma)."""
+    d = np.asarray(d, np.float64).reshape(7)
+    w, sigma = d[:3], float(d[6])
+    th = float(np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]))
+    if th < SIM3_TH_W:
+        t2 = th * th
+        sa = 1 - t2 / 6 * (1 - t2 / 20 * (1 - t2 / 42)); ca = 0.5 - t2 / 24 * (1 - t2 / 30 * (1 - t2 / 56))
+    else:
+        sa = np.sin(th) / th; ca = 2 * np.sin(0.5 * th) ** 2 / (th * th)
+    W = _hat3(w)
+    return _sim3_pack(np.exp(sigma), np.eye(3) + sa * W + ca * (W @ W), _sim3_v(w, sigma) @ d[3:6])
+
+
+def sim3_log(S):
+    """The tangent of a similarity, rotation angle in [0, pi): the inverse of sim3_exp."""
+    s, R, t = _sim3(S)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    q = np.empty(4)                                   # (x, y, z, w), Eigen's conversion
+    if tr > 0:
+        r = np.sqrt(tr + 1.0); q[3] = 0.5 * r; r = 0.5 / r
+        q[:3] = [(R[2, 1] - R[1, 2]) * r, (R[0, 2] - R[2, 0]) * r, (R[1, 0] - R[0, 1]) * r]
+    else:
+        i = 0
+        if R[1, 1] > R[0, 0]:
+            i = 1
+        if R[2, 2] > R[i, i]:
+            i = 2
+        j = (i + 1) % 3; k = (j + 1) % 3
+        r = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0); q[i] = 0.5 * r; r = 0.5 / r
+        q[3] = (R[k, j] - R[j, k]) * r; q[j] = (R[j, i] + R[i, j]) * r; q[k] = (R[k, i] + R[i, k]) * r
+    if q[3] < 0:
+        q = -q
+    q = q / np.sqrt(q @ q)
+    n = float(np.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]))
+    f = 2 / q[3] * (1 - (n / q[3]) ** 2 / 3) if n < SIM3_TH_LOG else 2 * np.arctan2(n, q[3]) / n
+    w, sigma = f * q[:3], float(np.log(s))
+    return np.concatenate([w, np.linalg.solve(_sim3_v(w, sigma), t), [sigma]])
+
+
+def sim3_inverse(S):
+    s, R, t = _sim3(S)
+    return _sim3_pack(1.0 / s, R.T, -(R.T @ t) / s)
+
+
+def sim3_compose(outer, inner):
+    """x -> outer(inner(x))"""
+    s1, R1, t1 = _sim3(outer); s2, R2, t2 = _sim3(inner)
+    return _sim3_pack(s1 * s2, R1 @ R2, s1 * (R1 @ t2) + t1)
+
+
+def track_vertices(poses, sim=None):
+    """Pose-graph vertices [N, 13] of world -> camera poses [N, 3, 4].  sim = (s, R, t) of align_maps, X_a = s R X_b + t, takes a
+    track of gauge B into gauge A: S_i = (1 / s, R_i R^T, t_i - R_i R^T t / s), so the camera frame keeps its own units."""
+    T = np.asarray(poses, np.float64).reshape(-1, 3, 4)
+    s, R, t = (1.0, np.eye(3), np.zeros(3)) if sim is None else (float(sim[0]), np.asarray(sim[1], np.float64).reshape(3, 3), np.asarray(sim[2], np.float64).reshape(3))
+    out = np.empty((len(T), 13))
+    for i, P in enumerate(T):
+        Rc = P[:, :3] @ R.T
+        out[i] = _sim3_pack(1.0 / s, Rc, P[:, 3] - Rc @ t / s)
+    return out
+
+
+def odometry_edges(vertices):
+    """The chain edges (i, i + 1) of a track: (edges [N - 1, 2] int32, meas [N - 1, 13]) with C = S_(i+1) S_i^-1."""
+    V = np.asarray(vertices, np.float64).reshape(-1, 13)
+    n = max(len(V) - 1, 0)
+    edges = np.stack([np.arange(n), np.arange(n) + 1], axis=1).astype(np.int32)
+    return edges, np.array([sim3_compose(V[i + 1], sim3_inverse(V[i])) for i in range(n)]).reshape(n, 13)
+
+
+def loop_edge(S_i, S_j_observed):
+    """The measurement C = S_j_observed S_i^-1 of an edge (i, j): where vertex j was observed to lie, as seen from vertex i."""
+    return sim3_compose(S_j_observed, sim3_inverse(S_i))
+
+
+def vertices_to_poses(vertices):
+    """[N, 3, 4] world -> camera poses [R | t / s] of pose-graph vertices: the same camera centres, unit scale."""
+    V = np.asarray(vertices, np.float64).reshape(-1, 13)
+    return np.concatenate([V[:, 1:10].reshape(-1, 3, 3), (V[:, 10:13] / V[:, :1])[..., None]], axis=-1)
+
+
+def correct_points(points, S_before, S_after):
+    """Map points [n, 3] seen from a vertex that moved: X' = S_after^-1 S_before X."""
+    s, R, t = _sim3(sim3_compose(sim3_inverse(S_after), S_before))
+    return s * (np.asarray(points, np.float64).reshape(-1, 3) @ R.T) + t
+
+
 def join_segments(segments, sims):
     """split_segments' list in ONE gauge, segment 0's.  sims[k - 1], for every later segment k, is the similarity that takes
     segment k's gauge to segment k - 1's — (scale, R, t) or a dict with those keys, as align_maps / estimate_similarity return for

@@ -192,3 +192,56 @@ def optimize_map(cameras, points, observations, camera_matrix, iterations=40, ct
     for i, p in enumerate(points):
         p.point = np.copy(r["points"][i])
     return r["chi2_before"], r["chi2_after"]
+
+
+def _pgo_problem(sims, fixed, edges, meas, info=None):
+    sims = np.array(sims, np.float64).reshape(-1, 13)
+    fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8)).ravel()
+    edges = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 13)
+    info = np.ones((len(edges), 7)) if info is None else np.ascontiguousarray(info, np.float64).reshape(-1, 7)
+    if len(fixed) != len(sims):
+        raise ValueError("one fixed flag per vertex")
+    if not (len(edges) == len(meas) == len(info)):
+        raise ValueError("edge arrays differ in length")
+    return sims, fixed, edges, meas, info
+
+
+def optimize_pose_graph_batch(problems, iterations=10, huber_delta=0.0, ctx=None):
+    """Sim(3) pose-graph optimisation (include/vo_hip.h, "pose graph") of B independent graphs in one launch, one workgroup each.
+    problems: a list of (sims [nv, 13] = s, R row-major, t of world -> camera, fixed [nv], edges [ne, 2] indexing that graph's rows,
+    meas [ne, 13], info [ne, 7] or None = all weights 1).  Returns one dict per problem: sims (a new array), chi2_initial, chi2_final,
+    iterations, trials, status (VO_OK; VO_ERR_UNSUPPORTED beyond 8192 vertices / 32 loop edges; VO_ERR_INVALID for a bad index, an
+    edge from a vertex to itself, a weight that is not positive, a vertex that reaches no fixed vertex: such a graph comes back unchanged).
+    iterations outside 1 .. 1000 raise VoError for the call."""
+    probs = [_pgo_problem(*p) for p in problems]
+    B = len(probs)
+    off = np.zeros((2, B + 1), np.int32)
+    for b, p in enumerate(probs):
+        off[:, b + 1] = off[:, b] + (len(p[0]), len(p[2]))
+    cat = lambda k, shape, dt: np.ascontiguousarray(np.concatenate([p[k] for p in probs]) if B else np.zeros(shape, dt))  # noqa: E731
+    sims, fixed, edges, meas, info = cat(0, (0, 13), np.float64), cat(1, 0, np.uint8), cat(2, (0, 2), np.int32), cat(3, (0, 13), np.float64), cat(4, (0, 7), np.float64)
+    chi2 = np.zeros((B, 2)); it = np.zeros(B, np.int32); tr = np.zeros(B, np.int32); st = np.zeros(B, np.int32)
+    opts = _lib.PgoOpts(int(iterations), float(huber_delta))
+    ctx = ctx or _lib.default_context()
+    ctx.check(ctx.lib.vo_pose_graph_batch(ctx.handle, B, off[0].ctypes.data, off[1].ctypes.data, sims.ctypes.data, fixed.ctypes.data,
+                                          edges.ctypes.data, meas.ctypes.data, info.ctypes.data, ctypes.addressof(opts), chi2.ctypes.data,
+                                          it.ctypes.data, tr.ctypes.data, st.ctypes.data))
+    return [dict(sims=sims[off[0, b]:off[0, b + 1]].copy(), chi2_initial=float(chi2[b, 0]), chi2_final=float(chi2[b, 1]),
+                 iterations=int(it[b]), trials=int(tr[b]), status=int(st[b])) for b in range(B)]
+
+
+def optimize_pose_graph(sims, fixed, edges, meas, info=None, iterations=10, huber_delta=0.0, ctx=None):
+    """One graph (vo_pose_graph): dict(sims, chi2_initial, chi2_final, iterations, trials, status).  A graph over capacity raises
+    NotImplementedError, an invalid one VoError, as do iterations outside 1 .. 1000; the inputs are not modified.  frontend.track_vertices, odometry_edges and loop_edge
+    build the arguments, frontend.vertices_to_poses and correct_points take the result back."""
+    sims, fixed, edges, meas, info = _pgo_problem(sims, fixed, edges, meas, info)
+    chi2 = np.zeros(2); it = np.zeros(1, np.int32); tr = np.zeros(1, np.int32)
+    opts = _lib.PgoOpts(int(iterations), float(huber_delta))
+    ctx = ctx or _lib.default_context()
+    rc = ctx.lib.vo_pose_graph(ctx.handle, sims.ctypes.data, fixed.ctypes.data, len(sims), edges.ctypes.data, meas.ctypes.data,
+                               info.ctypes.data, len(edges), ctypes.addressof(opts), chi2.ctypes.data, it.ctypes.data, tr.ctypes.data)
+    if rc == _lib.VO_ERR_UNSUPPORTED:
+        raise NotImplementedError(ctx.last_error())
+    ctx.check(rc)
+    return dict(sims=sims, chi2_initial=float(chi2[0]), chi2_final=float(chi2[1]), iterations=int(it[0]), trials=int(tr[0]), status=int(rc))
