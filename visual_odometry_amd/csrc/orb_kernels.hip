@@ -13,7 +13,7 @@
 #include <float.h>
 #include <stdlib.h>
 
-__constant__ int8_t c_pattern[256 * 4] = {
+__constant__ __attribute__((aligned(16))) int8_t c_pattern[256 * 4] = {      // k_brief reads a test's four bytes as one dword
 #include "orb_pattern.inc"
 };
 __constant__ int c_umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
@@ -1349,80 +1349,6 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
     return a;
 }
 
-// One wavefront per keypoint. The 31 x 32-byte patch rows are read as unaligned dwords starting at x0 - 15
-// (248 dwords = 4 per lane); a per-(|v|, dword) byte mask cuts the radius-15 disc; v_dot4_u32_u8 gives the
-// dword's pixel sum and its 0,1,2,3-weighted sum, so m10 and m01 cost two dot products per dword.
-// The integer moments are order independent and are reduced with shuffles.
-__constant__ uint32_t c_disc_mask[16][8] = {
-#define DM(u0, um) ((((u0) >= -(um) && (u0) <= (um)) ? 0x000000ffu : 0u) | (((u0) + 1 >= -(um) && (u0) + 1 <= (um)) ? 0x0000ff00u : 0u) | \
-                    (((u0) + 2 >= -(um) && (u0) + 2 <= (um)) ? 0x00ff0000u : 0u) | (((u0) + 3 >= -(um) && (u0) + 3 <= (um)) ? 0xff000000u : 0u))
-#define DROW(um) {DM(-15, um), DM(-11, um), DM(-7, um), DM(-3, um), DM(1, um), DM(5, um), DM(9, um), DM(13, um)}
-    DROW(15), DROW(15), DROW(15), DROW(15), DROW(14), DROW(14), DROW(14), DROW(13),
-    DROW(13), DROW(12), DROW(11), DROW(10), DROW(9), DROW(8), DROW(6), DROW(3)
-#undef DROW
-#undef DM
-};
-
-#ifndef ANG_KPW
-#define ANG_KPW 4                         // keypoints per wavefront: their dependent load chains overlap
-#endif
-__global__ __launch_bounds__(256) void k_angle(const uint8_t* pyr, PyrGeom g, FrameFeat ff, int blocks_per_frame)
-{
-    // keypoints are stored in (level, y, x) order: a contiguous run of them per XCD lets neighbouring patches
-    // share image lines through that XCD's L2 instead of fetching them once per XCD
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);
-    const int f = bid / blocks_per_frame, lane = threadIdx.x & 63;
-    const int k0 = ((bid % blocks_per_frame) * 4 + (threadIdx.x >> 6)) * ANG_KPW;
-    const int cnt = min(ff.kp_count[f], g.kp_cap);
-    if (k0 >= cnt) return;
-    // the kernel is bound by the latency of (keypoint record -> patch rows): all records first, then all 16 patch
-    // loads of the lane, then the arithmetic
-    const uint8_t* corner[ANG_KPW];
-    int stride[ANG_KPW];
-#pragma unroll
-    for (int q = 0; q < ANG_KPW; q++) {
-        const size_t ki = (size_t)f * g.kp_cap + min(k0 + q, cnt - 1);
-        const uint32_t pos = __builtin_amdgcn_readfirstlane(ff.kp_pos[ki]);
-        const int level = __builtin_amdgcn_readfirstlane(ff.kp_level[ki]);
-        stride[q] = g.lv[level].stride;
-        corner[q] = pyr + (size_t)f * g.frame_bytes + g.lv[level].off + (size_t)((int)(pos >> 16) - 15) * stride[q] + ((int)(pos & 0xffff) - 15);
-    }
-    uint32_t w[ANG_KPW][4];
-#pragma unroll
-    for (int q = 0; q < ANG_KPW; q++)
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int idx = min(it * 64 + lane, 247);
-            __builtin_memcpy(&w[q][it], corner[q] + (size_t)(idx >> 3) * stride[q] + 4 * (idx & 7), 4);
-        }
-    float m10f = 0.f, m01f = 0.f;
-#pragma unroll
-    for (int q = 0; q < ANG_KPW; q++) {
-        int m10 = 0, m01 = 0;
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int idx = it * 64 + lane;
-            const int r = min(idx, 247) >> 3, j = idx & 7, v = r - 15, av = v < 0 ? -v : v;
-            const uint32_t x = idx < 248 ? w[q][it] & c_disc_mask[av][j] : 0u;
-            const int sum = (int)__builtin_amdgcn_udot4(x, 0x01010101u, 0u, false);
-            const int wsum = (int)__builtin_amdgcn_udot4(x, 0x03020100u, 0u, false);
-            m10 += (4 * j - 15) * sum + wsum;
-            m01 += v * sum;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { m10 += __shfl_xor(m10, d, 64); m01 += __shfl_xor(m01, d, 64); }
-        if (lane == q) { m10f = (float)m10; m01f = (float)m01; }
-    }
-    // lane q finishes keypoint q
-    if (lane < ANG_KPW && k0 + lane < cnt) ff.kp_angle[(size_t)f * g.kp_cap + k0 + lane] = fast_atan2_deg(m01f, m10f);
-}
-
-void launch_angle(hipStream_t s, const uint8_t* pyr, const PyrGeom& g, FrameFeat ff, int F)
-{
-    const int bpf = (g.kp_cap + 4 * ANG_KPW - 1) / (4 * ANG_KPW);
-    hipLaunchKernelGGL(k_angle, dim3(bpf * F), dim3(256), 0, s, pyr, g, ff, bpf);
-}
-
 // ------------------------------------------------------------------ GaussianBlur(7x7, sigma 2), BORDER_REFLECT_101
 // sepFilter2D 8u integer path: taps {18,34,49,55,49,34,18}, (sum + 2^15) >> 16, saturated.
 __device__ __forceinline__ int reflect101(int i, int n)
@@ -1739,82 +1665,191 @@ __device__ __forceinline__ uint32_t brief_expand8_fp4(uint32_t b)       // bit 1
     return 0xAAAAAAAAu ^ (w << 3);
 }
 
-// cos / sin of the keypoint angle, one LANE per keypoint (in k_brief the same double-precision calls would run once
-// per wavefront, 64 lanes wide for one value).  Parked in kp_xy, which k_brief overwrites with the exported position.
-__global__ __launch_bounds__(256) void k_brief_trig(PyrGeom g, FrameFeat ff)
-{
-    const int f = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= min(ff.kp_count[f], g.kp_cap)) return;
-    const size_t ki = (size_t)f * g.kp_cap + k;
-    const float angle = ff.kp_angle[ki] * (float)(3.1415926535897932384626433832795 / 180.f);
-    ff.kp_xy[ki * 2] = (float)cos((double)angle);
-    ff.kp_xy[ki * 2 + 1] = (float)sin((double)angle);
-}
-
+// Orientation and descriptor in one kernel: the raw 31 x 31 patch (ICAngles) and the blurred 37-row window of a keypoint
+// have addresses that follow from the same record, and neither depends on the angle, so both sets of loads are in flight
+// together.  Per wavefront BR_KPW keypoints, per workgroup BR_WG = BR_WAVES BR_KPW:
+//   records (scalar loads) -> raw patch as 31 x 3 aligned 16-byte chunks + window as 37 x 3/4 chunks + the pattern
+//   -> integer moments, reduced over the wavefront without LDS (br_reduce4) -> window into LDS, moments into LDS
+//   -> barrier -> lane k of the first wavefront: fastAtan2 and the f64 cos / sin of keypoint k -> barrier -> 512 LDS gathers.
 // The 256 test pairs sample a disc of radius 18.4 around the keypoint (the pattern's extreme point is (-13, -13)):
-// 512 single-byte gathers per keypoint saturate the texture addresser, so each wavefront first copies its
-// keypoint's 37-row x 48/64-byte window into LDS with aligned 16-byte loads and then gathers from LDS.
+// 512 single-byte gathers per keypoint saturate the texture addresser, hence the LDS copy of the window.
 #define BR_R 18
 #define BR_ROWS (2 * BR_R + 1)
 #ifndef BR_KPW
-#define BR_KPW 2                          // keypoints per wavefront: their record -> window -> gather chains overlap
+#define BR_KPW 2                          // keypoints per wavefront: their record -> windows -> use chains overlap
 #endif
-__global__ __launch_bounds__(256) void k_brief(const uint8_t* blur, PyrGeom g, FrameFeat ff, uint8_t* desc_x, int cap_x, int blocks_per_frame, int fp4)
+#ifndef BR_WAVES
+#define BR_WAVES 4                        // wavefronts per workgroup: the cos / sin wavefront serves BR_WAVES BR_KPW keypoints
+#endif
+#define BR_WG (BR_WAVES * BR_KPW)         // keypoints per workgroup
+typedef uint32_t br_u32x4 __attribute__((ext_vector_type(4)));
+#define BR_RAW_CHUNKS (31 * 3)            // 16-byte chunks of the raw patch: columns x - 15 .. x + 15 start at byte 0 .. 15 of the first
+static_assert(BR_KPW >= 1 && BR_WG <= 64, "one lane of the first wavefront per keypoint of the workgroup");
+
+// Wave totals of four per-lane integers in 4 + 3 cross-lane steps: v_permlane32_swap / v_permlane16_swap halve the lanes
+// per value while doubling the values per register, row_ror finishes inside the 16-lane rows.  Every lane of row 0, 1, 2, 3
+// returns the total of a, c, b, d.
+__device__ __forceinline__ int br_reduce4(int a, int b, int c, int d)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[4][BR_KPW][BR_ROWS * 64];
-    const int bid = xcd_tile(blockIdx.x, gridDim.x);          // a contiguous run of keypoints per XCD (see k_angle)
-    const int f = bid / blocks_per_frame, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int k0 = ((bid % blocks_per_frame) * 4 + wave) * BR_KPW;
+    const auto h = __builtin_amdgcn_permlane32_swap(a, b, false, false);        // {a.lo | b.lo}, {a.hi | b.hi}
+    const auto k = __builtin_amdgcn_permlane32_swap(c, d, false, false);
+    const int ab = (int)h[0] + (int)h[1], cd = (int)k[0] + (int)k[1];           // rows a a b b, c c d d
+    const auto q = __builtin_amdgcn_permlane16_swap(ab, cd, false, false);      // odd rows of ab <-> even rows of cd
+    int s = (int)q[0] + (int)q[1];                                              // rows a c b d
+    s += __builtin_amdgcn_update_dpp(0, s, 0x128, 0xf, 0xf, false);             // row_ror:8
+    s += __builtin_amdgcn_update_dpp(0, s, 0x124, 0xf, 0xf, false);             // row_ror:4
+    s += __builtin_amdgcn_update_dpp(0, s, 0x122, 0xf, 0xf, false);             // row_ror:2
+    s += __builtin_amdgcn_update_dpp(0, s, 0x121, 0xf, 0xf, false);             // row_ror:1
+    return s;
+}
+
+// The window's 37 x 4 = 148 chunks over three passes of 64 lanes: the 44 lanes left over in the last pass copy chunks
+// 104 .. 147 a second time (same data to the same place), so neither the load nor the LDS store sits under a branch.
+__device__ __forceinline__ int br_win_chunk(int it, int lane)
+{
+    const int idx = it * 64 + lane;
+    return idx < BR_ROWS * 4 ? idx : idx - (3 * 64 - BR_ROWS * 4);
+}
+
+__global__ __launch_bounds__(64 * BR_WAVES) void k_brief(const uint8_t* pyr, const uint8_t* blur, PyrGeom g, FrameFeat ff, uint8_t* desc_x, int cap_x, int blocks_per_frame, int fp4)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[BR_WAVES][BR_KPW][BR_ROWS * 64];
+    __shared__ int s_mom[BR_WG][2];                            // m10, m01
+    __shared__ float s_trig[BR_WG][2];                         // cos, sin
+    // keypoints are stored in (level, y, x) order: a contiguous run of them per XCD lets neighbouring patches
+    // share image lines through that XCD's L2 instead of fetching them once per XCD
+    const int bid = xcd_tile(blockIdx.x, gridDim.x);
+    const int f = bid / blocks_per_frame, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);           // wave-uniform: count and records are scalar loads
+    const int kbase = (bid % blocks_per_frame) * BR_WG, k0 = kbase + wave * BR_KPW;
     const int cnt = min(ff.kp_count[f], g.kp_cap);
-    if (k0 >= cnt) return;
-    float ca[BR_KPW], cb[BR_KPW], kxs[BR_KPW], kys[BR_KPW], sfs[BR_KPW];
-    int coff[BR_KPW];
-    uint4 wv[BR_KPW][3];
+    if (kbase >= cnt) return;                                  // the whole workgroup: the barriers below see all of it or none
+    // the lane's chunks of a raw patch (idx = it * 64 + lane of 31 rows x 3 chunks): row, chunk and the byte range
+    // [off + rlo, off + rhi] of the disc inside the chunk, off = (x - 15) & 15 being the patch's start in its first chunk
+    int rrow[2], rcol[2], rlo[2], rhi[2];
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int idx = it * 64 + lane, i2 = min(idx, BR_RAW_CHUNKS - 1);
+        const int r = i2 / 3, c = i2 - 3 * r, av = r < 15 ? 15 - r : r - 15;
+        const int um = (int)((0x3689abcddeeeffffull >> (4 * av)) & 15);          // half-width of the disc's row |v| (c_umax)
+        rrow[it] = r; rcol[it] = c;
+        rlo[it] = 15 - um - 16 * c;
+        rhi[it] = idx < BR_RAW_CHUNKS ? 15 + um - 16 * c : -64;                  // past the patch: empty range
+    }
+    // every load of the wavefront's keypoints is issued before any is consumed; nothing loads under a branch (a clamped
+    // address whose result is masked or dropped instead)
+    uint32_t pat[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) pat[w] = ((const uint32_t*)c_pattern)[w * 64 + lane];
+    float kxs[BR_KPW], kys[BR_KPW], sfs[BR_KPW];
+    int coff[BR_KPW], roff[BR_KPW], rxs[BR_KPW], ry0[BR_KPW], wxs[BR_KPW], wy0[BR_KPW], nchunk[BR_KPW], stride[BR_KPW], lh[BR_KPW];
+    size_t lvoff[BR_KPW];
 #pragma unroll
     for (int q = 0; q < BR_KPW; q++) {
         const size_t ki = (size_t)f * g.kp_cap + min(k0 + q, cnt - 1);
-        const uint32_t pos = __builtin_amdgcn_readfirstlane(ff.kp_pos[ki]);
-        const int level = __builtin_amdgcn_readfirstlane(ff.kp_level[ki]);
+        const uint32_t pos = ff.kp_pos[ki];
+        const int level = ff.kp_level[ki];
         const float sf = g.lv[level].scale;
-        const int stride = g.lv[level].stride, lh = g.lv[level].h;
-        const float kx = (float)(pos & 0xffff) * sf, ky = (float)(pos >> 16) * sf;
-        // computeOrbDescriptors re-derives the level position from the scaled keypoint
-        const float inv = 1.f / sf;
-        const int cx = __float2int_rn(kx * inv), cy = __float2int_rn(ky * inv);
-        ca[q] = ff.kp_xy[ki * 2]; cb[q] = ff.kp_xy[ki * 2 + 1];             // k_brief_trig
-        kxs[q] = kx; kys[q] = ky; sfs[q] = sf;
-        const uint8_t* img = blur + (size_t)f * g.frame_bytes + g.lv[level].off;
-        const int xs = (cx - BR_R) & ~15;                      // window columns xs .. xs + 63 (keypoints keep 32 px to the border)
-        const int nchunk = (cx - BR_R - xs) + 2 * BR_R + 1 > 48 ? 4 : 3;     // 16-byte chunks the 37 columns really span
-        coff[q] = BR_R * 64 + (cx - xs);
+        stride[q] = g.lv[level].stride; lh[q] = g.lv[level].h;
+        lvoff[q] = (size_t)f * g.frame_bytes + g.lv[level].off;
+        const int px = (int)(pos & 0xffff), py = (int)(pos >> 16);
+        kxs[q] = (float)px * sf; kys[q] = (float)py * sf; sfs[q] = sf;
+        // computeOrbDescriptors re-derives the level position from the scaled keypoint as round((px * sf) * (1 / sf)): three
+        // float roundings, off by at most 3.1 * 2^-24 * px < 0.02 for px < 65536, so the result is px itself
+        // ICAngles: raw level, columns px - 15 .. px + 15 inside three aligned chunks from rxs
+        // The lower clamps are made here, on the scalar side.  Kept keypoints lie in [31, w - 32] x [31, h - 32] of their level
+        // (edgeThreshold 31), so every row and every chunk that holds a needed column is inside the level and is never clamped.
+        // The row pitch is align_up(w, 64): the only chunk the stride - 16 clamp can reach is one that starts at or past w,
+        // which holds no needed column; its bytes are masked out (raw patch) or never gathered (window).
+        rxs[q] = max((px - 15) & ~15, 0); roff[q] = (px - 15) & 15; ry0[q] = max(py - 15, 0);
+        const int xs = max((px - BR_R) & ~15, 0);              // window columns xs .. xs + 63
+        wxs[q] = xs; wy0[q] = max(py - BR_R, 0);
+        nchunk[q] = (px - BR_R - xs) + 2 * BR_R + 1 > 48 ? 4 : 3;           // 16-byte chunks the 37 columns really span
+        coff[q] = BR_R * 64 + (px - xs);
+    }
+    br_u32x4 rv[BR_KPW][2], wv[BR_KPW][3];                    // values, not structs: the loads stay where they are written
+#pragma unroll
+    for (int q = 0; q < BR_KPW; q++)                           // the raw patches first: they are consumed first
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const int gy = min(ry0[q] + rrow[it], lh[q] - 1), gx = min(rxs[q] + 16 * rcol[it], stride[q] - 16);
+            rv[q][it] = *(const br_u32x4*)(pyr + lvoff[q] + (uint32_t)(__mul24(gy, stride[q]) + gx));     // scalar base + 32-bit lane offset
+        }
+#pragma unroll
+    for (int q = 0; q < BR_KPW; q++)
 #pragma unroll
         for (int it = 0; it < 3; it++) {
-            const int idx = min(it * 64 + lane, BR_ROWS * 4 - 1);
+            const int idx = br_win_chunk(it, lane);
             const int r = idx >> 2, c = idx & 3;
             // an unneeded fourth chunk re-reads the first one (same line, no control flow around the loads)
-            const int gy = min(max(cy - BR_R + r, 0), lh - 1), gx = min(max(xs + (c < nchunk ? 16 * c : 0), 0), stride - 16);
-            wv[q][it] = *(const uint4*)(img + (size_t)gy * stride + gx);
+            const int gy = min(wy0[q] + r, lh[q] - 1), gx = min(wxs[q] + (c < nchunk[q] ? 16 * c : 0), stride[q] - 16);
+            wv[q][it] = *(const br_u32x4*)(blur + lvoff[q] + (uint32_t)(__mul24(gy, stride[q]) + gx));
         }
+    // moments of the raw patches: a 16-bit byte mask of the disc per chunk, spread to bytes per dword; v_dot4_u32_u8 gives
+    // the dword's pixel sum and its position-weighted sum.  Integer sums, so any split over lanes is exact.
+    int m10[BR_KPW], m01[BR_KPW];
+#pragma unroll
+    for (int q = 0; q < BR_KPW; q++) {
+        m10[q] = 0; m01[q] = 0;
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const int lo = max(roff[q] + rlo[it], 0), hi = min(roff[q] + rhi[it], 15);
+            const uint32_t bm = hi >= 0 ? ((2u << hi) - 1u) & (0xffffffffu << lo) : 0u;
+            const uint32_t x4[4] = {rv[q][it].x, rv[q][it].y, rv[q][it].z, rv[q][it].w};
+            uint32_t sum = 0u, wsum = 0u;
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                const uint32_t t = __umul24((bm >> (4 * d)) & 15u, 0x00204081u) & 0x01010101u;    // bit i -> byte i
+                const uint32_t x = x4[d] & ((0x80808080u - t) ^ 0x80808080u);       // byte 1 -> 0xff without the slow 32-bit multiply
+                sum = __builtin_amdgcn_udot4(x, 0x01010101u, sum, false);
+                wsum = __builtin_amdgcn_udot4(x, 0x03020100u + 0x04040404u * d, wsum, false);
+            }
+            // sum <= 16 * 255: 24-bit products
+            m10[q] += __mul24(16 * rcol[it] - roff[q] - 15, (int)sum) + (int)wsum;
+            m01[q] += __mul24(rrow[it] - 15, (int)sum);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < BR_KPW; q += 2) {
+        const bool two = q + 1 < BR_KPW;
+        const int s = br_reduce4(m10[q], m01[q], two ? m10[q + 1] : 0, two ? m01[q + 1] : 0);
+        const int row = lane >> 4;                             // rows: m10[q], m10[q + 1], m01[q], m01[q + 1]
+        if ((lane & 15) == 0 && (two || !(row & 1))) s_mom[wave * BR_KPW + q + (row & 1)][row >> 1] = s;
     }
 #pragma unroll
     for (int q = 0; q < BR_KPW; q++)
 #pragma unroll
         for (int it = 0; it < 3; it++) {
-            const int idx = it * 64 + lane;
-            if (idx < BR_ROWS * 4) *(uint4*)(s_win[wave][q] + idx * 16) = wv[q][it];
+            *(br_u32x4*)(s_win[wave][q] + br_win_chunk(it, lane) * 16) = wv[q][it];
         }
+    // the pattern, converted once per wavefront
+    float ptx0[4], pty0[4], ptx1[4], pty1[4];
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        ptx0[w] = (float)(int8_t)(pat[w] & 0xff); pty0[w] = (float)(int8_t)((pat[w] >> 8) & 0xff);
+        ptx1[w] = (float)(int8_t)((pat[w] >> 16) & 0xff); pty1[w] = (float)(int8_t)(pat[w] >> 24);
+    }
+    __syncthreads();
+    if (threadIdx.x < BR_WG) {                                 // lane k finishes keypoint kbase + k
+        const int k = kbase + (int)threadIdx.x;
+        const float angle = fast_atan2_deg((float)s_mom[threadIdx.x][1], (float)s_mom[threadIdx.x][0]);
+        if (k < cnt) ff.kp_angle[(size_t)f * g.kp_cap + k] = angle;
+        const float a = angle * (float)(3.1415926535897932384626433832795 / 180.f);
+        s_trig[threadIdx.x][0] = (float)cos((double)a);
+        s_trig[threadIdx.x][1] = (float)sin((double)a);
+    }
+    __syncthreads();
 #pragma unroll
     for (int q = 0; q < BR_KPW; q++) {
         const int k = k0 + q;
         if (k >= cnt) break;                                   // wave-uniform
         const size_t ki = (size_t)f * g.kp_cap + k;
         const uint8_t* center = s_win[wave][q] + coff[q];
-        const float a = ca[q], b = cb[q];
+        const float a = s_trig[wave * BR_KPW + q][0], b = s_trig[wave * BR_KPW + q][1];
         uint64_t words[4];
 #pragma unroll
         for (int w = 0; w < 4; w++) {
-            const int8_t* pt = c_pattern + (w * 64 + lane) * 4;
-            const float px0 = (float)pt[0], py0 = (float)pt[1], px1 = (float)pt[2], py1 = (float)pt[3];
+            const float px0 = ptx0[w], py0 = pty0[w], px1 = ptx1[w], py1 = pty1[w];
             const float xa = px0 * a - py0 * b, ya = px0 * b + py0 * a;
             const float xb = px1 * a - py1 * b, yb = px1 * b + py1 * a;
             const int t0 = center[__float2int_rn(ya) * 64 + __float2int_rn(xa)];
@@ -1847,12 +1882,11 @@ __global__ __launch_bounds__(256) void k_brief(const uint8_t* blur, PyrGeom g, F
 }
 
 // desc_x: this launch's first frame, cap_x rows of 256 B per frame
-void launch_brief(hipStream_t s, const uint8_t* blur, const PyrGeom& g, FrameFeat ff, int F, uint8_t* desc_x, int cap_x, int fp4)
+void launch_brief(hipStream_t s, const uint8_t* pyr, const uint8_t* blur, const PyrGeom& g, FrameFeat ff, int F, uint8_t* desc_x, int cap_x, int fp4)
 {
-    hipLaunchKernelGGL(k_brief_trig, dim3((g.kp_cap + 255) / 256, F), dim3(256), 0, s, g, ff);
-    const int bpf = (g.kp_cap + 4 * BR_KPW - 1) / (4 * BR_KPW);
+    const int bpf = (g.kp_cap + BR_WG - 1) / BR_WG;
     // the matcher's operand image (+-127 bytes or FP4 nibbles) is expanded by its own lane-per-32-bits kernel: inside k_brief
     // 8 (16) lanes of a wavefront did it while the other 56 (48) idled through the same instructions (16 % of the kernel)
-    hipLaunchKernelGGL(k_brief, dim3(bpf * F), dim3(256), 0, s, blur, g, ff, desc_x, cap_x, bpf, -1);
+    hipLaunchKernelGGL(k_brief, dim3(bpf * F), dim3(64 * BR_WAVES), 0, s, pyr, blur, g, ff, desc_x, cap_x, bpf, -1);
     launch_desc_expand(s, ff.desc, ff.kp_count, g.kp_cap, cap_x, desc_x, F, fp4);
 }

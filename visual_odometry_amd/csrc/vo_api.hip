@@ -577,13 +577,12 @@ static int run_detect(vo_ctx* ctx, int first_slot, int F, int upto)
         StageTimer t(ctx, ST_CV2_ORDER);
         launch_cv2_order(s, g, ff, cb, F, ctx->har_kept + (size_t)first_slot * VO_MAX_LEVELS);
     }
-    { StageTimer t(ctx, ST_ANGLE); launch_angle(s, pyr, g, ff, F); }
     { StageTimer t(ctx, ST_BLUR); launch_blur(s, pyr, blur, g, F); }
     {
-        StageTimer t(ctx, ST_BRIEF);
+        StageTimer t(ctx, ST_BRIEF);                            // orientation and descriptor: one kernel (ST_ANGLE has no launches)
         const int cx = desc_x_rows(g.kp_cap);
         const int fp4 = descx_begin_write(ctx, first_slot, F);
-        launch_brief(s, blur, g, ff, F, ctx->desc_x + (size_t)first_slot * cx * 256, cx, fp4);
+        launch_brief(s, pyr, blur, g, ff, F, ctx->desc_x + (size_t)first_slot * cx * 256, cx, fp4);
     }
     return VO_OK;
 }
@@ -2844,9 +2843,8 @@ extern "C" double vo_stage_bytes(vo_ctx* ctx, int stage, int F)
     case ST_FAST: b = total; break;                                               // FAST reads P (winner lists are a few KB)
     case ST_SELECT_FAST: b = 2 * 2 * N * 12; break;                               // ~2N kept winners: list entry read twice, 8 B written
     case ST_HARRIS: b = 2 * N * 81 + 2 * N * 4; break;
-    case ST_ANGLE: b = N * 749; break;
     case ST_BLUR: b = total + total; break;
-    case ST_BRIEF: b = N * 512 + N * 32 + N * 28; break;
+    case ST_BRIEF: b = N * 749 + N * 512 + N * 32 + N * 28; break;                 // the raw patch of the orientation + gathers, descriptor, record
     case ST_MATCH_NN: b = 2 * N * 32; break;                                       // per pair ~ per frame: both descriptor sets
     case ST_MATCH_SELECT: b = 16 * N; break;
     case ST_RANSAC: b = 33 * N; break;                                             // SURVEY 8(d) geometry 65 N: 4 f64 coords + mask per match ...

@@ -168,7 +168,6 @@ void launch_cv2_order(hipStream_t s, const PyrGeom& g, FrameFeat ff, Cv2Buf cb, 
 void launch_retain_raw(hipStream_t s, const float* resp, int n, int n_points, uint2* a, uint32_t* lpos, uint32_t* rpos,
                        int* order, int* n_out);
 void launch_select_harris(hipStream_t s, const PyrGeom& g, FrameFeat ff, int F, float* thr, int* kept);
-void launch_angle(hipStream_t s, const uint8_t* pyr, const PyrGeom& g, FrameFeat ff, int F);
 void launch_resize_linear(hipStream_t st, const uint8_t* src, int sw, int sh, int cn, int sstride, int64_t sframe,
                           uint8_t* dst, int dw, int dh, int dstride, int64_t dframe,
                           const int* xofs, const void* xa, const int* yofs, const void* yb, int area2, int F);
@@ -227,7 +226,8 @@ void launch_pnp_ransac(hipStream_t s, const double* obj, const double* img, cons
                        int refine_cv2, double* rvec, double* tvec, uint8_t* mask, int* ninl, int* status, int off_stride = 1);
 void launch_rodrigues(hipStream_t s, const double* in, int in_is_matrix, double* out);
 void launch_blur(hipStream_t s, const uint8_t* pyr, uint8_t* blur, const PyrGeom& g, int F);
-void launch_brief(hipStream_t s, const uint8_t* blur, const PyrGeom& g, FrameFeat ff, int F, uint8_t* desc_x, int cap_x, int fp4);
+// orientation (kp_angle) and descriptor of every keypoint: reads the raw pyramid and its blurred copy
+void launch_brief(hipStream_t s, const uint8_t* pyr, const uint8_t* blur, const PyrGeom& g, FrameFeat ff, int F, uint8_t* desc_x, int cap_x, int fp4);
 
 // Workgroups are dealt round-robin over the 8 XCDs (block b -> XCD b % 8, each with its own L2).  Neighbouring
 // work items share data (image tiles: halo rows and 128-byte lines; the row blocks of a pair: the other frame's
