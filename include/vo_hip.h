@@ -1027,6 +1027,75 @@ int vo_pose_graph_batch(vo_ctx* ctx, int B, const int32_t* vert_off /*[B + 1]*/,
 int vo_pose_graph(vo_ctx* ctx, double* sims /*[nv][13]*/, const uint8_t* fixed, int nv, const int32_t* edges /*[ne][2]*/, const double* meas,
                   const double* info, int ne, const vo_pgo_opts* opts, double* chi2 /*[2]*/, int32_t* iterations_run, int32_t* trials_run);
 
+/* ------------------------------------------------------------------ place recognition: device vocabulary, keyframe index, loop query
+ * vo_map_localize, vo_map_align and vo_pose_graph are all told which two frames see the same ground.  This section finds them: a bag
+ * of visual words, as DBoW2 and ORB-SLAM's loop detector use one.  Descriptor rows are quantised against a small vocabulary, one
+ * short histogram is kept per keyframe — it outlives the frame's slot — and histograms are compared instead of descriptors.  The
+ * reference has no counterpart, so the rules are this library's own; all of them are integers and no floating point is used, so a
+ * checker (tests/places_reference.py) is held to equality.  Rows are the configured detector's: D = 32 bytes compared by Hamming
+ * distance under an ORB batch configuration, D = 128 values 0..255 compared by the integer squared L2 distance under a SIFT one
+ * (|row|^2 <= 2^20 as in vo_map_stage).  Every entry that reads slots returns VO_ERR_NOT_CONFIGURED before a batch configuration.
+ *   Vocabulary: K words, each a row in the descriptor's own format; K a multiple of 256, 256 <= K <= 4096.
+ *   Quantiser: a row's word is its nearest word, the lowest word index winning a tie (the selection of vo_pair_opts.match_mode 3; the
+ *     device bodies are k_nn_map's and k_nn_map_orb's).
+ *   Training (vo_vocab_train): the training set is the descriptor rows of the F detected slots in slot-list order, then keypoint order,
+ *     n rows.  Start: word w = training row floor(w n / K), in 64-bit integers.  A round is an assignment of every row to its word
+ *     followed by an update: for a word with c > 0 rows, ORB bit b (bit b % 8 of byte b / 8) is 1 iff 2 ones_b > c — a strict
+ *     majority, a tie gives 0 — and SIFT component j is (2 sum_j + c) / (2 c) in integer division, the mean rounded half up; a word
+ *     with c = 0 keeps its row.  The sums are int32 (atomics; their order cannot matter).  At most `iterations` rounds (below 1 counts
+ *     as 1); from the second round on, a round whose assignment moved no row ends the training before its update.  *iterations_run =
+ *     updates done; the vocabulary is what the last update wrote.  Every word is written through the row store of the staged map, so
+ *     the matcher's operand image and norms exist for it.  Two runs on the same input give the same bytes.
+ *   Entry of the index: hist[w] = min(255, rows of the frame whose word is w), uint8 [K]; sum = the sum of those saturated bytes; id =
+ *     the caller's frame number, any int32.
+ *   Score: shared(q, d) = sum over w of min(hist_q[w], hist_d[w]) = (sum_q + sum_d - L1(hist_q, hist_d)) / 2, an int32 (L1 on
+ *     v_sad_u8, four bytes an instruction).
+ *   Query: for a query entry q, every other entry d is a candidate (an entry never meets itself, whatever min_gap is) unless
+ *     |id_q - id_d| < min_gap (compared in 64-bit) or shared(q, d) < min_shared.  Reported: the top_k candidates of largest shared, the
+ *     lower entry index first among equals, in descending order; unused places hold entry -1, shared 0.
+ * vo_vocab_train: VO_ERR_INVALID for K outside the rule, F < 1 or F > max_frames, a slot out of range, a slot flagged for its descriptor
+ *   norm (SIFT), a trained word over the norm bound; VO_ERR_TOO_FEW for n < K; VO_ERR_UNSUPPORTED for n > 2^22 rows.  After an error
+ *   past the argument checks there is no vocabulary.
+ * vo_vocab_set: the vocabulary from the host, words [K][D]: the parity seam, and how a saved vocabulary comes back.  VO_ERR_INVALID for
+ *   K outside the rule and for a SIFT word with |row|^2 > 2^20; nothing is set then, an earlier vocabulary and its index stay.
+ * vo_vocab_get: up to cap words back; *K = the vocabulary's size.  vo_vocab_words: the word index of every row of a detected slot (up to
+ *   cap; *n = the slot's rows): the parity seam of the quantiser.  VO_ERR_INVALID without a vocabulary.
+ * A new vocabulary, trained or set, closes the index: its histograms count another vocabulary's words.
+ * vo_places_open: an empty index of `capacity` entries, 1 <= capacity <= 65536 (hist [capacity][K] uint8, sum and id [capacity] int32);
+ *   it replaces an open one.  VO_ERR_INVALID without a vocabulary or for a capacity outside the range.
+ * vo_places_add: quantises F <= max_frames detected slots and appends their entries in order; *first_entry = the index of the first.
+ *   A slot without rows gives an all-zero entry.  VO_ERR_UNSUPPORTED when the capacity would be exceeded, nothing is added then;
+ *   VO_ERR_INVALID without an open index, for a slot out of range or flagged for its descriptor norm (SIFT).
+ * vo_places_add_hist: appends n given histograms [n][K] with their ids; it restores a saved index and is the parity seam of the scorer.
+ *   VO_ERR_UNSUPPORTED / VO_ERR_INVALID as vo_places_add.
+ * vo_places_entries: entries first .. first + n - 1 back (any of the three arrays may be NULL); VO_ERR_INVALID outside the index.
+ * vo_places_size: *n = entries held, *K = words of a histogram; VO_ERR_INVALID without an open index.
+ * vo_places_query: Q <= 65536 query entries, each an entry of the index (a live frame is added first and then asked about: one path,
+ *   no second quantiser); Q may be the whole index — the flight's all-against-all pass.  VO_ERR_INVALID without an open index, for
+ *   top_k outside 1 .. 16, for a query entry outside the index.
+ * Profiling stages: match_nn (the assignment: k_vocab_assign), misc (everything else).
+ * Lifetime: the vocabulary and the index are allocations of their own, released by vo_destroy and by a configure call.  Detections,
+ *   vo_pairs_run, the vo_slam_* calls, a live stream, the staged map and vo_map_align's buffers are left alone, and they leave these
+ *   alone: the index is meant to be fed chunk after chunk while a stream walks a flight.
+ * Out of scope: tf-idf weights, a vocabulary tree, inverted files, K above 4096, geometric verification inside the call (the candidates
+ * go to vo_map_localize / vo_map_align), automatic use inside the restart walks. */
+typedef struct {
+    int32_t top_k;              /* 3; 1 .. 16 */
+    int32_t min_gap;            /* 0: candidates at any distance in id */
+    int32_t min_shared;         /* 0 */
+} vo_places_opts;
+int vo_vocab_train(vo_ctx* ctx, const int32_t* slots, int F, int K, int iterations, int32_t* iterations_run);
+int vo_vocab_set(vo_ctx* ctx, const uint8_t* words /*[K][D]*/, int K);
+int vo_vocab_get(vo_ctx* ctx, uint8_t* words /*[cap][D]*/, int cap, int32_t* K);
+int vo_vocab_words(vo_ctx* ctx, int slot, int32_t* word /*[cap]*/, int cap, int32_t* n);
+int vo_places_open(vo_ctx* ctx, int capacity);
+int vo_places_add(vo_ctx* ctx, const int32_t* slots, int F, const int32_t* ids, int32_t* first_entry);
+int vo_places_add_hist(vo_ctx* ctx, const uint8_t* hist /*[n][K]*/, const int32_t* ids, int n, int32_t* first_entry);
+int vo_places_entries(vo_ctx* ctx, int first, int n, uint8_t* hist /*[n][K]*/, int32_t* sum, int32_t* ids);
+int vo_places_size(vo_ctx* ctx, int32_t* n, int32_t* K);
+int vo_places_query(vo_ctx* ctx, const int32_t* entries /*[Q]*/, int Q, const vo_places_opts* opts,
+                    int32_t* out_entry /*[Q][top_k]*/, int32_t* out_shared /*[Q][top_k]*/);
+
 /* ------------------------------------------------------------------ measurement
  * With profiling on, every kernel family of the batched path is bracketed by hipEvents on the
  * ctx stream; vo_profile_read returns accumulated milliseconds and launch counts per stage since

@@ -65,6 +65,10 @@ class AlignOpts(C.Structure):
                 ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
 
 
+class PlacesOpts(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("min_gap", C.c_int32), ("min_shared", C.c_int32)]
+
+
 PAIR_RESULT_DTYPE = np.dtype([("n_kp1", "<i4"), ("n_kp2", "<i4"), ("n_match", "<i4"), ("n_inl", "<i4"),
                               ("n_good", "<i4"), ("status", "<i4"), ("ransac_iters", "<i4"), ("reserved", "<i4"),
                               ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,))], align=True)
@@ -139,6 +143,16 @@ _SIGS = {
     "vo_sim3_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
+    "vo_vocab_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "vo_vocab_set": (C.c_int, [_P, _P, C.c_int]),
+    "vo_vocab_get": (C.c_int, [_P, _P, C.c_int, _P]),
+    "vo_vocab_words": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "vo_places_open": (C.c_int, [_P, C.c_int]),
+    "vo_places_add": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "vo_places_add_hist": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "vo_places_entries": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "vo_places_size": (C.c_int, [_P, _P, _P]),
+    "vo_places_query": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "vo_comm_unique_id": (C.c_int, [_P]),
     "vo_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "vo_comm_destroy": (C.c_int, [_P]),

@@ -842,3 +842,320 @@ void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, con
     hipLaunchKernelGGL(k_sim3_ransac, dim3(B), dim3(256), sizeof(Sim3Shared), s, src, dst, offsets, off_stride, iterations, max_error, confidence, seed,
                        rng_tab, rng_n, min_inliers, sim, mask, ninl, status);
 }
+
+// ================================================================== place recognition (vo_vocab_*, vo_places_*; include/vo_hip.h)
+//   k_vocab_store        K rows into the vocabulary, through the map's stores (map_store_row_sift / _orb)
+//   k_vocab_assign[_orb] the nearest word of every row of F slots: the bodies above, A = a slot's rows, B = the vocabulary
+//   k_vocab_accumulate   per word the rows assigned and their bit counts / component sums (int32 atomics: the order cannot matter),
+//                        and the number of rows that changed their word
+//   k_vocab_update       the majority word / the rounded mean, stored as k_vocab_store stores
+//   k_places_hist        a frame's saturated word counts, their sum and the caller's id: one entry of the index
+//   k_places_score       shared(q, d) of a block of queries against a range of entries on v_sad_u8, the best top_k per query
+//   k_places_merge       the ranges' lists into the answer
+// No floating point in any of them.
+__global__ __launch_bounds__(256) void k_vocab_store(MapBuf v, const uint8_t* src, const int* key)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (v.D == 128) {
+        for (int w = blockIdx.x * 4 + (tid >> 6); w < v.npt; w += gridDim.x * 4)
+            map_store_row_sift(v, w, src + (size_t)(key ? key[w] : w) * 128, lane);
+    } else {
+        for (int w = blockIdx.x * 32 + (tid >> 3); w < v.npt; w += gridDim.x * 32)
+            map_store_row_orb(v, w, src + (size_t)(key ? key[w] : w) * 32, tid & 7);
+    }
+}
+
+void launch_vocab_store(hipStream_t s, VocabBuf vb, const uint8_t* src, const int* key)
+{
+    const int per = vb.v.D == 128 ? 4 : 32;
+    hipLaunchKernelGGL(k_vocab_store, dim3((vb.v.npt + per - 1) / per), dim3(256), 0, s, vb.v, src, key);
+}
+
+// workgroup b: rows blk NM_BLOCK_ROWS .. of query q = b / blocks
+__global__ __launch_bounds__(NM_THREADS) void k_vocab_assign(VocabBuf vb, const uint8_t* desc_x, const int* norms, const int* kp_count, int kp_cap, int cap_x,
+                                                             int blocks)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_b[2][NM_STAGE_ROWS * 128];
+    const int q = blockIdx.x / blocks, row0 = (blockIdx.x % blocks) * NM_BLOCK_ROWS;
+    const int slot = vb.slots[q], nq = min(kp_count[slot], kp_cap);
+    if (row0 >= nq) return;
+    nn_map_l2_body(s_b, desc_x + (size_t)slot * cap_x * 128, norms + (size_t)slot * cap_x, nq, vb.v.img, vb.v.norms, vb.v.npt, row0,
+                   vb.word + (size_t)q * kp_cap, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_vocab_assign_orb(VocabBuf vb, const uint8_t* desc, const int* kp_count, int kp_cap, int blocks)
+{
+    __shared__ uint4 s_b[NO_TILE * 2];
+    const int q = blockIdx.x / blocks, row0 = (blockIdx.x % blocks) * NO_BLOCK_ROWS;
+    const int slot = vb.slots[q], nq = min(kp_count[slot], kp_cap);
+    if (row0 >= nq) return;
+    nn_map_hamming_body(s_b, desc + (size_t)slot * kp_cap * 32, nq, vb.v.rows, vb.v.npt, row0, vb.word + (size_t)q * kp_cap, nullptr);
+}
+
+void launch_vocab_assign(hipStream_t s, VocabBuf vb, int F, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
+                         int kp_cap, int cap_x)
+{
+    if (F <= 0) return;
+    const int blocks = (kp_cap + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
+    if (vb.v.D == 128) hipLaunchKernelGGL(k_vocab_assign, dim3((unsigned)F * blocks), dim3(NM_THREADS), 0, s, vb, desc_x, norms, kp_count, kp_cap, cap_x, blocks);
+    else hipLaunchKernelGGL(k_vocab_assign_orb, dim3((unsigned)F * blocks), dim3(256), 0, s, vb, desc, kp_count, kp_cap, blocks);
+}
+
+// Row g = q kp_cap + i of the call's slots, a wavefront (SIFT: lane l adds components 2 l, 2 l + 1) or eight lanes (ORB: lane `part`
+// adds the set bits of bytes 4 part .. 4 part + 3; bit b of the row is bit b % 8 of byte b / 8) per row.
+__global__ __launch_bounds__(256) void k_vocab_accumulate(VocabBuf vb, int F, const uint8_t* desc, const int* kp_count, int kp_cap)
+{
+    const int tid = threadIdx.x;
+    const bool l2 = vb.v.D == 128;
+    const int per = l2 ? 4 : 32, sub = l2 ? tid >> 6 : tid >> 3, part = l2 ? tid & 63 : tid & 7;
+    const long long total = (long long)F * kp_cap;
+    for (long long g = (long long)blockIdx.x * per + sub; g < total; g += (long long)gridDim.x * per) {
+        const int q = (int)(g / kp_cap), i = (int)(g % kp_cap), slot = vb.slots[q];
+        if (i >= min(kp_count[slot], kp_cap)) continue;
+        const int w = vb.word[g];
+        if (part == 0) {
+            if (vb.prev[g] != w) atomicAdd(vb.changed, 1);
+            vb.prev[g] = w;
+            atomicAdd(vb.cnt + w, 1);
+        }
+        if (l2) {
+            const unsigned v = *(const uint16_t*)(desc + ((size_t)slot * kp_cap + i) * 128 + 2 * part);
+            if (v & 255u) atomicAdd(vb.acc + (size_t)w * 128 + 2 * part, (int)(v & 255u));
+            if (v >> 8) atomicAdd(vb.acc + (size_t)w * 128 + 2 * part + 1, (int)(v >> 8));
+        } else {
+            uint32_t bits = *(const uint32_t*)(desc + ((size_t)slot * kp_cap + i) * 32 + 4 * part);
+            int* a = vb.acc + (size_t)w * 256 + 32 * part;
+            while (bits) { const int b = __ffs(bits) - 1; bits &= bits - 1; atomicAdd(a + b, 1); }
+        }
+    }
+}
+
+void launch_vocab_accumulate(hipStream_t s, VocabBuf vb, int F, const uint8_t* desc, const int* kp_count, int kp_cap)
+{
+    if (F <= 0) return;
+    const int per = vb.v.D == 128 ? 4 : 32;
+    const long long g = ((long long)F * kp_cap + per - 1) / per;
+    hipLaunchKernelGGL(k_vocab_accumulate, dim3((unsigned)(g < 8192 ? g : 8192)), dim3(256), 0, s, vb, F, desc, kp_count, kp_cap);
+}
+
+// Word w with c = cnt[w] > 0 rows: ORB bit b = 1 iff 2 ones_b > c (a tie gives 0); SIFT component j = (2 sum_j + c) / (2 c).  The new
+// row goes to vb.tmp and from there through the map's store, by the lanes that wrote it; a word without rows keeps its row.
+__global__ __launch_bounds__(256) void k_vocab_update(VocabBuf vb)
+{
+    const int tid = threadIdx.x;
+    if (vb.v.D == 128) {
+        const int lane = tid & 63;
+        for (int w = blockIdx.x * 4 + (tid >> 6); w < vb.v.npt; w += gridDim.x * 4) {
+            const int c = vb.cnt[w];
+            if (c <= 0) continue;
+            const int u0 = (2 * vb.acc[(size_t)w * 128 + 2 * lane] + c) / (2 * c), u1 = (2 * vb.acc[(size_t)w * 128 + 2 * lane + 1] + c) / (2 * c);
+            uint8_t* row = vb.tmp + (size_t)w * 128;
+            *(uint16_t*)(row + 2 * lane) = (uint16_t)(u0 | (u1 << 8));
+            map_store_row_sift(vb.v, w, row, lane);
+        }
+    } else {
+        const int part = tid & 7;
+        for (int w = blockIdx.x * 32 + (tid >> 3); w < vb.v.npt; w += gridDim.x * 32) {
+            const int c = vb.cnt[w];
+            if (c <= 0) continue;
+            const int* a = vb.acc + (size_t)w * 256 + 32 * part;
+            uint32_t bits = 0;
+#pragma unroll 8
+            for (int b = 0; b < 32; b++) bits |= (2 * a[b] > c ? 1u : 0u) << b;
+            uint8_t* row = vb.tmp + (size_t)w * 32;
+            *(uint32_t*)(row + 4 * part) = bits;
+            map_store_row_orb(vb.v, w, row, part);
+        }
+    }
+}
+
+void launch_vocab_update(hipStream_t s, VocabBuf vb)
+{
+    const int per = vb.v.D == 128 ? 4 : 32;
+    hipLaunchKernelGGL(k_vocab_update, dim3((vb.v.npt + per - 1) / per), dim3(256), 0, s, vb);
+}
+
+// ------------------------------------------------------------------ the keyframe index
+#define PL_MAX_K 4096
+// entry q of the call: hist[w] = min(255, rows of slot slots[q] whose word is w), sum = the sum of those bytes, id = ids[q]
+__global__ __launch_bounds__(256) void k_places_hist(VocabBuf vb, const int* kp_count, int kp_cap, uint8_t* hist, int* sum, int* id)
+{
+    __shared__ int s_h[PL_MAX_K];
+    __shared__ int s_w[4];
+    const int q = blockIdx.x, tid = threadIdx.x, K = vb.v.npt;
+    const int nq = min(kp_count[vb.slots[q]], kp_cap);
+    for (int w = tid; w < K; w += 256) s_h[w] = 0;
+    __syncthreads();
+    for (int i = tid; i < nq; i += 256) atomicAdd(&s_h[vb.word[(size_t)q * kp_cap + i]], 1);
+    __syncthreads();
+    int s = 0;
+    for (int w4 = tid; w4 < K / 4; w4 += 256) {
+        uint32_t pk = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const int c = min(255, s_h[4 * w4 + k]); s += c; pk |= (uint32_t)c << (8 * k); }
+        *(uint32_t*)(hist + (size_t)q * K + 4 * w4) = pk;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+    if ((tid & 63) == 0) s_w[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) { sum[q] = s_w[0] + s_w[1] + s_w[2] + s_w[3]; id[q] = vb.ids[q]; }
+}
+
+void launch_places_hist(hipStream_t s, VocabBuf vb, int F, const int* kp_count, int kp_cap, uint8_t* hist, int* sum, int* id)
+{
+    if (F <= 0) return;
+    hipLaunchKernelGGL(k_places_hist, dim3(F), dim3(256), 0, s, vb, kp_count, kp_cap, hist, sum, id);
+}
+
+// sum[e] of n given histograms, a wavefront each
+__global__ __launch_bounds__(256) void k_places_sums(const uint8_t* hist, int K, int n, int* sum)
+{
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (e >= n) return;
+    unsigned s = 0;
+    for (int w4 = lane; w4 < K / 4; w4 += 64) s = __builtin_amdgcn_sad_u8(*(const uint32_t*)(hist + (size_t)e * K + 4 * w4), 0u, s);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+    if (lane == 0) sum[e] = (int)s;
+}
+
+void launch_places_sums(hipStream_t s, const uint8_t* hist, int K, int n, int* sum)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_places_sums, dim3((n + 3) / 4), dim3(256), 0, s, hist, K, n, sum);
+}
+
+// ------------------------------------------------------------------ k_places_score: shared(q, d) = (sum_q + sum_d - L1(q, d)) / 2
+// A workgroup takes PQ_T query entries and the entries [sp per_split, (sp + 1) per_split) of the index, PQ_T at a time.  For a tile
+// of PQ_T x PQ_T pairs the histograms pass through LDS PQ_KC bytes of every row at a time (row pitch PQ_LD: the 16 rows a quarter
+// wavefront reads with one ds_read_b128 lie in 16 different bank groups); thread (ty, tx) holds the L1 sums of queries i 16 + ty and
+// entries j 16 + tx, i, j < 4, four bytes per v_sad_u8.  The tile's sums then go to LDS and lane q of wave 0 takes query q's 64
+// candidates in ascending entry order into its list of the best top_k keys (shared << 32 | ~entry: larger shared first, then the
+// lower entry), kept descending in LDS.  An entry never meets itself; |id_q - id_d| < min_gap (64-bit) and shared < min_shared drop
+// a candidate.  Key 0 is no candidate: ~entry is never 0.
+#define PQ_T 64
+#define PQ_KC 256
+#define PQ_LD (PQ_KC + 16)
+__global__ __launch_bounds__(256) void k_places_score(PlacesQuery p)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_q[PQ_T * PQ_LD];
+    __shared__ __attribute__((aligned(16))) uint8_t s_e[PQ_T * PQ_LD];
+    __shared__ int s_l1[PQ_T][PQ_T + 1];
+    __shared__ unsigned long long s_top[16][PQ_T];
+    __shared__ int s_qe[PQ_T], s_qs[PQ_T], s_qid[PQ_T], s_es[PQ_T], s_eid[PQ_T];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int q0 = (blockIdx.x / p.splits) * PQ_T, sp = blockIdx.x % p.splits;
+    const int e_begin = sp * p.per_split, e_end = min(p.n, e_begin + p.per_split);
+    if (tid < PQ_T) {
+        const int e = q0 + tid < p.Q ? p.qent[q0 + tid] : -1;
+        s_qe[tid] = e; s_qs[tid] = e >= 0 ? p.sum[e] : 0; s_qid[tid] = e >= 0 ? p.id[e] : 0;
+    }
+    for (int i = tid; i < 16 * PQ_T; i += 256) (&s_top[0][0])[i] = 0ull;
+    __syncthreads();
+    for (int e0 = e_begin; e0 < e_end; e0 += PQ_T) {
+        if (tid < PQ_T) {                                   // wave 0, after its selection of the tile before
+            const int d = e0 + tid;
+            s_es[tid] = d < e_end ? p.sum[d] : 0; s_eid[tid] = d < e_end ? p.id[d] : 0;
+        }
+        unsigned acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[i][j] = 0u;
+        for (int k0 = 0; k0 < p.K; k0 += PQ_KC) {
+            __syncthreads();                                // the stage before has been read (and wave 0 has left its selection)
+#pragma unroll
+            for (int t = tid; t < 2 * PQ_T * (PQ_KC / 16); t += 256) {
+                const int r = (t >> 4) & (PQ_T - 1), c = t & 15;
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (t < PQ_T * (PQ_KC / 16)) {
+                    const int e = s_qe[r];
+                    if (e >= 0) v = *(const uint4*)(p.hist + (size_t)e * p.K + k0 + c * 16);
+                    *(uint4*)(s_q + r * PQ_LD + c * 16) = v;
+                } else {
+                    const int e = e0 + r;
+                    if (e < e_end) v = *(const uint4*)(p.hist + (size_t)e * p.K + k0 + c * 16);
+                    *(uint4*)(s_e + r * PQ_LD + c * 16) = v;
+                }
+            }
+            __syncthreads();
+#pragma unroll 2
+            for (int c = 0; c < PQ_KC / 16; c++) {
+                uint4 a[4], b[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) { a[i] = *(const uint4*)(s_q + (i * 16 + ty) * PQ_LD + c * 16); b[i] = *(const uint4*)(s_e + (i * 16 + tx) * PQ_LD + c * 16); }
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        unsigned s = acc[i][j];
+                        s = __builtin_amdgcn_sad_u8(a[i].x, b[j].x, s); s = __builtin_amdgcn_sad_u8(a[i].y, b[j].y, s);
+                        s = __builtin_amdgcn_sad_u8(a[i].z, b[j].z, s); s = __builtin_amdgcn_sad_u8(a[i].w, b[j].w, s);
+                        acc[i][j] = s;
+                    }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) s_l1[i * 16 + ty][j * 16 + tx] = (int)acc[i][j];
+        __syncthreads();
+        if (tid < PQ_T && s_qe[tid] >= 0) {
+            const int qe = s_qe[tid], qs = s_qs[tid], lim = min(PQ_T, e_end - e0);
+            const long long qid = s_qid[tid];
+            unsigned long long worst = s_top[p.top_k - 1][tid];
+            for (int e = 0; e < lim; e++) {
+                const int d = e0 + e;
+                if (d == qe) continue;
+                long long gap = qid - (long long)s_eid[e];
+                gap = gap < 0 ? -gap : gap;
+                if (gap < (long long)p.min_gap) continue;
+                const int sh = (qs + s_es[e] - s_l1[tid][e]) >> 1;
+                if (sh < p.min_shared) continue;
+                const unsigned long long key = ((unsigned long long)(unsigned)sh << 32) | (unsigned)~(unsigned)d;
+                if (key <= worst) continue;
+                int pos = p.top_k - 1;
+                while (pos > 0 && s_top[pos - 1][tid] < key) { s_top[pos][tid] = s_top[pos - 1][tid]; pos--; }
+                s_top[pos][tid] = key;
+                worst = s_top[p.top_k - 1][tid];
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < PQ_T && q0 + tid < p.Q)
+        for (int k = 0; k < 16; k++) p.part[((size_t)(q0 + tid) * p.splits + sp) * 16 + k] = k < p.top_k ? s_top[k][tid] : 0ull;
+}
+
+// query q's lists of all splits (their entries are disjoint, so no key repeats) -> its top_k, a wavefront per query
+__global__ __launch_bounds__(256) void k_places_merge(PlacesQuery p)
+{
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= p.Q) return;
+    const unsigned long long* src = p.part + (size_t)q * p.splits * 16;
+    const int n = p.splits * 16;
+    unsigned long long k[VO_PLACES_MAX_SPLITS * 16 / 64];
+#pragma unroll
+    for (int t = 0; t < VO_PLACES_MAX_SPLITS * 16 / 64; t++) k[t] = t * 64 + lane < n ? src[t * 64 + lane] : 0ull;
+    for (int r = 0; r < p.top_k; r++) {
+        unsigned long long m = 0ull;
+#pragma unroll
+        for (int t = 0; t < VO_PLACES_MAX_SPLITS * 16 / 64; t++) m = k[t] > m ? k[t] : m;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_xor(m, d, 64); m = o > m ? o : m; }
+        if (lane == 0) {
+            p.out_entry[(size_t)q * p.top_k + r] = m ? (int)~(unsigned)(m & 0xffffffffull) : -1;
+            p.out_shared[(size_t)q * p.top_k + r] = (int)(m >> 32);
+        }
+#pragma unroll
+        for (int t = 0; t < VO_PLACES_MAX_SPLITS * 16 / 64; t++) k[t] = k[t] == m ? 0ull : k[t];
+    }
+}
+
+void launch_places_query(hipStream_t s, PlacesQuery p)
+{
+    if (p.Q <= 0) return;
+    const int qblocks = (p.Q + PQ_T - 1) / PQ_T;
+    hipLaunchKernelGGL(k_places_score, dim3((unsigned)qblocks * p.splits), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_places_merge, dim3((p.Q + 3) / 4), dim3(256), 0, s, p);
+}

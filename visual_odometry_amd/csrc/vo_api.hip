@@ -192,6 +192,7 @@ static void free_config(vo_ctx* c)
     clear_last_run(c);
     drop_slam_stream(c);
     drop_map(c);
+    drop_places(c);
     c->undistorted.clear();
 }
 
@@ -199,7 +200,7 @@ static void comm_release(vo_ctx* ctx);
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F);
 
-extern "C" int vo_version(void) { return 122; }
+extern "C" int vo_version(void) { return 123; }
 
 extern "C" int vo_create(int device_id, vo_ctx** out)
 {
@@ -333,6 +334,7 @@ extern "C" int vo_batch_configure(vo_ctx* ctx, int h, int w, const vo_orb_params
         clear_last_run(ctx);
         drop_slam_stream(ctx);
         drop_map(ctx);
+    drop_places(ctx);
         ctx->undistorted.clear();
         return VO_OK;
     }
@@ -2357,6 +2359,7 @@ extern "C" int vo_batch_configure_sift(vo_ctx* ctx, int h, int w, const vo_sift_
     clear_last_run(ctx);                                        // the pair buffers may be replaced below
     drop_slam_stream(ctx);
     drop_map(ctx);
+    drop_places(ctx);
     ctx->undistorted.clear();
     // frames per launch chain: the small octaves' launches are latency-bound (a dependent chain of ~50 launches per sub-batch)
     // and the wave-per-keypoint kernels like long grids, so the more frames share a chain the better (1280 x 720, pairs/s with

@@ -135,6 +135,23 @@ struct MapState {
     } al;
 };
 
+// Place recognition (places_api.hip): the vocabulary with its training buffers, and the keyframe index.  Two allocations of their own
+// lifetime, released by vo_destroy and by a configure call; nothing else touches them, and they touch nothing else.  A new
+// vocabulary closes the index (its histograms count another vocabulary's words).
+struct VocabState {
+    DevList mem;
+    bool valid = false;                   // a vocabulary has been trained or set
+    VocabBuf b{};
+    int K = 0, F_cap = 0, kp_cap = 0;     // what the buffers were sized for
+};
+struct PlacesState {
+    DevList mem;
+    bool open = false;
+    int capacity = 0, n = 0, K = 0;
+    uint8_t* hist = nullptr;              // [capacity][K]
+    int *sum = nullptr, *id = nullptr;    // [capacity]
+};
+
 // vo_slam_stream: the map one call leaves on the device for the next, with every table and work buffer of the walk — one
 // allocation that lives from the call that starts the stream (resume = 0) until the stream is dropped.
 struct SlamStream {
@@ -207,6 +224,9 @@ struct vo_ctx {
     LastRun last;
     SlamStream stream_map;                // vo_slam_stream's resident map (its own lifetime: see drop_slam_stream)
     MapState map;                         // the relocaliser's staged map (its own lifetime: see drop_map)
+    VocabState vocab;                     // place recognition: the vocabulary and the keyframe index (their own lifetimes: see drop_places)
+    PlacesState places;
+    Growable<uint8_t> places_work;        // vo_places_query's query list, partial lists and results on the device
     uint64_t scratch_epoch = 0;           // counts the layouts placed in `scratch`: what an earlier call left there is gone when it has moved
 
     // scratch for the single-call operators
@@ -279,6 +299,10 @@ static inline void drop_slam_stream(vo_ctx* ctx) { ctx->stream_map = SlamStream(
 
 // The end of the staged map: vo_destroy (the context's destructor) and the configure calls.  (vo_map_localize waits for the stream.)
 static inline void drop_map(vo_ctx* ctx) { ctx->map = MapState(); }
+
+// The end of the vocabulary and of the keyframe index: vo_destroy (the context's destructor) and the configure calls.  (Every
+// vo_vocab_* / vo_places_* call waits for the stream before it returns.)
+static inline void drop_places(vo_ctx* ctx) { ctx->places = PlacesState(); ctx->vocab = VocabState(); }
 
 static inline void forget_slam_maps(vo_ctx* ctx)
 {

@@ -513,5 +513,43 @@ void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, con
                         double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask, int* ninl,
                         int* status);
 
+// ---- place recognition (reloc_kernels.hip): vo_vocab_*, vo_places_*
+// The vocabulary is a map of K rows without points (v.xyz == nullptr, v.npt == v.cap_rows == K): the matcher's operand image and
+// norms exist for it because every word goes through map_store_row_sift / _orb.
+struct VocabBuf {
+    MapBuf   v;
+    uint8_t* tmp;                       // [K][D] the new words on their way into the store
+    int*     acc;                       // [K][256] ones per bit (ORB) / [K][128] sums per component (SIFT)
+    int*     cnt;                       // [K] rows assigned
+    int*     slots;                     // [F] the frame slots of a call
+    int*     word;                      // [F][kp_cap] the word of every row of slot slots[q]
+    int*     prev;                      // [F][kp_cap] ... in the assignment before
+    int*     changed;                   // [1] rows whose word differs from prev
+    int*     key;                       // [K] the start words: slot * kp_cap + keypoint
+    int*     ids;                       // [F] the caller's frame numbers on their way into the index
+};
+// rows of the vocabulary: row key[w] of src ([..][D]), or row w with key == nullptr
+void launch_vocab_store(hipStream_t s, VocabBuf vb, const uint8_t* src, const int* key);
+// the nearest word of every row of F slots (lowest index on a tie) -> vb.word
+void launch_vocab_assign(hipStream_t s, VocabBuf vb, int F, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
+                         int kp_cap, int cap_x);
+// vb.acc / vb.cnt / vb.changed (cleared by the caller) from vb.word; vb.prev <- vb.word
+void launch_vocab_accumulate(hipStream_t s, VocabBuf vb, int F, const uint8_t* desc, const int* kp_count, int kp_cap);
+void launch_vocab_update(hipStream_t s, VocabBuf vb);
+// entries first .. first + F - 1 of the index from vb.word and vb.ids
+void launch_places_hist(hipStream_t s, VocabBuf vb, int F, const int* kp_count, int kp_cap, uint8_t* hist, int* sum, int* id);
+void launch_places_sums(hipStream_t s, const uint8_t* hist, int K, int n, int* sum);
+#define VO_PLACES_MAX_SPLITS 64
+struct PlacesQuery {
+    const uint8_t* hist; const int* sum; const int* id;   // the index: [n][K], [n], [n]
+    int      n, K;
+    const int* qent; int Q;             // the query entries
+    int      top_k, min_gap, min_shared;
+    int      splits, per_split;         // the entries are dealt over `splits` workgroups per query block, per_split (a multiple of 64) each
+    unsigned long long* part;           // [Q][splits][16] the best keys of every split, descending, 0 = none
+    int*     out_entry; int* out_shared;   // [Q][top_k]
+};
+void launch_places_query(hipStream_t s, PlacesQuery p);
+
 void launch_tracks(hipStream_t s, const int* pair_frames, const int* match_off, const int* mq, const int* mt, int P, int max_m,
                    int F, int cap, unsigned long long* parent, int* root_frame, int* root_idx, int* hops, int* bad);

@@ -631,6 +631,119 @@ class FrontEnd:
         k = n.value
         return ai[:k].copy(), bi[:k].copy(), d[:k].copy(), m[:k].copy()
 
+    # ---- place recognition: device vocabulary, keyframe index, loop query (vo_vocab_*, vo_places_*) ------
+    def _slot_list(self, slots):
+        return np.ascontiguousarray(slots, dtype=np.int32).ravel()
+
+    def train_vocabulary(self, slots, K=1024, iterations=8):
+        """Train a vocabulary of K words (a multiple of 256, 256 .. 4096) on the descriptor rows of the detected `slots`, on the
+        device (vo_vocab_train): word w starts as training row floor(w n / K); a round assigns every row to its nearest word (lowest
+        index on a tie) and replaces every word by its rows' bitwise majority (ORB) or rounded mean (SIFT); at most `iterations`
+        rounds, fewer when an assignment moves no row.  Returns the number of updates done.  Closes an open index."""
+        sl = self._slot_list(slots)
+        c = self.ctx
+        run = C.c_int32(0)
+        rc = c.lib.vo_vocab_train(c.handle, sl.ctypes.data, len(sl), int(K), int(iterations), C.addressof(run))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return run.value
+
+    def set_vocabulary(self, words):
+        """Take a vocabulary from the host (vo_vocab_set): words [K, 32] uint8 under ORB, [K, 128] integer values 0..255 under SIFT —
+        what vocabulary() returned.  Closes an open index."""
+        w = self._map_rows_u8(words)
+        c = self.ctx
+        c.check(c.lib.vo_vocab_set(c.handle, w.ctypes.data, len(w)))
+
+    def vocabulary(self):
+        """The vocabulary's words [K, D] uint8 (vo_vocab_get)."""
+        c = self.ctx
+        k = C.c_int32(0)
+        c.check(c.lib.vo_vocab_get(c.handle, None, 0, C.addressof(k)))
+        w = np.zeros((k.value, self._map_row_width()), np.uint8)
+        c.check(c.lib.vo_vocab_get(c.handle, w.ctypes.data, k.value, C.addressof(k)))
+        return w
+
+    def words(self, slot):
+        """The word index of every descriptor row of a detected slot, [n] int32 (vo_vocab_words)."""
+        c = self.ctx
+        out = np.zeros(self.kp_cap, np.int32); n = C.c_int32(0)
+        c.check(c.lib.vo_vocab_words(c.handle, int(slot), out.ctypes.data, self.kp_cap, C.addressof(n)))
+        return out[:n.value].copy()
+
+    def places_open(self, capacity):
+        """Open an empty keyframe index of up to `capacity` entries (1 .. 65536) over the current vocabulary (vo_places_open)."""
+        c = self.ctx
+        c.check(c.lib.vo_places_open(c.handle, int(capacity)))
+
+    def places_add(self, slots, ids):
+        """Quantise the detected `slots` and append one entry each to the index, `ids` being the caller's frame numbers
+        (vo_places_add).  Returns the index of the first new entry.  NotImplementedError when the index is full (nothing is added)."""
+        sl = self._slot_list(slots)
+        fid = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if len(fid) != len(sl):
+            raise ValueError("one id per slot")
+        c = self.ctx
+        first = C.c_int32(0)
+        rc = c.lib.vo_places_add(c.handle, sl.ctypes.data, len(sl), fid.ctypes.data, C.addressof(first))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return first.value
+
+    def places_add_histograms(self, hist, ids):
+        """Append given histograms [n, K] uint8 with their ids (vo_places_add_hist): how a saved index comes back.  Returns the index
+        of the first new entry."""
+        _, K = self._places_size()
+        h = np.asarray(hist)
+        if h.dtype != np.uint8 or h.ndim != 2 or h.shape[1] != K:
+            raise ValueError(f"hist must be [n, {K}] uint8")
+        h = np.ascontiguousarray(h)
+        fid = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if len(fid) != len(h):
+            raise ValueError("one id per histogram")
+        c = self.ctx
+        first = C.c_int32(0)
+        rc = c.lib.vo_places_add_hist(c.handle, h.ctypes.data, fid.ctypes.data, len(h), C.addressof(first))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return first.value
+
+    def _places_size(self):
+        c = self.ctx
+        n, K = C.c_int32(0), C.c_int32(0)
+        c.check(c.lib.vo_places_size(c.handle, C.addressof(n), C.addressof(K)))
+        return n.value, K.value
+
+    def places_entries(self):
+        """The index back (vo_places_entries): dict(hist [n, K] uint8, sum [n] int32 — the sum of the saturated counts —, id [n]
+        int32): what to save, and what places_add_histograms takes later."""
+        n, K = self._places_size()
+        hist = np.zeros((n, K), np.uint8); s = np.zeros(n, np.int32); fid = np.zeros(n, np.int32)
+        c = self.ctx
+        c.check(c.lib.vo_places_entries(c.handle, 0, n, hist.ctypes.data, s.ctypes.data, fid.ctypes.data))
+        return dict(hist=hist, sum=s, id=fid)
+
+    def places_query(self, entries=None, top_k=3, min_gap=0, min_shared=0):
+        """For every query entry (entries=None: every entry of the index) the top_k other entries that share the most words with it
+        (vo_places_query): shared = sum over words of min(hist_q, hist_d); entries with |id_q - id_d| < min_gap or shared <
+        min_shared are left out; equal scores in ascending entry order.  Returns dict(entry [Q, top_k] int32, -1 in unused places;
+        id [Q, top_k] the found entries' ids (0 in unused places); shared [Q, top_k] int32)."""
+        n, _ = self._places_size()
+        q = np.arange(n, dtype=np.int32) if entries is None else np.ascontiguousarray(entries, dtype=np.int32).ravel()
+        Q = len(q)
+        opts = _lib.PlacesOpts(int(top_k), int(min_gap), int(min_shared))
+        ent = np.full((Q, max(int(top_k), 0)), -1, np.int32); sh = np.zeros(ent.shape, np.int32)
+        c = self.ctx
+        c.check(c.lib.vo_places_query(c.handle, q.ctypes.data, Q, C.addressof(opts), ent.ctypes.data, sh.ctypes.data))
+        ids = np.zeros(n, np.int32)
+        if n:
+            c.check(c.lib.vo_places_entries(c.handle, 0, n, None, None, ids.ctypes.data))
+        found = np.where(ent >= 0, ids[np.maximum(ent, 0)], 0).astype(np.int32) if n else np.zeros(ent.shape, np.int32)
+        return dict(entry=ent, id=found, shared=sh)
+
     # ---- measurement ------------------------------------------------------------------------
     def profile(self, on=True):
         c = self.ctx
@@ -650,6 +763,27 @@ class FrontEnd:
             if c.lib.vo_stage_name(i).decode() == stage_name:
                 return float(c.lib.vo_stage_bytes(c.handle, i, int(frames)))
         raise KeyError(stage_name)
+
+
+def loop_candidates(result, ids):
+    """The loop candidates of a places_query() result as a list of (id_query, id_found, shared), each unordered pair of frames once
+    (shared is symmetric, so a pair found from both ends carries one number), in the order the queries report them.  ids [Q]: the
+    frame numbers of the query entries, row for row of `result`."""
+    ids = np.asarray(ids).ravel()
+    ent, found, shared = (np.asarray(result[k]) for k in ("entry", "id", "shared"))
+    if len(ids) != len(ent):
+        raise ValueError("one id per query row")
+    seen, out = set(), []
+    for q in range(len(ent)):
+        for k in range(ent.shape[1]):
+            if ent[q, k] < 0:
+                continue
+            a, b = int(ids[q]), int(found[q, k])
+            key = (min(a, b), max(a, b))
+            if key not in seen:
+                seen.add(key)
+                out.append((a, b, int(shared[q, k])))
+    return out
 
 
 def sequence_offsets(seq_lengths, n_pairs):
