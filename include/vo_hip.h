@@ -513,7 +513,7 @@ int vo_tracks_pnp_batch(vo_ctx* ctx, int B, const double* K, int iterations, dou
  * keeps.  chi2: [B][2] = activeRobustChi2 before and after; iterations_run / trials_run: LM iterations started and linear
  * solves attempted.  Two calls on the same input return the same bytes (every sum has a fixed order).
  * status[b]: VO_OK; VO_ERR_UNSUPPORTED for a problem with more than VO_BA_MAX_CAMERAS cameras or VO_BA_MAX_FREE free ones
- * (a map that large needs a multi-workgroup solver); VO_ERR_INVALID for an observation that names a missing camera or
+ * (a map that large goes to vo_bundle_adjust_large, below); VO_ERR_INVALID for an observation that names a missing camera or
  * point.  Such a problem's data come back unchanged and the rest of the batch is solved.
  * vo_bundle_adjust: one problem; a negative status is the return value. */
 #define VO_BA_MAX_CAMERAS 64
@@ -532,6 +532,33 @@ int vo_bundle_adjust(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int n
                      const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs,
                      double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2 /* [2] */,
                      int32_t* iterations_run, int32_t* trials_run);
+
+/* ------------------------------------------------------------------ bundle adjustment, large maps
+ * vo_bundle_adjust for ONE map of hundreds of cameras (the joined flight after vo_pose_graph and correct_points, two maps joined
+ * by vo_map_align): the same Levenberg-Marquardt, rule for rule (tau 1e-5, lambda from the first linearisation, nu = 2, rho with
+ * g2o's + 1e-3, at most 10 trials per iteration, the Huber weight rho' only, unit-quaternion cameras, no convergence test), on
+ * other linear algebra.  The reduced camera system S (6 F x 6 F, g carried as its last row) lies in device memory and is factored
+ * exactly by a blocked dense Cholesky whose panels and trailing updates span the whole GPU; the host drives the LM loop and reads
+ * a 64-byte decision record once per trial.  Workgroups synchronise at kernel boundaries only; no floating-point atomics: every
+ * sum has one fixed order, so two calls on the same input return the same bytes (docs/kernels/k_bundle_adjust_large.md).
+ * Arguments, in / out conventions and vo_ba_opts as vo_bundle_adjust; obs_cam / obs_pt index this map's rows.
+ * Capacity: at most VO_BA_LARGE_MAX_FREE free cameras (S: 3073 x 3080 doubles = 75.7 MB), any number of fixed ones; points,
+ * observations and listed pairs (one observation each of free cameras c1 <= c2 on a shared point) are bounded by int32 and by
+ * the call's scratch.  With C cameras, F free, N points, O observations, B listed blocks, Q listed pairs, n = 6 F,
+ * ld = (n + 8) & ~7 and G = ceil(N / 256) the scratch is, each term rounded up to 256 bytes,
+ *   4 (C + F + N + 1 + 2 O + F + 1 + Of + B + 1) + 8 B + 8 Q + 16 O                      the lists (Of: observations by free cameras)
+ *   + 2 * 8 (12 C + 4 F + 3 N) + 8 (18 O + 15 N + 48 F)                                  estimates, W, H_pp, b_p, H_pp^-1, H_cc, b_c, delta_c
+ *   + 8 (n + 1) ld + 8 * 48 * 48 ceil(n / 48) + 3 * 8 max(G, 1) + 64                     S, the factored diagonal blocks, the reductions' partials, the record.
+ * Beyond the capacity: VO_ERR_UNSUPPORTED; an observation of a missing camera or point, a NULL argument or iterations > 1000:
+ * VO_ERR_INVALID; the data stay unchanged either way.  A fixed camera and a point without observations keep their input bytes, a
+ * free camera without observations takes delta = 0, F = 0 is structure only, a map without observations runs ten failed
+ * factorisations and moves nothing: as vo_bundle_adjust and tests/ba_reference.py.
+ * Out of scope: the band structure of a flight's S, batches of large maps, an iterative solver. */
+#define VO_BA_LARGE_MAX_FREE 512
+int vo_bundle_adjust_large(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed, int ncam, double* points, int npt,
+                           const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs,
+                           double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2 /* [2] */,
+                           int32_t* iterations_run, int32_t* trials_run);
 
 /* ------------------------------------------------------------------ the complete per-frame map step on resident data
  * vo_tracks_pnp_batch's walk joined to what ends every frame of VisualSlam.estimate_current_camera_position

@@ -19,6 +19,7 @@ VO_ERR_UNSUPPORTED = -7
 VO_STAGE_COUNT = 30
 VO_COMM_ID_BYTES, VO_RECORD_DOUBLES = 128, 16
 VO_BA_MAX_CAMERAS, VO_BA_MAX_FREE = 64, 16
+VO_BA_LARGE_MAX_FREE = 512
 VO_PGO_MAX_VERTICES, VO_PGO_MAX_LOOPS = 8192, 32
 VO_STATS_HIST = 64
 
@@ -166,6 +167,7 @@ _SIGS = {
     "vo_pose_graph": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "vo_bundle_adjust_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     "vo_bundle_adjust": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "vo_bundle_adjust_large": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P, _P]),
     "vo_rodrigues": (C.c_int, [_P, _P, C.c_int, _P]),

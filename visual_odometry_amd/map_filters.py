@@ -194,6 +194,38 @@ def optimize_map(cameras, points, observations, camera_matrix, iterations=40, ct
     return r["chi2_before"], r["chi2_after"]
 
 
+def bundle_adjust_large(poses, fixed, points, obs_cam, obs_pt, obs_xy, focal, cx, cy, iterations=40, huber_delta=1.0, ctx=None):
+    """One map of hundreds of cameras (vo_bundle_adjust_large): bundle_adjust's arguments, rules and dict, with the reduced
+    camera system factored in device memory by a blocked Cholesky over the whole GPU.  At most _lib.VO_BA_LARGE_MAX_FREE free
+    cameras, any number of fixed ones.  A map beyond that or an observation of a missing camera / point raises VoError; the
+    inputs are not modified."""
+    poses, fixed, points, oc, op, xy = _ba_problem(poses, fixed, points, obs_cam, obs_pt, obs_xy)
+    chi2 = np.zeros(2); it = np.zeros(1, np.int32); tr = np.zeros(1, np.int32)
+    opts = _lib.BaOpts(int(iterations), 0, float(huber_delta))
+    ctx = ctx or _lib.default_context()
+    rc = ctx.check(ctx.lib.vo_bundle_adjust_large(ctx.handle, poses.ctypes.data, fixed.ctypes.data, len(poses), points.ctypes.data, len(points),
+                                                  oc.ctypes.data, op.ctypes.data, xy.ctypes.data, len(oc), float(focal), float(cx), float(cy),
+                                                  ctypes.addressof(opts), chi2.ctypes.data, it.ctypes.data, tr.ctypes.data))
+    return dict(poses=poses.reshape(-1, 3, 4), points=points, chi2_before=float(chi2[0]), chi2_after=float(chi2[1]),
+                iterations=int(it[0]), trials=int(tr[0]), status=int(rc))
+
+
+def optimize_map_large(cameras, points, observations, camera_matrix, iterations=40, ctx=None):
+    """optimize_map for a map beyond vo_bundle_adjust's capacity: the same duck typing and write-back, through bundle_adjust_large."""
+    K = np.asarray(camera_matrix, np.float64).reshape(3, 3)
+    pts, oc, op, xy = _index_arrays(cameras, points, observations)
+    poses = np.zeros((len(cameras), 3, 4))
+    for i, c in enumerate(cameras):
+        poses[i, :, :3] = np.asarray(c.R, np.float64).reshape(3, 3); poses[i, :, 3] = np.asarray(c.t, np.float64).ravel()
+    r = bundle_adjust_large(poses, [bool(c.fixed) for c in cameras], pts, oc, op, xy, K[0, 0], K[0, 2], K[1, 2], iterations, 1.0, ctx)
+    for i, c in enumerate(cameras):
+        c.t = r["poses"][i, :, 3].copy()
+        c.R = r["poses"][i, :, :3].copy()
+    for i, p in enumerate(points):
+        p.point = np.copy(r["points"][i])
+    return r["chi2_before"], r["chi2_after"]
+
+
 def _pgo_problem(sims, fixed, edges, meas, info=None):
     sims = np.array(sims, np.float64).reshape(-1, 13)
     fixed = np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8)).ravel()
