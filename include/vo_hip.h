@@ -559,6 +559,17 @@ int vo_bundle_adjust_large(vo_ctx* ctx, double* poses, const uint8_t* cam_fixed,
                            const int32_t* obs_cam, const int32_t* obs_pt, const double* obs_xy, int nobs,
                            double focal, double cx, double cy, const vo_ba_opts* opts, double* chi2 /* [2] */,
                            int32_t* iterations_run, int32_t* trials_run);
+/* vo_ba_large_solve: the factorisation and solve of one trial of vo_bundle_adjust_large on a system of the caller's, A x = b with
+ * A symmetric positive definite, n = 6 F, 1 <= F <= VO_BA_LARGE_MAX_FREE: for callers that build their own normal equations, and
+ * for the tests, which hand the blocked Cholesky matrices no map produces (tests/test_gpu_ba_large_solve.py).  The same kernels
+ * in the same order as a trial runs them, nothing of the LM loop.  A: [n][n] row-major, of a row only the part up to its diagonal
+ * is used; b: [n].  x: [n]; L: [n][n], the Cholesky factor's lower triangle written, the rest left as it came, or NULL; y: [n],
+ * the forward-substituted b (L y = b, L^T x = y), or NULL.  *pivot_failed = 1 for a pivot that is not positive and finite: x, L
+ * and y are then left as they came and the return value is VO_OK; otherwise 0.  n that is no multiple of 6 or < 6, a NULL A, b, x
+ * or pivot_failed: VO_ERR_INVALID; n > 6 VO_BA_LARGE_MAX_FREE: VO_ERR_UNSUPPORTED; nothing is written then.  Scratch, each term
+ * rounded up to 256 bytes, ld = (n + 8) & ~7: 8 (n + 1) ld + 8 * 48 * 48 ceil(n / 48) + 8 n + 64. */
+int vo_ba_large_solve(vo_ctx* ctx, const double* A, const double* b, int n, double* x, double* L, double* y,
+                      int32_t* pivot_failed);
 
 /* ------------------------------------------------------------------ the complete per-frame map step on resident data
  * vo_tracks_pnp_batch's walk joined to what ends every frame of VisualSlam.estimate_current_camera_position

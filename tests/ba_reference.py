@@ -287,6 +287,34 @@ def args(m):
     return m["poses"], m["fixed"], m["points"], m["oc"], m["op"], m["xy"]
 
 
+BANDED_FIXED, BANDED_VIEWS = 2, 8
+
+
+def banded_map(free, seed=0, per_camera=300):
+    """A flight's shape for hundreds of cameras (bench_ba_large.py and the parity cases past 128 free cameras): free + 2 cameras
+    0.4 apart along x looking down z, the first two fixed at their true poses, points 6-12 deep; a point is seen by 8 consecutive
+    cameras, about per_camera points per camera.  Returns lm's arguments: poses, fixed, points, obs_cam, obs_pt, obs_xy."""
+    rng = np.random.default_rng(seed)
+    ncam = free + BANDED_FIXED
+    npt = ncam * per_camera // BANDED_VIEWS
+    Tt = np.zeros((ncam, 3, 4))
+    for c in range(ncam):
+        Tt[c, :, :3], _ = se3_exp(np.r_[rng.normal(0, 0.02, 3), 0, 0, 0])
+        Tt[c, :, 3] = [-0.4 * c, 0.05 * rng.normal(), 0.05 * rng.normal()]
+    start = rng.integers(0, ncam - BANDED_VIEWS + 1, npt)
+    mid = 0.4 * (start + 0.5 * (BANDED_VIEWS - 1))
+    Xt = np.c_[mid + rng.uniform(-1.5, 1.5, npt), rng.uniform(-2, 2, npt), rng.uniform(6, 12, npt)]
+    oc = (start[:, None] + np.arange(BANDED_VIEWS)[None]).ravel().astype(np.int32)
+    op = np.repeat(np.arange(npt), BANDED_VIEWS).astype(np.int32)
+    xy = np.array([project(Tt[c], Xt[p]) for c, p in zip(oc, op)]) + rng.normal(0, 0.5, (len(oc), 2))
+    T0 = Tt.copy()
+    for c in range(BANDED_FIXED, ncam):
+        dR, dt = se3_exp(np.r_[rng.normal(0, 0.01, 3), rng.normal(0, 0.05, 3)])
+        T0[c, :, :3] = dR @ Tt[c, :, :3]; T0[c, :, 3] = dR @ Tt[c, :, 3] + dt
+    fixed = np.zeros(ncam, bool); fixed[:BANDED_FIXED] = True
+    return T0, fixed, Xt + rng.normal(0, 0.05, Xt.shape), oc, op, xy
+
+
 # ---------------------------------------------------------------- parity cases and the tolerance rule
 # (seed, cameras, fixed, points, visibility, iterations).  Gauge fixed (>= 2 fixed cameras at their true poses), every point
 # seen by >= 3 cameras: 3-18 cameras; 1, 2, 12 and 16 free; 50-3000 points.  40 iterations as the reference runs wherever the

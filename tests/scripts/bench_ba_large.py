@@ -25,32 +25,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import ba_reference as R  # noqa: E402
 
-REPS, ITER, FIXED, VIEWS, PER_CAMERA = 5, 10, 2, 8, 300
+REPS, ITER = 5, 10
 PHASES = {"linearise": ("k_gba_lin_points", "k_gba_lin_cams", "k_gba_lambda0"), "build S": ("k_gba_hpi", "k_gba_build", "fillBuffer", "memset"),
           "factor": ("k_gba_panel", "k_gba_update", "k_gba_backsub"), "step and cost": ("k_gba_step_cams", "k_gba_step_points", "k_gba_decide")}
 
 
-def banded_map(free, seed=0):
-    """cameras 0.4 apart along x looking down z, points 6-12 deep; point p is seen by VIEWS consecutive cameras"""
-    rng = np.random.default_rng(seed)
-    ncam = free + FIXED
-    npt = ncam * PER_CAMERA // VIEWS
-    Tt = np.zeros((ncam, 3, 4))
-    for c in range(ncam):
-        Tt[c, :, :3], _ = R.se3_exp(np.r_[rng.normal(0, 0.02, 3), 0, 0, 0])
-        Tt[c, :, 3] = [-0.4 * c, 0.05 * rng.normal(), 0.05 * rng.normal()]
-    start = rng.integers(0, ncam - VIEWS + 1, npt)
-    mid = 0.4 * (start + 0.5 * (VIEWS - 1))
-    Xt = np.c_[mid + rng.uniform(-1.5, 1.5, npt), rng.uniform(-2, 2, npt), rng.uniform(6, 12, npt)]
-    oc = (start[:, None] + np.arange(VIEWS)[None]).ravel().astype(np.int32)
-    op = np.repeat(np.arange(npt), VIEWS).astype(np.int32)
-    xy = np.array([R.project(Tt[c], Xt[p]) for c, p in zip(oc, op)]) + rng.normal(0, 0.5, (len(oc), 2))
-    T0 = Tt.copy()
-    for c in range(FIXED, ncam):
-        dR, dt = R.se3_exp(np.r_[rng.normal(0, 0.01, 3), rng.normal(0, 0.05, 3)])
-        T0[c, :, :3] = dR @ Tt[c, :, :3]; T0[c, :, 3] = dR @ Tt[c, :, 3] + dt
-    fixed = np.zeros(ncam, bool); fixed[:FIXED] = True
-    return T0, fixed, Xt + rng.normal(0, 0.05, Xt.shape), oc, op, xy
+banded_map = R.banded_map                            # seed 0, 300 points per camera: the defaults
 
 
 def misc_ms(ctx, _lib):

@@ -14,7 +14,12 @@ the first one.  Order floors as measured on the CPU (R / t / X / chi2):
   (103, 40, 4, 500, 0.2)  3e-16 / 5e-15 / 1.9e-14 / 1.8e-11        (113, 11, 2, 150, 0.5)  2.0e-16 / 1.8e-15 / 1.1e-14 / 9.1e-13
   (102, 65, 2, 400, 0.1)  6e-15 / 5.8e-13 / 3.3e-13 / 4e-12        (114, 18, 2, 150, 0.5)  1.5e-16 / 2.7e-15 / 8.9e-15 / 2.3e-12
   (104, 130, 2, 600, 0.06) 4.7e-14 / 1.4e-11 / 3.5e-12 / 7e-12     (115, 19, 2, 150, 0.5)  2.2e-16 / 1.8e-15 / 3.6e-15 / 6.8e-12
-  reject (200, 0.3, 1.0, 3.0) 4.9e-11 / 5.9e-10 / 1.6e-09 / 4.5e-07; reject (200, 0.8, 2.0, 6.0) 7.3e-15 / 7.2e-14 / 3.4e-13 / 1.0e-08"""
+  reject (200, 0.3, 1.0, 3.0) 4.9e-11 / 5.9e-10 / 1.6e-09 / 4.5e-07; reject (200, 0.8, 2.0, 6.0) 7.3e-15 / 7.2e-14 / 3.4e-13 / 1.0e-08
+Past 128 free cameras the maps are banded flights (ba_reference.banded_map, 24 points per camera, 3 iterations, all trials accepted in
+both CPU orders): 250 free (the last panel 12 columns wide) 1.1e-14 / 1.1e-12 / 6.0e-14 / 1.4e-11, 512 free (the capacity) 1.8e-13 /
+2.0e-11 / 3.0e-13 / 5.4e-09; the checker takes about 8 s for both orders at 512, the device milliseconds.  One map of 66 000 points
+(3 cameras, 198 000 observations) gives the wide reductions 258 partials, past the 256 lanes that add them: 7.4e-16 / 6.7e-15 /
+4.1e-15 / 5.4e-09; its chi2 before holds _compare's 1e-12 relative like every other case (the two CPU orders differ by 5e-16)."""
 import importlib.util
 import os
 import sys
@@ -32,6 +37,7 @@ CAM = (R.F0, R.CX, R.CY)
 LARGE_CASES = [(101, 19, 2, 300, 0.4), (105, 66, 60, 300, 0.1), (103, 40, 4, 500, 0.2), (102, 65, 2, 400, 0.1), (104, 130, 2, 600, 0.06)]
 TILE_CASES = [(111, 9, 2, 150, 0.5), (112, 10, 2, 150, 0.5), (113, 11, 2, 150, 0.5), (114, 18, 2, 150, 0.5), (115, 19, 2, 150, 0.5)]
 REJECT_CASES = [(200, 0.3, 1.0, 3.0), (200, 0.8, 2.0, 6.0)]           # (seed, pert_r, pert_t, pert_x) of an 8-camera, 80-point map
+BANDED_FREE = [250, 512]                                              # past the 128 free cameras of LARGE_CASES, to VO_BA_LARGE_MAX_FREE
 SMALL_CASES = [R.PARITY_CASES[0], R.PARITY_CASES[9], R.PARITY_CASES[11]]
 
 
@@ -74,6 +80,19 @@ def test_parity_beyond_the_small_kernel(ctx, case):
 @pytest.mark.parametrize("case", TILE_CASES, ids=_case_id)
 def test_parity_at_panel_and_tile_boundaries(ctx, case):
     _compare(R.args(_large_map(case)), 10, case[0], label=case)
+
+
+@pytest.mark.parametrize("free", BANDED_FREE)
+def test_parity_to_capacity(ctx, free):
+    """Banded flights (ba_reference.banded_map, 24 points per camera, 3 iterations): S has a band of 8 block columns filled in by
+    the factorisation.  250 free cameras: 32 panels, the last one 12 columns wide; 512: the capacity, 64 panels, a 64 x 64 tile grid."""
+    _compare(R.banded_map(free, seed=300 + free, per_camera=24), 3, 300 + free, label=("banded", free))
+
+
+def test_parity_past_65536_points(ctx):
+    """66 000 points are 258 workgroups of the per-point kernels: the wide reductions' lanes take a second partial (t + 256)."""
+    g, _ = _compare(R.args(R.make_map(400, ncam=3, npt=66000, nfixed=2, vis=1.0)), 3, 400, label="258 partials")
+    assert len(g["points"]) > 256 * 256
 
 
 @pytest.mark.parametrize("case", REJECT_CASES, ids=lambda c: "seed%d_r%g" % c[:2])

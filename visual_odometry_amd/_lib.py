@@ -168,6 +168,7 @@ _SIGS = {
     "vo_bundle_adjust_batch": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     "vo_bundle_adjust": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
     "vo_bundle_adjust_large": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "vo_ba_large_solve": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P]),
     "vo_solve_pnp_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_uint64, _P, _P, _P, _P, _P]),
     "vo_rodrigues": (C.c_int, [_P, _P, C.c_int, _P]),

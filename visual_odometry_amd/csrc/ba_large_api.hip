@@ -81,3 +81,55 @@ extern "C" int vo_bundle_adjust_large(vo_ctx* ctx, double* poses, const uint8_t*
     if (ctx->prof) prof_collect(ctx);
     return VO_OK;
 }
+
+// The factorisation and solve of a trial on a system of the caller's (include/vo_hip.h): launch_gba_factor_solve between an upload
+// and a download, nothing of the LM loop.
+extern "C" int vo_ba_large_solve(vo_ctx* ctx, const double* A, const double* b, int n, double* x, double* L, double* y,
+                                 int32_t* pivot_failed)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!A || !b || !x || !pivot_failed) FAIL(VO_ERR_INVALID, "vo_ba_large_solve: bad arguments");
+    if (n < 6 || n % 6 != 0) FAIL(VO_ERR_INVALID, "vo_ba_large_solve: n must be 6 F with F >= 1, got %d", n);
+    if (n / 6 > VO_BA_LARGE_MAX_FREE) FAIL(VO_ERR_UNSUPPORTED, "vo_ba_large_solve holds at most n = 6 * %d", VO_BA_LARGE_MAX_FREE);
+
+    HIPCHK(hipSetDevice(ctx->device));
+    GbaBuf D{};
+    ScratchLayout sc;
+    gba_take_solve(sc, n, D);
+    int rc = sc.place(ctx); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t N = (size_t)n, ld = (size_t)D.ld, row = N * sizeof(double);
+    HIPCHK(hipMemsetAsync(D.rec, 0, sizeof(GbaRec), s));
+    // rows 0 .. n - 1 whole (the kernels read a row up to its diagonal only), b as row n
+    HIPCHK(hipMemcpy2DAsync(D.S, ld * sizeof(double), A, row, row, N, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(D.S + N * ld, b, row, hipMemcpyHostToDevice, s));
+    launch_gba_factor_solve(s, D);
+    GbaRec rec{};
+    HIPCHK(hipMemcpyAsync(&rec, D.rec, sizeof(GbaRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    if (rec.fail) {
+        HIPCHK(hipMemsetAsync(D.rec, 0, sizeof(GbaRec), s));          // the next call starts clean
+        HIPCHK(hipStreamSynchronize(s));
+        *pivot_failed = 1;
+        return VO_OK;
+    }
+    HIPCHK(hipMemcpyAsync(x, D.dc, row, hipMemcpyDeviceToHost, s));
+    if (y) HIPCHK(hipMemcpyAsync(y, D.S + N * ld, row, hipMemcpyDeviceToHost, s));
+    if (L) {
+        // the factor lies in two places: a row's columns left of its panel in S, those inside the diagonal block in Ld
+        const size_t panels = (N + GBA_NB - 1) / GBA_NB;
+        std::vector<double> hs(N * ld), hd(panels * GBA_NB * GBA_NB);
+        HIPCHK(hipMemcpyAsync(hs.data(), D.S, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hd.data(), D.Ld, hd.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t i = 0; i < N; i++) {
+            const size_t k = i / GBA_NB, c0 = k * GBA_NB;
+            for (size_t j = 0; j < c0; j++) L[i * N + j] = hs[i * ld + j];
+            for (size_t j = c0; j <= i; j++) L[i * N + j] = hd[k * GBA_NB * GBA_NB + (i - c0) * GBA_NB + (j - c0)];
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    *pivot_failed = 0;
+    return VO_OK;
+}

@@ -10,7 +10,8 @@
 //               owns a point (delta_p, the trial point, its robust residuals, its share of the gain denominator);
 //               k_gba_decide: accept / reject, lambda, nu and the stop conditions into the device record.
 // Every element of S sees its products subtracted one by one in ascending column order, each rounded (-ffp-contract=off), so
-// the factor has the bits of the unblocked column Cholesky of k_bundle_adjust.  Every sum has a fixed order: a lane adds its
+// the factor has the bits of the unblocked column Cholesky of k_bundle_adjust (tests/test_gpu_ba_large_solve.py compares them
+// through vo_ba_large_solve).  Every sum has a fixed order: a lane adds its
 // items in list order, 64 lane partials are combined by an xor butterfly, wave partials in wave order, workgroup partials
 // in workgroup order.  No floating-point atomics.  A non-positive or non-finite pivot, or a singular H_pp + lambda I,
 // sets GbaRec::fail; every later kernel of the trial reads it and returns; k_gba_decide then takes chi2 = DBL_MAX.
@@ -651,24 +652,32 @@ void launch_gba_linearise(hipStream_t s, const GbaBuf& D, const BaParams& P, int
     if (first) hipLaunchKernelGGL(k_gba_lambda0, dim3(1), dim3(GBA_THREADS), 0, s, D);
 }
 
-// One trial: 2 ceil(n / GBA_NB) + 5 kernels and one clear of S for F > 0 (the last panel has no trailing update: below it lies
-// g's row alone), 3 kernels for F = 0.
+// S x = g on the device, n = 6 F > 0: the lower triangle of S and g as row n go in; the factor comes out in Ld (diagonal blocks)
+// and S (below them), the forward-substituted g in row n, x in dc; a pivot that is not positive and finite sets rec->fail and
+// leaves dc as it was.  2 ceil(n / GBA_NB) kernels: the last panel has no trailing update (below it lies g's row alone).
+// Reads of D: S, Ld, dc, rec, n, ld.  A trial's solve (launch_gba_trial) and vo_ba_large_solve.
+void launch_gba_factor_solve(hipStream_t s, const GbaBuf& D)
+{
+    for (int c0 = 0; c0 < D.n; c0 += GBA_NB) {
+        const int nb = D.n - c0 < GBA_NB ? D.n - c0 : GBA_NB;
+        const int below = D.n + 1 - (c0 + nb);                       // >= 1: g's row
+        hipLaunchKernelGGL(k_gba_panel, dim3(gba_groups(below, GBA_PANEL_ROWS)), dim3(GBA_THREADS), 0, s, D, c0, nb);
+        if (below > 1) {                                             // with g's row alone there is nothing left to update
+            const int nt = gba_groups(below, GBA_TILE);
+            hipLaunchKernelGGL(k_gba_update, dim3(nt, nt), dim3(GBA_THREADS), 0, s, D, c0, nb);
+        }
+    }
+    hipLaunchKernelGGL(k_gba_backsub, dim3(1), dim3(GBA_BACK_THREADS), (size_t)D.n * sizeof(double), s, D);
+}
+
+// One trial: 2 ceil(n / GBA_NB) + 5 kernels and one clear of S for F > 0, 3 kernels for F = 0.
 void launch_gba_trial(hipStream_t s, const GbaBuf& D, const BaParams& P, int cur, bool first_trial)
 {
     if (D.npw > 0) hipLaunchKernelGGL(k_gba_hpi, dim3(D.npw), dim3(GBA_THREADS), 0, s, D);
     if (D.F > 0) {
         (void)hipMemsetAsync(D.S, 0, (size_t)(D.n + 1) * (size_t)D.ld * sizeof(double), s);
         hipLaunchKernelGGL(k_gba_build, dim3(gba_groups(D.nblk, GBA_WAVES)), dim3(GBA_THREADS), 0, s, D);
-        for (int c0 = 0; c0 < D.n; c0 += GBA_NB) {
-            const int nb = D.n - c0 < GBA_NB ? D.n - c0 : GBA_NB;
-            const int below = D.n + 1 - (c0 + nb);                   // >= 1: g's row
-            hipLaunchKernelGGL(k_gba_panel, dim3(gba_groups(below, GBA_PANEL_ROWS)), dim3(GBA_THREADS), 0, s, D, c0, nb);
-            if (below > 1) {                                         // with g's row alone there is nothing left to update
-                const int nt = gba_groups(below, GBA_TILE);
-                hipLaunchKernelGGL(k_gba_update, dim3(nt, nt), dim3(GBA_THREADS), 0, s, D, c0, nb);
-            }
-        }
-        hipLaunchKernelGGL(k_gba_backsub, dim3(1), dim3(GBA_BACK_THREADS), (size_t)D.n * sizeof(double), s, D);
+        launch_gba_factor_solve(s, D);
         hipLaunchKernelGGL(k_gba_step_cams, dim3(gba_groups(D.F, GBA_THREADS)), dim3(GBA_THREADS), 0, s, D, cur);
     }
     if (D.npw > 0) hipLaunchKernelGGL(k_gba_step_points, dim3(D.npw), dim3(GBA_THREADS), 0, s, D, P, cur);

@@ -39,6 +39,8 @@ struct GbaPlan {
     size_t s_doubles() const { return (size_t)(n + 1) * (size_t)ld; }
 };
 
+static inline int gba_ld(int n) { return (n + 1 + 7) & ~7; }    // row pitch of S in doubles: n columns and one more, a multiple of 8
+
 // VO_OK, VO_ERR_UNSUPPORTED (more than VO_BA_LARGE_MAX_FREE free cameras, or more pairs than an int32 counts) or
 // VO_ERR_INVALID (an observation of a missing camera or point).  Capacity is checked first, as vo_bundle_adjust does.
 static inline int gba_prepare(int ncam, const uint8_t* cam_fixed, int npt, int nobs, const int32_t* obs_cam, const int32_t* obs_pt,
@@ -52,7 +54,7 @@ static inline int gba_prepare(int ncam, const uint8_t* cam_fixed, int npt, int n
     for (int i = 0; i < nobs; i++)
         if (obs_cam[i] < 0 || obs_cam[i] >= ncam || obs_pt[i] < 0 || obs_pt[i] >= npt) return VO_ERR_INVALID;
     const int F = P.nfree;
-    P.n = 6 * F; P.ld = (P.n + 1 + 7) & ~7;
+    P.n = 6 * F; P.ld = gba_ld(P.n);
     P.npw = (npt + GBA_THREADS - 1) / GBA_THREADS;
     P.col.assign(ncam, -1); P.free_cam.resize(F);
     for (int i = 0, f = 0; i < ncam; i++) if (!cam_fixed[i]) { P.col[i] = f; P.free_cam[f++] = i; }
@@ -138,6 +140,16 @@ static inline void gba_take(ScratchLayout& sc, const GbaPlan& P, GbaBuf& D)
     D.ncam = P.ncam; D.npt = P.npt; D.nobs = P.nobs; D.F = P.nfree; D.n = P.n; D.ld = P.ld; D.nblk = (int)P.blocks.size(); D.npw = P.npw;
 }
 
+// vo_ba_large_solve's part of the layout: S, Ld, delta_c and the record of a system of n = 6 F unknowns, nothing else named.
+static inline void gba_take_solve(ScratchLayout& sc, int n, GbaBuf& D)
+{
+    D.F = n / 6; D.n = n; D.ld = gba_ld(n);
+    sc.take(&D.S, (size_t)(n + 1) * (size_t)D.ld);
+    sc.take(&D.Ld, (size_t)GBA_NB * GBA_NB * (size_t)((n + GBA_NB - 1) / GBA_NB));
+    sc.take(&D.dc, (size_t)n); sc.take(&D.rec, 1);
+}
+
 void launch_gba_init(hipStream_t s, const GbaBuf& D, const BaParams& P);
 void launch_gba_linearise(hipStream_t s, const GbaBuf& D, const BaParams& P, int cur, bool first);
 void launch_gba_trial(hipStream_t s, const GbaBuf& D, const BaParams& P, int cur, bool first_trial);
+void launch_gba_factor_solve(hipStream_t s, const GbaBuf& D);

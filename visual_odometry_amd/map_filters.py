@@ -210,6 +210,25 @@ def bundle_adjust_large(poses, fixed, points, obs_cam, obs_pt, obs_xy, focal, cx
                 iterations=int(it[0]), trials=int(tr[0]), status=int(rc))
 
 
+def ba_large_solve(A, b, want_factor=False, ctx=None):
+    """A x = b by bundle_adjust_large's blocked Cholesky (vo_ba_large_solve): A symmetric positive definite, n x n with n = 6 F,
+    1 <= F <= _lib.VO_BA_LARGE_MAX_FREE, of which the lower triangle is used.  dict(x, y, pivot_failed) and, with want_factor,
+    L (upper triangle zero); after a failed pivot x, y and L are None."""
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64).ravel()
+    n = len(b)
+    if A.shape != (n, n):
+        raise ValueError(f"A must be {n} x {n}, got {A.shape}")
+    x = np.zeros(n); y = np.zeros(n); L = np.zeros((n, n)) if want_factor else None
+    failed = np.zeros(1, np.int32)
+    ctx = ctx or _lib.default_context()
+    ctx.check(ctx.lib.vo_ba_large_solve(ctx.handle, A.ctypes.data, b.ctypes.data, n, x.ctypes.data, L.ctypes.data if want_factor else None,
+                                        y.ctypes.data, failed.ctypes.data))
+    out = dict(x=None, y=None, pivot_failed=bool(failed[0])) if failed[0] else dict(x=x, y=y, pivot_failed=False)
+    if want_factor:
+        out["L"] = None if failed[0] else L
+    return out
+
+
 def optimize_map_large(cameras, points, observations, camera_matrix, iterations=40, ctx=None):
     """optimize_map for a map beyond vo_bundle_adjust's capacity: the same duck typing and write-back, through bundle_adjust_large."""
     K = np.asarray(camera_matrix, np.float64).reshape(3, 3)
