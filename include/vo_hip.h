@@ -928,7 +928,33 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  *   where vo_slam_map / vo_slam_chains_map would refuse, and when another call has laid out the context's scratch buffer since the
  *   chain ran (the single-call operators, vo_tracks_pnp_batch, another chain): call it right after the chain.  VO_ERR_UNSUPPORTED for
  *   a stream's map (vo_slam_stream*, vo_slam_streams): its older frames have left their slots and their descriptor rows are gone —
- *   a stream keeps no descriptor store of its own; save each chunk's map with vo_slam_chains + vo_map_rows instead.
+ *   unless the stream is a vo_slam_stream that keeps a descriptor store (vo_set_stream_rows, below): then (0, 0) is
+ *   vo_map_from_stream(0, -1), and which = 1, the snapshot, stays VO_ERR_UNSUPPORTED.
+ * vo_set_stream_rows / vo_stream_rows_info / vo_map_from_stream: a stream's own descriptor store.  With it a vo_slam_stream keeps the
+ *   descriptor row of every map point on the device from the call the point is born in, in an allocation of the stream's lifetime
+ *   beside the walk's (capacity_rows D + 4 (total_pairs + 1) kp_cap bytes, D = 32 / 128), and its live map can be staged at any
+ *   later time — after the frames have lost their slots, between two calls, after a call that ended lost.
+ *   vo_set_stream_rows: capacity_rows 0 = no store (the default: every call then returns the bytes and the refusals it returns
+ *     without this section), -1 = (total_pairs + 1) kp_cap rows, which can never drop a point, > 0 = that many rows (at most
+ *     2^31 - 1: VO_ERR_INVALID at the call that starts the stream), < -1: VO_ERR_INVALID.  It takes effect at the next
+ *     vo_slam_stream(resume = 0); a live stream keeps the setting it started with (vo_set_slam_stats' rule).  vo_slam_stream_restart,
+ *     vo_slam_streams and the chains ignore it.
+ *   Append, at the end of every vo_slam_stream call (resume 0 or 1, also one that ends lost), one launch behind the walk while the
+ *     call's frames are in their slots: every point of the end map whose owning frame is one of this call's and whose feature has no
+ *     row takes the next free row IN MAP ORDER, and the row of its owning feature (the one vo_map_from_slam gathers) is copied there.
+ *     A point that finds the store full is counted as dropped and stays without a row for good; which points those are is a
+ *     function of the inputs alone.  A point born and removed inside one call never gets a row; a row whose point is removed later
+ *     stays as a hole (the store is not compacted; the store serves the LIVE map: a point the camera limit has removed is gone from
+ *     it, whatever its row).  The walk's kernels are untouched: with the store on, every output of the
+ *     stream is the bytes it is with the store off.
+ *   vo_stream_rows_info: the live stream's store: rows it holds, rows handed out, points dropped.  VO_ERR_INVALID without a live
+ *     vo_slam_stream that has a store.
+ *   vo_map_from_stream: stages the live stream's end map restricted to the points whose owning frame (pt_feature's frame, along the
+ *     stream) lies in [frame_first, frame_end); frame_end < 0: no upper bound.  Points and rows in map order, as vo_map_from_slam
+ *     stages a chain's map; points without a row are left out and counted in n_without_row.  An empty selection stages an empty
+ *     map.  VO_ERR_INVALID: no live vo_slam_stream with a store, frame_first < 0, 0 <= frame_end < frame_first.  VO_ERR_UNSUPPORTED:
+ *     more than 65536 points selected.  A failed call leaves no staged map.  The stream, the pair results and vo_slam_map's copies
+ *     are left alone: a later resume = 1 returns what it would have returned without the call.
  * vo_map_rows: the staged map back (up to cap points; *npt = its size): what a caller saves before the frames leave their slots.
  * vo_map_localize: Q <= max_pairs detected slots against the staged map in one call.  No staged map: VO_ERR_INVALID.  A slot flagged
  *   for its descriptor norm (SIFT): VO_ERR_INVALID AFTER the run, as vo_pairs_run reports it.  Profiling stages: match_nn (k_nn_map),
@@ -938,8 +964,9 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  * Lifetime: the staged map and vo_map_localize's work buffers are an allocation of their own, released by vo_destroy and by a
  *   configure call.  vo_pairs_run, the vo_slam_* calls and detections leave it alone; vo_map_localize leaves the pair results, the
  *   chain's maps and a live stream alone.  A new vo_map_stage / vo_map_from_slam replaces the map (also when it fails).
- * Out of scope: automatic use inside the restart walks, a stream's own descriptor store, ratio matching against the map, maps of
- * more than 65536 points.  (The similarity that joins two segments' gauges: map alignment, below.) */
+ * Out of scope: automatic use inside the walks, a descriptor store for restart streams and multi-streams (vo_slam_stream_restart,
+ * vo_slam_streams) and the archive of earlier segments they would need, staging a window of more than 65536 points, ratio matching
+ * against the map.  (The similarity that joins two segments' gauges: map alignment, below.) */
 typedef struct {
     double   max_distance;      /* 0: no filter */
     int32_t  pnp_iterations;    /* 100 */
@@ -950,6 +977,9 @@ typedef struct {
 } vo_reloc_opts;
 int vo_map_stage(vo_ctx* ctx, const uint8_t* rows /*[npt][D]*/, const double* points /*[npt][3]*/, int npt);
 int vo_map_from_slam(vo_ctx* ctx, int seq, int which);
+int vo_set_stream_rows(vo_ctx* ctx, int64_t capacity_rows);
+int vo_stream_rows_info(vo_ctx* ctx, int64_t* capacity, int64_t* stored, int64_t* dropped);
+int vo_map_from_stream(vo_ctx* ctx, int frame_first, int frame_end, int32_t* n_staged, int32_t* n_without_row);
 int vo_map_rows(vo_ctx* ctx, uint8_t* rows /*[cap][D]*/, double* points /*[cap][3]*/, int cap, int32_t* npt);
 int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* opts,
                     double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
@@ -997,8 +1027,9 @@ int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* 
  * Lifetime: the query maps and work buffers are an allocation of their own, made by the first vo_map_align and ended with the staged
  *   map's; a newly staged map forgets the queries.  The pair results, the chains' maps, a live stream and vo_map_localize's results
  *   are left alone.
- * Out of scope: a stream's own descriptor store, automatic joining inside the restart walks, bundle refinement after the join (the
- * pose-graph refinement is vo_pose_graph, below), ratio matching. */
+ * Out of scope: a descriptor store for restart streams and multi-streams and an archive of their earlier segments (a vo_slam_stream
+ * has one: vo_set_stream_rows), automatic joining inside the walks, staging a window of more than 65536 points, bundle refinement after
+ * the join (the pose-graph refinement is vo_pose_graph, below), ratio matching. */
 typedef struct {
     double   max_distance;      /* descriptor filter as in vo_reloc_opts; 0: none */
     double   max_error;         /* inlier bound in map A's units; > 0 */

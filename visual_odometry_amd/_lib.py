@@ -138,6 +138,9 @@ _SIGS = {
     "vo_slam_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_map_stage": (C.c_int, [_P, _P, _P, C.c_int]),
     "vo_map_from_slam": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vo_set_stream_rows": (C.c_int, [_P, C.c_int64]),
+    "vo_stream_rows_info": (C.c_int, [_P, _P, _P, _P]),
+    "vo_map_from_stream": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
     "vo_map_rows": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "vo_map_localize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),

@@ -3,8 +3,6 @@
 // vo_map_from_slam is in slam_api.hip, beside the maps it reads; it stages through map_stage_device like vo_map_stage.
 #include "vo_host.h"
 
-#define VO_MAP_MAX_POINTS 65536
-
 // Room for npt rows and for the work of max_pairs queries of kp_cap keypoints.  The allocation is kept while it fits (rows past npt
 // then keep what a larger map left); otherwise it is released as a whole and made again.
 static int map_reserve(vo_ctx* ctx, const Batch& b, int npt)

@@ -459,6 +459,106 @@ static int slam_stream_clear(vo_ctx* ctx, const SlamStream& st, int resume, cons
     return VO_OK;
 }
 
+// ------------------------------------------------------------------ a stream's descriptor store (vo_set_stream_rows)
+// One more allocation of the stream's lifetime, beside slam_layout's and not inside it: the walk's kernels never see it.  It is made
+// by the call that starts a vo_slam_stream while the setting is on; vo_slam_stream_restart and vo_slam_streams have none.
+extern "C" int vo_set_stream_rows(vo_ctx* ctx, int64_t capacity_rows)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (capacity_rows < -1) FAIL(VO_ERR_INVALID, "stream rows must be 0 (no store), -1 (a row for every feature the stream can hold) or a number of rows, got %lld", (long long)capacity_rows);
+    ctx->stream_rows = capacity_rows;
+    return VO_OK;
+}
+
+static int stream_rows_allocate(vo_ctx* ctx, SlamStream& st, int64_t setting, bool sift)
+{
+    SlamStream::Store& so = st.store;
+    StreamRows& d = so.d;
+    const size_t feats = st.dims.np[0];                               // (total_pairs + 1) kp_cap: below 2^31 (slam_stream_allocate)
+    const int64_t capacity = setting < 0 ? (int64_t)feats : setting;
+    if (capacity > INT32_MAX) FAIL(VO_ERR_INVALID, "vo_slam_stream: a descriptor store holds at most 2^31 - 1 rows (vo_set_stream_rows), got %lld", (long long)capacity);
+    d.D = sift ? 128 : 32; d.capacity = (int)capacity; d.kp_cap = st.cap; d.frames = st.total + 1;
+    d.sel_cap = (int)std::min(feats, (size_t)VO_MAP_MAX_POINTS);
+    ScratchLayout sc;
+    sc.take(&d.rows, (size_t)capacity * d.D); sc.take(&d.row_of, feats); sc.take(&d.counters, 2);
+    sc.take(&d.sel_key, (size_t)d.sel_cap); sc.take(&d.sel_xyz, (size_t)d.sel_cap * 3); sc.take(&d.sel_cnt, 2);
+    uint8_t* base = nullptr;
+    HIPCHK(so.mem.alloc(&base, sc.bytes));
+    sc.place_at(base);
+    HIPCHK(hipMemsetAsync(d.row_of, 0xFF, feats * sizeof(int), ctx->stream));     // -1: no feature has a row
+    HIPCHK(hipMemsetAsync(d.counters, 0, 2 * sizeof(int), ctx->stream));
+    so.counters[0] = so.counters[1] = 0;
+    so.on = true;
+    return VO_OK;
+}
+
+// The end of a vo_slam_stream call with a store: the rows of the points born in it, while their frames are in their slots.  On the
+// call's stream behind the walk; the counters come back with the call's results (slam_download waits).
+static int stream_rows_append(vo_ctx* ctx, SlamStream& st, const SlamMap& m, int frame0)
+{
+    SlamStream::Store& so = st.store;
+    const Batch b = batch(ctx);
+    {
+        StageTimer t(ctx, ST_MISC);
+        launch_stream_rows_append(ctx->stream, m, so.d, st.dims.np[0], b.desc, st.F * st.cap, frame0, so.counters[0], so.counters[1]);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(so.counters, so.d.counters, sizeof(so.counters), hipMemcpyDeviceToHost, ctx->stream));
+    return VO_OK;
+}
+
+// the live vo_slam_stream with a store, nullptr (and the reason in ctx->err) if there is none
+static SlamStream* stream_with_rows(vo_ctx* ctx, const char* who)
+{
+    SlamStream& st = ctx->stream_map;
+    const char* why = nullptr;
+    if (!st.live) why = "there is no live stream (none was started, or a configure or vo_slam_chain* call dropped it)";
+    else if (st.multi || st.restart) why = "the live stream was started by vo_slam_stream_restart or vo_slam_streams, which keep no descriptor store";
+    else if (!st.store.on) why = "the live stream was started without a descriptor store (vo_set_stream_rows before vo_slam_stream(resume = 0))";
+    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s: %s", who, why); return nullptr; }
+    return &st;
+}
+
+extern "C" int vo_stream_rows_info(vo_ctx* ctx, int64_t* capacity, int64_t* stored, int64_t* dropped)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!capacity || !stored || !dropped) FAIL(VO_ERR_INVALID, "bad arguments");
+    const SlamStream* st = stream_with_rows(ctx, "vo_stream_rows_info");
+    if (!st) return VO_ERR_INVALID;
+    *capacity = st->store.d.capacity; *stored = st->store.counters[0]; *dropped = st->store.counters[1];
+    return VO_OK;
+}
+
+// The relocaliser's map from the live stream's end map, at any time while the stream lives: k_stream_rows_select writes the store
+// rows of the window's points as a key list and their coordinates as a dense list, then the one staging path runs with the store as
+// the source of the rows.  Reads the stream's lists and writes the store's own selection buffers: the stream is left as it was.
+extern "C" int vo_map_from_stream(vo_ctx* ctx, int frame_first, int frame_end, int32_t* n_staged, int32_t* n_without_row)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    ctx->map.staged = false; ctx->map.last_Q = 0; ctx->map.al.last_Q = 0;          // a failed call leaves no staged map
+    if (!n_staged || !n_without_row) FAIL(VO_ERR_INVALID, "bad arguments");
+    *n_staged = 0; *n_without_row = 0;
+    SlamStream* st = stream_with_rows(ctx, "vo_map_from_stream");
+    if (!st) return VO_ERR_INVALID;
+    if (frame_first < 0 || (frame_end >= 0 && frame_end < frame_first))
+        FAIL(VO_ERR_INVALID, "vo_map_from_stream: the window [%d, %d) is not one (frame_first >= 0; frame_end >= frame_first, or negative for no upper bound)", frame_first, frame_end);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const StreamRows& d = st->store.d;
+    const SlamMap& m = st->b.sb.m;                                    // (one sequence: the whole arrays)
+    launch_stream_rows_select(s, m, d, st->dims.np[0], frame_first, frame_end);
+    HIPCHK(hipGetLastError());
+    int32_t cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cnt, d.sel_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_without_row = cnt[1];
+    if (cnt[0] > VO_MAP_MAX_POINTS)
+        FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_stream: a staged map holds at most %d points, the window [%d, %d) selects %d", VO_MAP_MAX_POINTS, frame_first, frame_end, cnt[0]);
+    const int rc = map_stage_device(ctx, d.rows, d.sel_key, d.capacity, d.sel_xyz, cnt[0], "vo_map_from_stream"); if (rc) return rc;
+    *n_staged = cnt[0];
+    return VO_OK;
+}
+
 // vo_slam_stream and vo_slam_stream_restart.  restart: vo_slam_chains_restart's step for the one chain of the stream, and the alive
 // flag and the segment state words stay on the device between the calls.
 static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
@@ -497,6 +597,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     rc = ensure_rng(ctx, o->seed); if (rc) return rc;
     if (!resume) {
         rc = slam_stream_allocate(ctx, st, restart, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
+        if (!rc && !restart && ctx->stream_rows != 0) rc = stream_rows_allocate(ctx, st, ctx->stream_rows, batch(ctx).sift);
         if (rc) { drop_slam_stream(ctx); return rc; }
     }
     rc = slam_stream_clear(ctx, st, resume, K); if (rc) return rc;
@@ -508,6 +609,7 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     const int gn = F + (st.carries & 1);
     const SlamWalk w{restart ? FAM_STREAM_RESTART : FAM_STREAM, resume != 0, F + 2, B, snap_seq, SlamCarry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.b.keep}, false};
     rc = slam_walk(ctx, w, st.dims, st.b, seq, K, o); if (rc) return rc;
+    if (st.store.on) { rc = stream_rows_append(ctx, st, seq[0].sb.m, resume ? st.done : 0); if (rc) return rc; }
     int32_t alive = 1;
     const SlamOut out{poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run, ba_trials_run,
                       segment, cause, seg_poses_pnp, seg_poses, n_carried, carried_frame, carried_poses, restart ? &alive : nullptr};
@@ -895,13 +997,20 @@ extern "C" int vo_map_from_slam(vo_ctx* ctx, int seq, int which)
 {
     if (!ctx) return VO_ERR_INVALID;
     const LastRun& l = ctx->last;
+    const SlamStream& st = ctx->stream_map;
+    if (st.live && !st.multi && st.store.on && seq == 0 && (which == 0 || which == 1)) {   // a vo_slam_stream with a descriptor store: the latest vo_slam_* call is its
+        if (which == 1) FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_slam: a stream's snapshot is not staged: the store serves the map at the end of the call");
+        int32_t n = 0, without = 0;
+        return vo_map_from_stream(ctx, 0, -1, &n, &without);
+    }
     const bool multi = !l.seq_map.empty();
     if (!multi && seq != 0) FAIL(VO_ERR_INVALID, "the most recent vo_slam_* call had one sequence: seq must be 0, got %d", seq);
     const LastRun::Map* m = multi ? slam_chains_map_of(ctx, seq, which) : slam_map_of(ctx, which);
     if (!m) return VO_ERR_INVALID;
     const LastRun::DevMaps& dv = l.dev;
     if (dv.stream)
-        FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_slam: a stream's map names frames that have left their slots, and their descriptor rows with them");
+        FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_slam: a stream's map names frames that have left their slots, and their descriptor rows with them "
+                                 "(vo_slam_stream keeps them with vo_set_stream_rows: vo_map_from_stream)");
     if (dv.epoch != ctx->scratch_epoch || (size_t)seq >= dv.seq.size())
         FAIL(VO_ERR_INVALID, "vo_map_from_slam: another call has used the scratch buffer the chain's map lay in; call it right after the chain");
     const LastRun::DevMaps::Lists& L = which == 1 ? dv.snap : dv.seq[(size_t)seq];

@@ -187,6 +187,15 @@ struct SlamStream {
     int S = 0;
     std::vector<Seq> seq;
     std::vector<int32_t> rows;
+    // vo_slam_stream with vo_set_stream_rows on when the stream began: the descriptor store, one more allocation of the stream's
+    // lifetime (StreamRows, stream_rows_kernels.hip).  counters: the device's two words as the last call left them, read back with
+    // the call's results — the next append starts from them.
+    struct Store {
+        DevList mem;
+        bool on = false;
+        StreamRows d{};
+        int32_t counters[2] = {0, 0};     // rows stored, points dropped
+    } store;
 };
 
 struct vo_ctx {
@@ -256,6 +265,7 @@ struct vo_ctx {
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
     int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it
+    int64_t stream_rows = 0;              // vo_set_stream_rows: rows of the descriptor store the next vo_slam_stream(resume = 0) starts with; 0 (default): none, -1: one per feature
     std::vector<uint8_t> undistorted;     // per slot: vo_frames_undistort has rewritten its kp_xy (empty: no slot); cleared by whatever gives the slot new keypoints
 };
 
@@ -351,7 +361,10 @@ int ensure_rng(vo_ctx* ctx, uint64_t seed);
 // inside the configuration, the pairs a chain of distinct frames (a0, b0), (b0, b1), ...: the order the reference walks a sequence in
 int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out);
 
+#define VO_MAP_MAX_POINTS 65536               // points a staged map holds (vo_map_stage, vo_map_from_slam, vo_map_from_stream)
+
 // The one way a map is staged (reloc_api.hip): npt rows through k_map_gather — row i of `src` (device, [npt][D]) with key ==
 // nullptr, else row key[i] of the slots' descriptors — and its coordinates xyz (device, [npt][3]).  vo_map_stage uploads and
-// comes here; vo_map_from_slam (slam_api.hip) comes here with the map's own lists.  Synchronous.
+// comes here; vo_map_from_slam (slam_api.hip) comes here with the map's own lists, vo_map_from_stream with the
+// stream's descriptor store as src and the key list k_stream_rows_select wrote.  Synchronous.
 int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int npt, const char* who);

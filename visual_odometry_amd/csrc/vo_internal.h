@@ -391,6 +391,24 @@ struct SlamCarry {
     const double* keep;                 // [2][12] the anchor camera as it entered the map / as the map last held it (the previous call's last rows)
 };
 void launch_slam_carry(hipStream_t s, SlamCarry c, ChainBuf cb, SlamBuf sb);
+// ---- a stream's descriptor store (stream_rows_kernels.hip; vo_set_stream_rows, vo_map_from_stream): an allocation beside the
+// walk's layout, which no kernel of the walk reads or writes.
+struct StreamRows {
+    int      D;                         // bytes of a descriptor row: 32 (ORB) or 128 (SIFT)
+    int      capacity;                  // rows the store holds
+    int      kp_cap, frames;            // row_of is [frames][kp_cap]: frames = total_pairs + 1
+    uint8_t* rows;                      // [capacity][D] raw rows as the slots' descriptor array holds them; a row whose point is gone stays (a hole)
+    int*     row_of;                    // [frames][kp_cap] the store row of feature (frame along the stream, keypoint), -1: none
+    int*     counters;                  // [2] rows stored, points dropped because the store was full
+    int      sel_cap;                   // entries sel_key / sel_xyz hold: the bound of a staged map, or the list's capacity if that is less
+    int*     sel_key;                   // [sel_cap] k_stream_rows_select: the store rows of the selected points, in map order
+    double*  sel_xyz;                   // [sel_cap][3] ... and their coordinates
+    int*     sel_cnt;                   // [2] points selected (may pass sel_cap: nothing is written past it), points of the window without a row
+};
+// pt_bound: points the map's list can hold (the grid is sized from it; the kernels read the count from m.cnt)
+void launch_stream_rows_append(hipStream_t s, SlamMap m, StreamRows st, size_t pt_bound, const uint8_t* desc, int n_keys, int frame0, int stored0,
+                               int dropped0);
+void launch_stream_rows_select(hipStream_t s, SlamMap m, StreamRows st, size_t pt_bound, int first, int end);
 // ---- ... on a stream that starts a new map after a lost frame (vo_slam_stream_restart): cb.rs is set, its state words and the
 // alive flag outlive the call.  k_slam_restart_stream goes between k_chain_pose and k_chain_triangulate of every step.
 void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb);

@@ -547,12 +547,46 @@ class FrontEnd:
         """Stage the map of the latest slam_chain (seq=0) or of sequence `seq` of the latest slam_chains (vo_map_from_slam; which
         as in slam_map), on the device: the map's coordinates, and per point the descriptor row of its owning feature
         (TrackedPoint.descriptor = match.descriptor1) gathered from the slot it was detected in.  Call it right after the chain,
-        while the slots still hold its frames.  A stream's map: NotImplementedError (its older frames have left their slots)."""
+        while the slots still hold its frames.  A stream's map: NotImplementedError (its older frames have left their slots) —
+        unless it is a slam_stream started with stream_rows() on: then which=0 is map_from_stream(), at any time."""
         c = self.ctx
         rc = c.lib.vo_map_from_slam(c.handle, int(seq), int(which))
         if rc == _lib.VO_ERR_UNSUPPORTED:
             raise NotImplementedError(c.last_error())
         c.check(rc)
+
+    def stream_rows(self, capacity=-1):
+        """Give the next slam_stream a descriptor store (vo_set_stream_rows; off by default): the stream then keeps the descriptor row
+        of every map point on the device from the call the point is born in, and map_from_stream() stages its live map at any later
+        time.  capacity: rows the store holds — -1 one per feature the stream can hold, (total_pairs + 1) * kp_cap, which never
+        drops a point; 0 switches the store off.  Memory: capacity * D + 4 * (total_pairs + 1) * kp_cap bytes (D = 32 ORB, 128 SIFT).
+        Takes effect at the next slam_stream(resume=False); a live stream keeps the setting it started with.  slam_stream_restart,
+        slam_streams and the chains ignore it.  The stream's own outputs do not change."""
+        c = self.ctx
+        c.check(c.lib.vo_set_stream_rows(c.handle, int(capacity)))
+
+    def stream_rows_info(self):
+        """The live slam_stream's descriptor store (vo_stream_rows_info): dict(capacity, stored — rows handed out so far, holes
+        included —, dropped — points that found the store full and stay without a row).  VoError without such a stream."""
+        c = self.ctx
+        v = [C.c_int64(0) for _ in range(3)]
+        c.check(c.lib.vo_stream_rows_info(c.handle, *[C.addressof(x) for x in v]))
+        return dict(capacity=v[0].value, stored=v[1].value, dropped=v[2].value)
+
+    def map_from_stream(self, first=0, end=None):
+        """Stage the live slam_stream's map from its descriptor store (vo_map_from_stream), restricted to the points whose owning
+        frame — pt_feature[:, 0], counted along the stream — lies in [first, end); end=None: no upper bound.  Works at any time
+        while the stream lives: after its frames have lost their slots, between two calls, after a call that ended lost.  Points and
+        rows come in map order (map_rows() returns them); points without a row (dropped at capacity) are left out.  Returns
+        dict(n=points staged, without_row=points of the window left out).  More than 65536 points: NotImplementedError — stage a
+        window.  The stream is left as it was."""
+        c = self.ctx
+        n, w = C.c_int32(0), C.c_int32(0)
+        rc = c.lib.vo_map_from_stream(c.handle, int(first), -1 if end is None else int(end), C.addressof(n), C.addressof(w))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return dict(n=n.value, without_row=w.value)
 
     def map_rows(self):
         """The staged map back (vo_map_rows): (rows [npt, D] uint8, points [npt, 3] float64) — what to save before a segment's
