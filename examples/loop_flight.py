@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A loop closed against the map a stream built: a flight that goes out and comes back, streamed in chunks with slot reuse.
 
-    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--width 640] [--height 480] [--nfeatures 1000]
+    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--width 640] [--height 480] [--nfeatures 1000] [--ratio R]
 
 The flight is synthetic and uses no files: frames 0 .. n of synth.sequence, then n - 1 .. 0 again, so the last frames see the ground
 of the first.  It is walked by slam_stream in chunks of --chunk pairs on a FrontEnd with only chunk + 2 frame slots: every chunk's
@@ -12,7 +12,8 @@ Every frame becomes an entry of the keyframe index while it is resident (train_v
 end places_query -> loop_candidates names pairs (old, new) of frames that see the same place.  For the best candidate whose `new`
 frame is still in a slot, map_from_stream(old - w, old + w + 1) stages the points owned by the frames around `old` — from the store,
 their slots are gone — and relocalize places `new` among them by its descriptors alone.  Printed: that pose against the pose the
-stream itself gave `new` through its chain of pairs; the difference is the drift the flight accumulated between the two visits.
+stream itself gave `new` through its chain of pairs (--ratio R: matched by Lowe's ratio rule, knnMatch(k=2) and
+`m.distance < R * n.distance`, instead of the cross-check); the difference is the drift the flight accumulated between the two visits.
 The loop_edge the pose graph would take for (old, new) is built from the two (optimize_pose_graph, examples/close_loop.py).
 
 The stream's map is its LIVE map: a point whose cameras have all been evicted (max_cameras) is gone from it, so this flight keeps
@@ -35,6 +36,7 @@ def main():
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--nfeatures", type=int, default=1000)
     ap.add_argument("--words", type=int, default=256)
+    ap.add_argument("--ratio", type=float, default=None, help="relocalize by the ratio rule with this ratio instead of the cross-check")
     a = ap.parse_args()
     from visual_odometry_amd import frontend as F
     from visual_odometry_amd import synth
@@ -85,7 +87,7 @@ def main():
     staged = fe.map_from_stream(first, end)
     print(f"best candidate ({old}, {new}), {shared} shared words (images {image[old]} and {image[new]}); "
           f"map_from_stream({first}, {end}): {staged['n']} points, {staged['without_row']} without a row")
-    r = fe.relocalize([slot_of[new]], K)
+    r = fe.relocalize([slot_of[new]], K) if a.ratio is None else fe.relocalize([slot_of[new]], K, match="ratio", ratio=a.ratio)
     if r["status"][0] != 0:
         print(f"relocalize: status {int(r['status'][0])} with {int(r['n_match'][0])} matches")
         return

@@ -908,7 +908,8 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  *     winning ties in both directions (vo_pair_opts.match_mode 0); ascending keypoint order; distance as cv2 reports it, float32:
  *     sqrtf((float)d^2) for SIFT rows, the integer as float for ORB rows — the value the reference's TODO asks for.  Then
  *     `m.distance < max_distance`, strict, the float32 value against the double (visual_odometry_template_02/visual_slam.py:205-208);
- *     max_distance <= 0: no filter.
+ *     max_distance <= 0: no filter.  That is map-match mode 0, the default; vo_set_map_match (below) selects Lowe's ratio rule on
+ *     knnMatch(k=2) in its place (mode 1) or on top of it (mode 2).
  *   2 correspondences in match order: obj[k] = the map point of trainIdx, img[k] = float64(kp_xy[queryIdx]).
  *   3 cv2.solvePnPRansac(obj, img, K, zeros(4)) with pnp_iterations, reproj_err, confidence, seed (cv2: 100, 8.0, 0.99, 2^64 - 1) and
  *     the context's vo_set_pnp_refine mode: exactly vo_solve_pnp_ransac_batch on those arrays (k_pnp_ransac, unchanged).
@@ -961,12 +962,31 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  *   match_select (k_map_select), misc (k_pnp_ransac and the poses).
  * vo_map_matches: query q's match list of the latest vo_map_localize — map point, keypoint, distance — and solvePnPRansac's inlier
  *   mask (0 / 1) over it.
+ * vo_set_map_match: the rule by which vo_map_localize AND vo_map_align match rows against the staged map; a context setting like
+ *   vo_set_pnp_refine: read by the next of those calls, kept across staging and configure calls.
+ *     mode 0 (default): the cross-check of step 1; `ratio` is not read.  Every byte those calls return is what it is without this entry.
+ *     mode 1: the ratio rule of src/feature_detection.py:20-26 against the map.  For query row i (a keypoint / a query map's row:
+ *       cv2's query) and the staged map as train, m, n = knnMatch(k=2): batchDistance's K = 2 insertion — ascending scan, strict `<`,
+ *       equal distances keep train order — so m.trainIdx is the lowest index among the nearest rows and n.distance the second-smallest
+ *       distance, a tie with m counting as a second neighbour.  Row i is kept iff the staged map has at least 2 rows and
+ *       (double)fd < ratio * (double)fd2, fd and fd2 the float32 distances cv2 reports (sqrtf((float)d^2) for SIFT rows, the integer as
+ *       float for ORB rows): vo_pair_opts.match_mode 1's expression.  A map of 0 or 1 rows gives no match.  No reverse direction is
+ *       computed.  Several query rows may keep one map point; all of them stay in the list.
+ *     mode 2: the cross-check AND the ratio rule: mode 0's list filtered by mode 1's rule on the forward neighbours.  This library's own
+ *       combination (cv2 refuses knnMatch(k=2) on a crossCheck matcher).
+ *     In every mode `m.distance < max_distance` applies as in step 1, strictly and conjunctively, and the list is in ascending query
+ *     order.  Statuses are unchanged: fewer than 4 (vo_map_localize) or 3 (vo_map_align) correspondences is VO_ERR_TOO_FEW.
+ *     VO_ERR_INVALID: a mode other than 0, 1, 2; in modes 1 and 2 a ratio that is not finite or not > 0.
+ * vo_map_match_seconds: n.distance (float32) for every entry of query q's match list, in list order; which = 0 the latest
+ *   vo_map_localize, 1 the latest vo_map_align.  FLT_MAX where there is no second neighbour.  The parity seam of the top-2 selection,
+ *   and what a caller needs to re-threshold on the host without another run.  VO_ERR_INVALID when that call ran in mode 0, and where
+ *   vo_map_matches / vo_map_align_matches would refuse q.
  * Lifetime: the staged map and vo_map_localize's work buffers are an allocation of their own, released by vo_destroy and by a
  *   configure call.  vo_pairs_run, the vo_slam_* calls and detections leave it alone; vo_map_localize leaves the pair results, the
  *   chain's maps and a live stream alone.  A new vo_map_stage / vo_map_from_slam replaces the map (also when it fails).
  * Out of scope: automatic use inside the walks, a descriptor store for restart streams and multi-streams (vo_slam_stream_restart,
- * vo_slam_streams) and the archive of earlier segments they would need, staging a window of more than 65536 points, ratio matching
- * against the map.  (The similarity that joins two segments' gauges: map alignment, below.) */
+ * vo_slam_streams) and the archive of earlier segments they would need, staging a window of more than 65536 points, knnMatch with
+ * k > 2 against the map.  (The similarity that joins two segments' gauges: map alignment, below.) */
 typedef struct {
     double   max_distance;      /* 0: no filter */
     int32_t  pnp_iterations;    /* 100 */
@@ -984,6 +1004,8 @@ int vo_map_rows(vo_ctx* ctx, uint8_t* rows /*[cap][D]*/, double* points /*[cap][
 int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* opts,
                     double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
 int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
+int vo_set_map_match(vo_ctx* ctx, int mode /*0 cross-check, 1 ratio, 2 both*/, double ratio);
+int vo_map_match_seconds(vo_ctx* ctx, int which /*0 localize, 1 align*/, int q, float* dist2, int cap, int32_t* n_out);
 
 /* ------------------------------------------------------------------ map alignment: the similarity that joins two maps, by descriptors
  * After a lost frame the restart walks start a new map, and every segment is a trajectory in a gauge of its own: its origin is its
@@ -1020,7 +1042,8 @@ int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* 
  *   bound: a flagged SIFT row is VO_ERR_INVALID for the call); matches = the cross-check match of query rows (cv2's query) against the
  *   staged rows (train) under vo_map_localize's rules — strict mutual nearest neighbours, lowest index winning ties in both
  *   directions, float32 `distance < max_distance` (<= 0: no filter), ascending query-row order; b = the query's point, a = the staged
- *   point; then exactly vo_sim3_ransac_batch on those lists.  sim[q] takes query map q's gauge to the staged map's.  An empty query map
+ *   point (vo_set_map_match modes 1 and 2: the ratio rule stated there, with the query map's rows as cv2's query, in the place of or on
+ *   top of the cross-check; vo_map_match_seconds(which = 1) returns the second distances); then exactly vo_sim3_ransac_batch on those lists.  sim[q] takes query map q's gauge to the staged map's.  An empty query map
  *   is VO_ERR_TOO_FEW for that query alone.  VO_ERR_UNSUPPORTED: Q > 64, off[Q] > 65536.  VO_ERR_INVALID: no staged map, max_error <= 0,
  *   confidence outside (0, 1), off[0] != 0 or decreasing offsets.  Profiling stages: match_nn, match_select, misc.
  * vo_map_align_matches: query q's match list of the latest vo_map_align — staged row, query row, distance — and the inlier mask.
@@ -1029,7 +1052,7 @@ int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* 
  *   are left alone.
  * Out of scope: a descriptor store for restart streams and multi-streams and an archive of their earlier segments (a vo_slam_stream
  * has one: vo_set_stream_rows), automatic joining inside the walks, staging a window of more than 65536 points, bundle refinement after
- * the join (the pose-graph refinement is vo_pose_graph, below), ratio matching. */
+ * the join (the pose-graph refinement is vo_pose_graph, below). */
 typedef struct {
     double   max_distance;      /* descriptor filter as in vo_reloc_opts; 0: none */
     double   max_error;         /* inlier bound in map A's units; > 0 */

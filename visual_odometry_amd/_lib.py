@@ -56,6 +56,9 @@ class SlamOpts(C.Structure):
                 ("snapshot_pair", C.c_int32), ("snapshot_stage", C.c_int32)]
 
 
+MAP_MATCH_MODES = {"cross": 0, "ratio": 1, "cross+ratio": 2}      # vo_set_map_match
+
+
 class RelocOpts(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("pnp_iterations", C.c_int32), ("reproj_err", C.c_double), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
@@ -144,6 +147,8 @@ _SIGS = {
     "vo_map_rows": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "vo_map_localize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
+    "vo_set_map_match": (C.c_int, [_P, C.c_int, C.c_double]),
+    "vo_map_match_seconds": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "vo_sim3_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
@@ -318,6 +323,13 @@ class Context:
         """'cv2' (default): solvePnPRansac's final pose as OpenCV computes it (DLT / homography start + CvLevMarq, <= 20
         iterations); 'fast': the same cost minimised from the best RANSAC model."""
         self.check(self.lib.vo_set_pnp_refine(self.handle, {"fast": 0, "cv2": 1}[kind]))
+
+    def set_map_match(self, match="cross", ratio=0.75):
+        """How relocalize / align_maps match rows against the staged map (vo_set_map_match): 'cross' (default) the cross-check,
+        'ratio' knnMatch(k=2) + `m.distance < ratio * n.distance`, 'cross+ratio' both.  `ratio` is read by the last two only."""
+        if match not in MAP_MATCH_MODES:
+            raise ValueError("match must be 'cross', 'ratio' or 'cross+ratio'")
+        self.check(self.lib.vo_set_map_match(self.handle, MAP_MATCH_MODES[match], float(ratio)))
 
     def last_error(self) -> str:
         msg = self.lib.vo_last_error(self.handle)

@@ -72,6 +72,7 @@ static int align_reserve(vo_ctx* ctx, int Q, int total, int pad_total)
     HIPCHK(mem.alloc(&a.flag, 1));
     if (D == 128) { HIPCHK(mem.alloc(&a.img, P * 128)); HIPCHK(mem.alloc(&a.norms, P)); }
     HIPCHK(mem.alloc(&a.nn_idx, P)); HIPCHK(mem.alloc(&a.nn_dist, P)); HIPCHK(mem.alloc(&a.rn_idx, q * (size_t)M.m.cap_rows));
+    HIPCHK(mem.alloc(&a.nn_dist2, P)); HIPCHK(mem.alloc(&a.m_d2, T));
     HIPCHK(mem.alloc(&a.m_b, T)); HIPCHK(mem.alloc(&a.m_a, T)); HIPCHK(mem.alloc(&a.m_d, T)); HIPCHK(mem.alloc(&a.m_count, q));
     HIPCHK(mem.alloc(&a.src, T * 3)); HIPCHK(mem.alloc(&a.dst, T * 3)); HIPCHK(mem.alloc(&a.poff, 2 * q));
     HIPCHK(mem.alloc(&a.sim, 13 * q)); HIPCHK(mem.alloc(&a.mask, T)); HIPCHK(mem.alloc(&a.ninl, q)); HIPCHK(mem.alloc(&a.status, q));
@@ -110,6 +111,7 @@ extern "C" int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* poin
     if (total > 0) { rc = ctx->staging.grow(ctx, (size_t)total * D); if (rc) return rc; }
     AlignBuf a = A.a;
     a.Q = Q; a.total = total;
+    const int mode = ctx->map_match;
     if (total > 0) {
         HIPCHK(hipMemcpyAsync(ctx->staging.p, rows, (size_t)total * D, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(a.xyz, points, (size_t)total * 24, hipMemcpyHostToDevice, s));
@@ -117,8 +119,8 @@ extern "C" int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* poin
     HIPCHK(hipMemcpyAsync(a.off, A.off.data(), ((size_t)Q + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(a.pad, A.pad.data(), ((size_t)Q + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(a.flag, 0, sizeof(int), s));
-    { StageTimer t(ctx, ST_MATCH_NN); launch_map_align_match(s, M.m, a, ctx->staging.p, max_rows); }
-    { StageTimer t(ctx, ST_MATCH_SELECT); launch_map_align_select(s, M.m, a, o->max_distance); }
+    { StageTimer t(ctx, ST_MATCH_NN); launch_map_align_match(s, M.m, a, ctx->staging.p, max_rows, mode); }
+    { StageTimer t(ctx, ST_MATCH_SELECT); launch_map_align_select(s, M.m, a, o->max_distance, mode, ctx->map_ratio); }
     {
         StageTimer t(ctx, ST_MISC);
         launch_sim3_ransac(s, a.src, a.dst, a.poff, 2, Q, o->iterations, o->max_error, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N, o->min_inliers,
@@ -135,7 +137,7 @@ extern "C" int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* poin
     if (ctx->prof) prof_collect(ctx);
     if (flag & 2) FAIL(VO_ERR_INVALID, "vo_map_align: a SIFT descriptor row of a query map broke the norm bound of the integer matcher (|row|^2 > 2^20)");
     A.a.Q = Q; A.a.total = total;
-    A.last_Q = Q;
+    A.last_Q = Q; A.last_mode = mode;
     return VO_OK;
 }
 

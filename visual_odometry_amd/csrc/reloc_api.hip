@@ -23,6 +23,7 @@ static int map_reserve(vo_ctx* ctx, const Batch& b, int npt)
     }
     HIPCHK(hipMemsetAsync(m.rows, 0, R * D, ctx->stream));
     HIPCHK(mem.alloc(&r.slots, Q)); HIPCHK(mem.alloc(&r.nn_idx, Q * C)); HIPCHK(mem.alloc(&r.nn_dist, Q * C)); HIPCHK(mem.alloc(&r.rn_idx, Q * R));
+    HIPCHK(mem.alloc(&r.nn_dist2, Q * C)); HIPCHK(mem.alloc(&r.m_d2, Q * C));
     HIPCHK(mem.alloc(&r.m_q, Q * C)); HIPCHK(mem.alloc(&r.m_t, Q * C)); HIPCHK(mem.alloc(&r.m_d, Q * C)); HIPCHK(mem.alloc(&r.m_count, Q));
     HIPCHK(mem.alloc(&r.obj, Q * C * 3)); HIPCHK(mem.alloc(&r.img, Q * C * 2)); HIPCHK(mem.alloc(&r.off, 2 * Q));
     HIPCHK(mem.alloc(&r.rvec, 3 * Q)); HIPCHK(mem.alloc(&r.tvec, 3 * Q)); HIPCHK(mem.alloc(&r.mask, Q * C));
@@ -109,12 +110,13 @@ extern "C" int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const d
     int rc = ensure_rng(ctx, o->seed); if (rc) return rc;
     hipStream_t s = ctx->stream;
     const RelocBuf& r = M.r;
-    const int cap = b.kp_cap;
+    const int cap = b.kp_cap, mode = ctx->map_match;
+    const double ratio = ctx->map_ratio;
     HIPCHK(hipMemcpyAsync(r.slots, slots, (size_t)Q * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(M.dK, K, 72, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(r.rvec, 0, (size_t)Q * 24, s)); HIPCHK(hipMemsetAsync(r.tvec, 0, (size_t)Q * 24, s));
-    { StageTimer t(ctx, ST_MATCH_NN); launch_nn_map(s, M.m, r, Q, b.desc, b.desc_x, b.norms, b.kp_count, cap, desc_x_rows(cap)); }
-    { StageTimer t(ctx, ST_MATCH_SELECT); launch_map_select(s, M.m, r, Q, b.kp_xy, b.kp_count, cap, o->max_distance); }
+    { StageTimer t(ctx, ST_MATCH_NN); launch_nn_map(s, M.m, r, Q, b.desc, b.desc_x, b.norms, b.kp_count, cap, desc_x_rows(cap), mode); }
+    { StageTimer t(ctx, ST_MATCH_SELECT); launch_map_select(s, M.m, r, Q, b.kp_xy, b.kp_count, cap, o->max_distance, mode, ratio); }
     {
         StageTimer t(ctx, ST_MISC);
         launch_pnp_ransac(s, r.obj, r.img, r.off, Q, M.dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
@@ -128,7 +130,7 @@ extern "C" int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const d
     HIPCHK(hipMemcpyAsync(status, r.status, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (ctx->prof) prof_collect(ctx);
-    M.last_Q = Q;
+    M.last_Q = Q; M.last_mode = mode;
     if (b.sift) {                                           // a flagged slot, reported after the run as vo_pairs_run reports it
         std::vector<int> fl((size_t)b.max_frames);
         HIPCHK(hipMemcpy(fl.data(), b.flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -156,5 +158,27 @@ extern "C" int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_i
         if (dist) HIPCHK(hipMemcpy(dist, M.r.m_d + o, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         if (inlier_mask) HIPCHK(hipMemcpy(inlier_mask, M.r.mask + o, (size_t)n, hipMemcpyDeviceToHost));
     }
+    return VO_OK;
+}
+
+// n.distance of knnMatch(k=2) for every entry of a match list: which = 0 the latest vo_map_localize, 1 the latest vo_map_align
+extern "C" int vo_map_match_seconds(vo_ctx* ctx, int which, int q, float* dist2, int cap, int32_t* n_out)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const MapState& M = ctx->map;
+    const MapState::Align& A = M.al;
+    if (which != 0 && which != 1) FAIL(VO_ERR_INVALID, "vo_map_match_seconds: which is 0 (vo_map_localize) or 1 (vo_map_align)");
+    const int last_Q = which ? A.last_Q : M.last_Q, mode = which ? A.last_mode : M.last_mode;
+    if (!M.staged || q < 0 || q >= last_Q || !n_out || cap < 0)
+        FAIL(VO_ERR_INVALID, "vo_map_match_seconds: no such query in the most recent %s", which ? "vo_map_align" : "vo_map_localize");
+    if (mode == 0) FAIL(VO_ERR_INVALID, "vo_map_match_seconds: that call ran in map-match mode 0, which finds no second neighbour (vo_set_map_match)");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, (which ? A.a.m_count : M.r.m_count) + q, sizeof(int), hipMemcpyDeviceToHost));
+    if (n > cap) n = cap;
+    *n_out = n;
+    const float* src = which ? A.a.m_d2 + (size_t)A.off[(size_t)q] : M.r.m_d2 + (size_t)q * M.kp_cap;
+    if (n > 0 && dist2) HIPCHK(hipMemcpy(dist2, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return VO_OK;
 }

@@ -9,12 +9,15 @@
 //   k_map_select   bf.match(frame, map) with crossCheck=True, the distance filter, and the 3D-2D correspondences in the layout
 //                  k_pnp_ransac takes (pnp_kernels.hip, launched unchanged)
 // Semantics follow OpenCV's batchDistance: ascending scan, strict `<`, so the lowest index wins ties, in both directions.
+// vo_set_map_match modes 1 and 2: Lowe's ratio rule on knnMatch(k=2) against the map (src/feature_detection.py:20-26) — the K2 instantiations
+// of the two bodies keep the second distance, k_map_select / k_align_select apply the rule; mode 1 launches no reverse blocks.
 // Further down: map alignment (vo_map_align, vo_sim3_ransac_batch) — k_align_gather, k_nn_align[_orb], k_align_select over the same stores
 // and bodies, and k_sim3_ransac.
 #include "vo_internal.h"
 #include "sift_rows.h"
 #include <limits.h>
 #include <float.h>
+#include <type_traits>
 
 // ------------------------------------------------------------------ the map store
 // Row `id` of the map from `src_row` (D bytes).  SIFT (D = 128): called by a whole wavefront, lane l moves bytes 2 l, 2 l + 1 —
@@ -77,9 +80,14 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 #define NM_STAGE_ROWS 128                 // rows of B per chunk (8 groups of 16, 16 KB)
 #define NM_LD (NM_STAGE_ROWS * 128 / 16 / NM_THREADS)   // 16-byte staging loads per thread and chunk
 
-// out_dist may be nullptr (the reverse direction: the mutual test needs the index only)
+// out_dist may be nullptr (the reverse direction: the mutual test needs the index only).
+// K2 (knnMatch(k=2): the ratio rule of k_map_select) keeps the second-largest value per element as well: bs <= bv always, so the
+// value that is second after `val` has been seen is the median of the three — one v_med3_i32 before the update of the best.  A
+// value equal to the best counts as a second neighbour.  out_dist2[row] = the second-smallest d^2 (INT_MAX when B has one row).
+// K2 is deduced from the last argument; a call without it is the code it was before there was a K2.
+template <bool K2 = false>
 __device__ __forceinline__ void nn_map_l2_body(uint8_t (*s_b)[NM_STAGE_ROWS * 128], const uint8_t* A, const int* nA, int na, const uint8_t* B, const int* nB,
-                                               int nb, int row0, int* out_idx, int* out_dist)
+                                               int nb, int row0, int* out_idx, int* out_dist, int* out_dist2 = nullptr, std::bool_constant<K2> = {})
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
@@ -95,6 +103,11 @@ __device__ __forceinline__ void nn_map_l2_body(uint8_t (*s_b)[NM_STAGE_ROWS * 12
     v4i bv[NM_RB], bg[NM_RB];
 #pragma unroll
     for (int rb = 0; rb < NM_RB; rb++) { bv[rb] = (v4i){INT_MIN, INT_MIN, INT_MIN, INT_MIN}; bg[rb] = (v4i){-1, -1, -1, -1}; }
+    v4i bs[K2 ? NM_RB : 1];
+    if constexpr (K2) {
+#pragma unroll
+        for (int rb = 0; rb < NM_RB; rb++) bs[rb] = (v4i){INT_MIN, INT_MIN, INT_MIN, INT_MIN};
+    }
 
     const int nstages = (nb + NM_STAGE_ROWS - 1) / NM_STAGE_ROWS;
 #define NM_GLDS(stage, buf)                                                                                        \
@@ -136,6 +149,7 @@ __device__ __forceinline__ void nn_map_l2_body(uint8_t (*s_b)[NM_STAGE_ROWS * 12
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int val = 2 * acc[rb][r] - nbj;             // larger = nearer
+                    if constexpr (K2) bs[rb][r] = max(min(val, bv[rb][r]), min(max(val, bv[rb][r]), bs[rb][r]));   // v_med3_i32
                     const bool gt = val > bv[rb][r];                  // strict: the earlier group of this lane's column stays
                     bv[rb][r] = gt ? val : bv[rb][r];
                     bg[rb][r] = gt ? gi : bg[rb][r];
@@ -152,19 +166,31 @@ __device__ __forceinline__ void nn_map_l2_body(uint8_t (*s_b)[NM_STAGE_ROWS * 12
         for (int r = 0; r < 4; r++) {
             const int g = bg[rb][r];
             unsigned long long k0 = g < 0 ? 0ull : ((unsigned long long)((unsigned)bv[rb][r] ^ 0x80000000u) << 32) | (unsigned)(0x7fffffff - (g * 16 + li));
+            const unsigned long long mine = k0;
 #pragma unroll
             for (int d = 1; d < 16; d <<= 1) { const unsigned long long u0 = __shfl_xor(k0, d, 64); k0 = k0 > u0 ? k0 : u0; }
+            // the row's second value: the winning lane's own second, every other lane's best (a tie with the winner included)
+            int v1 = INT_MIN;
+            if constexpr (K2) {
+                v1 = mine == k0 ? bs[rb][r] : bv[rb][r];
+#pragma unroll
+                for (int d = 1; d < 16; d <<= 1) v1 = max(v1, __shfl_xor(v1, d, 64));
+            }
             const int row = wrow0 + rb * 16 + lg * 4 + r;
             if (li == 0 && row < na) {
                 const int v0 = (int)((unsigned)(k0 >> 32) ^ 0x80000000u), j0 = 0x7fffffff - (int)(k0 & 0xffffffffu);
                 out_idx[row] = k0 ? j0 : -1;
                 if (out_dist) out_dist[row] = k0 ? nA[row] - v0 : INT_MAX;
+                if constexpr (K2) out_dist2[row] = nb >= 2 ? nA[row] - v1 : INT_MAX;
             }
         }
 }
 
 // Workgroup b of query q = b / (fwd_blocks + rev_blocks): the first fwd_blocks take NM_BLOCK_ROWS keypoints of the frame each and
 // walk the map; the others take NM_BLOCK_ROWS map rows each and walk the frame.
+// K2: the forward blocks keep the second distance too (nn_dist2).  The ratio rule alone (vo_set_map_match mode 1) needs no reverse
+// direction: it is launched with rev_blocks = 0.
+template <bool K2>
 __global__ __launch_bounds__(NM_THREADS) void k_nn_map(MapBuf m, RelocBuf r, const uint8_t* desc_x, const int* norms, const int* kp_count, int kp_cap,
                                                        int cap_x, int fwd_blocks, int rev_blocks)
 {
@@ -176,7 +202,8 @@ __global__ __launch_bounds__(NM_THREADS) void k_nn_map(MapBuf m, RelocBuf r, con
     if (blk < fwd_blocks) {
         const int row0 = blk * NM_BLOCK_ROWS;
         if (row0 >= nq) return;
-        nn_map_l2_body(s_b, F, nF, nq, m.img, m.norms, m.npt, row0, r.nn_idx + (size_t)q * kp_cap, r.nn_dist + (size_t)q * kp_cap);
+        nn_map_l2_body(s_b, F, nF, nq, m.img, m.norms, m.npt, row0, r.nn_idx + (size_t)q * kp_cap, r.nn_dist + (size_t)q * kp_cap,
+                       r.nn_dist2 + (size_t)q * kp_cap, std::bool_constant<K2>{});
     } else {
         const int row0 = (blk - fwd_blocks) * NM_BLOCK_ROWS;
         if (row0 >= m.npt) return;
@@ -194,14 +221,18 @@ __global__ __launch_bounds__(NM_THREADS) void k_nn_map(MapBuf m, RelocBuf r, con
 #define NO_Q 2
 #define NO_BLOCK_ROWS (256 * NO_Q)
 
-__device__ __forceinline__ void nn_map_hamming_body(uint4* s_b, const uint8_t* A, int na, const uint8_t* B, int nb, int row0, int* out_idx, int* out_dist)
+// K2: two keys, k1 = the second smallest (keys are distinct: a tied distance at a higher row is the second neighbour).
+template <bool K2 = false>
+__device__ __forceinline__ void nn_map_hamming_body(uint4* s_b, const uint8_t* A, int na, const uint8_t* B, int nb, int row0, int* out_idx, int* out_dist,
+                                                    int* out_dist2 = nullptr, std::bool_constant<K2> = {})
 {
     const int tid = threadIdx.x;
     uint4 ma[NO_Q], mb[NO_Q];
     int row[NO_Q];
-    uint32_t k0[NO_Q];
+    uint32_t k0[NO_Q], k1[NO_Q];
 #pragma unroll
     for (int q = 0; q < NO_Q; q++) {
+        k1[q] = 0xffffffffu;
         row[q] = row0 + q * 256 + tid;
         ma[q] = make_uint4(0, 0, 0, 0); mb[q] = ma[q];
         if (row[q] < na) { ma[q] = *(const uint4*)(A + (size_t)row[q] * 32); mb[q] = *(const uint4*)(A + (size_t)row[q] * 32 + 16); }
@@ -220,7 +251,9 @@ __device__ __forceinline__ void nn_map_hamming_body(uint4* s_b, const uint8_t* A
             for (int q = 0; q < NO_Q; q++) {
                 const int h = __popc(ma[q].x ^ ba.x) + __popc(ma[q].y ^ ba.y) + __popc(ma[q].z ^ ba.z) + __popc(ma[q].w ^ ba.w) +
                               __popc(mb[q].x ^ bb.x) + __popc(mb[q].y ^ bb.y) + __popc(mb[q].z ^ bb.z) + __popc(mb[q].w ^ bb.w);
-                k0[q] = min(k0[q], ((uint32_t)h << 16) | (uint32_t)(base + k));
+                const uint32_t key = ((uint32_t)h << 16) | (uint32_t)(base + k);
+                if constexpr (K2) k1[q] = min(k1[q], max(k0[q], key));
+                k0[q] = min(k0[q], key);
             }
         }
     }
@@ -230,9 +263,11 @@ __device__ __forceinline__ void nn_map_hamming_body(uint4* s_b, const uint8_t* A
             const bool has = k0[q] != 0xffffffffu;
             out_idx[row[q]] = has ? (int)(k0[q] & 0xffffu) : -1;
             if (out_dist) out_dist[row[q]] = has ? (int)(k0[q] >> 16) : INT_MAX;
+            if constexpr (K2) out_dist2[row[q]] = k1[q] != 0xffffffffu ? (int)(k1[q] >> 16) : INT_MAX;
         }
 }
 
+template <bool K2>
 __global__ __launch_bounds__(256) void k_nn_map_orb(MapBuf m, RelocBuf r, const uint8_t* desc, const int* kp_count, int kp_cap, int fwd_blocks, int rev_blocks)
 {
     __shared__ uint4 s_b[NO_TILE * 2];
@@ -242,7 +277,8 @@ __global__ __launch_bounds__(256) void k_nn_map_orb(MapBuf m, RelocBuf r, const 
     if (blk < fwd_blocks) {
         const int row0 = blk * NO_BLOCK_ROWS;
         if (row0 >= nq) return;
-        nn_map_hamming_body(s_b, F, nq, m.rows, m.npt, row0, r.nn_idx + (size_t)q * kp_cap, r.nn_dist + (size_t)q * kp_cap);
+        nn_map_hamming_body(s_b, F, nq, m.rows, m.npt, row0, r.nn_idx + (size_t)q * kp_cap, r.nn_dist + (size_t)q * kp_cap,
+                            r.nn_dist2 + (size_t)q * kp_cap, std::bool_constant<K2>{});
     } else {
         const int row0 = (blk - fwd_blocks) * NO_BLOCK_ROWS;
         if (row0 >= m.npt) return;
@@ -251,13 +287,19 @@ __global__ __launch_bounds__(256) void k_nn_map_orb(MapBuf m, RelocBuf r, const 
 }
 
 void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
-                   int kp_cap, int cap_x)
+                   int kp_cap, int cap_x, int mode)
 {
     if (Q <= 0) return;
     static_assert(NM_BLOCK_ROWS == NO_BLOCK_ROWS, "one grid formula for both kernels");
-    const int fwd = (kp_cap + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
-    if (m.D == 128) hipLaunchKernelGGL(k_nn_map, dim3((unsigned)Q * (fwd + rev)), dim3(NM_THREADS), 0, s, m, r, desc_x, norms, kp_count, kp_cap, cap_x, fwd, rev);
-    else hipLaunchKernelGGL(k_nn_map_orb, dim3((unsigned)Q * (fwd + rev)), dim3(256), 0, s, m, r, desc, kp_count, kp_cap, fwd, rev);
+    const int fwd = (kp_cap + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = mode == 1 ? 0 : (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
+    const dim3 grid((unsigned)Q * (fwd + rev));
+    if (m.D == 128) {
+        if (mode == 0) hipLaunchKernelGGL(k_nn_map<false>, grid, dim3(NM_THREADS), 0, s, m, r, desc_x, norms, kp_count, kp_cap, cap_x, fwd, rev);
+        else hipLaunchKernelGGL(k_nn_map<true>, grid, dim3(NM_THREADS), 0, s, m, r, desc_x, norms, kp_count, kp_cap, cap_x, fwd, rev);
+    } else {
+        if (mode == 0) hipLaunchKernelGGL(k_nn_map_orb<false>, grid, dim3(256), 0, s, m, r, desc, kp_count, kp_cap, fwd, rev);
+        else hipLaunchKernelGGL(k_nn_map_orb<true>, grid, dim3(256), 0, s, m, r, desc, kp_count, kp_cap, fwd, rev);
+    }
 }
 
 // ------------------------------------------------------------------ k_map_select: the match list and the correspondences, one workgroup per query
@@ -265,6 +307,18 @@ void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* de
 // then `m.distance < max_distance` on cv2's float32 distance (sqrtf((float)d^2) for SIFT rows, the integer as float for ORB rows;
 // max_distance <= 0: no filter), compacted in ascending keypoint order; obj[k] = the map point of trainIdx, img[k] =
 // float64(kp_xy[queryIdx]): MatchWithMap's orientation (src/visual_slam.py:211-217).
+// mode (vo_set_map_match) 0: that; 1: knnMatch(k=2) and `m.distance < ratio * n.distance` in the place of the mutual test (rn_idx
+// is not read: k_nn_map wrote none); 2: the mutual test and the ratio rule.  The rule is k_match_select's: no match when the map has
+// fewer than two rows, else (double)fd < ratio * (double)fd2 on cv2's float32 distances; fd2 goes to m_d2 in list order.
+__device__ __forceinline__ bool map_ratio_keeps(int mode, double ratio, bool l2, int npt, float fd, const int* fdist2, int i, float* fd2)
+{
+    if (mode == 0) return true;
+    if (npt < 2) return false;
+    const int d2 = fdist2[i];
+    *fd2 = d2 == INT_MAX ? FLT_MAX : l2 ? sqrtf((float)d2) : (float)d2;
+    return (double)fd < ratio * (double)*fd2;
+}
+
 __device__ __forceinline__ int ms_excl_scan_256(int v, int* s_w, int* total)
 {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -281,33 +335,36 @@ __device__ __forceinline__ int ms_excl_scan_256(int v, int* s_w, int* total)
     return off + inc - v;
 }
 
-__global__ __launch_bounds__(256) void k_map_select(MapBuf m, RelocBuf r, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance)
+__global__ __launch_bounds__(256) void k_map_select(MapBuf m, RelocBuf r, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance,
+                                                    int mode, double ratio)
 {
     __shared__ int s_w[4];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int slot = r.slots[q], nq = min(kp_count[slot], kp_cap);
     const size_t o = (size_t)q * kp_cap;
-    const int* fidx = r.nn_idx + o; const int* fdist = r.nn_dist + o;
+    const int* fidx = r.nn_idx + o; const int* fdist = r.nn_dist + o; const int* fdist2 = r.nn_dist2 + o;
     const int* ridx = r.rn_idx + (size_t)q * m.cap_rows;
     const float* xy = kp_xy + (size_t)slot * kp_cap * 2;
     const bool l2 = m.D == 128;
     int out_base = 0;
     for (int base = 0; base < nq; base += 256) {
         const int i = base + tid;
-        int t = -1; float fd = 0.f;
+        int t = -1; float fd = 0.f, fd2 = FLT_MAX;
         if (i < nq && m.npt > 0) {
             t = fidx[i];
-            if (t >= 0 && ridx[t] != i) t = -1;
+            if (mode != 1 && t >= 0 && ridx[t] != i) t = -1;
             if (t >= 0) {
                 const int d = fdist[i];
                 fd = l2 ? sqrtf((float)d) : (float)d;
                 if (max_distance > 0 && !((double)fd < max_distance)) t = -1;
+                if (t >= 0 && !map_ratio_keeps(mode, ratio, l2, m.npt, fd, fdist2, i, &fd2)) t = -1;
             }
         }
         int tot;
         const int pos = out_base + ms_excl_scan_256(t >= 0 ? 1 : 0, s_w, &tot);
         if (t >= 0) {
             r.m_q[o + pos] = i; r.m_t[o + pos] = t; r.m_d[o + pos] = fd;
+            if (mode != 0) r.m_d2[o + pos] = fd2;
             for (int k = 0; k < 3; k++) r.obj[(o + pos) * 3 + k] = m.xyz[(size_t)t * 3 + k];
             r.img[(o + pos) * 2] = (double)xy[2 * i]; r.img[(o + pos) * 2 + 1] = (double)xy[2 * i + 1];
         }
@@ -316,10 +373,11 @@ __global__ __launch_bounds__(256) void k_map_select(MapBuf m, RelocBuf r, const 
     if (tid == 0) { r.m_count[q] = out_base; r.off[2 * q] = (int)o; r.off[2 * q + 1] = (int)o + out_base; }
 }
 
-void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance)
+void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance,
+                       int mode, double ratio)
 {
     if (Q <= 0) return;
-    hipLaunchKernelGGL(k_map_select, dim3(Q), dim3(256), 0, s, m, r, kp_xy, kp_count, kp_cap, max_distance);
+    hipLaunchKernelGGL(k_map_select, dim3(Q), dim3(256), 0, s, m, r, kp_xy, kp_count, kp_cap, max_distance, mode, ratio);
 }
 
 // ================================================================== map-to-map alignment (vo_map_align, vo_sim3_ransac_batch)
@@ -355,6 +413,7 @@ __global__ __launch_bounds__(256) void k_align_gather(AlignBuf a, const uint8_t*
     }
 }
 
+template <bool K2>
 __global__ __launch_bounds__(NM_THREADS) void k_nn_align(MapBuf m, AlignBuf a, int fwd_blocks, int rev_blocks)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_b[2][NM_STAGE_ROWS * 128];
@@ -363,7 +422,8 @@ __global__ __launch_bounds__(NM_THREADS) void k_nn_align(MapBuf m, AlignBuf a, i
     if (blk < fwd_blocks) {
         const int row0 = blk * NM_BLOCK_ROWS;
         if (row0 >= f.npt) return;
-        nn_map_l2_body(s_b, f.img, f.norms, f.npt, m.img, m.norms, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q]);
+        nn_map_l2_body(s_b, f.img, f.norms, f.npt, m.img, m.norms, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q], a.nn_dist2 + a.pad[q],
+                       std::bool_constant<K2>{});
     } else {
         const int row0 = (blk - fwd_blocks) * NM_BLOCK_ROWS;
         if (row0 >= m.npt) return;
@@ -371,6 +431,7 @@ __global__ __launch_bounds__(NM_THREADS) void k_nn_align(MapBuf m, AlignBuf a, i
     }
 }
 
+template <bool K2>
 __global__ __launch_bounds__(256) void k_nn_align_orb(MapBuf m, AlignBuf a, int fwd_blocks, int rev_blocks)
 {
     __shared__ uint4 s_b[NO_TILE * 2];
@@ -379,7 +440,8 @@ __global__ __launch_bounds__(256) void k_nn_align_orb(MapBuf m, AlignBuf a, int 
     if (blk < fwd_blocks) {
         const int row0 = blk * NO_BLOCK_ROWS;
         if (row0 >= f.npt) return;
-        nn_map_hamming_body(s_b, f.rows, f.npt, m.rows, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q]);
+        nn_map_hamming_body(s_b, f.rows, f.npt, m.rows, m.npt, row0, a.nn_idx + a.pad[q], a.nn_dist + a.pad[q], a.nn_dist2 + a.pad[q],
+                            std::bool_constant<K2>{});
     } else {
         const int row0 = (blk - fwd_blocks) * NO_BLOCK_ROWS;
         if (row0 >= m.npt) return;
@@ -389,31 +451,33 @@ __global__ __launch_bounds__(256) void k_nn_align_orb(MapBuf m, AlignBuf a, int 
 
 // k_map_select's rules with a map's rows in the place of a frame's; the lists of query q start at off[q]: b_idx (query row),
 // a_idx (staged row), cv2's float32 distance, src[k] = the query's point, dst[k] = the staged map's point.
-__global__ __launch_bounds__(256) void k_align_select(MapBuf m, AlignBuf a, double max_distance)
+__global__ __launch_bounds__(256) void k_align_select(MapBuf m, AlignBuf a, double max_distance, int mode, double ratio)
 {
     __shared__ int s_w[4];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int o = a.off[q], nq = a.off[q + 1] - o;
-    const int* fidx = a.nn_idx + a.pad[q]; const int* fdist = a.nn_dist + a.pad[q];
+    const int* fidx = a.nn_idx + a.pad[q]; const int* fdist = a.nn_dist + a.pad[q]; const int* fdist2 = a.nn_dist2 + a.pad[q];
     const int* ridx = a.rn_idx + (size_t)q * m.cap_rows;
     const bool l2 = m.D == 128;
     int out_base = 0;
     for (int base = 0; base < nq; base += 256) {
         const int i = base + tid;
-        int t = -1; float fd = 0.f;
+        int t = -1; float fd = 0.f, fd2 = FLT_MAX;
         if (i < nq && m.npt > 0) {
             t = fidx[i];
-            if (t >= 0 && ridx[t] != i) t = -1;
+            if (mode != 1 && t >= 0 && ridx[t] != i) t = -1;
             if (t >= 0) {
                 const int d = fdist[i];
                 fd = l2 ? sqrtf((float)d) : (float)d;
                 if (max_distance > 0 && !((double)fd < max_distance)) t = -1;
+                if (t >= 0 && !map_ratio_keeps(mode, ratio, l2, m.npt, fd, fdist2, i, &fd2)) t = -1;
             }
         }
         int tot;
         const int pos = o + out_base + ms_excl_scan_256(t >= 0 ? 1 : 0, s_w, &tot);
         if (t >= 0) {
             a.m_b[pos] = i; a.m_a[pos] = t; a.m_d[pos] = fd;
+            if (mode != 0) a.m_d2[pos] = fd2;
             for (int k = 0; k < 3; k++) { a.src[(size_t)pos * 3 + k] = a.xyz[(size_t)(o + i) * 3 + k]; a.dst[(size_t)pos * 3 + k] = m.xyz[(size_t)t * 3 + k]; }
         }
         out_base += tot;
@@ -421,24 +485,30 @@ __global__ __launch_bounds__(256) void k_align_select(MapBuf m, AlignBuf a, doub
     if (tid == 0) { a.m_count[q] = out_base; a.poff[2 * q] = o; a.poff[2 * q + 1] = o + out_base; }
 }
 
-void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows)
+void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows, int mode)
 {
     if (a.Q <= 0) return;
     if (a.total > 0) {
         const int per = a.D == 128 ? 4 : 32, g = (a.total + per - 1) / per;
         hipLaunchKernelGGL(k_align_gather, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, a, src_rows);
     }
-    const int fwd = (max_rows + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
+    const int fwd = (max_rows + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = mode == 1 ? 0 : (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
     if (fwd + rev > 0) {
-        if (m.D == 128) hipLaunchKernelGGL(k_nn_align, dim3((unsigned)a.Q * (fwd + rev)), dim3(NM_THREADS), 0, s, m, a, fwd, rev);
-        else hipLaunchKernelGGL(k_nn_align_orb, dim3((unsigned)a.Q * (fwd + rev)), dim3(256), 0, s, m, a, fwd, rev);
+        const dim3 grid((unsigned)a.Q * (fwd + rev));
+        if (m.D == 128) {
+            if (mode == 0) hipLaunchKernelGGL(k_nn_align<false>, grid, dim3(NM_THREADS), 0, s, m, a, fwd, rev);
+            else hipLaunchKernelGGL(k_nn_align<true>, grid, dim3(NM_THREADS), 0, s, m, a, fwd, rev);
+        } else {
+            if (mode == 0) hipLaunchKernelGGL(k_nn_align_orb<false>, grid, dim3(256), 0, s, m, a, fwd, rev);
+            else hipLaunchKernelGGL(k_nn_align_orb<true>, grid, dim3(256), 0, s, m, a, fwd, rev);
+        }
     }
 }
 
-void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance)
+void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance, int mode, double ratio)
 {
     if (a.Q <= 0) return;
-    hipLaunchKernelGGL(k_align_select, dim3(a.Q), dim3(256), 0, s, m, a, max_distance);
+    hipLaunchKernelGGL(k_align_select, dim3(a.Q), dim3(256), 0, s, m, a, max_distance, mode, ratio);
 }
 
 // ------------------------------------------------------------------ k_sim3_ransac: X_a = s R X_b + t from 3D-3D correspondences

@@ -200,7 +200,7 @@ static void comm_release(vo_ctx* ctx);
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F);
 
-extern "C" int vo_version(void) { return 124; }
+extern "C" int vo_version(void) { return 125; }
 
 extern "C" int vo_create(int device_id, vo_ctx** out)
 {
@@ -307,6 +307,18 @@ extern "C" int vo_set_pnp_refine(vo_ctx* ctx, int kind)
     if (!ctx) return VO_ERR_INVALID;
     if (kind != 0 && kind != 1) FAIL(VO_ERR_INVALID, "pnp refine must be 1 (cv2's solvePnP(ITERATIVE) on the inliers) or 0 (fast minimiser from the RANSAC model)");
     ctx->pnp_refine = kind;
+    return VO_OK;
+}
+
+extern "C" int vo_set_map_match(vo_ctx* ctx, int mode, double ratio)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (mode < 0 || mode > 2) FAIL(VO_ERR_INVALID, "map match mode must be 0 (cross-check), 1 (ratio) or 2 (cross-check and ratio)");
+    if (mode != 0) {
+        if (!(ratio > 0 && ratio <= DBL_MAX)) FAIL(VO_ERR_INVALID, "map match ratio must be finite and positive");
+        ctx->map_ratio = ratio;
+    }
+    ctx->map_match = mode;
     return VO_OK;
 }
 

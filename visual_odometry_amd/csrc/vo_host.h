@@ -124,6 +124,7 @@ struct MapState {
     double* dK = nullptr;
     int Q_cap = 0, kp_cap = 0;            // what the work buffers were sized for
     int last_Q = 0;                       // queries of the most recent vo_map_localize (vo_map_matches); 0: none since the map was staged
+    int last_mode = 0;                    // ... and the vo_set_map_match mode it ran in (vo_map_match_seconds)
     // vo_map_align's query maps and work buffers: a second allocation, made by the first call that needs it and kept while the next
     // one fits; it ends with the staged map (drop_map), and a newly staged map forgets its queries
     struct Align {
@@ -131,6 +132,7 @@ struct MapState {
         AlignBuf a{};
         int Q_cap = 0, pad_cap = 0, total_cap = 0, map_rows = 0;   // what it was sized for
         int last_Q = 0;                   // queries of the most recent vo_map_align (vo_map_align_matches)
+        int last_mode = 0;                // ... and the vo_set_map_match mode it ran in
         std::vector<int32_t> off, pad;    // host copies of that call's offsets
     } al;
 };
@@ -262,6 +264,7 @@ struct vo_ctx {
     int kp_order = 1;                     // 1 (default): cv2's retainBest order — keypoint / match indices as cv2 numbers them; 0: canonical (octave, y, x)
     Cv2Buf cv2{};
     bool cv2_ready = false;
+    int map_match = 0; double map_ratio = 0.75;   // vo_set_map_match: 0 cross-check (default), 1 ratio, 2 both; read by vo_map_localize / vo_map_align
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
     int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it

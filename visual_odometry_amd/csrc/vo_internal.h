@@ -486,7 +486,9 @@ struct MapBuf {
 struct RelocBuf {
     int*     slots;                     // [Q] the queries' frame slots
     int*     nn_idx; int* nn_dist;      // [Q][kp_cap] nearest map row of every keypoint and its distance (SIFT: integer d^2; ORB: Hamming)
-    int*     rn_idx;                    // [Q][cap_rows] nearest keypoint of query q for every map row
+    int*     nn_dist2;                  // [Q][kp_cap] the second-smallest distance (knnMatch(k=2)'s n.distance): written in map-match modes 1, 2
+    int*     rn_idx;                    // [Q][cap_rows] nearest keypoint of query q for every map row (not written in mode 1)
+    float*   m_d2;                      // [Q][kp_cap] n.distance of every entry of the match list, in list order (modes 1, 2)
     int*     m_q; int* m_t; float* m_d; // [Q][kp_cap] the match list: keypoint, map point, cv2's float32 distance
     int*     m_count;                   // [Q]
     double*  obj; double* img;          // [Q][kp_cap][3], [Q][kp_cap][2]: query q's problem starts at row q kp_cap
@@ -500,8 +502,10 @@ struct RelocBuf {
 // key == nullptr, from src [npt][D] as it stands: both through the one store
 void launch_map_gather(hipStream_t s, MapBuf m, const uint8_t* src, const int* key, int n_keys, const double* xyz);
 void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
-                   int kp_cap, int cap_x);
-void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance);
+                   int kp_cap, int cap_x, int mode);
+// mode, ratio: vo_set_map_match (0 cross-check, 1 ratio, 2 both)
+void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* kp_xy, const int* kp_count, int kp_cap, double max_distance,
+                       int mode, double ratio);
 // [Rodrigues(rvec) | tvec] of B solved problems, zeros for the others; a model with fewer than min_inliers inliers becomes VO_ERR_NO_MODEL
 void launch_pnp_poses(hipStream_t s, const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses);
 // ---- map alignment: Q query maps against the staged one (reloc_kernels.hip): vo_map_align, vo_sim3_ransac_batch
@@ -514,7 +518,9 @@ struct AlignBuf {
     double*  xyz;                       // [total][3] the queries' points as uploaded
     int*     flag;                      // [1] bit 1: a SIFT row broke the norm bound
     int*     nn_idx; int* nn_dist;      // [pad[Q]] nearest staged row of every query row and its distance
-    int*     rn_idx;                    // [Q][cap_rows of the staged map] nearest row of query q for every staged row
+    int*     nn_dist2;                  // [pad[Q]] the second-smallest distance (map-match modes 1, 2)
+    int*     rn_idx;                    // [Q][cap_rows of the staged map] nearest row of query q for every staged row (not written in mode 1)
+    float*   m_d2;                      // [total] n.distance of every entry of the match lists, in list order (modes 1, 2)
     int*     m_b; int* m_a; float* m_d; // [total] the match lists, query q's at off[q]: query row, staged row, cv2's float32 distance
     int*     m_count;                   // [Q]
     double*  src; double* dst;          // [total][3] the correspondences: b = the query's point, a = the staged map's
@@ -524,8 +530,8 @@ struct AlignBuf {
     int*     ninl; int* status;         // [Q]
 };
 // the queries' rows (device, [total][D]) into their operands, then both directions' nearest neighbours; max_rows = the largest query map
-void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows);
-void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance);
+void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows, int mode);
+void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_distance, int mode, double ratio);
 // B problems src -> dst ([n][3] each); problem b is rows offsets[b off_stride] .. offsets[b off_stride + 1] - 1; sim [B][13]
 void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, const int* offsets, int off_stride, int B, int iterations, double max_error,
                         double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask, int* ninl,

@@ -598,10 +598,13 @@ class FrontEnd:
         c.check(c.lib.vo_map_rows(c.handle, rows.ctypes.data, pts.ctypes.data, n.value, C.addressof(n)))
         return rows, pts
 
-    def relocalize(self, slots, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0):
+    def relocalize(self, slots, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0,
+                   match="cross", ratio=0.75):
         """Place detected slots in the staged map by their descriptors (vo_map_localize), all in one call on the device:
         bf.match(frame, map) with crossCheck=True -> `distance < max_distance` (0: no filter) -> cv2.solvePnPRansac on the 3D-2D
-        matches.  Returns dict(poses [Q, 3, 4] world -> camera in the map's gauge, zeros where status != 0; n_match, n_inl,
+        matches.  match='ratio': knnMatch(frame, map, k=2) and `m.distance < ratio * n.distance` (src/feature_detection.py:20-26) in
+        the place of the cross-check — no reverse direction is computed, several keypoints may keep one map point;
+        match='cross+ratio': both.  The call sets the context's vo_set_map_match to what it is given.  Returns dict(poses [Q, 3, 4] world -> camera in the map's gauge, zeros where status != 0; n_match, n_inl,
         status [Q]: 0, VO_ERR_TOO_FEW (fewer than 4 matches) or VO_ERR_NO_MODEL (no model, or fewer than min_inliers inliers))."""
         sl = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         Q = len(sl)
@@ -609,6 +612,7 @@ class FrontEnd:
         opts = _lib.RelocOpts(float(max_distance), int(iterations), float(reproj_err), float(confidence), int(seed), int(min_inliers))
         poses = np.zeros((Q, 12)); nm = np.zeros(Q, np.int32); ni = np.zeros(Q, np.int32); st = np.zeros(Q, np.int32)
         c = self.ctx
+        c.set_map_match(match, ratio)
         c.check(c.lib.vo_map_localize(c.handle, sl.ctypes.data, Q, K.ctypes.data, C.addressof(opts), poses.ctypes.data, nm.ctypes.data,
                                       ni.ctypes.data, st.ctypes.data))
         return dict(poses=poses.reshape(Q, 3, 4), n_match=nm, n_inl=ni, status=st)
@@ -624,14 +628,31 @@ class FrontEnd:
         k = n.value
         return pi[:k].copy(), ki[:k].copy(), d[:k].copy(), m[:k].copy()
 
+    def _match_seconds(self, which, q, cap):
+        d2 = np.empty(max(int(cap), 1), np.float32); n = C.c_int32(0)
+        c = self.ctx
+        c.check(c.lib.vo_map_match_seconds(c.handle, which, int(q), d2.ctypes.data, len(d2), C.addressof(n)))
+        return d2[:n.value].copy()
+
+    def map_match_seconds(self, q):
+        """n.distance of knnMatch(k=2) for every entry of map_matches(q), float32, in list order (vo_map_match_seconds) — what the
+        ratio rule compared, and what re-thresholding on the host needs.  VoError after a relocalize(match='cross')."""
+        return self._match_seconds(0, q, self.kp_cap)
+
+    def map_align_match_seconds(self, q):
+        """The same for map_align_matches(q) of the latest align_maps(match='ratio' | 'cross+ratio')."""
+        rows = getattr(self, "_align_rows", ())
+        return self._match_seconds(1, q, rows[int(q)] if 0 <= int(q) < len(rows) else 1)
+
     # ---- map alignment: the similarity that joins two maps, by their descriptors (vo_map_align) ------
     def align_maps(self, rows, points, max_error, offsets=None, max_distance=0.0, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED,
-                   min_inliers=0):
+                   min_inliers=0, match="cross", ratio=0.75):
         """Align Q query maps to the staged map by their descriptors (vo_map_align), all in one call on the device: the cross-check
         match of every query map's rows against the staged rows -> `distance < max_distance` (0: no filter) -> RANSAC over the
         3D-3D matches for X_staged = scale R X_query + t.  rows [total, D] and points [total, 3] hold the query maps one after
         the other, map q being rows offsets[q]:offsets[q + 1] (offsets None: one map); what map_rows() returned for them.
-        max_error is the inlier bound in the STAGED map's units and has no default.  Returns dict(scale [Q], R [Q, 3, 3], t [Q, 3]
+        max_error is the inlier bound in the STAGED map's units and has no default.  match / ratio: as in relocalize(), with a
+        query map's rows in the place of a frame's (map_align_match_seconds(q) returns the second distances).  Returns dict(scale [Q], R [Q, 3, 3], t [Q, 3]
         (zeros where status != 0), n_match, n_inl, status [Q]: 0, VO_ERR_TOO_FEW (fewer than 3 matches) or VO_ERR_NO_MODEL).
         Up to 64 maps and 65536 rows in one call (NotImplementedError beyond)."""
         r = self._map_rows_u8(rows)
@@ -645,6 +666,7 @@ class FrontEnd:
         opts = _lib.AlignOpts(float(max_distance), float(max_error), int(iterations), float(confidence), int(seed), int(min_inliers))
         sim = np.zeros((Q, 13)); nm = np.zeros(Q, np.int32); ni = np.zeros(Q, np.int32); st = np.zeros(Q, np.int32)
         c = self.ctx
+        c.set_map_match(match, ratio)
         rc = c.lib.vo_map_align(c.handle, r.ctypes.data, p.ctypes.data, off.ctypes.data, Q, C.addressof(opts), sim.ctypes.data, nm.ctypes.data,
                                 ni.ctypes.data, st.ctypes.data)
         if rc == _lib.VO_ERR_UNSUPPORTED:
