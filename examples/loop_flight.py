@@ -1,23 +1,26 @@
 #!/usr/bin/env python3
 """A loop closed against the map a stream built: a flight that goes out and comes back, streamed in chunks with slot reuse.
 
-    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--width 640] [--height 480] [--nfeatures 1000] [--ratio R]
+    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--max-cameras 18] [--width 640] [--height 480] [--nfeatures 1000] [--ratio R]
 
 The flight is synthetic and uses no files: frames 0 .. n of synth.sequence, then n - 1 .. 0 again, so the last frames see the ground
 of the first.  It is walked by slam_stream in chunks of --chunk pairs on a FrontEnd with only chunk + 2 frame slots: every chunk's
 frames go into the slots the chunk before freed, and when the flight is back at its start the frames of its beginning have long left
-the device.  The stream runs with a descriptor store (stream_rows), so its map can still be matched against.
+the device.  The stream runs with a descriptor store (stream_rows) and an archive of evicted points (stream_archive), so what it
+has mapped can still be matched against.
 
 Every frame becomes an entry of the keyframe index while it is resident (train_vocabulary on the first chunk, places_add); at the
 end places_query -> loop_candidates names pairs (old, new) of frames that see the same place.  For the best candidate whose `new`
-frame is still in a slot, map_from_stream(old - w, old + w + 1) stages the points owned by the frames around `old` — from the store,
-their slots are gone — and relocalize places `new` among them by its descriptors alone.  Printed: that pose against the pose the
+frame is still in a slot, map_from_stream_archive(old - w, old + w + 1) stages the points owned by the frames around `old` — the live
+ones from the store, the ones the camera limit has removed from the archive; their slots are gone — and relocalize places `new`
+among them by its descriptors alone.  Printed: that pose against the pose the
 stream itself gave `new` through its chain of pairs (--ratio R: matched by Lowe's ratio rule, knnMatch(k=2) and
 `m.distance < R * n.distance`, instead of the cross-check); the difference is the drift the flight accumulated between the two visits.
 The loop_edge the pose graph would take for (old, new) is built from the two (optimize_pose_graph, examples/close_loop.py).
 
-The stream's map is its LIVE map: a point whose cameras have all been evicted (max_cameras) is gone from it, so this flight keeps
-every camera (max_cameras >= its frames).  An archive of what a longer flight has evicted is not built."""
+The stream's map is its LIVE map: a point the camera limit has removed (--max-cameras, the reference's 18 by default) is gone from
+it.  With the default flight of 17 frames nothing is evicted; fly further out (--out 20) or lower --max-cameras (--max-cameras 4) and
+the points around the flight's start are staged from the archive."""
 import argparse
 import os
 import sys
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--out", type=int, default=8, help="frames flown out before turning back")
     ap.add_argument("--chunk", type=int, default=4)
     ap.add_argument("--window", type=int, default=1)
+    ap.add_argument("--max-cameras", type=int, default=18, help="cameras the map keeps (limit_number_of_camera_in_map)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--nfeatures", type=int, default=1000)
@@ -43,11 +47,10 @@ def main():
     seq = synth.sequence(a.out + 1, a.width, a.height, step=4.0, cache_dir="/tmp")
     image = list(range(a.out + 1)) + list(range(a.out - 1, -1, -1))      # the image every frame of the flight shows
     n, pairs, K = len(image), len(image) - 1, seq["K"]
-    if n - 1 > 62:
-        raise SystemExit("keep the flight within 63 frames: its map keeps every camera (max_cameras)")
     n_slots = a.chunk + 2
     fe = F.FrontEnd(a.height, a.width, max_frames=n_slots, max_pairs=a.chunk, nfeatures=a.nfeatures)
     fe.stream_rows(-1)                                                    # a row for every feature the stream can hold: nothing is dropped
+    fe.stream_archive(-1)                                                 # ... and an entry: every point the camera limit removes is kept
 
     free, slot_of, poses, at = list(range(n_slots)), {}, np.zeros((n, 3, 4)), 0
     while at < pairs:
@@ -61,7 +64,7 @@ def main():
             fe.places_open(n)                                             # (a new vocabulary closes an open index: train first)
         fe.places_add([slot_of[f] for f in new], new)
         fe.run_pairs([[slot_of[at + j], slot_of[at + j + 1]] for j in range(b)], K, want_points=True)
-        out = fe.slam_stream(b, K, resume=at > 0, total_pairs=pairs, max_cameras=max(n, 2))
+        out = fe.slam_stream(b, K, resume=at > 0, total_pairs=pairs, max_cameras=a.max_cameras)
         if (out["status"] != 0).any():
             raise SystemExit(f"the stream lost track in the chunk at pair {at}: status {out['status'].tolist()}")
         for f, T in zip(out["carried_frame"], out["carried_poses"]):      # every frame's pose as the map last held it
@@ -71,9 +74,10 @@ def main():
             free.append(slot_of.pop(f))
         free.sort()
         at += b
-    info, m = fe.stream_rows_info(), fe.slam_map(0)
+    info, arc, m = fe.stream_rows_info(), fe.stream_archive_info(), fe.slam_map(0)
     print(f"{n} frames ({a.out} out, {a.out} back) in chunks of {a.chunk} pairs on {n_slots} slots; live map {len(m['points'])} points of "
-          f"{len(m['cam_frame'])} cameras; store: {info['stored']} rows of {info['capacity']}, {info['dropped']} dropped")
+          f"{len(m['cam_frame'])} cameras (at most {a.max_cameras}); store: {info['stored']} rows of {info['capacity']}, {info['dropped']} dropped; "
+          f"archive: {arc['stored']} evicted points of {arc['capacity']}, {arc['dropped']} dropped")
 
     ids = np.arange(n)
     res = fe.places_query(top_k=2, min_gap=a.chunk + 2)
@@ -84,9 +88,10 @@ def main():
         return
     old, new, shared = max(resident, key=lambda c: c[2])
     first, end = max(old - a.window, 0), old + a.window + 1
-    staged = fe.map_from_stream(first, end)
+    staged = fe.map_from_stream_archive(first, end)
     print(f"best candidate ({old}, {new}), {shared} shared words (images {image[old]} and {image[new]}); "
-          f"map_from_stream({first}, {end}): {staged['n']} points, {staged['without_row']} without a row")
+          f"map_from_stream_archive({first}, {end}): {staged['n']} points, {staged['n'] - staged['n_archived']} live and "
+          f"{staged['n_archived']} archived, {staged['without_row']} without a row")
     r = fe.relocalize([slot_of[new]], K) if a.ratio is None else fe.relocalize([slot_of[new]], K, match="ratio", ratio=a.ratio)
     if r["status"][0] != 0:
         print(f"relocalize: status {int(r['status'][0])} with {int(r['n_match'][0])} matches")

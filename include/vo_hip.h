@@ -956,6 +956,40 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  *     map.  VO_ERR_INVALID: no live vo_slam_stream with a store, frame_first < 0, 0 <= frame_end < frame_first.  VO_ERR_UNSUPPORTED:
  *     more than 65536 points selected.  A failed call leaves no staged map.  The stream, the pair results and vo_slam_map's copies
  *     are left alone: a later resume = 1 returns what it would have returned without the call.
+ * vo_set_stream_archive / vo_stream_archive_info / vo_stream_archive_read / vo_map_from_stream_archive: a stream's archive of the
+ *   points the camera limit has removed.  The store serves the live map; with max_cameras = 18 a long flight that returns to its
+ *   start has nothing of its start left to match against.  With the archive every point k_slam_limit removes is kept on the device,
+ *   in removal order, in one more allocation of the stream's lifetime: capacity_points (D + 40) bytes, plus 8 bytes per 256 entries
+ *   for the selection's tile counts and the 1.75 MiB of selection buffers.
+ *   vo_set_stream_archive: capacity_points 0 = no archive (the default: every call then returns the bytes and the refusals it
+ *     returns without this paragraph), -1 = (total_pairs + 1) kp_cap entries, which can never drop a point, > 0 = that many entries
+ *     (at most 2^31 - 1: VO_ERR_INVALID at the call that starts the stream), < -1: VO_ERR_INVALID.  Read by the next
+ *     vo_slam_stream(resume = 0); a live stream keeps the setting it started with.  An archive needs the store: the frames of
+ *     earlier calls have no slot, so their points' rows can only come from it — resume = 0 with the archive on and
+ *     vo_set_stream_rows off is VO_ERR_INVALID and starts nothing.  vo_slam_stream_restart, vo_slam_streams and the chains ignore it.
+ *   What is archived: at every step whose camera limit evicts a camera, exactly the points that step removes, by the limit's own
+ *     rule (observations counted among cameras other than the first; a point left with exactly one goes, a point with none stays),
+ *     in map order; evictions follow one another in pair order.  An entry holds feature = pt_feature (frame along the stream,
+ *     keypoint), xyz = the three doubles the limit read, evicted_at = the pair along the stream, and a COPY of the descriptor row:
+ *     from the slots by the point's key when the point was born in this call (feature frame >= the call's first frame), otherwise
+ *     from the store, otherwise none (has_row = 0, the row reads zeros: the store dropped the point at capacity).  The archive
+ *     owns its rows, so an entry is complete however the flight was chunked into calls.  A full archive counts the remaining
+ *     points as dropped, for good: the entries kept are the first in that order, so which are dropped follows from the inputs
+ *     alone.  No deduplication: a removed point's feature may later own a new point, and both are legitimate — the same feature can
+ *     occur in several entries, or in an entry and in the live map.  With the archive on, every output of the stream, its map
+ *     after every call and the store are the bytes they are with it off.
+ *   vo_stream_archive_info: entries it holds, entries stored, points dropped.  VO_ERR_INVALID without a live vo_slam_stream that
+ *     has an archive.
+ *   vo_stream_archive_read: entries first .. first + n - 1 back on the host, for tests and for saving; any pointer may be NULL.
+ *     VO_ERR_INVALID without such a stream, or when the range is not among the stored entries.
+ *   vo_map_from_stream_archive: vo_map_from_stream's window rule over the archive.  with_live = 1 stages the live points of the
+ *     window first, exactly as vo_map_from_stream stages them, then the archived entries of the window that have a row, in archive
+ *     order (on a duplicated row the live point wins the cross-check's lowest-index tie); with_live = 0 the archived entries only.
+ *     n_staged = points staged, n_archived = the archived ones among them, n_without_row = points of the window left out (live
+ *     and archived).  The staged map is the bytes vo_map_stage produces from the same rows and points (SIFT: the int8 operand
+ *     image, the norms and the norm flag included: the one row store).  VO_ERR_UNSUPPORTED: more than 65536 points selected;
+ *     VO_ERR_INVALID: no live vo_slam_stream with an archive, or no window.  A failed call leaves no staged map.  The stream is
+ *     left as it was.  vo_map_from_stream itself is unchanged.
  * vo_map_rows: the staged map back (up to cap points; *npt = its size): what a caller saves before the frames leave their slots.
  * vo_map_localize: Q <= max_pairs detected slots against the staged map in one call.  No staged map: VO_ERR_INVALID.  A slot flagged
  *   for its descriptor norm (SIFT): VO_ERR_INVALID AFTER the run, as vo_pairs_run reports it.  Profiling stages: match_nn (k_nn_map),
@@ -1000,6 +1034,12 @@ int vo_map_from_slam(vo_ctx* ctx, int seq, int which);
 int vo_set_stream_rows(vo_ctx* ctx, int64_t capacity_rows);
 int vo_stream_rows_info(vo_ctx* ctx, int64_t* capacity, int64_t* stored, int64_t* dropped);
 int vo_map_from_stream(vo_ctx* ctx, int frame_first, int frame_end, int32_t* n_staged, int32_t* n_without_row);
+int vo_set_stream_archive(vo_ctx* ctx, int64_t capacity_points);
+int vo_stream_archive_info(vo_ctx* ctx, int64_t* capacity, int64_t* stored, int64_t* dropped);
+int vo_stream_archive_read(vo_ctx* ctx, int64_t first, int64_t n, int32_t* feature /*[n][2]*/, double* xyz /*[n][3]*/, int32_t* evicted_at /*[n]*/,
+                           int32_t* has_row /*[n]*/, uint8_t* rows /*[n][D]*/);
+int vo_map_from_stream_archive(vo_ctx* ctx, int frame_first, int frame_end, int with_live, int32_t* n_staged, int32_t* n_archived,
+                               int32_t* n_without_row);
 int vo_map_rows(vo_ctx* ctx, uint8_t* rows /*[cap][D]*/, double* points /*[cap][3]*/, int cap, int32_t* npt);
 int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const vo_reloc_opts* opts,
                     double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);

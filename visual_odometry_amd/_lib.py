@@ -144,6 +144,10 @@ _SIGS = {
     "vo_set_stream_rows": (C.c_int, [_P, C.c_int64]),
     "vo_stream_rows_info": (C.c_int, [_P, _P, _P, _P]),
     "vo_map_from_stream": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "vo_set_stream_archive": (C.c_int, [_P, C.c_int64]),
+    "vo_stream_archive_info": (C.c_int, [_P, _P, _P, _P]),
+    "vo_stream_archive_read": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "vo_map_from_stream_archive": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "vo_map_rows": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "vo_map_localize": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),

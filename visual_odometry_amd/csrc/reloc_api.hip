@@ -35,9 +35,14 @@ static int map_reserve(vo_ctx* ctx, const Batch& b, int npt)
 
 int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int npt, const char* who)
 {
+    return map_stage_device2(ctx, src, key, n_keys, xyz, npt, MapPart2{nullptr, nullptr, 0, nullptr}, npt, who);
+}
+
+int map_stage_device2(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int n0, const MapPart2& p2, int npt, const char* who)
+{
     const Batch b = batch(ctx);
     if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "%s: vo_batch_configure[_sift] has not been called", who);
-    if (npt < 0) FAIL(VO_ERR_INVALID, "%s: npt must not be negative", who);
+    if (npt < 0 || n0 < 0 || n0 > npt) FAIL(VO_ERR_INVALID, "%s: npt must not be negative", who);
     if (npt > VO_MAP_MAX_POINTS) FAIL(VO_ERR_UNSUPPORTED, "%s: a staged map holds at most %d points, got %d", who, VO_MAP_MAX_POINTS, npt);
     HIPCHK(hipSetDevice(ctx->device));
     int rc = map_reserve(ctx, b, npt); if (rc) return rc;
@@ -46,7 +51,9 @@ int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys
     M.staged = false; M.last_Q = 0; M.al.last_Q = 0;
     M.m.npt = npt;
     HIPCHK(hipMemsetAsync(M.m.flag, 0, sizeof(int), s));
-    launch_map_gather(s, M.m, src, key, n_keys, xyz);
+    MapBuf head = M.m; head.npt = n0;                       // (the whole map without a second part: the launch it always was)
+    launch_map_gather(s, head, src, key, n_keys, xyz);
+    if (p2.src && n0 < npt) launch_map_gather_from(s, M.m, n0, p2.src, p2.key, p2.n_keys, p2.xyz);
     HIPCHK(hipGetLastError());
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, M.m.flag, sizeof(int), hipMemcpyDeviceToHost, s));

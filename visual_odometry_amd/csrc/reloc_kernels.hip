@@ -62,6 +62,33 @@ void launch_map_gather(hipStream_t s, MapBuf m, const uint8_t* src, const int* k
     hipLaunchKernelGGL(k_map_gather, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, m, src, key, n_keys, xyz);
 }
 
+// k_map_gather for the rows id0 .. m.npt - 1 of the map: the part vo_map_from_stream_archive stages behind the live points.  key
+// and xyz are indexed by the map row, as k_map_gather's are; a kernel of its own, so that k_map_gather's code is what it was.
+__global__ __launch_bounds__(256) void k_map_gather_from(MapBuf m, int id0, const uint8_t* src, const int* key, int n_keys, const double* xyz)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (m.D == 128) {
+        for (int id = id0 + blockIdx.x * 4 + (tid >> 6); id < m.npt; id += gridDim.x * 4) {
+            const int k = key[id];
+            map_store_row_sift(m, id, k < 0 || k >= n_keys ? nullptr : src + (size_t)k * 128, lane);
+            if (lane < 3) m.xyz[(size_t)id * 3 + lane] = xyz[(size_t)id * 3 + lane];
+        }
+    } else {
+        for (int id = id0 + blockIdx.x * 32 + (tid >> 3); id < m.npt; id += gridDim.x * 32) {
+            const int k = key[id], part = tid & 7;
+            map_store_row_orb(m, id, k < 0 || k >= n_keys ? nullptr : src + (size_t)k * 32, part);
+            if (part < 3) m.xyz[(size_t)id * 3 + part] = xyz[(size_t)id * 3 + part];
+        }
+    }
+}
+
+void launch_map_gather_from(hipStream_t s, MapBuf m, int id0, const uint8_t* src, const int* key, int n_keys, const double* xyz)
+{
+    if (id0 < 0 || m.npt <= id0) return;
+    const int per = m.D == 128 ? 4 : 32, g = (m.npt - id0 + per - 1) / per;
+    hipLaunchKernelGGL(k_map_gather_from, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, m, id0, src, key, n_keys, xyz);
+}
+
 // ------------------------------------------------------------------ k_nn_map: SIFT rows, integer d^2 on the matrix cores
 // The identity and the selection argument are k_nn_l2i8's (docs/kernels/k_nn_l2i8.md): d^2 = |a|^2 + |b|^2 - 2 a.b on
 // v_mfma_i32_16x16x64_i8 over rows shifted to int8, ordered by the integer (sqrtf is strictly increasing below 2^22; rows that

@@ -158,6 +158,7 @@ struct SlamWalk {
     int snap_seq;                         // the sequence whose map the snapshot copies, -1: none
     SlamCarry carry;                      // stream, stream-restart: the carry of a resumed call
     bool seats;                           // streams: some seat is vacant
+    const SlamArchive* archive = nullptr; // stream with an archive (vo_set_stream_archive): the limit that also appends what it removes
 };
 
 static int slam_walk(vo_ctx* ctx, const SlamWalk& w, const SlamDims& d, const SlamBufs& b, const std::vector<SlamSeq>& seq, const double* K, const vo_slam_opts* o)
@@ -212,7 +213,10 @@ static int slam_walk(vo_ctx* ctx, const SlamWalk& w, const SlamDims& d, const Sl
     auto limit = [&](int j) {
         switch (fam) {
         case FAM_CHAIN: launch_slam_limit(s, j, o->max_cameras, cb, sb); break;
-        case FAM_STREAM: launch_slam_limit_stream(s, j, o->max_cameras, cb, sb); break;
+        case FAM_STREAM:
+            if (w.archive) launch_slam_limit_stream_archive(s, j, o->max_cameras, cb, sb, *w.archive);
+            else launch_slam_limit_stream(s, j, o->max_cameras, cb, sb);
+            break;
         case FAM_STREAM_RESTART: launch_slam_limit_stream_restart(s, j, o->max_cameras, cb, sb); break;
         case FAM_SEQS: case FAM_SEQS_RESTART: launch_slam_limit_seqs(s, j, o->max_cameras, dseq, S); break;
         case FAM_STREAMS: launch_slam_limit_stream_restart_seqs(s, j, o->max_cameras, dseq, S); break;
@@ -507,6 +511,82 @@ static int stream_rows_append(vo_ctx* ctx, SlamStream& st, const SlamMap& m, int
     return VO_OK;
 }
 
+// ------------------------------------------------------------------ a stream's archive of evicted points (vo_set_stream_archive)
+// A third allocation of the stream's lifetime, made with the store's by the call that starts a vo_slam_stream while both settings are
+// on.  The one kernel of the walk that knows it is k_slam_limit_stream_archive, launched in k_slam_limit_stream's place.
+extern "C" int vo_set_stream_archive(vo_ctx* ctx, int64_t capacity_points)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (capacity_points < -1) FAIL(VO_ERR_INVALID, "a stream archive must be 0 (none), -1 (an entry for every feature the stream can hold) or a number of entries, got %lld", (long long)capacity_points);
+    ctx->stream_archive = capacity_points;
+    return VO_OK;
+}
+
+static int stream_archive_allocate(vo_ctx* ctx, SlamStream& st, int64_t setting)
+{
+    SlamStream::Archive& ar = st.archive;
+    StreamArchive& d = ar.d;
+    const size_t feats = st.dims.np[0];                               // (total_pairs + 1) kp_cap: below 2^31 (slam_stream_allocate)
+    const int64_t capacity = setting < 0 ? (int64_t)feats : setting;
+    if (capacity > INT32_MAX) FAIL(VO_ERR_INVALID, "vo_slam_stream: an archive holds at most 2^31 - 1 entries (vo_set_stream_archive), got %lld", (long long)capacity);
+    d.D = st.store.d.D; d.capacity = (int)capacity; d.sel_cap = VO_MAP_MAX_POINTS;
+    const size_t tiles = ((size_t)capacity + SA_TILE - 1) / SA_TILE;
+    ScratchLayout sc;
+    sc.take(&d.rows, (size_t)capacity * d.D); sc.take(&d.xyz, (size_t)capacity * 3); sc.take(&d.feature, (size_t)capacity * 2);
+    sc.take(&d.evicted_at, (size_t)capacity); sc.take(&d.has_row, (size_t)capacity); sc.take(&d.counters, 2); sc.take(&d.tile_cnt, tiles * 2);
+    sc.take(&d.sel_key, (size_t)d.sel_cap); sc.take(&d.sel_xyz, (size_t)d.sel_cap * 3); sc.take(&d.sel_cnt, 2);
+    uint8_t* base = nullptr;
+    HIPCHK(ar.mem.alloc(&base, sc.bytes));
+    sc.place_at(base);
+    HIPCHK(hipMemsetAsync(base, 0, sc.bytes, ctx->stream));           // no entries; an entry without a row reads zeros
+    ar.counters[0] = ar.counters[1] = 0;
+    ar.on = true;
+    return VO_OK;
+}
+
+// the live vo_slam_stream with an archive, nullptr (and the reason in ctx->err) if there is none
+static SlamStream* stream_with_archive(vo_ctx* ctx, const char* who)
+{
+    SlamStream& st = ctx->stream_map;
+    const char* why = nullptr;
+    if (!st.live) why = "there is no live stream (none was started, or a configure or vo_slam_chain* call dropped it)";
+    else if (st.multi || st.restart) why = "the live stream was started by vo_slam_stream_restart or vo_slam_streams, which keep no archive";
+    else if (!st.archive.on) why = "the live stream was started without an archive (vo_set_stream_archive before vo_slam_stream(resume = 0))";
+    if (why) { snprintf(ctx->err, sizeof(ctx->err), "%s: %s", who, why); return nullptr; }
+    return &st;
+}
+
+extern "C" int vo_stream_archive_info(vo_ctx* ctx, int64_t* capacity, int64_t* stored, int64_t* dropped)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    if (!capacity || !stored || !dropped) FAIL(VO_ERR_INVALID, "bad arguments");
+    const SlamStream* st = stream_with_archive(ctx, "vo_stream_archive_info");
+    if (!st) return VO_ERR_INVALID;
+    *capacity = st->archive.d.capacity; *stored = st->archive.counters[0]; *dropped = st->archive.counters[1];
+    return VO_OK;
+}
+
+extern "C" int vo_stream_archive_read(vo_ctx* ctx, int64_t first, int64_t n, int32_t* feature, double* xyz, int32_t* evicted_at, int32_t* has_row, uint8_t* rows)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const SlamStream* st = stream_with_archive(ctx, "vo_stream_archive_read");
+    if (!st) return VO_ERR_INVALID;
+    const StreamArchive& d = st->archive.d;
+    if (first < 0 || n < 0 || first + n > st->archive.counters[0])
+        FAIL(VO_ERR_INVALID, "vo_stream_archive_read: entries [%lld, %lld + %lld) are not among the %d the archive holds", (long long)first, (long long)first, (long long)n, st->archive.counters[0]);
+    if (n == 0) return VO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t f = (size_t)first, c = (size_t)n;
+    if (feature) HIPCHK(hipMemcpyAsync(feature, d.feature + 2 * f, c * 8, hipMemcpyDeviceToHost, s));
+    if (xyz) HIPCHK(hipMemcpyAsync(xyz, d.xyz + 3 * f, c * 24, hipMemcpyDeviceToHost, s));
+    if (evicted_at) HIPCHK(hipMemcpyAsync(evicted_at, d.evicted_at + f, c * 4, hipMemcpyDeviceToHost, s));
+    if (has_row) HIPCHK(hipMemcpyAsync(has_row, d.has_row + f, c * 4, hipMemcpyDeviceToHost, s));
+    if (rows) HIPCHK(hipMemcpyAsync(rows, d.rows + f * d.D, c * d.D, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VO_OK;
+}
+
 // the live vo_slam_stream with a store, nullptr (and the reason in ctx->err) if there is none
 static SlamStream* stream_with_rows(vo_ctx* ctx, const char* who)
 {
@@ -559,6 +639,43 @@ extern "C" int vo_map_from_stream(vo_ctx* ctx, int frame_first, int frame_end, i
     return VO_OK;
 }
 
+// vo_map_from_stream with the archived points of the window behind the live ones (with_live) or alone.  The live part is
+// k_stream_rows_select's, unchanged; its count stays on the device, where the archive's emit pass starts from it; then one wait for
+// the four counts, and the two parts go through the one staging path.
+extern "C" int vo_map_from_stream_archive(vo_ctx* ctx, int frame_first, int frame_end, int with_live, int32_t* n_staged, int32_t* n_archived, int32_t* n_without_row)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    ctx->map.staged = false; ctx->map.last_Q = 0; ctx->map.al.last_Q = 0;          // a failed call leaves no staged map
+    if (!n_staged || !n_archived || !n_without_row) FAIL(VO_ERR_INVALID, "bad arguments");
+    *n_staged = 0; *n_archived = 0; *n_without_row = 0;
+    SlamStream* st = stream_with_archive(ctx, "vo_map_from_stream_archive");
+    if (!st) return VO_ERR_INVALID;
+    if (frame_first < 0 || (frame_end >= 0 && frame_end < frame_first))
+        FAIL(VO_ERR_INVALID, "vo_map_from_stream_archive: the window [%d, %d) is not one (frame_first >= 0; frame_end >= frame_first, or negative for no upper bound)", frame_first, frame_end);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const StreamRows& d = st->store.d;
+    const StreamArchive& a = st->archive.d;
+    const SlamMap& m = st->b.sb.m;
+    if (with_live) launch_stream_rows_select(s, m, d, st->dims.np[0], frame_first, frame_end);
+    launch_stream_archive_select(s, a, st->archive.counters[0], frame_first, frame_end, with_live ? d.sel_cnt : nullptr);
+    HIPCHK(hipGetLastError());
+    int32_t live[2] = {0, 0}, arc[2] = {0, 0};
+    if (with_live) HIPCHK(hipMemcpyAsync(live, d.sel_cnt, sizeof(live), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(arc, a.sel_cnt, sizeof(arc), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_without_row = live[1] + arc[1];
+    const int64_t total = (int64_t)live[0] + arc[0];
+    if (total > VO_MAP_MAX_POINTS)
+        FAIL(VO_ERR_UNSUPPORTED, "vo_map_from_stream_archive: a staged map holds at most %d points, the window [%d, %d) selects %d live and %d archived", VO_MAP_MAX_POINTS,
+             frame_first, frame_end, live[0], arc[0]);
+    const int rc = map_stage_device2(ctx, d.rows, d.sel_key, d.capacity, d.sel_xyz, live[0], MapPart2{a.rows, a.sel_key, a.capacity, a.sel_xyz}, (int)total,
+                                     "vo_map_from_stream_archive");
+    if (rc) return rc;
+    *n_staged = (int32_t)total; *n_archived = arc[0];
+    return VO_OK;
+}
+
 // vo_slam_stream and vo_slam_stream_restart.  restart: vo_slam_chains_restart's step for the one chain of the stream, and the alive
 // flag and the segment state words stay on the device between the calls.
 static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pairs, int B, const double* K, const vo_slam_opts* o, double* poses_pnp, double* poses,
@@ -593,11 +710,14 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
         if (!slam_stream_same_setup(st, K, o)) FAIL(VO_ERR_INVALID, "%s: K and every option but the snapshot's must be those the stream was started with", who);
         if ((int64_t)st.done + B > st.total) FAIL(VO_ERR_INVALID, "%s: %d + %d pairs pass the stream's total_pairs = %d", who, st.done, B, st.total);
     } else if (total_pairs < B) FAIL(VO_ERR_INVALID, "%s: total_pairs = %d is less than the call's %d pairs", who, total_pairs, B);
+    if (!resume && !restart && ctx->stream_archive != 0 && ctx->stream_rows == 0)
+        FAIL(VO_ERR_INVALID, "vo_slam_stream: an archive (vo_set_stream_archive) needs the descriptor store (vo_set_stream_rows): the rows of earlier calls' points come from it");
     HIPCHK(hipSetDevice(ctx->device));
     rc = ensure_rng(ctx, o->seed); if (rc) return rc;
     if (!resume) {
         rc = slam_stream_allocate(ctx, st, restart, F, cap, batch(ctx).max_pairs, total_pairs, o, K);
         if (!rc && !restart && ctx->stream_rows != 0) rc = stream_rows_allocate(ctx, st, ctx->stream_rows, batch(ctx).sift);
+        if (!rc && !restart && ctx->stream_archive != 0) rc = stream_archive_allocate(ctx, st, ctx->stream_archive);
         if (rc) { drop_slam_stream(ctx); return rc; }
     }
     rc = slam_stream_clear(ctx, st, resume, K); if (rc) return rc;
@@ -607,8 +727,15 @@ static int slam_stream_run(vo_ctx* ctx, bool restart, int resume, int total_pair
     const int snap_seq = o->snapshot_pair >= 0 ? 0 : -1;
     st.live = false;                                                  // (until the call has come through)
     const int gn = F + (st.carries & 1);
-    const SlamWalk w{restart ? FAM_STREAM_RESTART : FAM_STREAM, resume != 0, F + 2, B, snap_seq, SlamCarry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.b.keep}, false};
+    SlamArchive sa{};
+    if (st.archive.on) {
+        const StreamRows& sr = st.store.d;
+        sa = SlamArchive{st.archive.d, batch(ctx).desc, st.F * st.cap, sr.rows, sr.capacity, sr.row_of, sr.kp_cap, sr.frames};
+    }
+    const SlamWalk w{restart ? FAM_STREAM_RESTART : FAM_STREAM, resume != 0, F + 2, B, snap_seq, SlamCarry{cap, F, st.anchor, gn, 2 * F + 1 - gn, st.b.keep}, false,
+                     st.archive.on ? &sa : nullptr};
     rc = slam_walk(ctx, w, st.dims, st.b, seq, K, o); if (rc) return rc;
+    if (st.archive.on) HIPCHK(hipMemcpyAsync(st.archive.counters, st.archive.d.counters, sizeof(st.archive.counters), hipMemcpyDeviceToHost, ctx->stream));
     if (st.store.on) { rc = stream_rows_append(ctx, st, seq[0].sb.m, resume ? st.done : 0); if (rc) return rc; }
     int32_t alive = 1;
     const SlamOut out{poses_pnp, poses, n_corr, n_inl, status, n_pts, n_obs, n_cam, chi2, ba_iterations_run, ba_trials_run,

@@ -410,6 +410,50 @@ void launch_slam_filter_stream_restart(hipStream_t s, PairBuf pb, const double* 
     hipLaunchKernelGGL(k_slam_filter_stream_restart, dim3(1), dim3(SLAM_THREADS), 0, s, pb, Kd, threshold, cb, sb);
 }
 
+// The archive's part of k_slam_limit_stream_archive (docs/kernels/k_stream_archive.md).  slam_archive_entry: entry e of the archive
+// from what the limit's scan holds for a removed point.  has_row takes the source of the row until slam_archive_rows has copied it:
+// 1 + key — row `key` of the slots' descriptors (the point was born in this call, its frame is in its slot); -1 - r — row r of the
+// descriptor store (a point of an earlier call); 0 — none (the store dropped the point at capacity).
+__device__ __forceinline__ void slam_archive_entry(const SlamArchive& ar, int e, int key, int ff, int fk, const double* X, int frame0, int p)
+{
+    if (e < 0 || e >= ar.a.capacity) return;                   // a full archive: the point is dropped, for good
+    int src = 0;
+    if (ff >= frame0 && key >= 0 && key < ar.n_keys) src = 1 + key;
+    else if (ff >= 0 && ff < ar.frames && fk >= 0 && fk < ar.kp_cap) {
+        const int r = ar.feat_row[(size_t)ff * ar.kp_cap + fk];
+        if (r >= 0 && r < ar.store_cap) src = -1 - r;
+    }
+    ar.a.feature[2 * (size_t)e] = ff; ar.a.feature[2 * (size_t)e + 1] = fk;
+    for (int a = 0; a < 3; a++) ar.a.xyz[3 * (size_t)e + a] = X[a];
+    ar.a.evicted_at[e] = frame0 + p;
+    ar.a.has_row[e] = src;
+}
+
+// ... then, behind a barrier: the rows of the nrem points this limit removed, entries cnt0 .. of the archive as far as it has room,
+// 16 bytes per lane (2 lanes move an ORB row, 8 a SIFT row: k_stream_rows_append's copy); has_row becomes 0 / 1; lane 0 advances
+// the two counters.  Plain vector loads and stores; the one workgroup of the limit, so no other reads or writes the archive.
+__device__ __forceinline__ void slam_archive_rows(const SlamArchive& ar, int cnt0, int nrem)
+{
+    __shared__ int s_src[SLAM_THREADS];
+    const int tid = threadIdx.x, D = ar.a.D, lsh = D == 128 ? 3 : 1;
+    const int n = min(nrem, max(ar.a.capacity - cnt0, 0));
+    for (int e0 = 0; e0 < n; e0 += SLAM_THREADS) {
+        const int e = e0 + tid;
+        int src = 0;
+        if (e < n) { src = ar.a.has_row[cnt0 + e]; ar.a.has_row[cnt0 + e] = src != 0 ? 1 : 0; }
+        s_src[tid] = src;
+        __syncthreads();
+        for (int k = tid; k < (SLAM_THREADS << lsh); k += SLAM_THREADS) {
+            const int i = k >> lsh, part = k & ((1 << lsh) - 1), sr = s_src[i];
+            if (sr == 0) continue;                             // (past n, or no row: the archive's row stays zero)
+            const uint8_t* from = sr > 0 ? ar.desc + (size_t)(sr - 1) * D : ar.store_rows + (size_t)(-1 - sr) * D;
+            *(uint4*)(ar.a.rows + (size_t)(cnt0 + e0 + i) * D + 16 * part) = *(const uint4*)(from + 16 * part);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) { ar.a.counters[0] = cnt0 + n; ar.a.counters[1] += nrem - n; }
+}
+
 // limit_number_of_camera_in_map (map.py:299-318): with more than max_cameras cameras, remove_camera_from_map(cameras[0])
 // (:188-232) with the quirk it has — observations are counted per point AMONG POINTS THAT STILL HAVE ONE (a defaultdict), so a
 // point left with one observation goes and a point with none stays.  A removed point leaves mappointdict: its feature id can
@@ -419,8 +463,11 @@ void launch_slam_filter_stream_restart(hipStream_t s, PairBuf pb, const double* 
 // whose key is none (k_slam_carry) has no entry in pt_of / in_map; pt_feat moves with pt_key.
 // RS (vo_slam_stream_restart): row 0 of a resumed call is the anchor's, never the first camera of a segment that starts at its pair 0;
 // SEG_FIRST names a pair of this call or none (k_slam_carry_restart), so a segment's first camera of an earlier call is a carried one.
-template <bool ST, bool RS = false>
-__device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf cb, SlamBuf sb)
+// AR (vo_set_stream_archive; k_slam_limit_stream_archive alone): every point removed here is appended to the stream's archive, in
+// map order — its feature, the coordinates read here and the pair, then a copy of its descriptor row (slam_archive_rows).  A removed
+// point's rank among the removed is q - at; its entry is count-before + rank, and an entry at or past the capacity is dropped.
+template <bool ST, bool RS = false, bool AR = false>
+__device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf cb, SlamBuf sb, const SlamArchive* ar = nullptr)
 {
     __shared__ int s_w[SLAM_WAVES];
     const int tid = threadIdx.x;
@@ -448,6 +495,8 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
             __syncthreads();
             // the points, in order; tmp becomes old index -> new index (-1: removed)
             int key = 0, ff = 0, fk = 0; double X[3] = {0, 0, 0};
+            int acnt0 = 0;
+            if constexpr (AR) acnt0 = ar->a.counters[0];
             const int npt2 = slam_scan(npt, s_w,
                 [&](int q) {
                     key = sb.m.pt_key[q]; for (int a = 0; a < 3; a++) X[a] = sb.m.pt_xyz[3 * (size_t)q + a];
@@ -456,12 +505,14 @@ __device__ __forceinline__ void slam_limit_wg(int p, int max_cameras, ChainBuf c
                 },
                 [&](int q, int at, int keep) {
                     const bool keyed = !ST || key >= 0;
+                    if constexpr (AR) if (!keep) slam_archive_entry(*ar, acnt0 + (q - at), key, ff, fk, X, sb.st.frame0, p);
                     if (!keep) { sb.tmp[q] = -1; if (keyed) { sb.pt_of[key] = 0; cb.in_map[key] = 0; } return; }
                     sb.tmp[q] = at; if (keyed) sb.pt_of[key] = at + 1; sb.m.pt_key[at] = key;
                     if (ST) { sb.m.pt_feat[2 * (size_t)at] = ff; sb.m.pt_feat[2 * (size_t)at + 1] = fk; }
                     for (int a = 0; a < 3; a++) sb.m.pt_xyz[3 * (size_t)at + a] = X[a];
                 });
             __syncthreads();
+            if constexpr (AR) slam_archive_rows(*ar, acnt0, npt - npt2);
             int ci = 0, pi = 0; double u = 0, v = 0;
             const int nobs2 = slam_scan(nobs, s_w,
                 [&](int i) {
@@ -491,6 +542,17 @@ __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit(int p, int max_came
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<true>(p, max_cameras, cb, sb); }
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream_restart(int p, int max_cameras, ChainBuf cb, SlamBuf sb) { slam_limit_wg<true, true>(p, max_cameras, cb, sb); }
+
+// vo_slam_stream with an archive: k_slam_limit_stream that also appends what it removes
+__global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_stream_archive(int p, int max_cameras, ChainBuf cb, SlamBuf sb, SlamArchive ar)
+{
+    slam_limit_wg<true, false, true>(p, max_cameras, cb, sb, &ar);
+}
+
+void launch_slam_limit_stream_archive(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb, SlamArchive ar)
+{
+    hipLaunchKernelGGL(k_slam_limit_stream_archive, dim3(1), dim3(SLAM_THREADS), 0, s, p, max_cameras, cb, sb, ar);
+}
 
 __global__ __launch_bounds__(SLAM_THREADS) void k_slam_limit_seqs(int j, int max_cameras, const SlamSeq* __restrict__ seqs)
 {

@@ -198,6 +198,14 @@ struct SlamStream {
         StreamRows d{};
         int32_t counters[2] = {0, 0};     // rows stored, points dropped
     } store;
+    // ... and with vo_set_stream_archive on as well: the archive of the points the camera limit removes, a third allocation of the
+    // stream's lifetime (StreamArchive; k_slam_limit_stream_archive appends, stream_archive_kernels.hip selects).  counters as above.
+    struct Archive {
+        DevList mem;
+        bool on = false;
+        StreamArchive d{};
+        int32_t counters[2] = {0, 0};     // entries stored, points dropped
+    } archive;
 };
 
 struct vo_ctx {
@@ -268,6 +276,7 @@ struct vo_ctx {
     int pnp_refine = 1;                   // solvePnPRansac's final pose: 1 = cv2's solvePnP(ITERATIVE) (default), 0 = fast minimiser
     int dk_early = 1;                     // five-point polynomial roots: 1 = noise-floor exit (default), 0 = fixed 300 sweeps
     int slam_stats = 0;                   // 1: every vo_slam_* call also runs k_slam_stats once per step (vo_set_slam_stats); 0 (default): nothing of it
+    int64_t stream_archive = 0;           // vo_set_stream_archive: entries of the archive of evicted points the next vo_slam_stream(resume = 0) starts with; 0 (default): none, -1: one per feature
     int64_t stream_rows = 0;              // vo_set_stream_rows: rows of the descriptor store the next vo_slam_stream(resume = 0) starts with; 0 (default): none, -1: one per feature
     std::vector<uint8_t> undistorted;     // per slot: vo_frames_undistort has rewritten its kp_xy (empty: no slot); cleared by whatever gives the slot new keypoints
 };
@@ -371,3 +380,7 @@ int chain_check(vo_ctx* ctx, int B, const char* who, int* F_out, int* cap_out);
 // comes here; vo_map_from_slam (slam_api.hip) comes here with the map's own lists, vo_map_from_stream with the
 // stream's descriptor store as src and the key list k_stream_rows_select wrote.  Synchronous.
 int map_stage_device(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int npt, const char* who);
+// ... with a second part behind the first: rows n0 .. npt - 1 of the map through k_map_gather_from, src2's row key2[i] and xyz2[i]
+// for map row i (vo_map_from_stream_archive: the archived points behind the live ones).  n0 == npt or src2 == nullptr: no second part.
+struct MapPart2 { const uint8_t* src; const int* key; int n_keys; const double* xyz; };
+int map_stage_device2(vo_ctx* ctx, const uint8_t* src, const int* key, int n_keys, const double* xyz, int n0, const MapPart2& p2, int npt, const char* who);

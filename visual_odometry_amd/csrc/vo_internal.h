@@ -409,6 +409,38 @@ struct StreamRows {
 void launch_stream_rows_append(hipStream_t s, SlamMap m, StreamRows st, size_t pt_bound, const uint8_t* desc, int n_keys, int frame0, int stored0,
                                int dropped0);
 void launch_stream_rows_select(hipStream_t s, SlamMap m, StreamRows st, size_t pt_bound, int first, int end);
+// ---- a stream's archive of evicted points (vo_set_stream_archive, vo_map_from_stream_archive; docs/kernels/k_stream_archive.md):
+// one more allocation beside the store's.  Every point the camera limit removes is appended by k_slam_limit_stream_archive
+// (slam_kernels.hip), in removal order, with a copy of its descriptor row; stream_archive_kernels.hip selects over the entries.
+#define SA_TILE 256                     // entries of a tile of the selection's count and emit passes
+struct StreamArchive {
+    int      D;                         // bytes of a descriptor row: 32 (ORB) or 128 (SIFT)
+    int      capacity;                  // entries the archive holds
+    int*     feature;                   // [capacity][2] the owning feature (frame along the stream, keypoint): pt_feat
+    double*  xyz;                       // [capacity][3] the coordinates the limit read
+    int*     evicted_at;                // [capacity] the pair along the stream whose limit removed the point
+    int*     has_row;                   // [capacity] 1: rows holds the entry's descriptor row; 0: there was none to copy
+    uint8_t* rows;                      // [capacity][D] the archive's own copies: an entry is complete however the flight was chunked
+    int*     counters;                  // [2] entries stored, points dropped because the archive was full
+    int*     tile_cnt;                  // [ceil(capacity / SA_TILE)][2] the count pass: per tile, entries selected with a row / without
+    int      sel_cap;                   // entries sel_key / sel_xyz hold: the bound of a staged map
+    int*     sel_key;                   // [sel_cap] indexed by staged position: the archive entry of an archived point
+    double*  sel_xyz;                   // [sel_cap][3] ... and its coordinates
+    int*     sel_cnt;                   // [2] entries selected with a row (may pass what fits: nothing is written past sel_cap), without
+};
+// What the limit of a stream with an archive needs beside its own arguments: where the rows come from.  An argument of its own;
+// SlamBuf is as it was.
+struct SlamArchive {
+    StreamArchive a;
+    const uint8_t* desc; int n_keys;    // the slots' descriptor rows [n_keys][D]: the row of a point born in this call, by pt_key
+    const uint8_t* store_rows; int store_cap;   // the descriptor store's rows [store_cap][D] ...
+    const int* feat_row;                // ... and its table [frames][kp_cap] of the store row of a feature, -1: none
+    int      kp_cap, frames;
+};
+void launch_slam_limit_stream_archive(hipStream_t s, int p, int max_cameras, ChainBuf cb, SlamBuf sb, SlamArchive ar);
+// the entries [0, stored) owned by frames [first, end): counts per tile, then the entries that have a row to a.sel_key / a.sel_xyz in
+// archive order, the first at staged position *live (device; nullptr: 0); a.sel_cnt <- {with a row, without}
+void launch_stream_archive_select(hipStream_t s, StreamArchive a, int stored, int first, int end, const int* live);
 // ---- ... on a stream that starts a new map after a lost frame (vo_slam_stream_restart): cb.rs is set, its state words and the
 // alive flag outlive the call.  k_slam_restart_stream goes between k_chain_pose and k_chain_triangulate of every step.
 void launch_slam_restart_stream(hipStream_t s, PairBuf pb, int kp_cap, int p, ChainBuf cb, SlamBuf sb);
@@ -501,6 +533,8 @@ struct RelocBuf {
 // rows of a map from the slots' descriptors (src [slot][kp_cap][D], key = slot kp_cap + keypoint, n_keys = rows src holds) or, with
 // key == nullptr, from src [npt][D] as it stands: both through the one store
 void launch_map_gather(hipStream_t s, MapBuf m, const uint8_t* src, const int* key, int n_keys, const double* xyz);
+// ... rows id0 .. m.npt - 1 of the map only, key and xyz indexed by the map row (a part staged behind another: vo_map_from_stream_archive)
+void launch_map_gather_from(hipStream_t s, MapBuf m, int id0, const uint8_t* src, const int* key, int n_keys, const double* xyz);
 void launch_nn_map(hipStream_t s, MapBuf m, RelocBuf r, int Q, const uint8_t* desc, const uint8_t* desc_x, const int* norms, const int* kp_count,
                    int kp_cap, int cap_x, int mode);
 // mode, ratio: vo_set_map_match (0 cross-check, 1 ratio, 2 both)

@@ -588,6 +588,59 @@ class FrontEnd:
         c.check(rc)
         return dict(n=n.value, without_row=w.value)
 
+    def stream_archive(self, capacity=-1):
+        """Give the next slam_stream an archive of evicted points (vo_set_stream_archive; off by default): every point the camera
+        limit removes is then kept on the device in removal order — its coordinates as the map held them, its owning feature, a
+        copy of its descriptor row and the pair at which it went — and map_from_stream_archive() stages those points long after
+        max_cameras has taken their cameras.  capacity: entries — -1 one per feature the stream can hold, which never drops a
+        point; 0 switches the archive off.  Memory: capacity * (D + 40) bytes (D = 32 ORB, 128 SIFT) plus 8 bytes per 256 entries.
+        Needs stream_rows() on as well (the rows of earlier calls' points come from the store): slam_stream(resume=False) raises
+        VoError otherwise.  Takes effect at the next slam_stream(resume=False); a live stream keeps the setting it started with.
+        slam_stream_restart, slam_streams and the chains ignore it.  The stream's own outputs, its map and its store do not change."""
+        c = self.ctx
+        c.check(c.lib.vo_set_stream_archive(c.handle, int(capacity)))
+
+    def stream_archive_info(self):
+        """The live slam_stream's archive (vo_stream_archive_info): dict(capacity, stored — entries so far —, dropped — removed
+        points that found the archive full, for good).  VoError without such a stream."""
+        c = self.ctx
+        v = [C.c_int64(0) for _ in range(3)]
+        c.check(c.lib.vo_stream_archive_info(c.handle, *[C.addressof(x) for x in v]))
+        return dict(capacity=v[0].value, stored=v[1].value, dropped=v[2].value)
+
+    def stream_archive_points(self, first=0, n=None):
+        """Entries first .. first + n - 1 of the live slam_stream's archive, in removal order (vo_stream_archive_read; n=None: all
+        from `first`): dict(feature [n, 2] int32 — frame along the stream, keypoint —, xyz [n, 3] float64, evicted_at [n] int32,
+        has_row [n] bool, rows [n, D] uint8 — zeros where has_row is False).  What to save, and what stage_map takes later."""
+        first = int(first)
+        if n is None:
+            n = max(self.stream_archive_info()["stored"] - first, 0)
+        n = int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        out = dict(feature=np.zeros((n, 2), np.int32), xyz=np.zeros((n, 3)), evicted_at=np.zeros(n, np.int32), has_row=np.zeros(n, np.int32),
+                   rows=np.zeros((n, self._map_row_width()), np.uint8))
+        c = self.ctx
+        c.check(c.lib.vo_stream_archive_read(c.handle, first, n, *[out[k].ctypes.data for k in ("feature", "xyz", "evicted_at", "has_row", "rows")]))
+        out["has_row"] = out["has_row"] != 0
+        return out
+
+    def map_from_stream_archive(self, first=0, end=None, live=True):
+        """map_from_stream() with the archived points (vo_map_from_stream_archive): the points the camera limit has removed whose
+        owning frame lies in [first, end), in removal order, behind the live points of the window (live=True: exactly what
+        map_from_stream(first, end) stages, first, so that a live point wins the cross-check's lowest-index tie on a duplicated row)
+        or alone (live=False).  Entries without a row are left out.  Returns dict(n=points staged, n_archived=archived ones among
+        them, without_row=points of the window left out).  More than 65536 points: NotImplementedError — stage a window.  The
+        stream and its archive are left as they were.  VoError on a stream started without stream_archive()."""
+        c = self.ctx
+        n, a, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rc = c.lib.vo_map_from_stream_archive(c.handle, int(first), -1 if end is None else int(end), 1 if live else 0, C.addressof(n), C.addressof(a),
+                                              C.addressof(w))
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        return dict(n=n.value, n_archived=a.value, without_row=w.value)
+
     def map_rows(self):
         """The staged map back (vo_map_rows): (rows [npt, D] uint8, points [npt, 3] float64) — what to save before a segment's
         frames leave their slots, and what stage_map takes later."""
