@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A loop closed against the map a stream built: a flight that goes out and comes back, streamed in chunks with slot reuse.
 
-    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--max-cameras 18] [--width 640] [--height 480] [--nfeatures 1000] [--ratio R]
+    python examples/loop_flight.py [--out 8] [--chunk 4] [--window 1] [--max-cameras 18] [--width 640] [--height 480] [--nfeatures 1000] [--ratio R] [--guided R]
 
 The flight is synthetic and uses no files: frames 0 .. n of synth.sequence, then n - 1 .. 0 again, so the last frames see the ground
 of the first.  It is walked by slam_stream in chunks of --chunk pairs on a FrontEnd with only chunk + 2 frame slots: every chunk's
@@ -17,6 +17,9 @@ among them by its descriptors alone.  Printed: that pose against the pose the
 stream itself gave `new` through its chain of pairs (--ratio R: matched by Lowe's ratio rule, knnMatch(k=2) and
 `m.distance < R * n.distance`, instead of the cross-check); the difference is the drift the flight accumulated between the two visits.
 The loop_edge the pose graph would take for (old, new) is built from the two (optimize_pose_graph, examples/close_loop.py).
+--guided R: before the edge is built, the wider window old - 3 w - 2 .. old + 3 w + 2 is staged and relocalize_guided matches its
+points by projection under the pose just found, within R pixels of each projection; matches and inliers before and after are printed,
+and the edge is built from the refined pose.
 
 The stream's map is its LIVE map: a point the camera limit has removed (--max-cameras, the reference's 18 by default) is gone from
 it.  With the default flight of 17 frames nothing is evicted; fly further out (--out 20) or lower --max-cameras (--max-cameras 4) and
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--nfeatures", type=int, default=1000)
     ap.add_argument("--words", type=int, default=256)
     ap.add_argument("--ratio", type=float, default=None, help="relocalize by the ratio rule with this ratio instead of the cross-check")
+    ap.add_argument("--guided", type=float, default=None, metavar="R",
+                    help="refine the pose by projection matching within R pixels against a wider window of the map")
     a = ap.parse_args()
     from visual_odometry_amd import frontend as F
     from visual_odometry_amd import synth
@@ -97,10 +102,23 @@ def main():
         print(f"relocalize: status {int(r['status'][0])} with {int(r['n_match'][0])} matches")
         return
     P, Q = r["poses"][0], poses[new]                                      # by the old frames' points; by the stream's own chain
+    print(f"relocalize: {int(r['n_match'][0])} matches, {int(r['n_inl'][0])} inliers")
+    if a.guided is not None:
+        wide = (max(old - 3 * a.window - 2, 0), old + 3 * a.window + 3)
+        staged = fe.map_from_stream_archive(*wide)
+        g = fe.relocalize_guided([slot_of[new]], K, r["poses"], a.guided)
+        print(f"guided, {a.guided:g} px under that pose against map_from_stream_archive{wide} ({staged['n']} points, {int(g['n_seen'][0])} with a keypoint "
+              f"in their window): {int(g['n_match'][0])} matches, {int(g['n_inl'][0])} inliers (before: {int(r['n_match'][0])}, {int(r['n_inl'][0])})")
+        if g["status"][0] != 0:
+            print(f"guided: status {int(g['status'][0])}: the descriptor-only pose is kept")
+        elif g["n_inl"][0] <= r["n_inl"][0]:
+            print("guided: no more inliers than before (the wider window adds few points this frame sees, or the radius is too small "
+                  "for the pose's error): the descriptor-only pose is kept")
+        else:
+            P = g["poses"][0]
     dR = np.degrees(np.arccos(np.clip((np.trace(P[:, :3] @ Q[:, :3].T) - 1) / 2, -1, 1)))
     cP, cQ = -P[:, :3].T @ P[:, 3], -Q[:, :3].T @ Q[:, 3]
     base = np.linalg.norm(-poses[1][:, :3].T @ poses[1][:, 3])            # the gauge's unit: the first pair's baseline
-    print(f"relocalize: {int(r['n_match'][0])} matches, {int(r['n_inl'][0])} inliers")
     print(f"frame {new} by the map around frame {old} against the stream's own pose: rotation {dR:.4f} deg, camera centre "
           f"{np.linalg.norm(cP - cQ):.5f} ({np.linalg.norm(cP - cQ) / max(base, 1e-12):.4f} baselines): the drift between the two visits")
     V = F.track_vertices(poses)

@@ -1020,7 +1020,8 @@ int vo_slam_stats(vo_ctx* ctx, int seq, int B, int C, double* total_sqerr /*[B]*
  *   chain's maps and a live stream alone.  A new vo_map_stage / vo_map_from_slam replaces the map (also when it fails).
  * Out of scope: automatic use inside the walks, a descriptor store for restart streams and multi-streams (vo_slam_stream_restart,
  * vo_slam_streams) and the archive of earlier segments they would need, staging a window of more than 65536 points, knnMatch with
- * k > 2 against the map.  (The similarity that joins two segments' gauges: map alignment, below.) */
+ * k > 2 against the map.  (The similarity that joins two segments' gauges: map alignment, below.  Matching by projection under a
+ * prior pose: guided relocalisation, below; vo_map_matches and vo_map_match_seconds(0, ...) serve the latest call of either kind.) */
 typedef struct {
     double   max_distance;      /* 0: no filter */
     int32_t  pnp_iterations;    /* 100 */
@@ -1046,6 +1047,60 @@ int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9],
 int vo_map_matches(vo_ctx* ctx, int q, int32_t* pt_idx, int32_t* kp_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
 int vo_set_map_match(vo_ctx* ctx, int mode /*0 cross-check, 1 ratio, 2 both*/, double ratio);
 int vo_map_match_seconds(vo_ctx* ctx, int which /*0 localize, 1 align*/, int q, float* dist2, int cap, int32_t* n_out);
+
+/* ------------------------------------------------------------------ guided relocalisation: map points matched by projection
+ * vo_map_localize compares every keypoint with every staged point: right when nothing is known about the frame's pose.  A caller
+ * that holds a prior — a stream's drifted pose, the pose of a frame just relocalised from a few dozen inliers, the pose of the frame
+ * before — projects the map with it and looks only at the keypoints in a window around each projection (ORB-SLAM's
+ * SearchByProjection): look-alike descriptors elsewhere in the image cannot win, and the work per query drops from
+ * npt x n_keypoints distances to a handful per point.  The reference has no counterpart; the rules are this library's own.
+ * The frame is slot slots[q]: nq = min(kp_count, kp_cap) keypoints, keypoint i at (x_i, y_i) in float32 with one descriptor row;
+ * the staged map has npt points X_j = (X, Y, Z) in float64 with one row each; P = prior[q], row-major 3 x 4.  Every operation below
+ * is one float64 rounding, in the order written (the library is built with -ffp-contract=off).
+ *   1 projection.  c_k = ((P[k][0] X + P[k][1] Y) + P[k][2] Z) + P[k][3], k = 0, 1, 2.  Point j takes part iff c_2 > 0 (strict; a
+ *     NaN fails it).  xn = c_0 / c_2, yn = c_1 / c_2; u = (K[0] xn + K[1] yn) + K[2], v = (K[3] xn + K[4] yn) + K[5]: K's third row
+ *     is not read.  There is no image-bounds test (vo_frames_undistort moves keypoints outside the image, and a batch configured
+ *     for 32 x 32 may carry keypoints from anywhere).
+ *   2 window.  Keypoint i is a candidate of point j iff dx dx + dy dy <= r2, dx = (double)x_i - u, dy = (double)y_i - v,
+ *     r2 = radius radius computed once.  A u or v that is infinite or NaN has no candidate under this rule.
+ *   3 distance.  d(i, j), the exact integer: Hamming for ORB rows, sum (a - b)^2 over the 128 uint8 values for SIFT rows (the rows as
+ *     vo_stage_sift_rows / the detector store them, and as vo_map_rows returns the map's).  Reported as cv2 reports it, float32:
+ *     fd = (float)d for ORB rows, sqrtf((float)d) for SIFT rows.
+ *   4 per point.  best(j) = the candidate with the smallest (d, i), lexicographically: the lowest keypoint wins a tie.  d2(j) = the
+ *     second-smallest d among the candidates as a multiset (a tie with the best counts as a second); fewer than two candidates:
+ *     fd2 = FLT_MAX.  n_seen[q] = the points with at least one candidate.
+ *   5 filters, per point, conjunctive.  opts->max_distance > 0: (double)fd < max_distance, strictly.  g->ratio > 0: the point is
+ *     kept iff it has fewer than two candidates or (double)fd < ratio * (double)fd2 (vo_set_map_match mode 1's expression).
+ *   6 one point per keypoint.  Among the points that pass step 5 and whose best is keypoint i, the one with the smallest (d, j)
+ *     keeps it.  The filters come first: a point that fails them blocks nobody.
+ *   7 the match list, in ascending keypoint order: (keypoint i, point j, fd, fd2), obj = X_j, img = (double)(x_i, y_i); at most nq
+ *     entries.
+ *   8 the pose: from here on exactly vo_map_localize's step 3 on those arrays — k_pnp_ransac unchanged, the same seed,
+ *     pnp_iterations, reproj_err, confidence, min_inliers and vo_set_pnp_refine mode, the same statuses and zeroed poses.
+ * vo_set_map_match is not read: the window rule has its own two options.  The result does not depend on scheduling: two calls on
+ * the same input return the same bytes.
+ * prior == NULL, the refinement pass: the priors are the poses of the most recent vo_map_localize on this staged map, taken from
+ *   the device buffer (nothing returns to the host between the descriptor-only pose and the guided one) and copied aside before
+ *   any work buffer is overwritten.  That call must have succeeded with the same Q and the same slots, and no vo_map_localize_guided
+ *   may have run since (it overwrites those poses): otherwise VO_ERR_INVALID.  A query whose status there was not VO_OK is not
+ *   matched: it keeps that status, with n_match = n_inl = n_seen = 0 and a zero pose.
+ * After the call vo_map_matches serves the most recent of vo_map_localize and vo_map_localize_guided, and
+ *   vo_map_match_seconds(0, q, ...) is valid after a guided call whatever `ratio` was.  A later vo_map_localize returns the bytes it
+ *   returns without this section.  The staged map, the pair results, the chains' maps and a live stream are left alone.
+ * VO_ERR_INVALID, the whole call failing and nothing written: what vo_map_localize refuses; g == NULL; a radius that is negative or
+ *   not finite; a ratio that is negative or not finite; a non-finite entry in a given prior; the prior == NULL conditions above.
+ *   A slot flagged for its descriptor norm (SIFT): VO_ERR_INVALID AFTER the run, as vo_map_localize reports it.
+ * Profiling stages: match_nn (k_guided_grid, k_guided_match), match_select (k_guided_select), misc (k_pnp_ransac and the poses).
+ * Out of scope: use inside the walks, octave and scale prediction, viewing-angle tests, more than one point per keypoint. */
+typedef struct {
+    double radius;              /* pixels, finite, >= 0 */
+    double ratio;               /* 0: no ratio rule; else finite and > 0 */
+} vo_guided_opts;
+int vo_map_localize_guided(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9],
+                           const double* prior /*[Q][12] world -> camera in the map's gauge, or NULL*/,
+                           const vo_guided_opts* g, const vo_reloc_opts* opts,
+                           double* poses /*[Q][12]*/, int32_t* n_match, int32_t* n_inl, int32_t* status,
+                           int32_t* n_seen /*[Q], may be NULL*/);
 
 /* ------------------------------------------------------------------ map alignment: the similarity that joins two maps, by descriptors
  * After a lost frame the restart walks start a new map, and every segment is a trajectory in a gauge of its own: its origin is its

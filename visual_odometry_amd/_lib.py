@@ -64,6 +64,10 @@ class RelocOpts(C.Structure):
                 ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
 
 
+class GuidedOpts(C.Structure):
+    _fields_ = [("radius", C.c_double), ("ratio", C.c_double)]
+
+
 class AlignOpts(C.Structure):
     _fields_ = [("max_distance", C.c_double), ("max_error", C.c_double), ("iterations", C.c_int32), ("confidence", C.c_double),
                 ("seed", C.c_uint64), ("min_inliers", C.c_int32)]
@@ -153,6 +157,7 @@ _SIGS = {
     "vo_map_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
     "vo_set_map_match": (C.c_int, [_P, C.c_int, C.c_double]),
     "vo_map_match_seconds": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "vo_map_localize_guided": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_sim3_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
@@ -334,6 +339,24 @@ class Context:
         if match not in MAP_MATCH_MODES:
             raise ValueError("match must be 'cross', 'ratio' or 'cross+ratio'")
         self.check(self.lib.vo_set_map_match(self.handle, MAP_MATCH_MODES[match], float(ratio)))
+
+    def map_localize_guided(self, slots, K, prior, radius, ratio, opts):
+        """vo_map_localize_guided on host arrays: slots [Q] int32, K [3, 3], prior [Q, 3, 4] float64 or None (the refinement pass),
+        opts a RelocOpts -> (poses [Q, 3, 4], n_match, n_inl, status, n_seen [Q] int32)."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        Q = len(sl)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
+        pr = None
+        if prior is not None:
+            pr = np.ascontiguousarray(prior, dtype=np.float64).reshape(-1)
+            if len(pr) != 12 * Q:
+                raise ValueError("prior must be [Q, 3, 4]")
+        g = GuidedOpts(float(radius), float(ratio))
+        poses = np.zeros((Q, 12))
+        nm, ni, st, ns = (np.zeros(Q, np.int32) for _ in range(4))
+        self.check(self.lib.vo_map_localize_guided(self.handle, sl.ctypes.data, Q, K.ctypes.data, ptr(pr), C.addressof(g), C.addressof(opts),
+                                                   poses.ctypes.data, nm.ctypes.data, ni.ctypes.data, st.ctypes.data, ns.ctypes.data))
+        return poses.reshape(Q, 3, 4), nm, ni, st, ns
 
     def last_error(self) -> str:
         msg = self.lib.vo_last_error(self.handle)

@@ -1,5 +1,6 @@
 // reloc_api.hip — the vo_map_* entry points of libvo_hip.so: a frame placed in a map by its descriptors (include/vo_hip.h,
-// "relocalisation").  Host code only; the kernels are reloc_kernels.hip and, unchanged, k_pnp_ransac (pnp_kernels.hip).
+// "relocalisation", "guided relocalisation").  Host code only; the kernels are reloc_kernels.hip, guided_kernels.hip and, unchanged,
+// k_pnp_ransac (pnp_kernels.hip).
 // vo_map_from_slam is in slam_api.hip, beside the maps it reads; it stages through map_stage_device like vo_map_stage.
 #include "vo_host.h"
 
@@ -28,6 +29,10 @@ static int map_reserve(vo_ctx* ctx, const Batch& b, int npt)
     HIPCHK(mem.alloc(&r.obj, Q * C * 3)); HIPCHK(mem.alloc(&r.img, Q * C * 2)); HIPCHK(mem.alloc(&r.off, 2 * Q));
     HIPCHK(mem.alloc(&r.rvec, 3 * Q)); HIPCHK(mem.alloc(&r.tvec, 3 * Q)); HIPCHK(mem.alloc(&r.mask, Q * C));
     HIPCHK(mem.alloc(&r.ninl, Q)); HIPCHK(mem.alloc(&r.status, Q)); HIPCHK(mem.alloc(&r.poses, 12 * Q)); HIPCHK(mem.alloc(&M.dK, 9));
+    GuidedBuf& g = M.g;                                     // vo_map_localize_guided's: the keypoint grid, the claim table, the priors
+    HIPCHK(mem.alloc(&g.cell_off, Q * (GUIDED_CELLS + 1))); HIPCHK(mem.alloc(&g.cell_kp, Q * C)); HIPCHK(mem.alloc(&g.box, 4 * Q));
+    HIPCHK(mem.alloc(&g.claim, Q * C)); HIPCHK(mem.alloc(&g.pt_d2, Q * R)); HIPCHK(mem.alloc(&g.prior, 12 * Q));
+    HIPCHK(mem.alloc(&g.skip, Q)); HIPCHK(mem.alloc(&g.n_seen, Q));
     m.D = D; m.cap_rows = rows; m.npt = 0;
     M.Q_cap = b.max_pairs; M.kp_cap = b.kp_cap;
     return VO_OK;
@@ -48,7 +53,7 @@ int map_stage_device2(vo_ctx* ctx, const uint8_t* src, const int* key, int n_key
     int rc = map_reserve(ctx, b, npt); if (rc) return rc;
     MapState& M = ctx->map;
     hipStream_t s = ctx->stream;
-    M.staged = false; M.last_Q = 0; M.al.last_Q = 0;
+    M.staged = false; M.last_Q = 0; M.al.last_Q = 0; M.loc_ok = false;
     M.m.npt = npt;
     HIPCHK(hipMemsetAsync(M.m.flag, 0, sizeof(int), s));
     MapBuf head = M.m; head.npt = n0;                       // (the whole map without a second part: the launch it always was)
@@ -111,7 +116,7 @@ extern "C" int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const d
     if (Q < 0 || Q > b.max_pairs || Q > M.Q_cap) FAIL(VO_ERR_INVALID, "vo_map_localize: 0 <= Q <= max_pairs queries, got %d", Q);
     if (!K || !o || (Q > 0 && (!slots || !poses || !n_match || !n_inl || !status))) FAIL(VO_ERR_INVALID, "bad arguments");
     for (int q = 0; q < Q; q++) if (slots[q] < 0 || slots[q] >= b.max_frames) FAIL(VO_ERR_INVALID, "vo_map_localize: slot %d out of range", slots[q]);
-    M.last_Q = 0;
+    M.last_Q = 0; M.loc_ok = false;
     if (Q == 0) return VO_OK;
     HIPCHK(hipSetDevice(ctx->device));
     int rc = ensure_rng(ctx, o->seed); if (rc) return rc;
@@ -139,6 +144,80 @@ extern "C" int vo_map_localize(vo_ctx* ctx, const int32_t* slots, int Q, const d
     if (ctx->prof) prof_collect(ctx);
     M.last_Q = Q; M.last_mode = mode;
     if (b.sift) {                                           // a flagged slot, reported after the run as vo_pairs_run reports it
+        std::vector<int> fl((size_t)b.max_frames);
+        HIPCHK(hipMemcpy(fl.data(), b.flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int q = 0; q < Q; q++)
+            if (fl[(size_t)slots[q]] & 2) FAIL(VO_ERR_INVALID, "a SIFT descriptor row broke the norm bound of the integer matcher (slot %d)", (int)slots[q]);
+    }
+    M.loc_slots.assign(slots, slots + Q); M.loc_ok = true;  // what a refinement pass (vo_map_localize_guided, prior == NULL) starts from
+    return VO_OK;
+}
+
+// Matching by projection under a prior pose (include/vo_hip.h, "guided relocalisation"): k_guided_grid, k_guided_match and
+// k_guided_select (guided_kernels.hip) in the place of k_nn_map and k_map_select; from the match list on it is vo_map_localize.
+extern "C" int vo_map_localize_guided(vo_ctx* ctx, const int32_t* slots, int Q, const double K[9], const double* prior, const vo_guided_opts* gopt,
+                                      const vo_reloc_opts* o, double* poses, int32_t* n_match, int32_t* n_inl, int32_t* status, int32_t* n_seen)
+{
+    if (!ctx) return VO_ERR_INVALID;
+    const Batch b = batch(ctx);
+    if (!b.ready) FAIL(VO_ERR_NOT_CONFIGURED, "vo_map_localize_guided: vo_batch_configure[_sift] has not been called");
+    MapState& M = ctx->map;
+    if (!M.staged) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: no map is staged (vo_map_stage, vo_map_from_slam)");
+    if (Q < 0 || Q > b.max_pairs || Q > M.Q_cap) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: 0 <= Q <= max_pairs queries, got %d", Q);
+    if (!K || !o || !gopt || (Q > 0 && (!slots || !poses || !n_match || !n_inl || !status))) FAIL(VO_ERR_INVALID, "bad arguments");
+    if (!std::isfinite(gopt->radius) || gopt->radius < 0) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: the radius must be finite and >= 0");
+    if (!std::isfinite(gopt->ratio) || gopt->ratio < 0) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: the ratio must be 0 (no rule) or finite and > 0");
+    for (int q = 0; q < Q; q++) if (slots[q] < 0 || slots[q] >= b.max_frames) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: slot %d out of range", slots[q]);
+    if (prior) {
+        for (size_t k = 0; k < (size_t)Q * 12; k++)
+            if (!std::isfinite(prior[k])) FAIL(VO_ERR_INVALID, "vo_map_localize_guided: prior %d has an entry that is not finite", (int)(k / 12));
+    } else if (!M.loc_ok || (int)M.loc_slots.size() != Q || !std::equal(M.loc_slots.begin(), M.loc_slots.end(), slots))
+        FAIL(VO_ERR_INVALID, "vo_map_localize_guided: prior == NULL needs the most recent call on this staged map to be a vo_map_localize of the same slots");
+    if (Q == 0) { M.last_Q = 0; M.loc_ok = false; return VO_OK; }
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc = ensure_rng(ctx, o->seed); if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const RelocBuf& r = M.r;
+    const GuidedBuf& g = M.g;
+    const int cap = b.kp_cap;
+    M.last_Q = 0; M.loc_ok = false;
+    // the priors first: a refinement pass takes them from the buffers this call goes on to overwrite
+    if (prior) {
+        HIPCHK(hipMemcpyAsync(g.prior, prior, (size_t)Q * 96, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(g.skip, 0, (size_t)Q * sizeof(int), s));
+    } else {
+        HIPCHK(hipMemcpyAsync(g.prior, r.poses, (size_t)Q * 96, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(g.skip, r.status, (size_t)Q * sizeof(int), hipMemcpyDeviceToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(r.slots, slots, (size_t)Q * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(M.dK, K, 72, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(r.rvec, 0, (size_t)Q * 24, s)); HIPCHK(hipMemsetAsync(r.tvec, 0, (size_t)Q * 24, s));
+    HIPCHK(hipMemsetAsync(g.claim, 0xff, (size_t)Q * cap * sizeof(unsigned long long), s));
+    HIPCHK(hipMemsetAsync(g.n_seen, 0, (size_t)Q * sizeof(int), s));
+    {
+        StageTimer t(ctx, ST_MATCH_NN);
+        launch_guided_match(s, M.m, r, g, Q, b.desc, b.kp_xy, b.kp_count, cap, M.dK, gopt->radius, o->max_distance, gopt->ratio);
+    }
+    { StageTimer t(ctx, ST_MATCH_SELECT); launch_guided_select(s, M.m, r, g, Q, b.kp_xy, b.kp_count, cap); }
+    {
+        StageTimer t(ctx, ST_MISC);
+        launch_pnp_ransac(s, r.obj, r.img, r.off, Q, M.dK, o->pnp_iterations, o->reproj_err, o->confidence, o->seed, ctx->rng_tab, RNG_TAB_N,
+                          ctx->pnp_refine, r.rvec, r.tvec, r.mask, r.ninl, r.status, 2);
+        launch_pnp_poses(s, r.rvec, r.tvec, r.ninl, r.status, Q, o->min_inliers, r.poses);
+        launch_guided_keep(s, r, g, Q);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> seen((size_t)Q);                   // (the caller's n_seen may be NULL)
+    HIPCHK(hipMemcpyAsync(poses, r.poses, (size_t)Q * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_match, r.m_count, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_inl, r.ninl, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, r.status, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(seen.data(), g.n_seen, (size_t)Q * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n_seen) std::copy(seen.begin(), seen.end(), n_seen);
+    if (ctx->prof) prof_collect(ctx);
+    M.last_Q = Q; M.last_mode = 1;                          // every guided list carries its second distances (vo_map_match_seconds)
+    if (b.sift) {
         std::vector<int> fl((size_t)b.max_frames);
         HIPCHK(hipMemcpy(fl.data(), b.flags, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int q = 0; q < Q; q++)

@@ -125,6 +125,9 @@ struct MapState {
     int Q_cap = 0, kp_cap = 0;            // what the work buffers were sized for
     int last_Q = 0;                       // queries of the most recent vo_map_localize (vo_map_matches); 0: none since the map was staged
     int last_mode = 0;                    // ... and the vo_set_map_match mode it ran in (vo_map_match_seconds)
+    GuidedBuf g{};                        // vo_map_localize_guided's work buffers, allocated with the others
+    bool loc_ok = false;                  // r.poses / r.status hold a vo_map_localize of this map over loc_slots (the priors of a refinement pass)
+    std::vector<int32_t> loc_slots;
     // vo_map_align's query maps and work buffers: a second allocation, made by the first call that needs it and kept while the next
     // one fits; it ends with the staged map (drop_map), and a newly staged map forgets its queries
     struct Align {

@@ -542,6 +542,26 @@ void launch_map_select(hipStream_t s, MapBuf m, RelocBuf r, int Q, const float* 
                        int mode, double ratio);
 // [Rodrigues(rvec) | tvec] of B solved problems, zeros for the others; a model with fewer than min_inliers inliers becomes VO_ERR_NO_MODEL
 void launch_pnp_poses(hipStream_t s, const double* rvec, const double* tvec, const int* ninl, int* status, int B, int min_inliers, double* poses);
+// ---- guided relocalisation: the staged map's points matched by projection under a prior pose (guided_kernels.hip): vo_map_localize_guided
+#define GUIDED_G 64                     // the keypoint grid is GUIDED_G x GUIDED_G square cells over the keypoints' own box
+#define GUIDED_CELLS (GUIDED_G * GUIDED_G)
+#define GUIDED_TILE 256                 // points per workgroup of k_guided_match, one lane each
+struct GuidedBuf {
+    int*     cell_off;                  // [Q][GUIDED_CELLS + 1] where a cell's keypoints start in cell_kp (row-major cells: cy GUIDED_G + cx)
+    int*     cell_kp;                   // [Q][kp_cap] the query's keypoints in cell order
+    double*  box;                       // [Q][4] x0, y0, 1 / cell edge, cell edge
+    unsigned long long* claim;          // [Q][kp_cap] (d << 32) | point of the point that keeps the keypoint; all ones: nobody
+    int*     pt_d2;                     // [Q][cap_rows] a claiming point's second distance (INT_MAX: fewer than two candidates)
+    double*  prior;                     // [Q][12]
+    int*     skip;                      // [Q] not VO_OK: the query is not matched and keeps this status (the refinement pass)
+    int*     n_seen;                    // [Q]
+};
+// k_guided_grid + k_guided_match, then k_guided_select: RelocBuf's match list, correspondences and offsets as launch_map_select leaves them
+void launch_guided_match(hipStream_t s, MapBuf m, RelocBuf r, GuidedBuf g, int Q, const uint8_t* desc, const float* kp_xy, const int* kp_count,
+                         int kp_cap, const double* Kd, double radius, double max_distance, double ratio);
+void launch_guided_select(hipStream_t s, MapBuf m, RelocBuf r, GuidedBuf g, int Q, const float* kp_xy, const int* kp_count, int kp_cap);
+// after launch_pnp_poses: a skipped query takes its earlier status back, with no inliers and a zero pose
+void launch_guided_keep(hipStream_t s, RelocBuf r, GuidedBuf g, int Q);
 // ---- map alignment: Q query maps against the staged one (reloc_kernels.hip): vo_map_align, vo_sim3_ransac_batch
 struct AlignBuf {
     int      Q, D, total;               // query maps, bytes of a row, rows of all of them

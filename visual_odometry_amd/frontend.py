@@ -652,13 +652,16 @@ class FrontEnd:
         return rows, pts
 
     def relocalize(self, slots, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0,
-                   match="cross", ratio=0.75):
+                   match="cross", ratio=0.75, refine_radius=None):
         """Place detected slots in the staged map by their descriptors (vo_map_localize), all in one call on the device:
         bf.match(frame, map) with crossCheck=True -> `distance < max_distance` (0: no filter) -> cv2.solvePnPRansac on the 3D-2D
         matches.  match='ratio': knnMatch(frame, map, k=2) and `m.distance < ratio * n.distance` (src/feature_detection.py:20-26) in
         the place of the cross-check — no reverse direction is computed, several keypoints may keep one map point;
         match='cross+ratio': both.  The call sets the context's vo_set_map_match to what it is given.  Returns dict(poses [Q, 3, 4] world -> camera in the map's gauge, zeros where status != 0; n_match, n_inl,
-        status [Q]: 0, VO_ERR_TOO_FEW (fewer than 4 matches) or VO_ERR_NO_MODEL (no model, or fewer than min_inliers inliers))."""
+        status [Q]: 0, VO_ERR_TOO_FEW (fewer than 4 matches) or VO_ERR_NO_MODEL (no model, or fewer than min_inliers inliers)).
+        refine_radius=R (pixels): the refinement pass on top — relocalize_guided(prior=None, radius=R) with the same options and no
+        ratio rule, started from these poses on the device; the result is that call's (n_seen included), with this pass's counts
+        as first_n_match and first_n_inl.  None (default): no such pass."""
         sl = np.ascontiguousarray(slots, dtype=np.int32).ravel()
         Q = len(sl)
         K = np.ascontiguousarray(K, dtype=np.float64).reshape(3, 3)
@@ -668,7 +671,26 @@ class FrontEnd:
         c.set_map_match(match, ratio)
         c.check(c.lib.vo_map_localize(c.handle, sl.ctypes.data, Q, K.ctypes.data, C.addressof(opts), poses.ctypes.data, nm.ctypes.data,
                                       ni.ctypes.data, st.ctypes.data))
-        return dict(poses=poses.reshape(Q, 3, 4), n_match=nm, n_inl=ni, status=st)
+        if refine_radius is None:
+            return dict(poses=poses.reshape(Q, 3, 4), n_match=nm, n_inl=ni, status=st)
+        out = self.relocalize_guided(sl, K, None, refine_radius, 0.0, max_distance, iterations, reproj_err, confidence, seed, min_inliers)
+        out.update(first_n_match=nm, first_n_inl=ni)
+        return out
+
+    def relocalize_guided(self, slots, K, prior, radius, ratio=0.0, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99,
+                          seed=OPENCV_RNG_SEED, min_inliers=0):
+        """Place detected slots in the staged map by projection under a prior pose (vo_map_localize_guided; ORB-SLAM's
+        SearchByProjection), all in one call on the device: every map point in front of the camera prior[q] ([Q, 3, 4] world ->
+        camera in the map's gauge) is projected with K, takes the keypoint with the nearest descriptor among those within `radius`
+        pixels of its projection (ratio > 0: only if it has one candidate or `distance < ratio * second distance`; max_distance > 0:
+        only if `distance < max_distance`), a keypoint keeps the nearest point that took it, and cv2.solvePnPRansac runs on those
+        3D-2D matches as in relocalize().  prior=None: the refinement pass — the priors are the poses the relocalize() just before
+        this call left on the device (same slots, same staged map; VoError otherwise), and a query that failed there keeps its
+        status with zero counts.  Returns relocalize()'s dict plus n_seen [Q]: the points with at least one keypoint in their
+        window.  map_matches(q) and map_match_seconds(q) serve this call afterwards."""
+        opts = _lib.RelocOpts(float(max_distance), int(iterations), float(reproj_err), float(confidence), int(seed), int(min_inliers))
+        poses, nm, ni, st, ns = self.ctx.map_localize_guided(slots, K, prior, radius, ratio, opts)
+        return dict(poses=poses, n_match=nm, n_inl=ni, status=st, n_seen=ns)
 
     def map_matches(self, q):
         """Query q's matches of the latest relocalize(): (map point [n], keypoint [n], distance [n] float32 as cv2 reports it —

@@ -232,17 +232,8 @@ def Rodrigues(src, ctx=None):
     return out, None
 
 
-def relocalize(map_points, map_descriptors, keypoints_xy, descriptors, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99,
-               seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None, match="cross", ratio=0.75):
-    """Place one frame in a map by its descriptors, from host arrays (FrontEnd.stage_map + set_*_rows + relocalize in one call):
-    map_points [npt, 3] float64, map_descriptors [npt, D], keypoints_xy [n, 2], descriptors [n, D]; D = 32 (ORB rows, uint8:
-    Hamming) or 128 (SIFT rows, integer values 0..255: L2).  What the reference's MatchWithMap is for and never does
-    (src/visual_slam.py:211-217): bf.match(descriptors, map_descriptors) with crossCheck=True, `distance < max_distance` (0: no
-    filter), cv2.solvePnPRansac on the matches; match='ratio' | 'cross+ratio' and ratio as FrontEnd.relocalize takes them (the
-    result then has seconds = n.distance per match).  Returns dict(status, pose [3, 4] world -> camera in the map's gauge (zeros when
-    status != 0), n_match, n_inl, matches = (map point, keypoint, distance float32, inlier mask)).
-    The context is configured for this call (a small batch configuration sized to the frame); a caller with resident frames uses
-    FrontEnd.relocalize instead."""
+def _one_frame_against_a_map(map_points, map_descriptors, keypoints_xy, descriptors, ctx):
+    """A FrontEnd configured for one frame of host arrays in slot 0 and the map staged: what relocalize() and relocalize_guided() share."""
     from .frontend import FrontEnd
     d = np.asarray(descriptors)
     if d.ndim != 2 or d.shape[1] not in (32, 128):
@@ -263,12 +254,43 @@ def relocalize(map_points, map_descriptors, keypoints_xy, descriptors, K, max_di
         fe = FrontEnd(64, 64, max_frames=1, max_pairs=1, nfeatures=max(len(d), 1), nlevels=1, ctx=ctx)
         fe.set_orb_rows(0, d, xy)
     fe.stage_map(map_descriptors, map_points)
+    return fe
+
+
+def relocalize(map_points, map_descriptors, keypoints_xy, descriptors, K, max_distance=0.0, iterations=100, reproj_err=8.0, confidence=0.99,
+               seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None, match="cross", ratio=0.75):
+    """Place one frame in a map by its descriptors, from host arrays (FrontEnd.stage_map + set_*_rows + relocalize in one call):
+    map_points [npt, 3] float64, map_descriptors [npt, D], keypoints_xy [n, 2], descriptors [n, D]; D = 32 (ORB rows, uint8:
+    Hamming) or 128 (SIFT rows, integer values 0..255: L2).  What the reference's MatchWithMap is for and never does
+    (src/visual_slam.py:211-217): bf.match(descriptors, map_descriptors) with crossCheck=True, `distance < max_distance` (0: no
+    filter), cv2.solvePnPRansac on the matches; match='ratio' | 'cross+ratio' and ratio as FrontEnd.relocalize takes them (the
+    result then has seconds = n.distance per match).  Returns dict(status, pose [3, 4] world -> camera in the map's gauge (zeros when
+    status != 0), n_match, n_inl, matches = (map point, keypoint, distance float32, inlier mask)).
+    The context is configured for this call (a small batch configuration sized to the frame); a caller with resident frames uses
+    FrontEnd.relocalize instead."""
+    fe = _one_frame_against_a_map(map_points, map_descriptors, keypoints_xy, descriptors, ctx)
     out = fe.relocalize([0], K, max_distance, iterations, reproj_err, confidence, seed, min_inliers, match=match, ratio=ratio)
     res = dict(status=int(out["status"][0]), pose=out["poses"][0], n_match=int(out["n_match"][0]), n_inl=int(out["n_inl"][0]),
                matches=fe.map_matches(0))
     if match != "cross":
         res["seconds"] = fe.map_match_seconds(0)
     return res
+
+
+def relocalize_guided(map_points, map_descriptors, keypoints_xy, descriptors, K, prior, radius, ratio=0.0, max_distance=0.0, iterations=100,
+                      reproj_err=8.0, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None):
+    """relocalize() by projection under a prior pose, from host arrays (FrontEnd.stage_map + set_*_rows + relocalize_guided in one
+    call): prior [3, 4] world -> camera in the map's gauge; every map point in front of it takes the keypoint with the nearest
+    descriptor within `radius` pixels of its projection.  Arguments and result as relocalize(), plus n_seen (map points with a
+    keypoint in their window) and seconds (the second distance per match, FLT_MAX without one).  The context is configured for
+    this call; a caller with resident frames uses FrontEnd.relocalize_guided instead."""
+    P = np.ascontiguousarray(prior, dtype=np.float64)
+    if P.shape != (3, 4):
+        raise ValueError("prior must be [3, 4]")
+    fe = _one_frame_against_a_map(map_points, map_descriptors, keypoints_xy, descriptors, ctx)
+    out = fe.relocalize_guided([0], K, P[None], radius, ratio, max_distance, iterations, reproj_err, confidence, seed, min_inliers)
+    return dict(status=int(out["status"][0]), pose=out["poses"][0], n_match=int(out["n_match"][0]), n_inl=int(out["n_inl"][0]),
+                n_seen=int(out["n_seen"][0]), matches=fe.map_matches(0), seconds=fe.map_match_seconds(0))
 
 
 def estimate_similarity_batch(src, dst, offsets, max_error, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0, ctx=None):
