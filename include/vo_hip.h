@@ -1162,6 +1162,59 @@ int vo_map_align(vo_ctx* ctx, const uint8_t* rows, const double* points, const i
                  double* sim /*[Q][13]*/, int32_t* n_match, int32_t* n_inl, int32_t* status);
 int vo_map_align_matches(vo_ctx* ctx, int q, int32_t* a_idx, int32_t* b_idx, float* dist, uint8_t* inlier_mask, int cap, int32_t* n_out);
 
+/* ------------------------------------------------------------------ guided map alignment: two maps' points matched in space
+ * vo_map_align matches query rows against staged rows by descriptor alone: look-alike rows anywhere in the other map win or block a
+ * match, the weakness vo_map_localize_guided removed for frames.  Once a similarity is known — from the descriptor-only call, from a
+ * loop edge, from join_segments — the question is spatial: for each query point moved into the staged map's gauge, which staged point
+ * lies within a radius of it and has the nearest descriptor?  (The 3D-3D half of ORB-SLAM's SearchAndFuse.)  On that result the
+ * similarity is refitted from many more inliers.  The reference has no counterpart; the rules are this library's own.
+ * Query map q holds points b_i and rows off[q] .. off[q + 1] - 1 of the caller's arrays; the staged map holds points a_j with one row
+ * each; S = prior[q] = s, R row-major, t, taking the query map's gauge to the staged map's.  Every operation below is one float64
+ * rounding, in the order written (the library is built with -ffp-contract=off).
+ *   1 transform.  y_k = s * ((R[k][0] bx + R[k][1] by) + R[k][2] bz) + t_k, k = 0, 1, 2.  Point i takes part iff all three y_k are
+ *     finite.
+ *   2 window.  Staged point j is a candidate of i iff (dx dx + dy dy) + dz dz <= r2, d = a_j - y componentwise, r2 = radius radius
+ *     computed once.  g->radius is a length in the STAGED map's units here (in vo_map_localize_guided it is pixels).  A staged point
+ *     with a coordinate that is not finite is never a candidate under this rule.
+ *   3 distance.  d(i, j), the exact integer: Hamming for ORB rows, sum (a - b)^2 over the 128 raw uint8 values for SIFT rows (the rows
+ *     as vo_map_stage and vo_map_align take them).  Reported as cv2 reports it, float32: fd = (float)d for ORB rows,
+ *     sqrtf((float)d) for SIFT rows.
+ *   4 per query point.  best(i) = the candidate with the smallest (d, j), lexicographically: the lowest staged point wins a tie.
+ *     d2(i) = the second-smallest d among the candidates as a multiset (a tie with the best counts as a second); fewer than two
+ *     candidates: fd2 = FLT_MAX.  n_seen[q] = the query points with at least one candidate.
+ *   5 filters, per query point, conjunctive.  opts->max_distance > 0: (double)fd < max_distance, strictly.  g->ratio > 0: the point
+ *     is kept iff it has fewer than two candidates or (double)fd < ratio * (double)fd2.
+ *   6 one query point per staged point.  Among the points that pass step 5 and whose best is j, the one with the smallest (d, i)
+ *     keeps j.  The filters come first: a point that fails them blocks nobody.
+ *   7 the match list of query q, in ascending query-row order: (query row i, staged row j, fd, fd2), src = b_i (the untransformed
+ *     point), dst = a_j; fd2 is there for every entry.
+ *   8 the similarity: from here on exactly vo_map_align's tail — k_sim3_ransac unchanged on those lists, the same max_error,
+ *     iterations, confidence, seed and min_inliers, the same statuses, failed models zeroed the same way.
+ * vo_set_map_match is not read.  The result does not depend on scheduling: two calls on the same input return the same bytes.
+ * rows == points == off == prior == NULL, the refinement pass: the query maps are the ones the most recent vo_map_align on this staged
+ *   map left on the device and the priors are the sims it left there; nothing is uploaded and nothing returns to the host in between,
+ *   and the sims are copied aside before any work buffer is overwritten.  Q must equal that call's Q, no map may have been staged
+ *   since and no vo_map_align_guided may have run since (it overwrites those sims): otherwise VO_ERR_INVALID.  A query whose status
+ *   there was not VO_OK is not matched: it keeps that status, with n_match = n_inl = n_seen = 0 and a zero sim.  A second pass takes
+ *   its priors explicitly.
+ * After the call vo_map_align_matches and vo_map_match_seconds(1, q, ...) serve the most recent of vo_map_align and
+ *   vo_map_align_guided, and vo_map_match_seconds(1, q, ...) is valid after a guided call whatever `ratio` was.  A later vo_map_align
+ *   returns the bytes it returns without this section.  Limits are vo_map_align's: Q <= 64, off[Q] <= 65536 (VO_ERR_UNSUPPORTED).
+ * VO_ERR_INVALID, the whole call failing and nothing written: what vo_map_align refuses; g == NULL; a radius that is negative or not
+ *   finite; a ratio that is negative or not finite; a non-finite entry in a given prior; some but not all of rows, points, off and
+ *   prior NULL; the refinement conditions above.  A flagged SIFT row of a query map: VO_ERR_INVALID AFTER the run, as vo_map_align
+ *   reports it.
+ * Profiling stages: match_nn (k_fuse_grid, k_fuse_match), match_select (k_fuse_select), misc (k_sim3_ransac).
+ * Merging the two maps afterwards — one list, each ground point once, and the table that says where every old point went — is host
+ * work on these match lists: frontend.merge_maps, FrontEnd.fuse_map.
+ * Out of scope: fusing on the device and inside the walks, redirecting a stream's observations, merged maps beyond 65536 points,
+ * averaging the positions of fused points, a scale-aware or covariance-aware radius, a grid cached across calls on one staged map. */
+int vo_map_align_guided(vo_ctx* ctx, const uint8_t* rows, const double* points, const int32_t* off /*[Q + 1]*/, int Q,
+                        const double* prior /*[Q][13] s, R row-major, t: query gauge -> staged gauge*/,
+                        const vo_guided_opts* g, const vo_align_opts* opts,
+                        double* sim /*[Q][13]*/, int32_t* n_match, int32_t* n_inl, int32_t* status,
+                        int32_t* n_seen /*[Q], may be NULL*/);
+
 /* ------------------------------------------------------------------ pose graph: Sim(3) pose-graph optimisation on the device
  * The restart walks cut a flight into segments, vo_map_localize places a frame in an older map, vo_map_align measures the similarity
  * between two maps: a loop closure arrives as seven numbers.  This section uses it: loop and join constraints are distributed over

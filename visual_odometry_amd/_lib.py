@@ -161,6 +161,7 @@ _SIGS = {
     "vo_sim3_ransac_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "vo_map_align_matches": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P]),
+    "vo_map_align_guided": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vo_vocab_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "vo_vocab_set": (C.c_int, [_P, _P, C.c_int]),
     "vo_vocab_get": (C.c_int, [_P, _P, C.c_int, _P]),
@@ -357,6 +358,32 @@ class Context:
         self.check(self.lib.vo_map_localize_guided(self.handle, sl.ctypes.data, Q, K.ctypes.data, ptr(pr), C.addressof(g), C.addressof(opts),
                                                    poses.ctypes.data, nm.ctypes.data, ni.ctypes.data, st.ctypes.data, ns.ctypes.data))
         return poses.reshape(Q, 3, 4), nm, ni, st, ns
+
+    def map_align_guided(self, rows, points, off, prior, radius, ratio, opts):
+        """vo_map_align_guided on host arrays: rows [total, D] uint8, points [total, 3] float64, off [Q + 1] int32, prior [Q, 13]
+        float64 (s, R row-major, t), opts an AlignOpts — or rows = points = prior = None and off = Q, the number of query maps of
+        the preceding vo_map_align (the refinement pass: nothing is uploaded) -> (rc, sim [Q, 13], n_match, n_inl, status, n_seen
+        [Q] int32).  rc is returned unchecked so that the caller can tell VO_ERR_UNSUPPORTED from the rest."""
+        refine = rows is None
+        if refine:
+            Q = int(off)
+        else:
+            off = np.ascontiguousarray(off, dtype=np.int32).ravel()
+            Q = len(off) - 1
+        if refine != (points is None) or refine != (prior is None):
+            raise ValueError("rows, points and prior are given together or all left None")
+        pr = None
+        if not refine:
+            pr = np.ascontiguousarray(prior, dtype=np.float64).reshape(-1)
+            if len(pr) != 13 * Q:
+                raise ValueError("prior must be [Q, 13]")
+            rows = np.ascontiguousarray(rows, dtype=np.uint8); points = np.ascontiguousarray(points, dtype=np.float64)
+        g = GuidedOpts(float(radius), float(ratio))
+        sim = np.zeros((Q, 13))
+        nm, ni, st, ns = (np.zeros(Q, np.int32) for _ in range(4))
+        rc = self.lib.vo_map_align_guided(self.handle, ptr(rows), ptr(points), None if refine else off.ctypes.data, Q, ptr(pr), C.addressof(g),
+                                          C.addressof(opts), sim.ctypes.data, nm.ctypes.data, ni.ctypes.data, st.ctypes.data, ns.ctypes.data)
+        return rc, sim, nm, ni, st, ns
 
     def last_error(self) -> str:
         msg = self.lib.vo_last_error(self.handle)

@@ -512,13 +512,17 @@ __global__ __launch_bounds__(256) void k_align_select(MapBuf m, AlignBuf a, doub
     if (tid == 0) { a.m_count[q] = out_base; a.poff[2 * q] = o; a.poff[2 * q + 1] = o + out_base; }
 }
 
+void launch_map_align_gather(hipStream_t s, AlignBuf a, const uint8_t* src_rows)
+{
+    if (a.Q <= 0 || a.total <= 0) return;
+    const int per = a.D == 128 ? 4 : 32, g = (a.total + per - 1) / per;
+    hipLaunchKernelGGL(k_align_gather, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, a, src_rows);
+}
+
 void launch_map_align_match(hipStream_t s, MapBuf m, AlignBuf a, const uint8_t* src_rows, int max_rows, int mode)
 {
     if (a.Q <= 0) return;
-    if (a.total > 0) {
-        const int per = a.D == 128 ? 4 : 32, g = (a.total + per - 1) / per;
-        hipLaunchKernelGGL(k_align_gather, dim3(g < 4096 ? g : 4096), dim3(256), 0, s, a, src_rows);
-    }
+    launch_map_align_gather(s, a, src_rows);
     const int fwd = (max_rows + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS, rev = mode == 1 ? 0 : (m.npt + NM_BLOCK_ROWS - 1) / NM_BLOCK_ROWS;
     if (fwd + rev > 0) {
         const dim3 grid((unsigned)a.Q * (fwd + rev));

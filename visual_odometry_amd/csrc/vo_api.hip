@@ -200,7 +200,7 @@ static void comm_release(vo_ctx* ctx);
 static int sift_frames_upload_enqueue(vo_ctx* ctx, const uint8_t* frames, int F, int row_stride, int64_t frame_stride, int first_slot);
 static int sift_frames_detect_enqueue(vo_ctx* ctx, int first_slot, int F);
 
-extern "C" int vo_version(void) { return 127; }
+extern "C" int vo_version(void) { return 128; }
 
 extern "C" int vo_create(int device_id, vo_ctx** out)
 {

@@ -135,8 +135,10 @@ struct MapState {
         AlignBuf a{};
         int Q_cap = 0, pad_cap = 0, total_cap = 0, map_rows = 0;   // what it was sized for
         int last_Q = 0;                   // queries of the most recent vo_map_align (vo_map_align_matches)
-        int last_mode = 0;                // ... and the vo_set_map_match mode it ran in
+        int last_mode = 0;                // ... and the vo_set_map_match mode it ran in (1 after a vo_map_align_guided: its lists carry seconds)
         std::vector<int32_t> off, pad;    // host copies of that call's offsets
+        FuseBuf f{};                      // vo_map_align_guided's work buffers, allocated with the others
+        bool guided = false;              // the most recent of the two align calls was the guided one: a.sim / a.status are no priors
     } al;
 };
 

@@ -590,6 +590,29 @@ void launch_map_align_select(hipStream_t s, MapBuf m, AlignBuf a, double max_dis
 void launch_sim3_ransac(hipStream_t s, const double* src, const double* dst, const int* offsets, int off_stride, int B, int iterations, double max_error,
                         double confidence, uint64_t seed, const uint32_t* rng_tab, int rng_n, int min_inliers, double* sim, uint8_t* mask, int* ninl,
                         int* status);
+// the gather of launch_map_align_match alone: the queries' rows (device, [total][D]) into their operands
+void launch_map_align_gather(hipStream_t s, AlignBuf a, const uint8_t* src_rows);
+// ---- guided map alignment: the query maps' points matched in space under a prior similarity (map_fuse_kernels.hip): vo_map_align_guided
+#define FUSE_G 16                       // the grid over the staged map is FUSE_G^3 cells over its points' own box, an edge per axis
+#define FUSE_CELLS (FUSE_G * FUSE_G * FUSE_G)
+#define FUSE_TILE 256                   // query points per workgroup of k_fuse_match, one lane each
+struct FuseBuf {
+    int*     cell_off;                  // [FUSE_CELLS + 1] where a cell's points start in cell_pt (cells (cz FUSE_G + cy) FUSE_G + cx)
+    int*     cell_pt;                   // [cap_rows of the staged map] the staged points in cell order
+    double*  box;                       // [3][2] per axis: lowest finite coordinate, 1 / cell edge (0: the axis is one cell)
+    unsigned long long* claim;          // [Q][cap_rows] (d << 32) | query row of the row that keeps the staged point; all ones: nobody
+    unsigned long long* pt_best;        // [total] (d << 32) | staged point of a query row that passed the filters; all ones: none
+    int*     pt_d2;                     // [total] ... its second distance (INT_MAX: fewer than two candidates)
+    double*  prior;                     // [Q][13]
+    int*     skip;                      // [Q] not VO_OK: the query is not matched and keeps this status (the refinement pass)
+    int*     n_seen;                    // [Q]
+};
+// k_fuse_grid + k_fuse_match, then k_fuse_select: AlignBuf's match lists, correspondences and offsets as launch_map_align_select leaves
+// them (m_d2 always written); max_rows = the largest query map
+void launch_fuse_match(hipStream_t s, MapBuf m, AlignBuf a, FuseBuf f, int max_rows, double radius, double max_distance, double ratio);
+void launch_fuse_select(hipStream_t s, MapBuf m, AlignBuf a, FuseBuf f);
+// after launch_sim3_ransac: a skipped query takes its earlier status back, with no inliers and a zero similarity
+void launch_fuse_keep(hipStream_t s, AlignBuf a, FuseBuf f);
 
 // ---- place recognition (reloc_kernels.hip): vo_vocab_*, vo_places_*
 // The vocabulary is a map of K rows without points (v.xyz == nullptr, v.npt == v.cap_rows == K): the matcher's operand image and

@@ -721,7 +721,7 @@ class FrontEnd:
 
     # ---- map alignment: the similarity that joins two maps, by their descriptors (vo_map_align) ------
     def align_maps(self, rows, points, max_error, offsets=None, max_distance=0.0, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED,
-                   min_inliers=0, match="cross", ratio=0.75):
+                   min_inliers=0, match="cross", ratio=0.75, refine_radius=None):
         """Align Q query maps to the staged map by their descriptors (vo_map_align), all in one call on the device: the cross-check
         match of every query map's rows against the staged rows -> `distance < max_distance` (0: no filter) -> RANSAC over the
         3D-3D matches for X_staged = scale R X_query + t.  rows [total, D] and points [total, 3] hold the query maps one after
@@ -729,7 +729,10 @@ class FrontEnd:
         max_error is the inlier bound in the STAGED map's units and has no default.  match / ratio: as in relocalize(), with a
         query map's rows in the place of a frame's (map_align_match_seconds(q) returns the second distances).  Returns dict(scale [Q], R [Q, 3, 3], t [Q, 3]
         (zeros where status != 0), n_match, n_inl, status [Q]: 0, VO_ERR_TOO_FEW (fewer than 3 matches) or VO_ERR_NO_MODEL).
-        Up to 64 maps and 65536 rows in one call (NotImplementedError beyond)."""
+        Up to 64 maps and 65536 rows in one call (NotImplementedError beyond).
+        refine_radius=R (a length in the staged map's units): the refinement pass on top — align_maps_guided(None, ..., radius=R)
+        with the same options and no ratio rule, started from these similarities on the device; the result is that call's (n_seen
+        included), with this pass's counts as first_n_match and first_n_inl.  None (default): no such pass."""
         r = self._map_rows_u8(rows)
         p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         if len(p) != len(r):
@@ -748,7 +751,77 @@ class FrontEnd:
             raise NotImplementedError(c.last_error())
         c.check(rc)
         self._align_rows = np.diff(off)
-        return dict(scale=sim[:, 0].copy(), R=sim[:, 1:10].reshape(Q, 3, 3).copy(), t=sim[:, 10:].copy(), n_match=nm, n_inl=ni, status=st)
+        if refine_radius is None:
+            return dict(scale=sim[:, 0].copy(), R=sim[:, 1:10].reshape(Q, 3, 3).copy(), t=sim[:, 10:].copy(), n_match=nm, n_inl=ni, status=st)
+        out = self.align_maps_guided(None, None, None, refine_radius, max_error, max_distance=max_distance, iterations=iterations,
+                                     confidence=confidence, seed=seed, min_inliers=min_inliers)
+        out.update(first_n_match=nm, first_n_inl=ni)
+        return out
+
+    def align_maps_guided(self, rows, points, prior, radius, max_error, offsets=None, ratio=0.0, max_distance=0.0, iterations=1000,
+                          confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0):
+        """Align Q query maps to the staged map by matching their points in space under a prior similarity (vo_map_align_guided; the
+        3D-3D half of ORB-SLAM's SearchAndFuse), all in one call on the device: every query point is moved into the staged map's
+        gauge by prior[q] = (scale, R, t) — a tuple of arrays [Q], [Q, 3, 3], [Q, 3] as align_maps returns them, or [Q, 13] —,
+        takes the staged point with the nearest descriptor among those within `radius` (staged units) of it (ratio > 0: only if it
+        has one candidate or `distance < ratio * second distance`; max_distance > 0: only if `distance < max_distance`), a staged
+        point keeps the nearest query point that took it, and the similarity is refitted by align_maps' RANSAC on those matches.
+        rows=None (points and prior None too): the refinement pass — the query maps and the priors are the ones the align_maps()
+        just before this call left on the device (same staged map; VoError otherwise), and a query that failed there keeps its
+        status with zero counts.  Returns align_maps' dict plus n_seen [Q]: the query points with at least one staged point in
+        their sphere.  map_align_matches(q) and map_align_match_seconds(q) serve this call afterwards."""
+        c = self.ctx
+        opts = _lib.AlignOpts(float(max_distance), float(max_error), int(iterations), float(confidence), int(seed), int(min_inliers))
+        if rows is None:
+            if points is not None or prior is not None or offsets is not None:
+                raise ValueError("the refinement pass takes no rows, points, prior or offsets")
+            rc, sim, nm, ni, st, ns = c.map_align_guided(None, None, len(getattr(self, "_align_rows", ())), None, radius, ratio, opts)
+        else:
+            r = self._map_rows_u8(rows)
+            p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+            if len(p) != len(r):
+                raise ValueError("points must be [total, 3]")
+            off = np.ascontiguousarray([0, len(r)] if offsets is None else offsets, dtype=np.int32).ravel()
+            Q = len(off) - 1
+            if Q < 0 or int(off[-1]) != len(r):
+                raise ValueError("offsets must be [Q + 1] and end at the number of rows")
+            if isinstance(prior, (tuple, list)) and len(prior) == 3 and np.ndim(prior[1]) >= 2:
+                s, R, t = prior
+                prior = np.concatenate([np.reshape(np.asarray(s, np.float64), (-1, 1)), np.reshape(np.asarray(R, np.float64), (-1, 9)),
+                                        np.reshape(np.asarray(t, np.float64), (-1, 3))], axis=1)
+            rc, sim, nm, ni, st, ns = c.map_align_guided(r, p, off, prior, radius, ratio, opts)
+        if rc == _lib.VO_ERR_UNSUPPORTED:
+            raise NotImplementedError(c.last_error())
+        c.check(rc)
+        if rows is not None:
+            self._align_rows = np.diff(off)
+        Q = len(sim)
+        return dict(scale=sim[:, 0].copy(), R=sim[:, 1:10].reshape(Q, 3, 3).copy(), t=sim[:, 10:].copy(), n_match=nm, n_inl=ni, status=st, n_seen=ns)
+
+    def fuse_map(self, rows, points, max_error, radius, max_distance=0.0, iterations=1000, confidence=0.99, seed=OPENCV_RNG_SEED, min_inliers=0,
+                 match="cross", ratio=0.75):
+        """Fuse map B (rows [nb, D], points [nb, 3]) into the staged map A: map_rows() for A, align_maps(B) by descriptors, the
+        refinement pass within `radius` (A's units), map_align_matches, merge_maps on the host, and stage_map of the result — one
+        map, each ground point once.  Returns dict(rows, points — the merged map, now staged —, index_b [nb] (where each point
+        of B went), n_fused, n_a, the refined align result as `align` and its map_align_matches(0) as `matches`).  When the alignment
+        fails (status != 0) nothing is merged
+        or staged: rows and points are None, index_b None, n_fused 0.  A merged map of more than 65536 points: NotImplementedError,
+        as stage_map raises it, with A still staged."""
+        rows_a, pts_a = self.map_rows()
+        r = self._map_rows_u8(rows)
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        al = self.align_maps(r, p, max_error, max_distance=max_distance, iterations=iterations, confidence=confidence, seed=seed,
+                             min_inliers=min_inliers, match=match, ratio=ratio, refine_radius=radius)
+        out = dict(rows=None, points=None, index_b=None, n_fused=0, n_a=len(rows_a), align=al)
+        if al["status"][0] != 0:
+            return out
+        out["matches"] = ai, bi, _, mask = self.map_align_matches(0)      # (staging the merged map forgets them on the device)
+        m = merge_maps(rows_a, pts_a, r, p, al["scale"][0], al["R"][0], al["t"][0], ai, bi, mask)
+        if len(m["rows"]) > 65536:
+            raise NotImplementedError("a staged map holds at most 65536 points, the merged map has %d" % len(m["rows"]))
+        self.stage_map(m["rows"], m["points"])
+        out.update(m)
+        return out
 
     def map_align_matches(self, q):
         """Query map q's matches of the latest align_maps(): (staged row [n], query row [n], distance [n] float32 as cv2 reports
@@ -980,6 +1053,35 @@ def apply_similarity(poses, scale, R, t):
     R = np.asarray(R, np.float64).reshape(3, 3); t = np.asarray(t, np.float64).reshape(3)
     Rc = T[..., :3] @ R.T
     return np.concatenate([Rc, (float(scale) * T[..., 3] - Rc @ t)[..., None]], axis=-1)
+
+
+def merge_maps(rows_a, points_a, rows_b, points_b, scale, R, t, a_idx, b_idx, mask):
+    """One map from two aligned ones: B's points go into A's gauge by X_a = scale R X_b + t (componentwise, in the operation order of
+    vo_map_align_guided's transform); every match (a_idx[k], b_idx[k]) with mask[k] == 1 is a duplicate, and A's row and point are
+    kept for it; the merged map is all of A, then B's non-duplicates in B's order.  The lists are what map_align_matches returns:
+    a row of either map appears in at most one match.  Returns dict(rows [n, D], points [n, 3], index_b [nb] int32 — the merged row
+    of every point of B: a row of A for a fused point, n_a + its rank among the others otherwise —, n_fused).  A's points keep
+    their rows, so its own table is the identity.  Pure numpy; positions of fused points are not averaged."""
+    ra = np.asarray(rows_a); rb = np.asarray(rows_b)
+    pa = np.asarray(points_a, np.float64).reshape(-1, 3); pb = np.asarray(points_b, np.float64).reshape(-1, 3)
+    if len(pa) != len(ra) or len(pb) != len(rb) or (len(ra) and len(rb) and ra.shape[1:] != rb.shape[1:]):
+        raise ValueError("rows and points of both maps must agree in length and width")
+    ai = np.asarray(a_idx, np.int64).ravel(); bi = np.asarray(b_idx, np.int64).ravel(); keep = np.asarray(mask).ravel() != 0
+    if not (len(ai) == len(bi) == len(keep)):
+        raise ValueError("a_idx, b_idx and mask must have one entry per match")
+    ai, bi = ai[keep], bi[keep]
+    if len(ai) and (ai.min() < 0 or ai.max() >= len(ra) or bi.min() < 0 or bi.max() >= len(rb)):
+        raise ValueError("a match names a row outside its map")
+    if len(np.unique(ai)) != len(ai) or len(np.unique(bi)) != len(bi):
+        raise ValueError("a row appears in more than one inlier match")
+    R = np.asarray(R, np.float64).reshape(3, 3); t = np.asarray(t, np.float64).reshape(3); s = float(scale)
+    moved = np.stack([s * ((R[k, 0] * pb[:, 0] + R[k, 1] * pb[:, 1]) + R[k, 2] * pb[:, 2]) + t[k] for k in range(3)], axis=1).reshape(-1, 3)
+    fused = np.zeros(len(rb), bool); fused[bi] = True
+    index_b = np.empty(len(rb), np.int32)
+    index_b[bi] = ai
+    index_b[~fused] = len(ra) + np.arange(int((~fused).sum()))
+    rows = np.concatenate([ra, rb[~fused]]) if len(rb) else ra.copy()
+    return dict(rows=rows, points=np.concatenate([pa, moved[~fused]]), index_b=index_b, n_fused=int(fused.sum()))
 
 
 def compose_similarity(outer, inner):
